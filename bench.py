@@ -9,9 +9,13 @@ frame g -> rank g mod N; the only exchange is a ring shift of t
 blocks (RCCL send/recv to rank + 1) so that the owner of frame g holds frame g-1's descriptors.  Weak scaling: every rank
 processes its own 256 frames per step.
 
-Rank 0 writes the full report (every object named below, ~20 KB) to gpurun_out/bench_detail.json and prints, as the LAST
-and only JSON line of stdout, a compact headline (< 4 KB: `headline()` below) that carries the contract fields plus one
-`roofline` object, one `cpu_baseline` object, the parity counts and one scalar per extra leg.  The report's objects:
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline figure needs: set up, W warm-up steps, N timed
+steps, the outputs of the last timed step if --dump-outputs DIR is given (dump_outputs()), and the line — the contract
+fields, the run's configuration and the roofline objects of the timed steps' own kernel events.  Everything else below
+runs with --full only.
+With --full, rank 0 writes the full report (every object named below, ~20 KB) to a side file (write_detail()) and prints,
+as the LAST and only JSON line of stdout, a compact headline (< 4 KB: `headline()` below) that carries the contract fields
+plus one `roofline` object, one `cpu_baseline` object, the parity counts and one scalar per extra leg.  The report's objects:
   roofline        — the kernel family with the largest time per step when the GPU is its alone (isolated pass), timed
                     in the run by the launches' own start/stop events: achieved = the kernel's algorithmic bytes
                     (what it must read and write once, given what it fuses: DESIGN.md §5; for the gather kernel the
@@ -104,8 +108,17 @@ def main():
     ap.add_argument("--detail-stdout", action="store_true", help="also print the full report (one {\"bench_detail\": ...} line) before "
                     "the headline; by default it only goes to gpurun_out/bench_detail.json")
     ap.add_argument("--dump-matches", default=None, help="write per-global-frame keypoint/match counts to this .npy")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the instrumented pass "
+                    "(phase_ms_per_step), the isolated pass, the gather model, the device probe, the CPU baselines and the "
+                    "parity checks against the oracle, configs_extra, and the detail report.  Off: set up, warm up, time "
+                    "--steps steps, dump (--dump-outputs) and print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed "
+                    "step computed (rank 0) as DIR/<name>.npy, float32: keypoint_counts, match_counts (or neighbours), and "
+                    "the keypoints, descriptors and match pairs of a fixed seeded sample of frames (dump_outputs())")
     args = ap.parse_args()
-    if args.pmc_run:
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.pmc_run or not args.full:
         args.no_cpu_baseline = args.no_extras = args.no_isolated = True
     if args.share_device and args.gpus > 1 and args.backend == "nccl":
         args.backend = "gloo"         # RCCL refuses two ranks on one device; the smoke test of N > 1 on one GPU runs over gloo
@@ -117,7 +130,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args, sys.argv[1:])          # (does not return: exec of torch.distributed.run with the same arguments)
+        self_launch(args, sys.argv[1:])          # (does not return: torch.distributed.run with the same arguments, then exit)
     if args.gpus != world:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     assert torch.cuda.is_available(), "bench.py needs the MI355X (there is no CPU fallback)"
@@ -339,7 +352,12 @@ def main():
     _lib.check(L.hm_timing_enable(matcher.handle, 0), "hm_timing_enable")
     fam_pipe = read_families(ctx)                 # kernel families over the timed region (all streams busy)
     desc_k_ms, desc_k_launches, _ = ctx.timing_get(25)
-    INSTR_STEPS = 0 if args.pmc_run else 2
+    if args.dump_outputs and rank == 0:
+        # the last timed step's output set, before anything else runs on the GPU
+        t = (step_no[0] - 1) & 1
+        dump_outputs(args.dump_outputs, kps2[t], descs2[t], counts2[t], pairs2[t], npairs2[t], knn_out2[t], K,
+                     match_slots(NF, MB, sharded, shift_mode, rank))
+    INSTR_STEPS = 2 if args.full and not args.pmc_run else 0
     fed_ms = ss_ms = all_ms = desc_ms = refine_ms = 0.0
     if INSTR_STEPS:
         ctx.timing_enable(1)
@@ -400,20 +418,9 @@ def main():
         dist.barrier()
 
     if args.dump_matches:
-        # per GLOBAL frame g = j*world + rank: [keypoints, matches of (g, g-1)]; problem order follows `js`
-        # within each micro-batch, so the match count of local frame j is looked up through the same schedule
-        slot_of = {}
-        for m0 in range(0, NF, MB):
-            if sharded and not shift_mode:
-                js, base = list(range(m0, m0 + MB)), None        # all-gather route: slot = frame
-            elif sharded and rank > 0:
-                js, base = list(range(m0, m0 + MB)), m0
-            elif sharded:
-                js, base = list(range(m0 + 1, m0 + MB)) + ([m0] if m0 > 0 else []) + ([0] if m0 + MB == NF else []), m0
-            else:
-                js, base = [j for j in range(m0, m0 + MB) if j > 0] + ([0] if m0 + MB == NF else []), m0
-            for q, j in enumerate(js):
-                slot_of[j] = j if base is None else base + q
+        # per GLOBAL frame g = j*world + rank: [keypoints, matches of (g, g-1)]; the match count of local frame j is
+        # looked up through the step's schedule
+        slot_of = match_slots(NF, MB, sharded, shift_mode, rank)
         per_frame = torch.zeros((NF, 2), dtype=torch.int32, device=dev)
         per_frame[:, 0] = counts
         if K == 1:
@@ -445,12 +452,13 @@ def main():
         total_frames = NF * world * args.steps
         fps = total_frames / elapsed
         gather = None
-        try:
-            gs = sorted({0, NF // 3, NF // 2, NF - 1})
-            hk = [kps[j].cpu().numpy().view(_lib.KP_DTYPE).reshape(-1) for j in gs]
-            gather = gather_model(ctx, hk, [int(counts[j].item()) for j in gs])
-        except Exception as e:                 # the model is reporting only: never fail the run for it
-            print(f"bench.py: gather model skipped ({e})", file=sys.stderr)
+        if args.full:
+            try:
+                gs = sorted({0, NF // 3, NF // 2, NF - 1})
+                hk = [kps[j].cpu().numpy().view(_lib.KP_DTYPE).reshape(-1) for j in gs]
+                gather = gather_model(ctx, hk, [int(counts[j].item()) for j in gs])
+            except Exception as e:             # the model is reporting only: never fail the run for it
+                print(f"bench.py: gather model skipped ({e})", file=sys.stderr)
         tops = roofline_entries(fam_pipe, fam_iso, MB, args.steps, gather, ISO_REPS)
         if knn_ms.value > 0:
             # the matcher as a family of its own: 2 directions x nq x nt x 512-bit contractions per frame pair as MACs (2 ops each)
@@ -551,7 +559,8 @@ def main():
             out["end_to_end_hbm_frac"] = round(traffic["bytes"] * fps / world / (HBM_PEAK_GBS * 1e9), 4)
             # the same for the VALU: wave-instructions of the library's kernels per frame x 64 lanes x frames/s against the issue peak
             out["end_to_end_valu_frac"] = round(traffic["valu_insts"] * 64.0 * fps / world / (VALU_ISSUE_PEAK_T * 1e12), 4)
-        out["device"] = device_probe(torch, dev)
+        if args.full:
+            out["device"] = device_probe(torch, dev)
         rc = 0
         if world == 1 and not args.no_cpu_baseline:
             base, oracle_out = cpu_baseline(frames, args.cpu_frames)
@@ -581,7 +590,7 @@ def main():
                 if v.get("parity", {}).get("mismatches"):
                     rc = 1
         flush_c_stdio()                     # (RCCL writes a version banner through C stdio: it must not follow the line)
-        detail = write_detail(out)
+        detail = write_detail(out) if args.full else None
         if args.detail_stdout:
             print(json.dumps({"bench_detail": out}), flush=True)
         print(headline(out, detail), flush=True)        # the LAST line of stdout, < 4 KB
@@ -676,10 +685,76 @@ def write_detail(out):
         return None
 
 
+def match_slots(NF, MB, sharded, shift_mode, rank):
+    """local frame j -> the row of the step's pair lists that holds the matches of (j, its predecessor): problem order
+    follows `js` of step() within each micro-batch."""
+    slot_of = {}
+    for m0 in range(0, NF, MB):
+        if sharded and not shift_mode:
+            js, base = list(range(m0, m0 + MB)), None        # all-gather route: slot = frame
+        elif sharded and rank > 0:
+            js, base = list(range(m0, m0 + MB)), m0
+        elif sharded:
+            js, base = list(range(m0 + 1, m0 + MB)) + ([m0] if m0 > 0 else []) + ([0] if m0 + MB == NF else []), m0
+        else:
+            js, base = [j for j in range(m0, m0 + MB) if j > 0] + ([0] if m0 + MB == NF else []), m0
+        for q, j in enumerate(js):
+            slot_of[j] = j if base is None else base + q
+    return slot_of
+
+
+DUMP_SAMPLE_SEED = 0x5EED
+DUMP_LIMIT = 60 << 20        # bytes of the sampled arrays at full capacity (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, kps, descs, counts, pairs, npairs, knn_out, K, slot_of):
+    """What the timed path hands its caller for this rank's frames, as float32 .npy files under `path` (every value is
+    exact in float32: keypoint fields are f32 or small integers, descriptor bytes, indices < 2^24, distances <= 512):
+      keypoint_counts  [NF]           keypoints per frame
+      match_counts     [NF]           pairs of (frame j, frame j-1) per frame (K = 1)
+      sample_frames    [n]            the local frames sampled below: a fixed seeded choice, sorted
+      keypoints        [sum c, 7]     x, y, response, size, angle, octave, class_id of the sampled frames, frame after frame
+      descriptors      [sum c, 64]    their descriptor bytes
+      matches          [sum m, 2]     (K = 1) their pair lists: [keypoint of frame j, keypoint of frame j-1]
+      neighbours       [sum c, K, 2, 2]  (K > 1) {index, distance} of the 2 nearest in each of the K views
+    The sample holds as many frames as fit DUMP_LIMIT at the block capacity (16 at most)."""
+    from cv_amd import _lib
+    os.makedirs(path, exist_ok=True)
+    NF = kps.shape[0]
+    cnt = np.minimum(counts.cpu().numpy().astype(np.int64), CAP)
+    per_frame = CAP * (7 + 64) * 4 + (CAP * 2 * 4 if K == 1 else CAP * K * 4 * 4)
+    n = max(1, min(16, NF, DUMP_LIMIT // per_frame))
+    sample = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(NF, n, replace=False))
+    arrays = {"keypoint_counts": counts.cpu().numpy(), "sample_frames": sample}
+    kp, ds, extra = [], [], []
+    for j in sample:
+        c = int(cnt[j])
+        k = kps[j, :c].cpu().numpy().view(_lib.KP_DTYPE).reshape(-1)
+        kp.append(np.stack([k[f].astype(np.float32) for f in k.dtype.names], 1))
+        ds.append(descs[j, :c].cpu().numpy())
+        if K == 1:
+            s = slot_of[j]
+            extra.append(pairs[s, :int(npairs[s].item())].cpu().numpy())
+        else:
+            extra.append(knn_out[j, :, :c].cpu().numpy().transpose(1, 0, 2, 3))
+    arrays["keypoints"] = np.concatenate(kp)
+    arrays["descriptors"] = np.concatenate(ds)
+    if K == 1:
+        hn = npairs.cpu().numpy()
+        arrays["match_counts"] = np.array([hn[slot_of[j]] for j in range(NF)])
+        arrays["matches"] = np.concatenate(extra).reshape(-1, 2)
+    else:
+        arrays["neighbours"] = np.concatenate(extra)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def self_launch(args, argv):
-    """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: become the launcher of N ranks of this same command
-    on this node (127.0.0.1 rendezvous, a free port), one rank per GPU — or all on cuda:0 with --share-device."""
+    """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: start torch.distributed.run with N ranks of this
+    same command on this node (127.0.0.1 rendezvous, a free port), one rank per GPU — or all on cuda:0 with --share-device —
+    and exit with its status."""
     import socket
+    import subprocess
     if not args.share_device:
         import torch
         have = torch.cuda.device_count()
@@ -695,7 +770,7 @@ def self_launch(args, argv):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "8")
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def flush_c_stdio():

@@ -224,19 +224,21 @@ def test_headline_is_compact_and_parseable():
 
 def test_gpus_n_without_a_launcher_starts_its_own_ranks(monkeypatch):
     """`python bench.py --gpus 2 ...` with no WORLD_SIZE in the environment (the driver's N = 1 command shape with another
-    N) must become the launcher of its own ranks: exec of torch.distributed.run on 127.0.0.1 with the same arguments."""
+    N) must become the launcher of its own ranks: a child torch.distributed.run on 127.0.0.1 with the same arguments, whose
+    exit status it returns."""
     import os
+    import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
     import bench
     seen = {}
 
-    def fake_execve(exe, argv, env):
-        seen["exe"], seen["argv"], seen["env"] = exe, list(argv), dict(env)
-        raise SystemExit(0)
+    def fake_call(cmd, env=None):
+        seen["exe"], seen["argv"], seen["env"] = cmd[0], list(cmd), dict(env)
+        return 0
     import torch
-    monkeypatch.setattr(os, "execve", fake_execve)
+    monkeypatch.setattr(subprocess, "call", fake_call)
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5"])
     # a node with fewer GPUs than ranks: a clear refusal instead of N ranks failing one by one
@@ -256,6 +258,72 @@ def test_gpus_n_without_a_launcher_starts_its_own_ranks(monkeypatch):
     assert "--nproc-per-node=2" in a and a[a.index("--master-addr") + 1] == "127.0.0.1"
     assert a[-6:] == ["--gpus", "2", "--steps", "20", "--warmup", "5"] and a[-7].endswith("bench.py")
     assert seen["env"].get("HSA_ENABLE_IPC_MODE_LEGACY") == "0"
+
+
+def _dump_inputs(nf, k, seed):
+    """Output buffers of bench.py's step() filled to the block capacity (the largest dump), as host tensors."""
+    import torch
+    import bench
+    from cv_amd import _lib
+    rng = np.random.default_rng(seed)
+    cap = bench.CAP
+    kp = np.zeros((nf, cap), _lib.KP_DTYPE)
+    for f in ("x", "y", "response", "size", "angle"):
+        kp[f] = rng.uniform(0, 1920, kp.shape).astype(np.float32)
+    kp["octave"], kp["class_id"] = rng.integers(0, 4, kp.shape), rng.integers(0, 16, kp.shape)
+    counts = np.full(nf, cap, np.int32)
+    counts[1] = 7                                          # a short frame among them
+    pairs = rng.integers(0, cap, (nf + 2, cap, 2)).astype(np.int32)
+    npairs = rng.integers(0, cap + 1, nf + 2).astype(np.int32)
+    knn = rng.integers(0, cap, (nf, k, cap, 2, 2)).astype(np.int32) if k > 1 else None
+    t = torch.from_numpy
+    return (t(kp.view(np.uint8).reshape(nf, cap, 28)), t(rng.integers(0, 256, (nf, cap, 64), dtype=np.uint8)), t(counts),
+            t(pairs), t(npairs), None if knn is None else t(knn))
+
+
+@pytest.mark.parametrize("k", [1, 8])
+def test_dump_outputs_writes_the_timed_paths_arrays(tmp_path, k):
+    """bench.py --dump-outputs: float32 .npy files of what the timed path returns — keypoint and match counts of every
+    frame, the keypoints, descriptors and pair lists (or, K > 1, the neighbour lists) of a fixed seeded sample of frames —
+    the same sample on every run, under 64 MB in all even with every block full; pair lists are read through the step's
+    schedule (match_slots)."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from cv_amd import _lib
+    nf, mb = 16, 8
+    kps, descs, counts, pairs, npairs, knn = _dump_inputs(nf, k, 3)
+    slots = bench.match_slots(nf, mb, False, False, 0)
+    assert sorted(slots) == list(range(nf)) and slots[1] == 0 and slots[0] == nf and slots[8] == 8
+    bench.dump_outputs(str(tmp_path / "a"), kps, descs, counts, pairs, npairs, knn, k, slots)
+    bench.dump_outputs(str(tmp_path / "b"), kps, descs, counts, pairs, npairs, knn, k, slots)
+    names = sorted(os.listdir(tmp_path / "a"))
+    want = ["descriptors.npy", "keypoint_counts.npy", "keypoints.npy", "sample_frames.npy"]
+    want += ["match_counts.npy", "matches.npy"] if k == 1 else ["neighbours.npy"]
+    assert names == sorted(want) and sorted(os.listdir(tmp_path / "b")) == names
+    d = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float32 for a in d.values())
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64 << 20
+    for n in names:                                           # the same sample, the same bytes
+        assert (tmp_path / "a" / n).read_bytes() == (tmp_path / "b" / n).read_bytes(), n
+    sample = d["sample_frames"].astype(int)
+    assert len(sample) >= 1 and len(set(sample)) == len(sample) and list(sample) == sorted(sample)
+    c = counts.numpy()
+    assert np.array_equal(d["keypoint_counts"], c)
+    kp = kps.numpy().view(_lib.KP_DTYPE).reshape(nf, -1)
+    got_kp = np.concatenate([kp[j, :c[j]] for j in sample])
+    assert d["keypoints"].shape == (len(got_kp), 7)
+    for i, f in enumerate(_lib.KP_DTYPE.names):
+        assert np.array_equal(d["keypoints"][:, i], got_kp[f].astype(np.float32)), f
+    assert np.array_equal(d["descriptors"], np.concatenate([descs.numpy()[j, :c[j]] for j in sample]))
+    if k == 1:
+        hp, hn = pairs.numpy(), npairs.numpy()
+        assert np.array_equal(d["match_counts"], [hn[slots[j]] for j in range(nf)])
+        assert np.array_equal(d["matches"], np.concatenate([hp[slots[j], :hn[slots[j]]] for j in sample]))
+    else:
+        hk = knn.numpy()
+        assert np.array_equal(d["neighbours"], np.concatenate([hk[j, :, :c[j]].transpose(1, 0, 2, 3) for j in sample]))
 
 
 def test_pixel_normalisation_shortcut_is_exact():

@@ -2348,6 +2348,41 @@ def test_bench_gpus_8_on_one_device_equals_single_rank(gpu, tmp_path):
         assert len(want) == a[g, 1] and len(want) > 500
 
 
+def test_plain_bench_run_dumps_its_last_step(gpu, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, prints the contract fields and nothing that needs a run
+    of its own, and --dump-outputs writes the last timed step's outputs: the same arrays whatever --steps is (the inputs
+    are the same on every run), and the pair lists of its sampled frames are those --dump-matches writes."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--frames", "16", "--micro-batch", "8", "--warmup", "1"]
+    lines, dirs = [], []
+    for steps in (3, 1):
+        d = tmp_path / f"out{steps}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--dump-outputs", str(d),
+                            "--dump-matches", str(tmp_path / f"m{steps}.npy")] + common,
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dirs.append(d)
+    for h, steps in zip(lines, (3, 1)):
+        assert h["steps"] == steps and h["ms_per_step"] > 0 and h["dtype"] == "f32" and h["unit"] == "frames/s"
+        assert abs(h["value"] - 16 * 1e3 / h["ms_per_step"]) < 0.01 * h["value"]
+        for k in ("cpu_baseline", "parity", "extras", "scale_space_isolated_frames_per_s", "detail"):
+            assert k not in h, k
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and "matches.npy" in names
+    a = {n[:-4]: np.load(dirs[0] / n) for n in names}
+    for n in names:
+        assert a[n[:-4]].dtype == np.float32 and np.array_equal(a[n[:-4]], np.load(dirs[1] / n)), n
+    counts = np.load(tmp_path / "m3.npy")
+    assert np.array_equal(a["keypoint_counts"], counts[:, 0]) and np.array_equal(a["match_counts"], counts[:, 1])
+    pl = np.load(str(tmp_path / "m3.npy") + ".r0.npz")
+    want = np.concatenate([pl[f"g{j}"] for j in a["sample_frames"].astype(int)])
+    assert np.array_equal(a["matches"], want.astype(np.float32))
+    assert a["keypoints"].shape == (counts[a["sample_frames"].astype(int), 0].sum(), 7) and len(a["descriptors"]) == len(a["keypoints"])
+
+
 @pytest.mark.parametrize("dtype,channels", [(np.uint8, 3), (np.uint8, 4), (np.uint16, 3), (np.float32, 3), (np.float32, 4)])
 def test_colour_input_arms(gpu, oracle, dtype, channels):
     """The colour arms of GrayFloatImage::from_dynamic (akaze/src/image.rs:45-46, 87-106) on the C ABI (akz_extract_color):
