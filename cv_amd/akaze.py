@@ -198,36 +198,44 @@ class Context:
     def handle(self):
         return self._h
 
-    def extract_batch(self, images):
-        """images: list of same-shaped HxW uint8 or float32 arrays. Returns [(kp_array, desc[n,64])]."""
+    def extract_batch(self, images, keep_stride=False):
+        """images: list of same-shaped HxW uint8, uint16 or float32 arrays. Returns [(kp_array, desc[n,64])].
+        keep_stride: pass row-strided views (e.g. buf[:, :w] of a wider buffer) to the library as they are, with their
+        row pitch as akz_extract_batch's `stride`, instead of packing them first; every image needs the same pitch."""
         n = len(images)
-        imgs = [np.ascontiguousarray(im) for im in images]
+        imgs = [np.asarray(im) for im in images] if keep_stride else [np.ascontiguousarray(im) for im in images]
         h, w = imgs[0].shape
         fmt = {np.dtype(np.uint8): _lib.FMT_U8, np.dtype(np.uint16): _lib.FMT_U16}.get(imgs[0].dtype, _lib.FMT_F32)
-        if fmt == _lib.FMT_F32:
+        if fmt == _lib.FMT_F32 and imgs[0].dtype != np.float32:
             imgs = [np.ascontiguousarray(im, dtype=np.float32) for im in imgs]
         assert all(im.shape == (h, w) and im.dtype == imgs[0].dtype for im in imgs)
+        stride = _row_stride(imgs[0])
+        assert all(_row_stride(im) == stride for im in imgs), "images of one call share one row pitch"
         cap = self.max_kp
         # (outputs are not cleared: the library writes cnt[i] entries per frame and only those are returned)
         kps = np.empty((n, cap), KP_DTYPE)
         descs = np.empty((n, cap, 64), np.uint8)
         cnt = np.zeros(n, np.uint32)
         ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
-        st = _lib.lib().akz_extract_batch(self._h, ptrs, fmt, n, w, h, w, kps.ctypes.data, descs.ctypes.data, cap,
+        st = _lib.lib().akz_extract_batch(self._h, ptrs, fmt, n, w, h, stride, kps.ctypes.data, descs.ctypes.data, cap,
                                           cnt.ctypes.data)
         if st == -7:
             raise AkzError(st, "akz_extract_batch: " + self.overflow_report())
         check(st, "akz_extract_batch")
         return [(kps[i, :cnt[i]].copy(), descs[i, :cnt[i]].copy()) for i in range(n)]
 
-    def extract_color(self, image):
-        """One HxWx3/4 uint8 / uint16 / float32 image through akz_extract_color.  Returns (kp_array, desc[n,64])."""
-        img = np.ascontiguousarray(image)
+    def extract_color(self, image, keep_stride=False):
+        """One HxWx3/4 uint8 / uint16 / float32 image through akz_extract_color.  Returns (kp_array, desc[n,64]).
+        keep_stride: pass a row-strided view (pixels packed within a row) as it is, its row pitch as the `stride`."""
+        img = np.asarray(image)
+        if not keep_stride or img.strides[1:] != (img.shape[2] * img.itemsize, img.itemsize):
+            img = np.ascontiguousarray(img)
         h, w, ch = img.shape
         fmt = {np.dtype(np.uint8): _lib.FMT_U8, np.dtype(np.uint16): _lib.FMT_U16, np.dtype(np.float32): _lib.FMT_F32}[img.dtype]
+        stride = _row_stride(img)
         cap = self.max_kp
         kps = np.empty(cap, KP_DTYPE); descs = np.empty((cap, 64), np.uint8); cnt = C.c_uint32()
-        st = _lib.lib().akz_extract_color(self._h, img.ctypes.data, fmt, ch, w, h, w * ch, kps.ctypes.data, descs.ctypes.data, cap,
+        st = _lib.lib().akz_extract_color(self._h, img.ctypes.data, fmt, ch, w, h, stride, kps.ctypes.data, descs.ctypes.data, cap,
                                           C.byref(cnt))
         if st == -7:
             raise AkzError(st, "akz_extract_color: " + self.overflow_report())
@@ -304,6 +312,15 @@ class Context:
         ms = C.c_double(); la = C.c_uint64(); un = C.c_uint64()
         check(_lib.lib().akz_timing_get(self._h, which, C.byref(ms), C.byref(la), C.byref(un)))
         return ms.value, la.value, un.value
+
+
+def _row_stride(img):
+    """The row pitch of an image whose samples are packed within each row, in elements (the ABI's `stride`)."""
+    if img.strides[1:] != tuple(int(np.prod(img.shape[2 + i:])) * img.itemsize for i in range(img.ndim - 1)):
+        raise ValueError("the samples of a row must be packed (only the row pitch may exceed the row)")
+    if img.strides[0] % img.itemsize or img.strides[0] < img.strides[1] * img.shape[1]:
+        raise ValueError("the row pitch must be a whole number of samples, at least one row")
+    return img.strides[0] // img.itemsize
 
 
 def grayscale(rgb):
