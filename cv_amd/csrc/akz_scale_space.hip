@@ -48,14 +48,7 @@ constexpr bool kArithHalfSeq = (AKZ_ARITH & 4) != 0;
 
 constexpr int kTW = 64;  // output tile width  (one wave wide: a wave reads/writes one contiguous row segment)
 constexpr int kTH = 32;  // output tile height
-constexpr int kFTH = 32; // row tile of the contrast passes: 32 rows x 512 threads, every thread a 4-pixel patch in the gradient phase
-                         // (24 rows — three blocks of 53 KB per CU instead of two of 62 — left a quarter of the threads idle there:
-                         // 1 543 vs 1 328 us per 256 frames once the fine histogram had joined the block's LDS)
 constexpr int kDTH = 12; // output tile height of the two-frame determinant kernel
-constexpr int kCTiles = 17; // row tiles per block of the contrast passes in a batch (17 x 32 rows: two blocks per 1080p column;
-                           // 5 / 9 / 12 / 17 tiles: 1 452 / 1 377 / 1 340 / 1 328 us); a few-frame call takes kCTilesFew
-constexpr int kCTilesFew = 4; // ... so that one frame still fills the chip (1080p: 30 x 9 blocks)
-constexpr int kFNT = 512; // its block size: 2 blocks x 8 waves per CU
 
 enum { EPI_BLUR = 0, EPI_FLOW = 1, EPI_CMAX = 2, EPI_CHIST = 3 };
 
@@ -592,6 +585,14 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 3) void k_level_front2(const In
     }
 }
 
+template <int CTRL>
+__device__ __forceinline__ v2f dpp_row(v2f v)   // value of the lane CTRL selects within the 16-lane row (0x138 / 0x130: the
+{                                               // wave_shr:1 / wave_shl:1 neighbour); 0 outside it
+    int x = __builtin_amdgcn_update_dpp(0, __float_as_int(v.x), CTRL, 0xF, 0xF, true);
+    int y = __builtin_amdgcn_update_dpp(0, __float_as_int(v.y), CTRL, 0xF, 0xF, true);
+    return (v2f){__int_as_float(x), __int_as_float(y)};
+}
+
 // ---- contrast factor without the histogram pass -------------------------------------------------------------
 // contrast_factor.rs:41-64 walks the histogram until the running count reaches threshold = floor(npoints *
 // percentile): the bin it stops after is the bin of the threshold-th smallest non-zero magnitude, so the result is
@@ -700,8 +701,8 @@ __global__ __launch_bounds__(256) void k_contrast_resolve(const unsigned long lo
 }
 
 // ---------------------------------------------------------------------------------------------
-// Contrast factor on two frames per block (contrast_factor.rs:16-64): the same blurred two-frame tile as the
-// level front-end (sigma 1.0, one-pixel ring), then the simple Scharr gradient and
+// Contrast factor on two frames per wave (contrast_factor.rs:16-64): the blur (sigma 1.0), then the simple
+// Scharr gradient and
 //   pass CMAX : the per-frame maximum of v = f64(lx*lx) + f64(ly*ly) over interior pixels,
 //   pass CHIST: the histogram of floor(nbins * (sqrt(v) / hmax)).
 // The histogram pass does not evaluate the f64 square root and division per pixel.  The bin index is a
@@ -735,32 +736,80 @@ __global__ __launch_bounds__(512) void k_contrast_thresholds(const unsigned long
     T[k] = __longlong_as_double((long long)lo);
 }
 
-template <typename InT, int EPI>
-__global__ __launch_bounds__(kFNT) void k_contrast_pair(const InT* __restrict__ in, int w, int h, size_t fs, int n,
-                                                        GaussTaps taps, unsigned long long* __restrict__ cmax,
-                                                        const double* __restrict__ thr, uint32_t* __restrict__ hist,
-                                                        uint32_t* __restrict__ npoints, int nbins,
-                                                        uint32_t* __restrict__ fine, const uint32_t* __restrict__ flag, int ctiles)
+// The passes stream (k_det_stream's form): a wave walks one column band of one row segment of a frame pair down the
+// rows, every lane two adjacent columns of both frames as {frame a, frame b} pairs.  Per input row: the lane's pixels,
+// the two columns on either side from the neighbouring lanes by DPP wave shifts, the horizontal blur into a ring of the
+// last five H-blurred rows, the vertical blur of the ring's middle row, and that blurred row's simple Scharr partials
+// (its outer columns again by a wave shift) into a ring of two rows: row r's gradient comes out when row r + 1 is
+// blurred.  No LDS tile and no barrier inside the walk.  A band is 64 lanes x 2 columns; 3 columns on either side are
+// halo (2 for the blur, 1 for Scharr), so with band starts on 4-column boundaries a wave answers for kCBand columns
+// (lanes 2 .. 61).  The last band is aligned to the right edge and answers only for the columns the band before it
+// left.  Lanes left / right of the image hold its first / last column, rows above / below it its first / last row: the
+// reference's edge replication.  The blur is lane4_dot_v and the Scharr and epilogue lines are the tile path's, so every
+// rounded intermediate is the same.  (Four columns per lane need about 150 registers: the two rings and the prefetched
+// rows grow with the columns, and at 96 the compiler spills.)  Requires w % 4 == 0.
+constexpr int kCBand = 120;          // output columns per wave
+constexpr int kCWaves = 4;           // waves per block: bands / segments of ONE frame pair, sharing the fine-key table
+constexpr int kCWavesBatch = 8192;   // waves a batch call is cut into: 8 per SIMD of the 256 CUs
+constexpr int kCSegFew = 16;         // rows per segment of a few-frame call (one 1080p frame: 16 bands x 68 segments)
+
+// px_over_255 / px_over_65535 of two pixels (the same three roundings per pixel, packed)
+template <int D>
+__device__ __forceinline__ v2f px_over_v(v2f v)
 {
-    constexpr int R = 2, SG = 1, TH = kFTH, NT = kFNT;
-    constexpr int CI = kTW + 16, CG = kTW + 8;
-    constexpr int GH = TH + 2 * SG, IH = GH + 2 * R;
-    __shared__ __attribute__((aligned(16))) v2f s_a[IH * CI];
-    __shared__ __attribute__((aligned(16))) v2f s_h[IH * CG];
+    const v2f r = splat(1.0f / (float)D), q0 = v * r;
+    return __builtin_elementwise_fma(__builtin_elementwise_fma(splat(-(float)D), q0, v), r, q0);
+}
+// Two adjacent pixels of a row, raw, and the lane's two columns of both frames from them.  sel: the loaded columns, or
+// (left / right of the image) twice the first / the last of them — a byte selector for the integer inputs.
+template <typename InT> struct CRaw { typedef float2 type; static constexpr uint32_t kId = 0x03020100u, kLeft = 1u, kRight = 2u; };
+template <> struct CRaw<uint8_t> { typedef uint16_t type; static constexpr uint32_t kId = 0x03020100u, kLeft = 0u, kRight = 0x01010101u; };
+template <> struct CRaw<uint16_t> { typedef uint32_t type; static constexpr uint32_t kId = 0x03020100u, kLeft = 0x01000100u, kRight = 0x03020302u; };
+__device__ __forceinline__ void crow_px(uint16_t a, uint16_t b, uint32_t sel, v2f (&p)[2])
+{
+    const uint32_t ua = __builtin_amdgcn_perm(0u, (uint32_t)a, sel), ub = __builtin_amdgcn_perm(0u, (uint32_t)b, sel);
+    p[0] = px_over_v<255>((v2f){(float)(ua & 0xFFu), (float)(ub & 0xFFu)});
+    p[1] = px_over_v<255>((v2f){(float)((ua >> 8) & 0xFFu), (float)((ub >> 8) & 0xFFu)});
+}
+__device__ __forceinline__ void crow_px(uint32_t a, uint32_t b, uint32_t sel, v2f (&p)[2])
+{
+    const uint32_t ua = __builtin_amdgcn_perm(0u, a, sel), ub = __builtin_amdgcn_perm(0u, b, sel);
+    p[0] = px_over_v<65535>((v2f){(float)(ua & 0xFFFFu), (float)(ub & 0xFFFFu)});
+    p[1] = px_over_v<65535>((v2f){(float)(ua >> 16), (float)(ub >> 16)});
+}
+__device__ __forceinline__ void crow_px(float2 a, float2 b, uint32_t sel, v2f (&p)[2])
+{
+    p[0] = (v2f){a.x, b.x};
+    p[1] = (v2f){a.y, b.y};
+    if (sel == CRaw<float>::kLeft) p[1] = p[0];
+    else if (sel == CRaw<float>::kRight) p[0] = p[1];
+}
+
+template <typename InT, int EPI>
+__global__ __launch_bounds__(64 * kCWaves) __attribute__((amdgpu_waves_per_eu(5))) void k_contrast_pair(const InT* __restrict__ in, int w, int h, size_t fs, int n,
+                                                                GaussTaps taps, unsigned long long* __restrict__ cmax,
+                                                                const double* __restrict__ thr, uint32_t* __restrict__ hist,
+                                                                uint32_t* __restrict__ npoints, int nbins,
+                                                                uint32_t* __restrict__ fine, const uint32_t* __restrict__ flag,
+                                                                int nbands, int seg_rows)
+{
+    constexpr int NT = 64 * kCWaves;
+    constexpr int PF = sizeof(InT) <= 2 ? 4 : 2;   // input rows in flight (one register per frame; two for f32)
+    typedef typename CRaw<InT>::type Raw;
     __shared__ uint32_t s_hist[(EPI == EPI_CHIST) ? 2 * 512 : 1];
     __shared__ double s_thr[(EPI == EPI_CHIST) ? 2 * 512 : 1];
-    __shared__ double s_red[(EPI == EPI_CMAX) ? 2 * (NT / 64) : 1];
+    __shared__ double s_red[(EPI == EPI_CMAX) ? 2 * kCWaves : 1];
     __shared__ uint32_t s_fine[(EPI == EPI_CMAX) ? 2 * kFineBins : 1];
-    const uint3 tile = xcd_tile(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z));
-    const int fa = 2 * (int)tile.z;
+    const int tid = threadIdx.x, lane = tid & 63;
+    // wave-uniform, so that the row walk (row numbers, clamps, row addresses, loop control) stays on the scalar unit
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fa = 2 * (int)blockIdx.y;
     const bool has_b = fa + 1 < n;
     const int fb = has_b ? fa + 1 : fa;
-    const int tx0 = (int)tile.x * kTW;
-    const int tid = threadIdx.x, lane = tid & 63;
     // the exact histogram is only needed for the frames k_contrast_resolve could not settle
     if (EPI == EPI_CHIST && flag && !flag[fa] && !flag[fb]) return;
     if (EPI == EPI_CMAX && fine) {
-        for (int i = tid; i < 2 * kFineBins; i += NT) s_fine[i] = 0;   // ordered before use by the tile barriers
+        for (int i = tid; i < 2 * kFineBins; i += NT) s_fine[i] = 0;
     }
     if (EPI == EPI_CHIST) {
         for (int i = tid; i < 2 * 512; i += NT) {
@@ -769,7 +818,6 @@ __global__ __launch_bounds__(kFNT) void k_contrast_pair(const InT* __restrict__ 
             s_thr[i] = kk <= nbins ? thr[(size_t)(f ? fb : fa) * 512 + kk] : 0.0;
         }
     }
-    const float4* g4 = reinterpret_cast<const float4*>(s_a);
     double lmax[2] = {-1.0, -1.0};
     float inv_hmax[2] = {0.0f, 0.0f};
     uint32_t npts[2] = {0u, 0u};
@@ -777,64 +825,110 @@ __global__ __launch_bounds__(kFNT) void k_contrast_pair(const InT* __restrict__ 
         inv_hmax[0] = 1.0f / sqrtf((float)__longlong_as_double((long long)cmax[fa]));
         inv_hmax[1] = 1.0f / sqrtf((float)__longlong_as_double((long long)cmax[fb]));
     }
-    // ctiles vertically adjacent tiles per block: the per-frame maximum / histogram is flushed to HBM once
-    // per block, and with one flush per tile the device-scope atomics on the 300 bins of a frame (1350 blocks
-    // each) took as long as the arithmetic (rocprof: 850 us vs 405 us for the max pass)
-    PairTileRegs<R, SG, TH, NT, InT> regs;
-    if (tx0 >= 8 && tx0 + kTW + 8 <= w) regs.fetch(in, w, h, fs, fa, fb, tx0, (int)tile.y * ctiles * TH);
-    for (int it = 0; it < ctiles; ++it) {
-    const int ty0 = ((int)tile.y * ctiles + it) * TH;
-    if (ty0 >= h) break;
-    if (it) __syncthreads();                     // the previous tile's readers are done with s_a
-    const int ty1 = (it + 1 < ctiles && ty0 + TH < h) ? ty0 + TH : -1;
-    pair_blur_tile<R, SG, TH, NT, InT>(in, w, h, fs, fa, fb, tx0, ty0, ty1, taps, regs, s_a, s_h);   // ends with a barrier
-    for (int idx = tid; idx < TH * (kTW / 4); idx += NT) {
-        const int q = idx / (kTW / 4), c = idx - q * (kTW / 4);
-        const int x0 = tx0 + 4 * c, y = ty0 + q;
-        if (x0 >= w || y < 1 || y > h - 2) continue;   // contrast_factor.rs:27-37: interior pixels only
-        const int r0 = q + SG;
-        v2f m[12], z[12], pz[12];
-        lds_read12<CG, 3, 8>(g4, r0 - 1, c, m);
-        lds_read12<CG, 3, 8>(g4, r0, c, z);
-        lds_read12<CG, 3, 8>(g4, r0 + 1, c, pz);
+    __syncthreads();
+    // the wave's band and segment; it answers for the segment's interior rows [ra, rb) (contrast_factor.rs:27-37)
+    const int item = (int)blockIdx.x * kCWaves + wv;
+    const int band = item % nbands, seg = item / nbands;
+    const int ra = max(seg * seg_rows, 1), rb = min(seg * seg_rows + seg_rows, h - 1);
+    if (ra < rb) {   // (waves past the last segment only take part in the block's barriers)
+        const int ox = band * kCBand;                                // first column the band answers for
+        const int x0 = min(ox, max(w - kCBand, 0)) - 4 + 2 * lane;   // the lane's columns x0, x0 + 1
+        const uint32_t coff = (uint32_t)clampi(x0, 0, w - 2) * (uint32_t)sizeof(InT);
+        const uint32_t sel = x0 < 0 ? CRaw<InT>::kLeft : (x0 >= w ? CRaw<InT>::kRight : CRaw<InT>::kId);
+        const int lo = max(ox, 1), hi = min(ox + kCBand, w - 1);     // columns [lo, hi) of the lane's produce a value
+        const InT* A = in + (size_t)fa * fs;
+        const InT* B = in + (size_t)fb * fs;
+        auto load = [&](const InT* F, int y) {
+            return *reinterpret_cast<const Raw*>(at_bytes(F + (size_t)clampi(y, 0, h - 1) * w, coff));
+        };
+        // H-blurred rows ra - 3 .. rb + 2: at H row yi the blurred row yi - 2 is made and the output row yi - 3 is done
+        const int y_first = ra - 3, y_last = rb + 2;
+        Raw pa[5], pb[5];        // input rows in flight, slot (row - y_first) % 5
+        v2f hr[5][2];            // H-blurred rows, slot (row - y_first) % 5
+        v2f sx[2][2], sy[2][2];  // Scharr partials hx, hy of the blurred rows r - 1 ([0]) and r ([1])
 #pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            // simple Scharr (derivatives.rs:3-11) in the reference's lane order
-            v2f hx_m = m[5 + o] - m[3 + o];
-            v2f hx_0 = z[5 + o] - z[3 + o];
-            v2f hx_p = pz[5 + o] - pz[3 + o];
-            v2f lx = (splat(3.0f) * hx_m + splat(10.0f) * hx_0) + splat(3.0f) * hx_p;
-            v2f hy_m = (splat(3.0f) * m[3 + o] + splat(10.0f) * m[4 + o]) + splat(3.0f) * m[5 + o];
-            v2f hy_p = (splat(3.0f) * pz[3 + o] + splat(10.0f) * pz[4 + o]) + splat(3.0f) * pz[5 + o];
-            v2f ly = hy_p - hy_m;
-            v2f lx2 = lx * lx, ly2 = ly * ly;           // squares in f32, sum in f64
-            const int x = x0 + o;
-            if (x < 1 || x > w - 2) continue;
+        for (int i = 0; i < PF; ++i) {
+            pa[i] = load(A, y_first + i);
+            pb[i] = load(B, y_first + i);
+        }
+        for (int base = y_first; base <= y_last; base += 5) {
 #pragma unroll
-            for (int f = 0; f < 2; ++f) {
-                if (f == 1 && !has_b) continue;
-                const double v = (double)lx2[f] + (double)ly2[f];
-                if (EPI == EPI_CMAX) {
-                    lmax[f] = v > lmax[f] ? v : lmax[f];
-                    if (fine && v != 0.0) {            // modg != 0: counted, and filed by magnitude for the order statistic
-                        atomicAdd(&s_fine[f * kFineBins + fine_key(v)], 1u);
-                        npts[f] += 1u;
+            for (int kk = 0; kk < 5; ++kk) {
+                const int yi = base + kk;
+                if (yi > y_last) break;
+                const Raw ca = pa[kk], cb = pb[kk];
+                pa[(kk + PF) % 5] = load(A, yi + PF);
+                pb[(kk + PF) % 5] = load(B, yi + PF);
+                {
+                    v2f p[2];
+                    crow_px(ca, cb, sel, p);
+                    // columns x0 - 2 .. x0 + 3: the left lane's two, the lane's two, the right lane's two
+                    const v2f win[6] = {dpp_row<0x138>(p[0]), dpp_row<0x138>(p[1]), p[0], p[1],
+                                        dpp_row<0x130>(p[0]), dpp_row<0x130>(p[1])};
+#pragma unroll
+                    for (int o = 0; o < 2; ++o) hr[kk][o] = lane4_dot_v<5>(win + o, taps.k);
+                }
+                if (yi < y_first + 4) continue;                      // the ring is not full yet
+                // blurred row yi - 2 from the H rows yi - 4 .. yi
+                v2f g[2];
+#pragma unroll
+                for (int o = 0; o < 2; ++o) {
+                    v2f col[5];
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) col[i] = hr[(kk + 1 + i) % 5][o];
+                    g[o] = lane4_dot_v<5>(col, taps.k);
+                }
+                // its simple Scharr partials (derivatives.rs:3-11): columns x0 - 1 .. x0 + 2
+                const v2f G[4] = {dpp_row<0x138>(g[1]), g[0], g[1], dpp_row<0x130>(g[0])};
+                v2f hx[2], hy[2];
+#pragma unroll
+                for (int o = 0; o < 2; ++o) {
+                    hx[o] = G[o + 2] - G[o];
+                    hy[o] = (splat(3.0f) * G[o] + splat(10.0f) * G[o + 1]) + splat(3.0f) * G[o + 2];
+                }
+                if (yi - 3 >= ra) {                                  // output row yi - 3 (wave-uniform)
+#pragma unroll
+                    for (int o = 0; o < 2; ++o) {
+                        // simple Scharr in the reference's lane order
+                        const v2f lx = (splat(3.0f) * sx[0][o] + splat(10.0f) * sx[1][o]) + splat(3.0f) * hx[o];
+                        const v2f ly = hy[o] - sy[0][o];
+                        const v2f lx2 = lx * lx, ly2 = ly * ly;      // squares in f32, sum in f64
+                        const int x = x0 + o;
+                        if (x < lo || x >= hi) continue;
+#pragma unroll
+                        for (int f = 0; f < 2; ++f) {
+                            if (f == 1 && !has_b) continue;
+                            const double v = (double)lx2[f] + (double)ly2[f];
+                            if (EPI == EPI_CMAX) {
+                                lmax[f] = fmax(v, lmax[f]);          // v >= +0 and never NaN for a finite image
+                                if (fine && v != 0.0) {             // modg != 0: counted, and filed by magnitude for the order statistic
+                                    atomicAdd(&s_fine[f * kFineBins + fine_key(v)], 1u);
+                                    npts[f] += 1u;
+                                }
+                            } else if (v != 0.0) {                  // modg != 0
+                                const double* T = s_thr + f * 512;
+                                int b = (int)((float)nbins * (sqrtf((float)v) * inv_hmax[f]));
+                                b = b < 0 ? 0 : (b > nbins - 1 ? nbins - 1 : b);
+                                b += (v >= T[b + 1] ? 1 : 0) - (v < T[b] ? 1 : 0);   // the f32 estimate is off by at most one bin
+                                if (v < T[b] || v >= T[b + 1]) {                      // (kept exact regardless)
+                                    while (b > 0 && v < T[b]) --b;
+                                    while (b < nbins - 1 && v >= T[b + 1]) ++b;
+                                }
+                                atomicAdd(&s_hist[f * 512 + b], 1u);
+                                npts[f] += 1u;
+                            }
+                        }
                     }
-                } else if (v != 0.0) {                 // modg != 0
-                    const double* T = s_thr + f * 512;
-                    int b = (int)((float)nbins * (sqrtf((float)v) * inv_hmax[f]));
-                    b = b < 0 ? 0 : (b > nbins - 1 ? nbins - 1 : b);
-                    b += (v >= T[b + 1] ? 1 : 0) - (v < T[b] ? 1 : 0);   // the f32 estimate is off by at most one bin
-                    if (v < T[b] || v >= T[b + 1]) {                      // (kept exact regardless)
-                        while (b > 0 && v < T[b]) --b;
-                        while (b < nbins - 1 && v >= T[b + 1]) ++b;
-                    }
-                    atomicAdd(&s_hist[f * 512 + b], 1u);
-                    npts[f] += 1u;
+                }
+#pragma unroll
+                for (int o = 0; o < 2; ++o) {
+                    sx[0][o] = sx[1][o];
+                    sx[1][o] = hx[o];
+                    sy[0][o] = sy[1][o];
+                    sy[1][o] = hy[o];
                 }
             }
         }
-    }
     }
     if (EPI == EPI_CMAX) {
         // non-negative doubles order like their bit patterns: wave max by shuffles, one atomic per block and frame
@@ -845,14 +939,7 @@ __global__ __launch_bounds__(kFNT) void k_contrast_pair(const InT* __restrict__ 
                 double o = __shfl_down(v, off);
                 v = o > v ? o : v;
             }
-            if ((tid & 63) == 0) s_red[f * (NT / 64) + (tid >> 6)] = v;
-        }
-        __syncthreads();
-        if (tid < 2) {
-            double mx = s_red[tid * (NT / 64)];
-            for (int i = 1; i < NT / 64; ++i) mx = s_red[tid * (NT / 64) + i] > mx ? s_red[tid * (NT / 64) + i] : mx;
-            if (mx >= 0.0 && (tid == 0 || has_b))
-                atomicMax(&cmax[tid ? fb : fa], (unsigned long long)__double_as_longlong(mx));
+            if (lane == 0) s_red[f * kCWaves + wv] = v;
         }
         if (fine) {
 #pragma unroll
@@ -861,6 +948,15 @@ __global__ __launch_bounds__(kFNT) void k_contrast_pair(const InT* __restrict__ 
                 for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
                 if (lane == 0 && v && (f == 0 || has_b)) atomicAdd(&npoints[f ? fb : fa], v);
             }
+        }
+        __syncthreads();
+        if (tid < 2) {
+            double mx = s_red[tid * kCWaves];
+            for (int i = 1; i < kCWaves; ++i) mx = s_red[tid * kCWaves + i] > mx ? s_red[tid * kCWaves + i] : mx;
+            if (mx >= 0.0 && (tid == 0 || has_b))
+                atomicMax(&cmax[tid ? fb : fa], (unsigned long long)__double_as_longlong(mx));
+        }
+        if (fine) {
             for (int i = tid; i < 2 * kFineBins; i += NT) {   // s_fine is complete: the barrier above
                 const int f = i / kFineBins;
                 if (s_fine[i] && (f == 0 || has_b)) atomicAdd(&fine[(size_t)(f ? fb : fa) * kFineBins + (i - f * kFineBins)], s_fine[i]);
@@ -1189,14 +1285,6 @@ constexpr int fed_halo_patches(int T) { return (T + 3) / 4; }
 constexpr int fed_tile_edge(int T) { return 64 - 8 * fed_halo_patches(T); }
 
 __device__ __forceinline__ v2f fed_flow2(v2f ht, v2f ca, v2f cb, v2f a, v2f b) { return (ht * (ca + cb)) * (b - a); }
-
-template <int CTRL>
-__device__ __forceinline__ v2f dpp_row(v2f v)   // value of the lane CTRL selects within the 16-lane row; 0 outside it
-{
-    int x = __builtin_amdgcn_update_dpp(0, __float_as_int(v.x), CTRL, 0xF, 0xF, true);
-    int y = __builtin_amdgcn_update_dpp(0, __float_as_int(v.y), CTRL, 0xF, 0xF, true);
-    return (v2f){__int_as_float(x), __int_as_float(y)};
-}
 
 // The FED steps of a launch on the register-resident patches (shared by k_fed_pair and k_front_fed).  Every flow is
 // evaluated by ONE thread and handed to the other pixel it belongs to: the flow through a patch's right edge goes to the
@@ -3139,11 +3227,15 @@ static int32_t scale_space_impl(akz_ctx* c, const InT* d_imgs, int n)
     akz_timer_begin(c, AKZ_T_CONTRAST, s);
     const bool fine = pairc && c->contrast_fine;
     if (pairc) {
-        const int ctiles = n <= kLatencyFrames ? kCTilesFew : kCTiles;
-        dim3 gridc(akz_div_up(w, kTW), akz_div_up(akz_div_up(h, kFTH), ctiles), (n + 1) / 2);
-        AKZ_LAUNCH((k_contrast_pair<InT, EPI_CMAX>), gridc, dim3(kFNT), 0, s, d_imgs, w, h, P0, n, t1, S.d_cmax,
+        // one wave per (frame pair, band, row segment): a batch is cut into kCWavesBatch waves, a few-frame call into
+        // kCSegFew-row segments so that one frame still fills the chip
+        const int nbands = akz_div_up(w, kCBand), npairs = (n + 1) / 2;
+        const int seg_rows = n <= kLatencyFrames ? kCSegFew
+                                                 : std::max(akz_div_up(h, akz_div_up(kCWavesBatch, npairs * nbands)), kCSegFew);
+        dim3 gridc(akz_div_up(nbands * akz_div_up(h, seg_rows), kCWaves), npairs);
+        AKZ_LAUNCH((k_contrast_pair<InT, EPI_CMAX>), gridc, dim3(64 * kCWaves), 0, s, d_imgs, w, h, P0, n, t1, S.d_cmax,
                            (const double*)S.d_cthr, S.d_hist, S.d_npoints, nbins, fine ? S.d_fine : (uint32_t*)nullptr,
-                           (const uint32_t*)nullptr, ctiles);
+                           (const uint32_t*)nullptr, nbands, seg_rows);
         AKZ_LAUNCH_CHECK();
         AKZ_LAUNCH(k_contrast_thresholds, dim3(n), dim3(512), 0, s, S.d_cmax, nbins, S.d_cthr);
         AKZ_LAUNCH_CHECK();
@@ -3153,9 +3245,9 @@ static int32_t scale_space_impl(akz_ctx* c, const InT* d_imgs, int n)
                                S.d_invk, S.d_cflag, c->contrast_force_odd ? 1 : 0);
             AKZ_LAUNCH_CHECK();
         }
-        AKZ_LAUNCH((k_contrast_pair<InT, EPI_CHIST>), gridc, dim3(kFNT), 0, s, d_imgs, w, h, P0, n, t1, S.d_cmax,
+        AKZ_LAUNCH((k_contrast_pair<InT, EPI_CHIST>), gridc, dim3(64 * kCWaves), 0, s, d_imgs, w, h, P0, n, t1, S.d_cmax,
                            (const double*)S.d_cthr, S.d_hist, S.d_npoints, nbins, (uint32_t*)nullptr,
-                           fine ? (const uint32_t*)S.d_cflag : (const uint32_t*)nullptr, ctiles);
+                           fine ? (const uint32_t*)S.d_cflag : (const uint32_t*)nullptr, nbands, seg_rows);
         AKZ_LAUNCH_CHECK();
     } else {
         AKZ_TRY((launch_blur<2, 1, InT, EPI_CMAX>(c, d_imgs, w, h, P0, t1, nullptr, nullptr, 0, 0, n)));
