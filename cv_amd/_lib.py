@@ -105,6 +105,16 @@ class Camera(C.Structure):
                 ("k1", C.c_double), ("use_k1", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TriangulateParams(C.Structure):
+    """rs_triangulate_params (include/akz.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_sweeps", C.c_uint32), ("eps", C.c_double),
+                ("robust_minimum_observations", C.c_uint32), ("n_views", C.c_uint32),
+                ("incidence_minimum_cosine_distance", C.c_double)]
+
+
+TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
+
+
 class OverflowInfo(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("needed_candidates", C.c_uint32), ("candidate_capacity", C.c_uint32),
                 ("keypoint_capacity", C.c_uint32)]
@@ -124,7 +134,7 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("size", "
 NB_DTYPE = np.dtype([("index", "<u4"), ("distance", "<u4")])
 assert KP_DTYPE.itemsize == 28 and NB_DTYPE.itemsize == 8
 
-ABI_VERSION = 8          # include/akz.h AKZ_ABI_VERSION this file's argtypes were written against
+ABI_VERSION = 9          # include/akz.h AKZ_ABI_VERSION this file's argtypes were written against
 
 # every symbol include/akz.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
@@ -139,6 +149,8 @@ ABI_SYMBOLS = [
     "hm_stream", "rs_create", "rs_destroy", "rs_calibrate", "rs_essential_batch", "rs_essential_arrsac", "rs_p3p_arrsac", "rs_arrsac_samples",
     "rs_p3p_batch", "rs_debug_counts", "rs_debug_poses", "rs_batch_reserve", "rs_essential_arrsac_batch_device", "rs_sync",
     "rs_stream", "rs_debug_scene", "rs_debug_residuals", "rs_p3p_arrsac_batch_device", "hm_landmark_pairs_batch_device", "hm_landmark_matches_batch_device", "hm_landmark_matches_ordered_batch_device", "hm_set_targets", "hm_targets_generation", "hm_knn_targets", "rs_debug_scene_world", "rs_debug_far",
+    "rs_triangulate_params_default", "rs_triangulate_observations", "rs_triangulate_landmarks_device", "rs_triangulate_merged_device",
+    "rs_triangulate_pairs_batch_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -255,6 +267,14 @@ def lib():
     L.rs_debug_scene.argtypes = [vp, u32, C.POINTER(u32), vp, vp, vp, u32]
     L.rs_debug_residuals.argtypes = [vp, vp, u32, vp, vp, u32, i32, vp]
     L.rs_debug_far.argtypes = [vp, vp, u32, vp, vp, u32, C.c_double, vp]
+    tp = C.POINTER(TriangulateParams)
+    L.rs_triangulate_params_default.argtypes = [tp]
+    L.rs_triangulate_observations.argtypes = [vp, vp, vp, u32, tp, vp, vp]
+    L.rs_triangulate_landmarks_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(Camera), vp, vp, u32, u32, tp, vp, vp, vp]
+    L.rs_triangulate_merged_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(Camera), vp, vp, u32, u32, tp, vp, vp, vp, u32, u32,
+                                               vp, vp, vp]
+    L.rs_triangulate_pairs_batch_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, C.POINTER(Camera), C.POINTER(Camera),
+                                                    vp, vp, vp, vp, tp, vp, vp, vp]
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

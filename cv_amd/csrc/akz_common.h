@@ -125,6 +125,17 @@ static inline int32_t akz_guard(F&& f) noexcept
     }
 }
 
+// What rs_triangulate.hip needs of an rs_ctx (defined in rs_ransac.hip): its device, its stream and wait event, and the
+// per-scene frame lists of the batch arena ([2][max_scenes] u32; max_scenes == 0: no arena).
+struct RsHandles {
+    int device;
+    hipStream_t stream;
+    hipEvent_t ev;
+    uint32_t* d_frames;
+    uint32_t max_scenes;
+};
+RsHandles rs_internal_handles(rs_ctx* c);
+
 static inline int akz_div_up(int a, int b) { return (a + b - 1) / b; }
 static inline size_t akz_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 

@@ -1380,6 +1380,9 @@ struct rs_ctx : RsArena {
     uint32_t last_hyp = 0;
 };
 
+// (akz_common.h) what rs_triangulate.hip enqueues with
+RsHandles rs_internal_handles(rs_ctx* c) { return RsHandles{c->device, c->stream, c->ev, c->d_frames, c->max_scenes}; }
+
 static void rs_free_arena(RsArena* c)
 {
     hipFree(c->d_n); hipFree(c->d_a); hipFree(c->d_b); hipFree(c->d_poses); hipFree(c->d_best_pose); hipFree(c->d_order);

@@ -177,6 +177,19 @@ class EssentialConsensus:
             _lib.RS_BATCH_SHUFFLE if shuffle else 0, d_pose, d_best_id, d_inliers, d_n_inliers, d_stats, stream_to_wait),
             "rs_p3p_arrsac_batch_device")
 
+    def triangulate_inliers(self, d_kps_a, d_kps_b, cap_per_img, ia, ib, d_pairs, d_npairs, cam_a, cam_b, d_pose, d_best_id,
+                            d_inliers, d_n_inliers, d_points, d_reason=None, params=None, stream_to_wait=None):
+        """rs_triangulate_pairs_batch_device behind model_inliers_batch_device (same arguments, that call's outputs): the
+        CameraPoint of every inlier (cv-sfm/src/lib.rs:1023-1029, 1332) -> d_points [scenes][cap_per_img][4] f64, d_reason
+        (optional) [scenes][cap_per_img] u8; scenes without a model write nothing.  Enqueues and returns."""
+        from .triangulation import make_params
+        n = len(ia)
+        a = (C.c_uint32 * n)(*ia); b = (C.c_uint32 * n)(*ib)
+        prm = params or make_params()
+        check(_lib.lib().rs_triangulate_pairs_batch_device(
+            self._h, d_kps_a, d_kps_b, cap_per_img, a, b, d_pairs, d_npairs, n, C.byref(cam_a), C.byref(cam_b), d_pose, d_best_id,
+            d_inliers, d_n_inliers, C.byref(prm), d_points, d_reason, stream_to_wait), "rs_triangulate_pairs_batch_device")
+
     def sync(self):
         check(_lib.lib().rs_sync(self._h), "rs_sync")
 

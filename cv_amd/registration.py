@@ -13,9 +13,11 @@ The reference walks this per feature on the CPU; here one call enqueues, for ALL
 hm_hash_bag_device -> hm_knn_batch_device (k = 3, frames x views problems) -> hm_best_of_views_batch_device ->
 hm_landmark_matches_batch_device -> rs_p3p_arrsac_batch_device on the blocks where akz_extract_batch_device left them; nothing
 returns to the host in between.  What stays with the caller is the reference's control plane: which views a frame is matched
-against, which landmark each stored feature observes, the table of triangulated landmarks, and for the merge candidates
-(decision 2) the graph test are_landmarks_sharing_view plus the merged triangulation — handed in as a mask and extra world
-rows between match_views() and consensus().  There is no CPU fallback.
+against, which landmark each stored feature observes (and so which features observe each landmark: a LandmarkTable), and
+for the merge candidates (decision 2) the graph test are_landmarks_sharing_view — handed in as a mask.  The table of
+triangulated landmarks is made on the device from the poses and the observation lists: triangulate() for the rows indexed
+by landmark key, triangulate_merged() between match_views() and consensus() for the rows of the merge candidates
+(cv-sfm/src/lib.rs:1590-1593, 2958-3000); a caller may still bring a table of its own.  There is no CPU fallback.
 """
 import ctypes as C
 
@@ -25,6 +27,7 @@ from . import _lib
 from ._lib import check
 from .knn import Matcher
 from .ransac import EssentialConsensus
+from . import triangulation
 
 
 def _u32(vals):
@@ -57,6 +60,7 @@ class Registration:
                                          max_candidates=max_candidates, halve=True, sprt=True,
                                          estimations_per_block=estimations_per_block)
         self.cam = self.cons.camera(camera)
+        self.tri_prm = triangulation.make_params()       # LinearEigenTriangulator::new(), cv-sfm's robustness defaults
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.dev)
         F, V, k = max_frames, n_views, self.k
         self.hash = z((F, self.n_codewords // 8), torch.uint8)
@@ -126,6 +130,32 @@ class Registration:
         check(L.hm_best_of_views_batch_device(h, self.knn.data_ptr(), d_counts.data_ptr(), fb_p, self.cap, it_p, F, V, self.k,
                                               d_landmarks.data_ptr(), d_counts.data_ptr(), self.better_by, self.best.data_ptr(),
                                               self.decision.data_ptr(), None), "hm_best_of_views_batch_device")
+
+    def triangulate(self, table, d_kps, d_poses, d_world=None, d_reason=None, params=None, stream_to_wait=None):
+        """The world table on the device: row l of d_world = triangulate_landmark_robust(landmark l) (cv-sfm/src/lib.rs:
+        2990-3000) for the landmarks of `table` (a triangulation.LandmarkTable), from the keypoint blocks d_kps [blocks][cap]
+        and their WorldToCamera poses d_poses [blocks][12] f64.  A row without a robust triangulation is {0, 0, 0, -1}.
+        d_world: at least table.n_landmarks rows (default: a new table with room for the merge candidates' rows, all
+        "None"); d_reason (optional) [n_landmarks] uint8.  Enqueued on rs_stream() after stream_to_wait (the stream d_kps /
+        d_poses were written on); returns d_world.  Pass rs_stream() as consensus()'s stream_to_wait."""
+        if d_world is None:
+            d_world = table.new_world(self.F * self.cap)
+        assert d_world.shape[0] >= table.n_landmarks and d_poses.shape[0] == d_kps.shape[0]
+        triangulation.triangulate_landmarks_device(self.cons._h, table, d_kps, self.cap, d_kps.shape[0], d_poses, self.cam,
+                                                   params or self.tri_prm, d_world, d_reason, stream_to_wait)
+        return d_world
+
+    def triangulate_merged(self, table, d_kps, d_poses, d_merge_ok, d_world, n_world, d_reason=None, params=None):
+        """The rows of the merge candidates of the last match_views(): for slot f, feature j with decision 2 and
+        d_merge_ok[f][j] != 0, row n_world + f * cap + j of d_world = triangulate_merged_landmark_robust([best0, best1])
+        (cv-sfm/src/lib.rs:2958-2972).  Reads self.best / decision where match_views() left them: enqueued on rs_stream()
+        behind the matcher's stream, no host step.  d_merge_ok must be complete when this is called (or written on the
+        matcher's stream)."""
+        F = len(self._fb)
+        assert d_world.shape[0] >= n_world + F * self.cap
+        triangulation.triangulate_merged_device(self.cons._h, table, d_kps, self.cap, d_kps.shape[0], d_poses, self.cam,
+                                                params or self.tri_prm, self.best, self.decision, d_merge_ok, F, n_world, d_world,
+                                                d_reason, self.hm_stream())
 
     def consensus(self, d_kps, d_counts, d_world, n_world, shuffle=None, d_merge_ok=None, stream_to_wait=None, d_obs_counts=None):
         """The duplicate-landmark filter, the FeatureWorldMatch lists and single_view_consensus.model_inliers for the frames of

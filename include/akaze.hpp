@@ -547,6 +547,69 @@ private:
 
 }  // namespace arrsac
 
+// cv_geom::triangulation::LinearEigenTriangulator (cv-geom/src/triangulation.rs:39-130) with the two traits it implements
+// (cv-core/src/triangulation.rs:8-67) over rs_triangulate_observations: the points are computed on the device; std::nullopt
+// where the reference returns None.  A point is the reference's Projective form {x, y, z, w}.
+namespace cv_geom {
+class LinearEigenTriangulator {
+public:
+    explicit LinearEigenTriangulator(int device = 0) : device_(device) { rs_triangulate_params_default(&p_); }
+    LinearEigenTriangulator(const LinearEigenTriangulator& o) : p_(o.p_), device_(o.device_) {}
+    LinearEigenTriangulator& operator=(const LinearEigenTriangulator&) = delete;
+    ~LinearEigenTriangulator() { if (ctx_) rs_destroy(ctx_); }
+    LinearEigenTriangulator epsilon(double e) const { LinearEigenTriangulator t(*this); t.p_.eps = e; return t; }
+    LinearEigenTriangulator max_iterations(std::size_t n) const
+    {
+        LinearEigenTriangulator t(*this);
+        t.p_.max_sweeps = n == 0 || n > 0x7FFFFFFFu ? 0x7FFFFFFFu : (uint32_t)n;     // (nalgebra: 0 = no limit)
+        return t;
+    }
+    // TriangulatorObservations::triangulate_observations: (WorldToCamera, bearing) pairs -> WorldPoint
+    std::optional<std::array<double, 4>> triangulate_observations(
+        const std::vector<std::pair<cv_core::WorldToCamera, std::array<double, 3>>>& pairs)
+    {
+        std::vector<double> poses, bearings;
+        for (const auto& pr : pairs) {
+            poses.insert(poses.end(), pr.first.rt.begin(), pr.first.rt.end());
+            bearings.insert(bearings.end(), pr.second.begin(), pr.second.end());
+        }
+        if (!ctx_) {
+            akaze::require_abi();
+            akaze::check(rs_create(device_, 8, 1, &ctx_), "rs_create");
+        }
+        std::array<double, 4> point{};
+        uint8_t why = 0;
+        akaze::check(rs_triangulate_observations(ctx_, poses.data(), bearings.data(), (uint32_t)pairs.size(), &p_, point.data(), &why),
+                     "rs_triangulate_observations");
+        last_reason_ = why;
+        if (why != RS_TRI_OK) return std::nullopt;
+        return point;
+    }
+    // TriangulatorObservations::triangulate_observations_to_camera: the first camera is the world (identity)
+    std::optional<std::array<double, 4>> triangulate_observations_to_camera(
+        const std::array<double, 3>& center_bearing, const std::vector<std::pair<cv_core::CameraToCamera, std::array<double, 3>>>& pairs)
+    {
+        std::vector<std::pair<cv_core::WorldToCamera, std::array<double, 3>>> all;
+        all.push_back({cv_core::WorldToCamera{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}}, center_bearing});
+        for (const auto& pr : pairs) all.push_back({cv_core::WorldToCamera{pr.first.rt}, pr.second});
+        return triangulate_observations(all);
+    }
+    // TriangulatorRelative::triangulate_relative
+    std::optional<std::array<double, 4>> triangulate_relative(const cv_core::CameraToCamera& pose, const std::array<double, 3>& a,
+                                                              const std::array<double, 3>& b)
+    {
+        return triangulate_observations_to_camera(a, {{pose, b}});
+    }
+    uint8_t last_reason() const { return last_reason_; }   // RS_TRI_* of the last call
+
+private:
+    rs_triangulate_params p_;
+    int device_;
+    rs_ctx* ctx_ = nullptr;
+    uint8_t last_reason_ = 0;
+};
+}  // namespace cv_geom
+
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over
 // hm_hash_bag / hm_hash_knn.  The hashing crate is not vendored in the reference: see oracle/lsh_oracle.c for what
 // is restated (nearest-codeword bag hash, one bit per codeword).

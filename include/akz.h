@@ -353,7 +353,8 @@ int32_t hm_best_of_views_batch_device(hm_ctx* ctx, const void* d_knn, const void
  * d_merge_ok [n_frames][cap] u8 (non-zero: the merge may be attempted), NULL when no merge candidate passes — is the match
  * ([best0, best1], feature).  landmark_counts covers every landmark of every original match, both landmarks of a merge
  * included, and a match survives only if each of its landmarks was counted once (:1549-1563).  A survivor whose
- * triangulation is None is dropped (:1583-1604, filter_map): d_world is the caller's table of homogeneous world points,
+ * triangulation is None is dropped (:1583-1604, filter_map): d_world is the table of homogeneous world points
+ * (rs_triangulate_landmarks_device / rs_triangulate_merged_device make it on the device; a caller may bring its own),
  * rows [0, n_world) indexed by landmark key (triangulate_landmark_robust) and — only with a merge mask — rows
  * n_world + f * cap + j = triangulate_merged_landmark_robust of frame f's feature j; a row with w < 0 (impossible for a
  * Projective point) or a landmark key >= n_world says "None".  d_best / d_decision / d_nq / iq as
@@ -570,7 +571,7 @@ int32_t rs_essential_arrsac_batch_device(rs_ctx* ctx, const void* d_kps_a, const
 /* The registration path's consensus for a micro-batch of new frames (cv-sfm/src/lib.rs:1571-1622: FeatureWorldMatch(bearing,
  * point) list -> single_view_consensus.model_inliers(&LambdaTwist, ..)).  Scene s: pair list s of d_pairs ([cap_per_img][2]
  * u32, count d_npairs[s]) whose entries are {feature index into keypoint block ik[s] of d_kps, index into d_world};
- * d_world [n_world][4] f64 homogeneous world points (the caller's triangulated landmarks).  A scene whose pair list names a
+ * d_world [n_world][4] f64 homogeneous world points (the triangulated landmarks: rs_triangulate_landmarks_device).  A scene whose pair list names a
  * feature >= cap_per_img or a world point >= n_world is refused as a whole (no model; nothing is read out of bounds); the
  * two-view entry point above treats a pair that points outside its keypoint blocks the same way.   bearing = calibrate(keypoint); each
  * scene runs rs_p3p_arrsac's procedure with the scene seed as above.  Outputs as above (pose = WorldToCamera [R | t];
@@ -579,6 +580,74 @@ int32_t rs_p3p_arrsac_batch_device(rs_ctx* ctx, const void* d_kps, uint32_t cap_
                                    const void* d_npairs, uint32_t n_scenes, const void* d_world, uint32_t n_world,
                                    const rs_camera* cam, const rs_arrsac_params* params, uint32_t flags, void* d_pose,
                                    void* d_best_id, void* d_inliers, void* d_n_inliers, void* d_stats, void* stream_to_wait);
+
+/* ---- triangulation on the device: the world table of the registration chain, the points of a two-view consensus ----
+ * cv-geom's LinearEigenTriangulator::triangulate_observations (cv-geom/src/triangulation.rs:82-130) — one 4 x 4 symmetric
+ * eigen-problem per point — and around it cv-sfm's triangulate_landmark_robust / triangulate_merged_landmark_robust
+ * (cv-sfm/src/lib.rs:2895-3000).  The arithmetic is include/akz_triangulate_math.h (compiled for the device and, by the
+ * tests, for the host: equal bit for bit); nalgebra's eigen-solver and product order and the order of a landmark's
+ * observations (a HashMap in the reference, the caller's list here) are unpinned.
+ * "None" is written as the row {0, 0, 0, -1} — the w < 0 the registration chain reads as "no robust triangulation" — and,
+ * where a reason array is given, one byte per row says why: */
+enum {
+    RS_TRI_OK = 0, RS_TRI_TOO_FEW = 1 /* fewer than 2 observations */, RS_TRI_NOT_ROBUST = 2, RS_TRI_EIGEN = 3 /* the solver
+    did not converge within max_sweeps */, RS_TRI_NOT_FINITE = 4, RS_TRI_CHEIRALITY = 5 /* behind an observing camera */,
+    RS_TRI_BAD_INDEX = 6 /* an observation or a list names something outside the caller's arrays: nothing is read out of bounds */
+};
+enum { RS_TRI_MAX_SWEEPS = 1024 };   /* sweeps the device runs at the most, whatever max_sweeps says (a 4 x 4 problem needs < 20) */
+typedef struct rs_triangulate_params {
+    uint32_t struct_size;                       /* sizeof(rs_triangulate_params) */
+    uint32_t max_sweeps;                        /* LinearEigenTriangulator::max_iterations (1000), >= 1: sweeps of the cyclic Jacobi
+                                                 * iteration, as the residual path passes to akz_rm_jacobi4_sym; values above
+                                                 * RS_TRI_MAX_SWEEPS count as RS_TRI_MAX_SWEEPS */
+    double eps;                                 /* LinearEigenTriangulator::epsilon, default 1e-12 */
+    uint32_t robust_minimum_observations;       /* cv-sfm/src/settings.rs:344-350: 3 */
+    uint32_t n_views;                           /* views of the reconstruction, for the min() of lib.rs:2913-2917 */
+    double incidence_minimum_cosine_distance;   /* 1e-3 */
+} rs_triangulate_params;
+/* the reference's defaults; n_views = 0xFFFFFFFF (the min() then is robust_minimum_observations) */
+int32_t rs_triangulate_params_default(rs_triangulate_params* params);
+/* triangulate_observations for ONE list: poses [n][12] row-major [R | t] WorldToCamera, bearings [n][3] unit vectors — host
+ * buffers in and out, computed on the device; the robustness test is NOT applied.  point [4], reason (optional) one byte.
+ * A convenience for single lists: every call allocates, copies, launches one lane and waits.  A loop over the inliers of a
+ * consensus belongs on rs_triangulate_pairs_batch_device, a loop over landmarks on rs_triangulate_landmarks_device. */
+int32_t rs_triangulate_observations(rs_ctx* ctx, const double* poses, const double* bearings, uint32_t n,
+                                    const rs_triangulate_params* params, double* point, uint8_t* reason);
+/* The world table: row l of d_world ([>= n_landmarks][4] f64) = triangulate_landmark_robust(landmark l) for every l <
+ * n_landmarks.  Landmark l's observations are entries d_obs_start[l] .. d_obs_start[l + 1] (d_obs_start [n_landmarks + 1]
+ * u32, ascending) of d_obs ([n_obs][2] u32 {block, feature}), in that order; observation {b, j} = the calibrated bearing of
+ * keypoint j of block b of d_kps ([n_blocks][cap_per_img] akz_keypoint, akz_extract_batch_device's output) under the pose
+ * d_poses[b] ([n_blocks][12] f64 WorldToCamera).  A list that names a block >= n_blocks or a feature >= cap_per_img, or
+ * whose range leaves [0, n_obs], gives reason 6 for that landmark.  d_reason (optional) [n_landmarks] u8.  One launch on
+ * rs_stream() after stream_to_wait (may be NULL); returns after enqueueing. */
+int32_t rs_triangulate_landmarks_device(rs_ctx* ctx, const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks,
+                                        const void* d_poses, const rs_camera* cam, const void* d_obs_start, const void* d_obs,
+                                        uint32_t n_obs, uint32_t n_landmarks, const rs_triangulate_params* params, void* d_world,
+                                        void* d_reason, void* stream_to_wait);
+/* The rows of the merge candidates: for frame slot f < n_frames and feature j < cap_per_img with d_decision[f][j] == 2 and
+ * d_merge_ok[f][j] != 0 (d_best [n_frames][cap][3] {landmark, distance} and d_decision [n_frames][cap] as
+ * hm_best_of_views_batch_device leaves them, d_merge_ok [n_frames][cap] u8 the caller's are_landmarks_sharing_view verdicts)
+ * row n_world + f * cap_per_img + j of d_world = triangulate_merged_landmark_robust([best0, best1]): the observations of
+ * landmark d_best[f][j][0] followed by those of d_best[f][j][1], the robustness test on the concatenation
+ * (cv-sfm/src/lib.rs:2958-2972).  No other row is written.  A landmark >= n_landmarks: reason 6.  d_reason (optional)
+ * [n_frames][cap] u8, written where a row is. */
+int32_t rs_triangulate_merged_device(rs_ctx* ctx, const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks, const void* d_poses,
+                                     const rs_camera* cam, const void* d_obs_start, const void* d_obs, uint32_t n_obs,
+                                     uint32_t n_landmarks, const rs_triangulate_params* params, const void* d_best,
+                                     const void* d_decision, const void* d_merge_ok, uint32_t n_frames, uint32_t n_world,
+                                     void* d_world, void* d_reason, void* stream_to_wait);
+/* The CameraPoint of every inlier of a two-view consensus (cv-sfm/src/lib.rs:1023-1029, 1332: triangulate_relative(pose, a,
+ * b) = triangulate_observations on (identity, a), (pose, b)), behind rs_essential_arrsac_batch_device with the same
+ * keypoints, frame lists, pair lists and cameras and that call's outputs: scene s with a model (d_best_id[s] !=
+ * 0xFFFFFFFF), inlier i < d_n_inliers[s]: d_points[s][i] ([n_scenes][cap_per_img][4] f64), d_reason (optional)
+ * [n_scenes][cap_per_img] u8.  No robustness test on this path (the reference has none).  A scene without a model writes
+ * nothing.  n_scenes within rs_batch_reserve's room (AKZ_E_TOO_LARGE beyond it).  ia / ib travel through the context's own
+ * per-scene frame lists, the ones the consensus call filled: hand over the same lists. */
+int32_t rs_triangulate_pairs_batch_device(rs_ctx* ctx, const void* d_kps_a, const void* d_kps_b, uint32_t cap_per_img,
+                                          const uint32_t* ia, const uint32_t* ib, const void* d_pairs, const void* d_npairs,
+                                          uint32_t n_scenes, const rs_camera* cam_a, const rs_camera* cam_b, const void* d_pose,
+                                          const void* d_best_id, const void* d_inliers, const void* d_n_inliers,
+                                          const rs_triangulate_params* params, void* d_points, void* d_reason, void* stream_to_wait);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched
@@ -628,7 +697,7 @@ const char* akz_version(void);
 /* The ABI number: raised whenever a declared signature, struct layout or enum value of this header changes (additions
  * included).  A binding compares akz_abi_version() of the library it loaded with the AKZ_ABI_VERSION it was written against
  * and refuses to run on a mismatch (cv_amd/_lib.py, rust/akaze-mi355x/src/lib.rs, include/akaze.hpp do). */
-#define AKZ_ABI_VERSION 8u
+#define AKZ_ABI_VERSION 9u
 uint32_t akz_abi_version(void);
 
 /* HIP-event timing of the kernel families of a batch (bench.py's roofline objects).  Kernel families (every id but the

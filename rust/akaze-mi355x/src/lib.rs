@@ -9,9 +9,9 @@
 //! consensus and the place-recognition hasher.
 use bitarray::BitArray;
 use cv_core::{
-    nalgebra::{IsometryMatrix3, Matrix3, Point2, Rotation3, Translation3, UnitVector3, Vector3},
+    nalgebra::{Vector4, IsometryMatrix3, Matrix3, Point2, Rotation3, Translation3, UnitVector3, Vector3},
     sample_consensus::{Consensus, Estimator},
-    CameraToCamera, FeatureMatch, FeatureWorldMatch, ImagePoint, Projective, WorldToCamera,
+    CameraToCamera, FeatureMatch, FeatureWorldMatch, ImagePoint, Projective, TriangulatorObservations, WorldPoint, WorldToCamera,
 };
 use ::image::{DynamicImage, ImageResult};
 use std::{cell::{Cell, RefCell}, os::raw::c_void, path::Path, ptr};
@@ -99,6 +99,9 @@ extern "C" {
     fn rs_p3p_arrsac(ctx: *mut c_void, bearings: *const f64, world: *const f64, n: u32, sample_idx: *const u32,
                      params: *const RsArrsacParams, best_pose: *mut f64, best_id: *mut u32, inlier_idx: *mut u32, cap: u32,
                      n_inliers: *mut u32, stats: *mut c_void) -> i32;
+    fn rs_triangulate_params_default(params: *mut RsTriangulateParams) -> i32;
+    fn rs_triangulate_observations(ctx: *mut c_void, poses: *const f64, bearings: *const f64, n: u32,
+                                   params: *const RsTriangulateParams, point: *mut f64, reason: *mut u8) -> i32;
     fn hm_create(device: i32, max_q: u32, max_t: u32, out: *mut *mut c_void) -> i32;
     fn hm_destroy(ctx: *mut c_void) -> i32;
     fn hm_knn2(ctx: *mut c_void, q: *const [u8; 64], nq: u32, t: *const [u8; 64], nt: u32, out: *mut AkzNeighbor) -> i32;
@@ -233,7 +236,7 @@ static ARITH: std::sync::atomic::AtomicU32 = std::sync::atomic::AtomicU32::new(0
 
 /// The thread's matcher context, grown to hold `n` descriptors a side.
 /// include/akz.h AKZ_ABI_VERSION these bindings were written against; the loaded library must export the same number.
-const AKZ_ABI_VERSION: u32 = 8;
+const AKZ_ABI_VERSION: u32 = 9;
 fn require_abi() {
     let got = unsafe { akz_abi_version() };
     assert_eq!(got, AKZ_ABI_VERSION, "libakz exports ABI {got}, akaze-mi355x was written against {AKZ_ABI_VERSION}");
@@ -708,4 +711,86 @@ impl Consensus<lambda_twist::LambdaTwist, FeatureWorldMatch> for Arrsac {
 /// own (cv-pinhole/src/lib.rs:108-117) and stays on the host — it is a handful of flops per keypoint.
 pub fn bearing(v: [f64; 3]) -> UnitVector3<f64> {
     UnitVector3::new_unchecked(Vector3::new(v[0], v[1], v[2]))
+}
+
+/// `rs_triangulate_params` (include/akz.h).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsTriangulateParams {
+    struct_size: u32,
+    max_sweeps: u32,
+    eps: f64,
+    robust_minimum_observations: u32,
+    n_views: u32,
+    incidence_minimum_cosine_distance: f64,
+}
+
+/// `cv_geom::triangulation::LinearEigenTriangulator` (cv-geom/src/triangulation.rs:39-130) computed on the MI355X
+/// (`rs_triangulate_observations`).  `TriangulatorObservations` gives `triangulate_observations_to_camera` and, through
+/// cv-core's blanket impl, `TriangulatorRelative::triangulate_relative` (cv-core/src/triangulation.rs:21-36, 52-67).
+/// The device-resident forms (`rs_triangulate_landmarks_device`, `.._merged_device`, `.._pairs_batch_device`) take device
+/// pointers and belong to the caller that owns those buffers.
+pub struct LinearEigenTriangulator {
+    params: RsTriangulateParams,
+    ctx: Cell<*mut c_void>,
+}
+impl LinearEigenTriangulator {
+    pub fn new() -> Self {
+        let mut params = RsTriangulateParams { struct_size: 0, max_sweeps: 0, eps: 0.0, robust_minimum_observations: 0, n_views: 0,
+                                                incidence_minimum_cosine_distance: 0.0 };
+        unsafe { rs_triangulate_params_default(&mut params) };
+        Self { params, ctx: Cell::new(ptr::null_mut()) }
+    }
+    #[must_use]
+    pub fn epsilon(mut self, epsilon: f64) -> Self {
+        self.params.eps = epsilon;
+        self
+    }
+    #[must_use]
+    pub fn max_iterations(mut self, max_iterations: usize) -> Self {
+        // (nalgebra reads 0 as "no limit")
+        self.params.max_sweeps = if max_iterations == 0 || max_iterations > 0x7FFF_FFFF { 0x7FFF_FFFF } else { max_iterations as u32 };
+        self
+    }
+}
+impl Default for LinearEigenTriangulator {
+    fn default() -> Self {
+        Self::new()
+    }
+}
+impl Drop for LinearEigenTriangulator {
+    fn drop(&mut self) {
+        if !self.ctx.get().is_null() {
+            unsafe { rs_destroy(self.ctx.get()) };
+        }
+    }
+}
+impl TriangulatorObservations for LinearEigenTriangulator {
+    fn triangulate_observations(&self, pairs: impl Iterator<Item = (WorldToCamera, UnitVector3<f64>)> + Clone) -> Option<WorldPoint> {
+        let mut poses = Vec::new();
+        let mut bearings = Vec::new();
+        for (pose, bearing) in pairs {
+            let r = pose.0.rotation.matrix();
+            let t = pose.0.translation.vector;
+            for i in 0..3 {
+                poses.extend_from_slice(&[r[(i, 0)], r[(i, 1)], r[(i, 2)], t[i]]);
+            }
+            bearings.extend_from_slice(&[bearing.x, bearing.y, bearing.z]);
+        }
+        if self.ctx.get().is_null() {
+            require_abi();
+            let mut ctx = ptr::null_mut();
+            assert_eq!(unsafe { rs_create(0, 8, 1, &mut ctx) }, 0, "rs_create");
+            self.ctx.set(ctx);
+        }
+        let mut point = [0.0f64; 4];
+        let mut reason = 0u8;
+        let st = unsafe {
+            rs_triangulate_observations(self.ctx.get(), poses.as_ptr(), bearings.as_ptr(), (bearings.len() / 3) as u32, &self.params,
+                                        point.as_mut_ptr(), &mut reason)
+        };
+        assert_eq!(st, 0, "rs_triangulate_observations");
+        // (the device has already normalised xyz: from_homogeneous_unchecked would do; from_homogeneous is idempotent on it)
+        (reason == 0).then(|| WorldPoint::from_homogeneous(Vector4::new(point[0], point[1], point[2], point[3])))
+    }
 }

@@ -6,6 +6,9 @@ integer factors): disassembles the gfx950 code object inside a built cv_amd/lib/
                     inside the match loop — not flattened into selects — and the loop is unrolled twice (two groups of
                     ds_read_b128 in its body).  Flattened: 3.7 times the kernel's time; not unrolled: +10 to +25 %.
 
+  k_tri_landmarks, k_tri_merged, k_tri_pairs   (rs_triangulate.hip) the design matrix and the 16 eigenvector components of a
+                    lane's 4 x 4 eigen-problem stay in registers: zero scratch bytes, no spilled VGPRs, no LDS.
+
 `python tools/check_isa.py` prints one line per check and exits 1 on a failure (tests/test_abi.py runs it)."""
 import os
 import re
@@ -57,6 +60,38 @@ def check_score_p3p(kernels):
     return ok and n_groups >= 3, detail      # (two matches in the unrolled body + the remainder iteration)
 
 
+def kernel_metadata(obj):
+    """{kernel symbol: {metadata key: int}} from the code object's amdhsa.kernels note (llvm-readelf --notes)."""
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
+        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj, os.path.join(d, "copy.o")])
+        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+        text = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
+    out = {}
+    for block in re.split(r"\n\s*- \.", "\n" + text.split("amdhsa.kernels:", 1)[-1]):
+        name = re.search(r"\.name:\s+(\S+)", "." + block)
+        if name:
+            out[name.group(1)] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", "." + block, re.M)}
+    return out
+
+
+def check_triangulate_registers(meta):
+    good, lines = True, []
+    for kern in ("k_tri_landmarks", "k_tri_merged", "k_tri_pairs"):
+        sym = [k for k in meta if kern in k]
+        if len(sym) != 1:
+            good = False
+            lines.append(f"{kern}: {len(sym)} symbols")
+            continue
+        m = meta[sym[0]]
+        ok = m.get("private_segment_fixed_size", -1) == 0 and m.get("vgpr_spill_count", -1) == 0 and m.get("group_segment_fixed_size", -1) == 0
+        good = good and ok
+        lines.append(f"{kern}: {m.get('private_segment_fixed_size')} scratch bytes, {m.get('vgpr_spill_count')} spilled VGPRs, "
+                     f"{m.get('group_segment_fixed_size')} LDS bytes, {m.get('vgpr_count')} VGPRs")
+    return good, "; ".join(lines)
+
+
 def main():
     obj = os.path.join(ROOT, "cv_amd", "lib", "rs_ransac_hip.o")
     kernels = disassemble(obj)
@@ -65,6 +100,9 @@ def main():
         ok, msg = chk(kernels)
         print(("ok   " if ok else "FAIL ") + msg)
         good = good and ok
+    ok, msg = check_triangulate_registers(kernel_metadata(os.path.join(ROOT, "cv_amd", "lib", "rs_triangulate_hip.o")))
+    print(("ok   " if ok else "FAIL ") + msg)
+    good = good and ok
     return 0 if good else 1
 
 
