@@ -1154,6 +1154,26 @@ int orc_scale_space_u8(orc_ctx* c, const uint8_t* image, int stride)
     return 0;
 }
 
+/* Test probe: find_scale_space_extrema on GIVEN Ldet planes (planes[i]: width x height floats of level i, orc_level's
+ * sizes), so that a test can put exact ties in front of every comparison of the search and of both suppression passes
+ * (tests/test_akaze_statement.py).  The list is left at stage 0; the other stages are emptied. */
+uint32_t orc_extrema_of_planes(orc_ctx* c, const float* const* planes)
+{
+    free_results(c);
+    for (int i = 0; i < c->nlev; ++i) {
+        akz_level_info li;
+        orc_level(c, i, &li);
+        img_free(&c->ev[i].Ldet);
+        c->ev[i].Ldet = img_new(li.width, li.height);
+        memcpy(c->ev[i].Ldet.d, planes[i], sizeof(float) * (size_t)li.width * (size_t)li.height);
+    }
+    kpvec ext = {0, 0, 0};
+    find_scale_space_extrema(c, &ext);
+    c->kp_extrema = ext.v;
+    c->n_extrema = ext.n;
+    return ext.n;
+}
+
 /* ---- accessors ---- */
 const float* orc_level_buffer(const orc_ctx* c, int lvl, int which, int* w, int* h)
 {

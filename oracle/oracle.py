@@ -78,6 +78,8 @@ def lib():
         L.orc_extract_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.orc_extract_u16.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.orc_scale_space_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.orc_extrema_of_planes.restype = C.c_uint32
+        L.orc_extrema_of_planes.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.orc_level_buffer.restype = fp
         L.orc_level_buffer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.orc_contrast.restype = C.c_double
@@ -275,6 +277,16 @@ class Akaze:
     def scale_space(self, img):
         img = np.ascontiguousarray(img, np.uint8)
         lib().orc_scale_space_u8(self._c, img.ctypes.data, self.w)
+
+    def extrema_of_planes(self, planes):
+        """find_scale_space_extrema on given Ldet planes (one float32 [height, width] array per level): the stage-0 list."""
+        planes = [_f32(p) for p in planes]
+        assert len(planes) == self.num_levels
+        for i, p in enumerate(planes):
+            assert p.shape == (self.level(i).height, self.level(i).width), (i, p.shape)
+        ptrs = (C.c_void_p * len(planes))(*[p.ctypes.data for p in planes])
+        lib().orc_extrema_of_planes(self._c, ptrs)
+        return self.keypoints(0)
 
     def keypoints(self, stage):
         p = C.c_void_p()
