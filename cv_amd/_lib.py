@@ -96,6 +96,7 @@ class ArrsacStats(C.Structure):
 
 
 RS_PRUNE_BOUND, RS_PRUNE_SPRT, RS_PRUNE_HALVE = 1, 2, 4
+RS_ESTIMATOR_FIVE_POINT = 8
 RS_BATCH_SHUFFLE = 1
 
 
@@ -134,7 +135,7 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("size", "
 NB_DTYPE = np.dtype([("index", "<u4"), ("distance", "<u4")])
 assert KP_DTYPE.itemsize == 28 and NB_DTYPE.itemsize == 8
 
-ABI_VERSION = 9          # include/akz.h AKZ_ABI_VERSION this file's argtypes were written against
+ABI_VERSION = 10         # include/akz.h AKZ_ABI_VERSION this file's argtypes were written against
 
 # every symbol include/akz.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
@@ -146,7 +147,7 @@ ABI_SYMBOLS = [
     "akz_half_size", "akz_sample_colors_rgb8", "hm_create", "hm_create_ex", "hm_destroy", "hm_knn2", "hm_knn", "hm_knn_views_device", "hm_knn_batch_device", "hm_best_of_views_device", "hm_best_of_views_batch_device", "hm_match",
     "hm_match_batch_device", "hm_sync", "hm_hash_bag", "hm_hash_bag_device", "hm_hash_knn", "hm_timing_enable",
     "hm_timing_get",
-    "hm_stream", "rs_create", "rs_destroy", "rs_calibrate", "rs_essential_batch", "rs_essential_arrsac", "rs_p3p_arrsac", "rs_arrsac_samples",
+    "hm_stream", "rs_create", "rs_destroy", "rs_calibrate", "rs_essential_batch", "rs_five_point_batch", "rs_debug_essentials", "rs_essential_arrsac", "rs_p3p_arrsac", "rs_arrsac_samples",
     "rs_p3p_batch", "rs_debug_counts", "rs_debug_poses", "rs_batch_reserve", "rs_essential_arrsac_batch_device", "rs_sync",
     "rs_stream", "rs_debug_scene", "rs_debug_residuals", "rs_p3p_arrsac_batch_device", "hm_landmark_pairs_batch_device", "hm_landmark_matches_batch_device", "hm_landmark_matches_ordered_batch_device", "hm_set_targets", "hm_targets_generation", "hm_knn_targets", "rs_debug_scene_world", "rs_debug_far",
     "rs_triangulate_params_default", "rs_triangulate_observations", "rs_triangulate_landmarks_device", "rs_triangulate_merged_device",
@@ -248,6 +249,8 @@ def lib():
     L.rs_destroy.argtypes = [vp]
     L.rs_calibrate.argtypes = [vp, i32, C.c_double, vp, u32, vp]
     L.rs_essential_batch.argtypes = [vp, vp, vp, u32, vp, u32, C.c_double, vp, C.POINTER(u32), vp, u32, C.POINTER(u32)]
+    L.rs_five_point_batch.argtypes = L.rs_essential_batch.argtypes
+    L.rs_debug_essentials.argtypes = [vp, vp, vp, u32]
     L.rs_essential_arrsac.argtypes = [vp, vp, vp, u32, vp, C.POINTER(ArrsacParams), vp, C.POINTER(u32), vp, u32, C.POINTER(u32),
                                       C.POINTER(ArrsacStats)]
     L.rs_p3p_arrsac.argtypes = L.rs_essential_arrsac.argtypes

@@ -25,6 +25,7 @@
 #include "akz_common.h"
 #include "../../include/akz_ransac_math.h"
 #include "../../include/akz_p3p_math.h"
+#include "../../include/akz_five_point_math.h"
 
 namespace {
 
@@ -88,57 +89,12 @@ __device__ __forceinline__ bool rs_w2c_inlier(const double* __restrict__ pose, c
     return akz_w2c_residual(pose, a, w) < thresh;
 }
 
-// EightPoint::from_matches + possible_unscaled_poses for one minimal sample, ONE LANE, registers only: the 9 x 9
-// normal matrix (upper triangle) and its 81 eigenvector components never leave the register file (akz_rm_jacobi9_sym;
-// the kernel is compiled for one wave per SIMD, 512 VGPRs).  a / b: the scene's bearings; smp: 8 match indices.
-// Returns validity; poses[4][12] row-major [R | t] in the reference's order (t,R1), (t,R2), (-t,R1), (-t,R2).
-__device__ __forceinline__ bool rs_eight_point_poses(const double* __restrict__ ba, const double* __restrict__ bb,
-                                                     const uint32_t* __restrict__ smp, double* __restrict__ out)
+// EssentialMatrix::possible_unscaled_poses (cv-pinhole/src/essential.rs:114-162, 217-231) for one essential matrix E
+// (row-major), ONE LANE, registers only: the step the eight-point and the five-point hypotheses share.  good: what the
+// caller already knows about E (finite).  Returns validity; out[4][12] row-major [R | t] in the reference's order
+// (t,R1), (t,R2), (-t,R1), (-t,R2).
+__device__ __forceinline__ bool rs_essential_poses(const double* __restrict__ E, bool good, double* __restrict__ out)
 {
-    double M[81], V[81];
-#pragma unroll
-    for (int i = 0; i < 81; ++i) M[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t m = smp[i];
-        const double* a = ba + (size_t)3 * m;
-        const double* b = bb + (size_t)3 * m;
-        const double az = a[2];
-        const double ap[3] = {a[0] / az, a[1] / az, a[2] / az};
-        const double bp[3] = {b[0] / az, b[1] / az, b[2] / az};  // sic: divided by a.z (eight-point/src/lib.rs:16)
-        double A[9];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) A[3 * j + k] = ap[j] * bp[k];
-        // M(r,c) = sum_i A_i[r] A_i[c], i ascending, starting from +0 — entry by entry the oracle's sum
-#pragma unroll
-        for (int r = 0; r < 9; ++r)
-#pragma unroll
-            for (int c = r; c < 9; ++c) M[r * 9 + c] += A[r] * A[c];
-    }
-    akz_rm_jacobi9_sym(M, V, kEpsHyp, kItersHyp);
-    // eigenvector of the smallest eigenvalue (first minimum), selected without a runtime index
-    double bestv = M[0];
-    double ev[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) ev[e] = V[e * 9];
-#pragma unroll
-    for (int i = 1; i < 9; ++i) {
-        const bool take = M[i * 9 + i] < bestv;
-        bestv = take ? M[i * 9 + i] : bestv;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) ev[e] = take ? V[e * 9 + i] : ev[e];
-    }
-    double E[9];
-    bool good = true;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            E[r * 3 + c] = ev[c * 3 + r];  // Matrix3::from_iterator is column-major
-            good = good && finite_d(E[r * 3 + c]);
-        }
     // possible_unscaled_poses: SVD of E through the eigen-decomposition of E^T E
     double M3[9], V3[9];
 #pragma unroll
@@ -244,6 +200,60 @@ __device__ __forceinline__ bool rs_eight_point_poses(const double* __restrict__ 
         }
     }
     return good;
+}
+
+// EightPoint::from_matches + possible_unscaled_poses for one minimal sample, ONE LANE, registers only: the 9 x 9
+// normal matrix (upper triangle) and its 81 eigenvector components never leave the register file (akz_rm_jacobi9_sym;
+// the kernel is compiled for one wave per SIMD, 512 VGPRs).  a / b: the scene's bearings; smp: 8 match indices.
+// Returns validity; poses[4][12] row-major [R | t] in the reference's order (t,R1), (t,R2), (-t,R1), (-t,R2).
+__device__ __forceinline__ bool rs_eight_point_poses(const double* __restrict__ ba, const double* __restrict__ bb,
+                                                     const uint32_t* __restrict__ smp, double* __restrict__ out)
+{
+    double M[81], V[81];
+#pragma unroll
+    for (int i = 0; i < 81; ++i) M[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t m = smp[i];
+        const double* a = ba + (size_t)3 * m;
+        const double* b = bb + (size_t)3 * m;
+        const double az = a[2];
+        const double ap[3] = {a[0] / az, a[1] / az, a[2] / az};
+        const double bp[3] = {b[0] / az, b[1] / az, b[2] / az};  // sic: divided by a.z (eight-point/src/lib.rs:16)
+        double A[9];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) A[3 * j + k] = ap[j] * bp[k];
+        // M(r,c) = sum_i A_i[r] A_i[c], i ascending, starting from +0 — entry by entry the oracle's sum
+#pragma unroll
+        for (int r = 0; r < 9; ++r)
+#pragma unroll
+            for (int c = r; c < 9; ++c) M[r * 9 + c] += A[r] * A[c];
+    }
+    akz_rm_jacobi9_sym(M, V, kEpsHyp, kItersHyp);
+    // eigenvector of the smallest eigenvalue (first minimum), selected without a runtime index
+    double bestv = M[0];
+    double ev[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) ev[e] = V[e * 9];
+#pragma unroll
+    for (int i = 1; i < 9; ++i) {
+        const bool take = M[i * 9 + i] < bestv;
+        bestv = take ? M[i * 9 + i] : bestv;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) ev[e] = take ? V[e * 9 + i] : ev[e];
+    }
+    double E[9];
+    bool good = true;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            E[r * 3 + c] = ev[c * 3 + r];  // Matrix3::from_iterator is column-major
+            good = good && finite_d(E[r * 3 + c]);
+        }
+    return rs_essential_poses(E, good, out);
 }
 
 // CameraToCamera::residual for one (pose, match) — cv-core/src/pose.rs:249-295.
@@ -440,6 +450,9 @@ struct RsB {
     double* best_pose;          // [S][12]
     uint32_t* first;            // [S] first slot a re-sampling round appended
     uint32_t* enable;           // [S] the round drew samples (enough inliers)
+    double* fp_basis;           // [S][4 H] five-point: the 9 x 4 null-space basis of sample h at 36 h (36 (H / 10) <= 4 H)
+    double* fp_E;               // [S][H][9] five-point: the essential matrix of every hypothesis slot (sample h: slots 10 h ..)
+    uint32_t* fp_nsol;          // [S][H] five-point: solutions of sample h (nullspace kernel: 1 = basis valid)
     __device__ __forceinline__ const double* sa(uint32_t s) const { return a + (size_t)s * n_cap * 3; }
     __device__ __forceinline__ const double* sb(uint32_t s) const { return b + (size_t)s * n_cap * 4; }
     __device__ __forceinline__ uint32_t* ssamples(uint32_t s) const { return samples + (size_t)s * H * 8; }
@@ -603,6 +616,96 @@ __global__ __launch_bounds__(64) void k_rsb_hypotheses(RsB B, uint32_t h0, uint3
     // validity per pose; bit 1: the pose's R is orthonormal to 1e-9 (what rs_pair_far's angle argument needs: a product of
     // Jacobi rotations is, but nothing here depends on the SVD's third column having come out that way)
     for (int p = 0; p < 4; ++p) ok[p] = good ? (rs_rotation_checked(P + p * 12) ? 3u : 1u) : 0u;
+}
+
+// ---- the five-point estimator (nister-stewenius; include/akz_five_point_math.h) -----------------------------------
+// A minimal sample of five matches has up to ten essential matrices; sample h owns the hypothesis slots 10 h .. 10 h + 9 of
+// the [hypothesis][4 poses] layout, one per solution in ascending order of the action matrix's eigenvalue, unused slots
+// ok = 0 — so that everything downstream (live list, scoring, prune, append, best-inliers) is the eight-point path's.
+// Three kernels, because the three phases want different shapes:
+//   k_rsb_five_point_nullspace   one lane per sample, registers only (the 9 x 9 Jacobi of the eight-point kernel)
+//   k_rsb_five_point_solve       one lane per sample, its 10 x 20 constraint matrix and the 10 x 10 eigen work in LDS:
+//                                AKZ_FP_WORK doubles per lane, element k of lane l at work[k * 64 + l] (a wave's ds_read_b64
+//                                of one element touches 64 consecutive doubles: conflict-free) — 120 KiB per wave of 64
+//                                samples, one workgroup per CU.  Everything indexed at run time is there; no scratch.
+//   k_rsb_five_point_hypotheses  one lane per SLOT: E -> the four poses (rs_essential_poses), ten times the parallelism
+// h0 / nh count samples in the first two, slots in the third.  gate: see k_rsb_hypotheses.
+__global__ __launch_bounds__(64) void k_rsb_five_point_nullspace(RsB B, uint32_t h0, uint32_t nh, const uint32_t* __restrict__ gate)
+{
+    const uint32_t s = blockIdx.y;
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= nh) return;
+    const uint32_t hh = h0 + i;
+    uint32_t* nsol = B.fp_nsol + (size_t)s * B.H + hh;
+    if (B.n[s] < 5u || (gate && !gate[s])) {
+        *nsol = 0u;
+        return;
+    }
+    const uint32_t* sp = B.ssamples(s) + (size_t)hh * 5;
+    const double* ba = B.sa(s);
+    const double* bb = B.sb(s);
+    double a5[15], b5[15];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const uint32_t m = sp[k];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            a5[3 * k + q] = ba[(size_t)3 * m + q];
+            b5[3 * k + q] = bb[(size_t)3 * m + q];
+        }
+    }
+    double basis[36];
+    const int good = akz_fp_nullspace(a5, b5, AKZ_FP_JACOBI_EPS, AKZ_FP_JACOBI_SWEEPS, basis);
+    if (good) {
+        double* out = B.fp_basis + (size_t)s * B.H * 4 + (size_t)hh * 36;
+#pragma unroll
+        for (int k = 0; k < 36; ++k) out[k] = basis[k];
+    }
+    *nsol = good ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(64) void k_rsb_five_point_solve(RsB B, uint32_t h0, uint32_t nh)
+{
+    __shared__ double work[AKZ_FP_WORK * 64];
+    const uint32_t s = blockIdx.y;
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= nh) return;                     // (no barrier below: a lane's region of `work` is its own)
+    const uint32_t hh = h0 + i;
+    uint32_t* nsol = B.fp_nsol + (size_t)s * B.H + hh;
+    if (*nsol == 0u) return;
+    const double* in = B.fp_basis + (size_t)s * B.H * 4 + (size_t)hh * 36;
+    double basis[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) basis[k] = in[k];
+    double* E = B.fp_E + ((size_t)s * B.H + (size_t)hh * 10) * 9;
+    *nsol = (uint32_t)akz_fp_solve(basis, work + threadIdx.x, 64, E, 1);
+}
+
+__global__ __launch_bounds__(64) void k_rsb_five_point_hypotheses(RsB B, uint32_t slot0, uint32_t nslots)
+{
+    const uint32_t s = blockIdx.y;
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= nslots) return;
+    const uint32_t slot = slot0 + i, smp = slot / 10u, sol = slot - smp * 10u;
+    uint32_t* ok = B.ok + B.p4(s) + (size_t)slot * 4;
+    if (sol >= B.fp_nsol[(size_t)s * B.H + smp]) {
+        for (int p = 0; p < 4; ++p) ok[p] = 0u;
+        return;
+    }
+    const double* in = B.fp_E + ((size_t)s * B.H + slot) * 9;
+    double E[9];
+    bool good = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        E[k] = in[k];
+        good = good && finite_d(E[k]);
+    }
+    double P[48];
+    good = rs_essential_poses(E, good, P);
+    double* out = B.sposes(s) + (size_t)slot * 48;
+#pragma unroll
+    for (int k = 0; k < 48; ++k) out[k] = P[k];
+    for (int p = 0; p < 4; ++p) ok[p] = good ? (rs_rotation_checked(P + p * 12) ? 3u : 1u) : 0u;   // (bits: k_rsb_hypotheses)
 }
 
 // ---- PnP: Lambda Twist hypotheses (row R5), same indexing; bearings in a, world points [n][4] in b ----
@@ -1365,9 +1468,9 @@ __global__ __launch_bounds__(256) void k_rs_debug_far(const double* __restrict__
 struct RsArena {
     uint32_t max_scenes = 0;
     uint32_t* d_n = nullptr;
-    double *d_a = nullptr, *d_b = nullptr, *d_poses = nullptr, *d_best_pose = nullptr;
+    double *d_a = nullptr, *d_b = nullptr, *d_poses = nullptr, *d_best_pose = nullptr, *d_fp_basis = nullptr, *d_fp_E = nullptr;
     uint32_t *d_order = nullptr, *d_samples = nullptr, *d_ok = nullptr, *d_counts = nullptr, *d_alive = nullptr, *d_nalive = nullptr,
-             *d_best = nullptr, *d_inl = nullptr, *d_ninl = nullptr, *d_first = nullptr, *d_enable = nullptr, *d_frames = nullptr;
+             *d_best = nullptr, *d_inl = nullptr, *d_ninl = nullptr, *d_first = nullptr, *d_enable = nullptr, *d_frames = nullptr, *d_fp_nsol = nullptr;
     unsigned long long* d_neval = nullptr;
     rs_arrsac_stats* d_stats = nullptr;
 };
@@ -1378,6 +1481,7 @@ struct rs_ctx : RsArena {
     uint32_t max_matches = 0, max_hyp = 0;
     double* d_logtab = nullptr;                                        // ln(k), k = 0 .. max_matches (host libm values)
     uint32_t last_hyp = 0;
+    uint32_t last_five_samples = 0;                                    // samples of the last single-scene five-point call
 };
 
 // (akz_common.h) what rs_triangulate.hip enqueues with
@@ -1388,7 +1492,7 @@ static void rs_free_arena(RsArena* c)
     hipFree(c->d_n); hipFree(c->d_a); hipFree(c->d_b); hipFree(c->d_poses); hipFree(c->d_best_pose); hipFree(c->d_order);
     hipFree(c->d_samples); hipFree(c->d_ok); hipFree(c->d_counts); hipFree(c->d_alive); hipFree(c->d_nalive); hipFree(c->d_best);
     hipFree(c->d_inl); hipFree(c->d_ninl); hipFree(c->d_first); hipFree(c->d_enable); hipFree(c->d_frames); hipFree(c->d_neval);
-    hipFree(c->d_stats);
+    hipFree(c->d_stats); hipFree(c->d_fp_basis); hipFree(c->d_fp_E); hipFree(c->d_fp_nsol);
     *c = RsArena();
 }
 
@@ -1414,6 +1518,9 @@ static int32_t rs_alloc_arena_into(RsArena* A, size_t n, size_t H, uint32_t S)
     AKZ_HIP(hipMalloc(&A->d_enable, sizeof(uint32_t) * s));
     AKZ_HIP(hipMalloc(&A->d_frames, sizeof(uint32_t) * 2 * s));
     AKZ_HIP(hipMalloc(&A->d_stats, sizeof(rs_arrsac_stats) * s));
+    AKZ_HIP(hipMalloc(&A->d_fp_basis, sizeof(double) * 4 * H * s));
+    AKZ_HIP(hipMalloc(&A->d_fp_E, sizeof(double) * 9 * H * s));
+    AKZ_HIP(hipMalloc(&A->d_fp_nsol, sizeof(uint32_t) * H * s));
     A->max_scenes = S;
     return AKZ_OK;
 }
@@ -1458,6 +1565,9 @@ static RsB rs_view(const rs_ctx* c, bool with_order)
     B.best_pose = c->d_best_pose;
     B.first = c->d_first;
     B.enable = c->d_enable;
+    B.fp_basis = c->d_fp_basis;
+    B.fp_E = c->d_fp_E;
+    B.fp_nsol = c->d_fp_nsol;
     return B;
 }
 
@@ -1591,30 +1701,55 @@ static int32_t rs_fetch_single(rs_ctx* c, double* best_pose, uint32_t* best_id, 
     return ninl > cap ? AKZ_E_CAPACITY : AKZ_OK;
 }
 
-// exhaustive scoring of caller-provided minimal samples, one scene (slot 0 of the arena)
+// five-point hypotheses of the samples [h0, h0 + nh) of S scenes -> the slots [10 h0, 10 (h0 + nh))
+static int32_t rs_five_point_launch(hipStream_t s, const RsB& B, uint32_t S, uint32_t h0, uint32_t nh, const uint32_t* gate)
+{
+    hipLaunchKernelGGL(k_rsb_five_point_nullspace, dim3((nh + 63) / 64, S), dim3(64), 0, s, B, h0, nh, gate);
+    AKZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_rsb_five_point_solve, dim3((nh + 63) / 64, S), dim3(64), 0, s, B, h0, nh);
+    AKZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_rsb_five_point_hypotheses, dim3((10 * nh + 63) / 64, S), dim3(64), 0, s, B, 10 * h0, 10 * nh);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+// exhaustive scoring of caller-provided minimal samples, one scene (slot 0 of the arena).  five (two-view only): the
+// samples are five-point ones, n_smp of them, ten hypothesis slots each.
 template <bool P3P>
 static int32_t exhaustive_run(rs_ctx* c, const double* in_a, const double* in_b, uint32_t n, const uint32_t* sample_idx,
-                              uint32_t n_hyp, double thresh, double* best_pose, uint32_t* best_id, uint32_t* inlier_idx,
-                              uint32_t cap, uint32_t* n_inliers)
+                              uint32_t n_smp, double thresh, double* best_pose, uint32_t* best_id, uint32_t* inlier_idx,
+                              uint32_t cap, uint32_t* n_inliers, bool five = false)
 {
-    constexpr uint32_t K = P3P ? 3u : 8u, BW = P3P ? 4u : 3u;
+    const uint32_t K = P3P ? 3u : (five ? 5u : 8u);
+    constexpr uint32_t BW = P3P ? 4u : 3u;
     if (!c || !in_a || !in_b || !sample_idx || !best_pose || !best_id || !n_inliers || (cap && !inlier_idx)) return AKZ_E_INVALID;
     RS_NEED_ARENA(c);
+    if (five) {
+        if (n_smp == 0 || (uint64_t)n_smp * 10u > c->max_hyp) return AKZ_E_INVALID;   // ten slots per sample
+        if (n < K) {                                                                    // MIN_SAMPLES (nister-stewenius/src/lib.rs:308): no model
+            *best_id = 0xFFFFFFFFu;
+            *n_inliers = 0;
+            return AKZ_OK;
+        }
+    }
+    const uint32_t n_hyp = five ? n_smp * 10u : n_smp;
     if (n < K || n_hyp == 0) return AKZ_E_INVALID;  // MIN_SAMPLES (eight-point/src/lib.rs:73, lambda-twist/src/lib.rs:333)
     if (n > c->max_matches || n_hyp > c->max_hyp) return AKZ_E_TOO_LARGE;
-    for (size_t i = 0; i < (size_t)n_hyp * K; ++i)
+    for (size_t i = 0; i < (size_t)n_smp * K; ++i)
         if (sample_idx[i] >= n) return AKZ_E_INVALID;
     AKZ_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     AKZ_HIP(hipMemcpyAsync(c->d_a, in_a, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s));
     AKZ_HIP(hipMemcpyAsync(c->d_b, in_b, sizeof(double) * BW * (size_t)n, hipMemcpyHostToDevice, s));
-    AKZ_HIP(hipMemcpyAsync(c->d_samples, sample_idx, sizeof(uint32_t) * K * (size_t)n_hyp, hipMemcpyHostToDevice, s));
+    AKZ_HIP(hipMemcpyAsync(c->d_samples, sample_idx, sizeof(uint32_t) * K * (size_t)n_smp, hipMemcpyHostToDevice, s));
     AKZ_HIP(hipMemsetD32Async((hipDeviceptr_t)c->d_n, (int)n, 1, s));
     AKZ_HIP(hipMemsetAsync(c->d_counts, 0, sizeof(uint32_t) * 4 * (size_t)n_hyp, s));
     AKZ_HIP(hipMemsetAsync(c->d_neval, 0, sizeof(unsigned long long), s));
     const RsB B = rs_view(c, false);
     if (P3P)
         hipLaunchKernelGGL(k_rsb_p3p_hypotheses, dim3((n_hyp + 63) / 64, 1), dim3(64), 0, s, B, 0u, n_hyp, (const uint32_t*)nullptr);
+    else if (five)
+        AKZ_TRY(rs_five_point_launch(s, B, 1, 0u, n_smp, nullptr));
     else
         hipLaunchKernelGGL(k_rsb_hypotheses, dim3((n_hyp + 63) / 64, 1), dim3(64), 0, s, B, 0u, n_hyp, (const uint32_t*)nullptr);
     AKZ_LAUNCH_CHECK();
@@ -1643,6 +1778,7 @@ static int32_t exhaustive_run(rs_ctx* c, const double* in_a, const double* in_b,
                        c->d_inl, n, c->d_ninl, c->d_best_pose);
     AKZ_LAUNCH_CHECK();
     c->last_hyp = n_hyp;
+    c->last_five_samples = five ? n_smp : 0u;
     return rs_fetch_single(c, best_pose, best_id, inlier_idx, cap, n_inliers, nullptr, nullptr);
 }
 
@@ -1653,6 +1789,18 @@ extern "C" int32_t rs_essential_batch(rs_ctx* c, const double* bearings_a, const
     return akz_guard([&]() -> int32_t {
         return exhaustive_run<false>(c, bearings_a, bearings_b, n, sample_idx, n_hyp, thresh, best_pose, best_id, inlier_idx, cap,
                                      n_inliers);
+    });
+}
+
+// Consensus::model_inliers(&NisterStewenius::new(), matches) with the sampler factored out: n_samples minimal samples of
+// five matches, up to ten essential matrices each; best_id = (10 sample + solution) 4 + pose
+extern "C" int32_t rs_five_point_batch(rs_ctx* c, const double* bearings_a, const double* bearings_b, uint32_t n,
+                                       const uint32_t* sample_idx, uint32_t n_samples, double thresh, double* best_pose,
+                                       uint32_t* best_id, uint32_t* inlier_idx, uint32_t cap, uint32_t* n_inliers)
+{
+    return akz_guard([&]() -> int32_t {
+        return exhaustive_run<false>(c, bearings_a, bearings_b, n, sample_idx, n_samples, thresh, best_pose, best_id, inlier_idx, cap,
+                                     n_inliers, true);
     });
 }
 
@@ -1667,15 +1815,19 @@ extern "C" int32_t rs_p3p_batch(rs_ctx* c, const double* bearings, const double*
     });
 }
 
-static int32_t rs_check_params(const rs_ctx* c, const rs_arrsac_params* prm, uint32_t n_max, uint32_t* blocks_max)
+// two_view: the entry point has a choice of estimator (RS_ESTIMATOR_FIVE_POINT is refused by the P3P ones)
+static int32_t rs_check_params(const rs_ctx* c, const rs_arrsac_params* prm, uint32_t n_max, uint32_t* blocks_max, bool two_view)
 {
     if (prm->struct_size != sizeof(rs_arrsac_params)) return AKZ_E_INVALID;
     if (prm->n_hypotheses == 0 || prm->block_size == 0) return AKZ_E_INVALID;
-    if (prm->reserved != 0 || (prm->flags & ~(RS_PRUNE_BOUND | RS_PRUNE_SPRT | RS_PRUNE_HALVE))) return AKZ_E_INVALID;
-    // every block but the last may add E hypotheses: they need room in the context's pose arrays
+    const uint32_t known = RS_PRUNE_BOUND | RS_PRUNE_SPRT | RS_PRUNE_HALVE | (two_view ? (uint32_t)RS_ESTIMATOR_FIVE_POINT : 0u);
+    if (prm->reserved != 0 || (prm->flags & ~known)) return AKZ_E_INVALID;
+    // every block but the last may add E hypotheses: they need room in the context's pose arrays (a five-point sample
+    // takes ten slots: n_hypotheses and estimations_per_block count samples)
+    const uint64_t per = (prm->flags & RS_ESTIMATOR_FIVE_POINT) ? 10u : 1u;
     const uint64_t n_blocks_max = ((uint64_t)n_max + prm->block_size - 1) / prm->block_size;
-    if (n_max > c->max_matches || prm->n_hypotheses > c->max_hyp ||
-        (uint64_t)prm->n_hypotheses + (uint64_t)prm->estimations_per_block * n_blocks_max > c->max_hyp)
+    if (n_max > c->max_matches || per * prm->n_hypotheses > c->max_hyp ||
+        per * ((uint64_t)prm->n_hypotheses + (uint64_t)prm->estimations_per_block * n_blocks_max) > c->max_hyp)
         return AKZ_E_TOO_LARGE;
     if ((prm->flags & RS_PRUNE_SPRT) && !(prm->sprt_delta > 0.0 && prm->sprt_delta < 1.0 && prm->sprt_ratio > 1.0))
         return AKZ_E_INVALID;
@@ -1690,12 +1842,19 @@ template <bool P3P>
 static int32_t arrsac_engine(rs_ctx* c, uint32_t S, uint32_t n_max, const rs_arrsac_params* prm, bool have_samples, bool with_order,
                              const RsOut& out_in, uint32_t* blocks_run, uint32_t* hyp_made)
 {
-    constexpr uint32_t K = P3P ? 3u : 8u;
+    // five-point (two-view only): n_hypotheses and estimations_per_block count SAMPLES, ten hypothesis slots each; from the
+    // hypothesis kernels on, the loop below sees slots and nothing else changes
+    const bool five = !P3P && (prm->flags & RS_ESTIMATOR_FIVE_POINT) != 0;
+    const uint32_t K = P3P ? 3u : (five ? 5u : 8u), per = five ? 10u : 1u;
     hipStream_t s = c->stream;
     const RsB B = rs_view(c, with_order);
-    const uint32_t n_hyp = prm->n_hypotheses, E = prm->estimations_per_block;
+    const uint32_t n_smp = prm->n_hypotheses, E_smp = prm->estimations_per_block;
+    const uint32_t n_hyp = n_smp * per, E = E_smp * per;
     if (!have_samples) {
-        hipLaunchKernelGGL((k_rsb_sample<(int)K>), dim3((n_hyp + 255) / 256, S), dim3(256), 0, s, B, (unsigned long long)prm->seed, n_hyp);
+        if (five)
+            hipLaunchKernelGGL((k_rsb_sample<5>), dim3((n_smp + 255) / 256, S), dim3(256), 0, s, B, (unsigned long long)prm->seed, n_smp);
+        else
+            hipLaunchKernelGGL((k_rsb_sample<(P3P ? 3 : 8)>), dim3((n_smp + 255) / 256, S), dim3(256), 0, s, B, (unsigned long long)prm->seed, n_smp);
         AKZ_LAUNCH_CHECK();
     }
     // counters of the initial poses (re-sampled poses zero theirs when they join); slot stride 4 H
@@ -1704,6 +1863,8 @@ static int32_t arrsac_engine(rs_ctx* c, uint32_t S, uint32_t n_max, const rs_arr
     AKZ_HIP(hipMemsetAsync(c->d_neval, 0, sizeof(unsigned long long) * S, s));
     if (P3P)
         hipLaunchKernelGGL(k_rsb_p3p_hypotheses, dim3((n_hyp + 63) / 64, S), dim3(64), 0, s, B, 0u, n_hyp, (const uint32_t*)nullptr);
+    else if (five)
+        AKZ_TRY(rs_five_point_launch(s, B, S, 0u, n_smp, nullptr));
     else
         hipLaunchKernelGGL(k_rsb_hypotheses, dim3((n_hyp + 63) / 64, S), dim3(64), 0, s, B, 0u, n_hyp, (const uint32_t*)nullptr);
     AKZ_LAUNCH_CHECK();
@@ -1777,11 +1938,17 @@ static int32_t arrsac_engine(rs_ctx* c, uint32_t S, uint32_t n_max, const rs_arr
                 // samples among them, estimate, and let the valid poses join the live list after catching up on [0, seen)
                 hipLaunchKernelGGL((k_rsb_best_inliers<P3P>), dim3(S), dim3(kChainNT), 0, s, B, m_lo, 0u, prm->threshold, out_in);
                 AKZ_LAUNCH_CHECK();
-                hipLaunchKernelGGL((k_rsb_resample<(int)K>), dim3((E + 255) / 256, S), dim3(256), 0, s, B, (unsigned long long)prm->seed,
-                                   next_h, E);
+                if (five)
+                    hipLaunchKernelGGL((k_rsb_resample<5>), dim3((E_smp + 255) / 256, S), dim3(256), 0, s, B, (unsigned long long)prm->seed,
+                                       next_h / 10u, E_smp);
+                else
+                    hipLaunchKernelGGL((k_rsb_resample<(P3P ? 3 : 8)>), dim3((E + 255) / 256, S), dim3(256), 0, s, B,
+                                       (unsigned long long)prm->seed, next_h, E);
                 AKZ_LAUNCH_CHECK();
                 if (P3P)
                     hipLaunchKernelGGL(k_rsb_p3p_hypotheses, dim3((E + 63) / 64, S), dim3(64), 0, s, B, next_h, E, (const uint32_t*)c->d_enable);
+                else if (five)
+                    AKZ_TRY(rs_five_point_launch(s, B, S, next_h / 10u, E_smp, (const uint32_t*)c->d_enable));
                 else
                     hipLaunchKernelGGL(k_rsb_hypotheses, dim3((E + 63) / 64, S), dim3(64), 0, s, B, next_h, E, (const uint32_t*)c->d_enable);
                 AKZ_LAUNCH_CHECK();
@@ -1814,12 +1981,14 @@ static int32_t arrsac_run(rs_ctx* c, const double* in_a, const double* in_b, uin
                           const rs_arrsac_params* prm, double* best_pose, uint32_t* best_id, uint32_t* inlier_idx,
                           uint32_t cap, uint32_t* n_inliers, rs_arrsac_stats* stats)
 {
-    constexpr uint32_t K = P3P ? 3u : 8u, BW = P3P ? 4u : 3u;   // sample size; doubles per element of the second input
+    constexpr uint32_t BW = P3P ? 4u : 3u;                      // doubles per element of the second input
     if (!c || !in_a || !in_b || !prm || !best_pose || !best_id || !n_inliers || (cap && !inlier_idx)) return AKZ_E_INVALID;
     RS_NEED_ARENA(c);
-    if (n < K) return AKZ_E_INVALID;   // MIN_SAMPLES (eight-point/src/lib.rs:73, lambda-twist/src/lib.rs:333)
+    const bool five = !P3P && (prm->flags & RS_ESTIMATOR_FIVE_POINT) != 0;
+    const uint32_t K = P3P ? 3u : (five ? 5u : 8u);             // sample size
+    if (n < K) return AKZ_E_INVALID;   // MIN_SAMPLES (eight-point/src/lib.rs:73, lambda-twist/src/lib.rs:333, nister-stewenius/src/lib.rs:308)
     uint32_t blocks_max = 0;
-    AKZ_TRY(rs_check_params(c, prm, n, &blocks_max));
+    AKZ_TRY(rs_check_params(c, prm, n, &blocks_max, !P3P));
     if (sample_idx)
         for (size_t i = 0; i < (size_t)prm->n_hypotheses * K; ++i)
             if (sample_idx[i] >= n) return AKZ_E_INVALID;
@@ -1844,6 +2013,7 @@ static int32_t arrsac_run(rs_ctx* c, const double* in_a, const double* in_b, uin
     unsigned long long neval = 0;
     const int32_t st = rs_fetch_single(c, best_pose, best_id, inlier_idx, cap, n_inliers, &survivors, &neval);
     c->last_hyp = made;
+    c->last_five_samples = five ? made / 10u : 0u;
     if (stats) {
         stats->poses = made * 4;
         stats->survivors = survivors;
@@ -1896,10 +2066,10 @@ extern "C" int32_t rs_essential_arrsac_batch_device(rs_ctx* c, const void* d_kps
         RS_NEED_ARENA(c);
         if (n_scenes > c->max_scenes) return AKZ_E_TOO_LARGE;
         const uint32_t n_max = cap_per_img < c->max_matches ? cap_per_img : c->max_matches;
-        if (n_max < 8) return AKZ_E_INVALID;
+        if (n_max < ((prm->flags & RS_ESTIMATOR_FIVE_POINT) ? 5u : 8u)) return AKZ_E_INVALID;
         if ((flags & RS_BATCH_SHUFFLE) && n_max > kRadixSortMax) return AKZ_E_TOO_LARGE;   // the shuffle sorts a scene's keys in LDS
         uint32_t blocks_max = 0;
-        AKZ_TRY(rs_check_params(c, prm, n_max, &blocks_max));
+        AKZ_TRY(rs_check_params(c, prm, n_max, &blocks_max, true));
         AKZ_HIP(hipSetDevice(c->device));
         hipStream_t s = c->stream;
         if (stream_to_wait) {
@@ -1936,6 +2106,7 @@ extern "C" int32_t rs_essential_arrsac_batch_device(rs_ctx* c, const void* d_kps
         uint32_t blocks = 0, made = 0;
         AKZ_TRY((arrsac_engine<false>(c, n_scenes, n_max, prm, false, shuffle, O, &blocks, &made)));
         c->last_hyp = made;
+        c->last_five_samples = 0;
         return AKZ_OK;
     });
 }
@@ -1961,7 +2132,7 @@ extern "C" int32_t rs_p3p_arrsac_batch_device(rs_ctx* c, const void* d_kps, uint
         if (n_max < 3) return AKZ_E_INVALID;
         if ((flags & RS_BATCH_SHUFFLE) && n_max > kRadixSortMax) return AKZ_E_TOO_LARGE;
         uint32_t blocks_max = 0;
-        AKZ_TRY(rs_check_params(c, prm, n_max, &blocks_max));
+        AKZ_TRY(rs_check_params(c, prm, n_max, &blocks_max, false));
         AKZ_HIP(hipSetDevice(c->device));
         hipStream_t s = c->stream;
         if (stream_to_wait) {
@@ -2038,9 +2209,10 @@ extern "C" int32_t rs_debug_scene_world(rs_ctx* c, uint32_t scene, uint32_t* n, 
 extern "C" int32_t rs_arrsac_samples(uint64_t seed, uint32_t n, uint32_t n_hyp, uint32_t sample_size, uint32_t* sample_idx)
 {
     return akz_guard([&]() -> int32_t {
-        if (!sample_idx || (sample_size != 8 && sample_size != 3) || n < sample_size) return AKZ_E_INVALID;
+        if (!sample_idx || (sample_size != 8 && sample_size != 3 && sample_size != 5) || n < sample_size) return AKZ_E_INVALID;
         for (uint32_t h = 0; h < n_hyp; ++h) {
             if (sample_size == 8) rs_draw_sample<8>((unsigned long long)seed, h, n, sample_idx + (size_t)h * 8);
+            else if (sample_size == 5) rs_draw_sample<5>((unsigned long long)seed, h, n, sample_idx + (size_t)h * 5);
             else rs_draw_sample<3>((unsigned long long)seed, h, n, sample_idx + (size_t)h * 3);
         }
         return AKZ_OK;
@@ -2056,6 +2228,24 @@ extern "C" int32_t rs_debug_counts(rs_ctx* c, uint32_t* counts, uint32_t cap)
         if (cap < c->last_hyp * 4) return AKZ_E_CAPACITY;
         AKZ_HIP(hipSetDevice(c->device));
         AKZ_HIP(hipMemcpy(counts, c->d_counts, sizeof(uint32_t) * 4 * (size_t)c->last_hyp, hipMemcpyDeviceToHost));
+        return AKZ_OK;
+    });
+}
+
+// parity tap: the essential matrices [n_samples][10][9] (row-major, b^T E a = 0; unused slots zero-filled) and the solution
+// counts [n_samples] of the last single-scene five-point call
+extern "C" int32_t rs_debug_essentials(rs_ctx* c, double* E, uint32_t* n_solutions, uint32_t n_samples)
+{
+    return akz_guard([&]() -> int32_t {
+        if (!c || !E || !n_solutions) return AKZ_E_INVALID;
+        RS_NEED_ARENA(c);
+        if (n_samples > c->last_five_samples) return AKZ_E_INVALID;
+        AKZ_HIP(hipSetDevice(c->device));
+        AKZ_HIP(hipStreamSynchronize(c->stream));
+        AKZ_HIP(hipMemcpy(E, c->d_fp_E, sizeof(double) * 90 * (size_t)n_samples, hipMemcpyDeviceToHost));
+        AKZ_HIP(hipMemcpy(n_solutions, c->d_fp_nsol, sizeof(uint32_t) * (size_t)n_samples, hipMemcpyDeviceToHost));
+        for (uint32_t h = 0; h < n_samples; ++h)
+            for (uint32_t k = 9u * (n_solutions[h] < 10u ? n_solutions[h] : 10u); k < 90u; ++k) E[(size_t)90 * h + k] = 0.0;
         return AKZ_OK;
     });
 }

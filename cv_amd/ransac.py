@@ -33,6 +33,13 @@ class CameraIntrinsics:
         return out
 
 
+def _estimator_flag(estimator):
+    """"eight_point" (EightPoint) -> 0, "five_point" (NisterStewenius) -> RS_ESTIMATOR_FIVE_POINT"""
+    if estimator not in ("eight_point", "five_point"):
+        raise ValueError(f"estimator must be 'eight_point' or 'five_point', not {estimator!r}")
+    return _lib.RS_ESTIMATOR_FIVE_POINT if estimator == "five_point" else 0
+
+
 class EssentialConsensus:
     """Owns one rs_ctx.  model_inliers() is the batched Consensus::model_inliers for EightPoint."""
 
@@ -66,28 +73,56 @@ class EssentialConsensus:
             return None
         return pose, inl[:ninl.value].copy(), best.value
 
+    def five_point_model_inliers(self, bearings_a, bearings_b, sample_idx, threshold):
+        """Consensus::model_inliers(&NisterStewenius::new(), ...) with the sampler factored out (rs_five_point_batch):
+        sample_idx [n_samples, 5]; the context needs 10 x n_samples hypothesis slots.  Returns (pose [3,4], inlier indices,
+        best_id = (10 sample + solution) 4 + pose) or None when no sample gave a model."""
+        a = np.ascontiguousarray(bearings_a, np.float64); b = np.ascontiguousarray(bearings_b, np.float64)
+        si = np.ascontiguousarray(sample_idx, np.uint32).reshape(-1, 5)
+        n = len(a)
+        pose = np.empty((3, 4), np.float64); best = C.c_uint32(); ninl = C.c_uint32()
+        inl = np.empty(max(n, 1), np.uint32)
+        check(_lib.lib().rs_five_point_batch(self._h, a.ctypes.data, b.ctypes.data, n, si.ctypes.data, len(si),
+                                             float(threshold), pose.ctypes.data, C.byref(best), inl.ctypes.data, n,
+                                             C.byref(ninl)), "rs_five_point_batch")
+        if best.value == 0xFFFFFFFF:
+            return None
+        return pose, inl[:ninl.value].copy(), best.value
+
+    def essentials(self, n_samples):
+        """(E [n_samples, 10, 3, 3] with b^T E a = 0, unused slots zero; n_solutions [n_samples]) of the last single-scene
+        five-point call (rs_debug_essentials)."""
+        E = np.zeros((n_samples, 10, 3, 3), np.float64); n = np.zeros(n_samples, np.uint32)
+        check(_lib.lib().rs_debug_essentials(self._h, E.ctypes.data, n.ctypes.data, n_samples), "rs_debug_essentials")
+        return E, n
+
     def arrsac_model_inliers(self, bearings_a, bearings_b, threshold, n_hypotheses=8192, seed=0, sample_idx=None,
                              block_size=64, init_blocks=4, max_candidates=1024, bound=True, sprt=True, sprt_delta=0.05,
-                             sprt_ratio=1e3, p3p=False, estimations_per_block=0, halve=False):
+                             sprt_ratio=1e3, p3p=False, estimations_per_block=0, halve=False, estimator="eight_point"):
         """Arrsac::new(threshold, Xoshiro256PlusPlus::seed_from_u64(seed)).initialization_hypotheses(n)
         .max_candidate_hypotheses(k).model_inliers(&EightPoint::new(), matches) in this library's shape (include/akz.h:
         rs_essential_arrsac).  p3p=True: the same for LambdaTwist (bearings_a = bearings [n,3], bearings_b = world
         points [n,4]; 3-match samples; rs_p3p_arrsac).  estimations_per_block: hypotheses re-sampled from the best
         pose's inliers after every block (.estimations_per_block(e)); halve: the candidate cap halves block by block.
         The context needs room for n_hypotheses + estimations_per_block x ceil(n / block_size) hypotheses.
+        estimator="five_point": NisterStewenius instead of EightPoint (RS_ESTIMATOR_FIVE_POINT): n_hypotheses and
+        estimations_per_block count 5-match samples, ten hypothesis slots each; sample_idx is [n, 5].
         Returns (pose, inliers, best_id, stats dict) or None."""
+        five = _estimator_flag(estimator)
+        if five and p3p:
+            raise ValueError("estimator applies to the two-view consensus")
         a = np.ascontiguousarray(bearings_a, np.float64); b = np.ascontiguousarray(bearings_b, np.float64)
         n = len(a)
         prm = _lib.ArrsacParams()
         prm.struct_size = C.sizeof(_lib.ArrsacParams)
         prm.n_hypotheses, prm.block_size, prm.init_blocks, prm.max_candidates = n_hypotheses, block_size, init_blocks, max_candidates
         prm.flags = ((_lib.RS_PRUNE_BOUND if bound else 0) | (_lib.RS_PRUNE_SPRT if sprt else 0)
-                     | (_lib.RS_PRUNE_HALVE if halve else 0))
+                     | (_lib.RS_PRUNE_HALVE if halve else 0) | five)
         prm.estimations_per_block, prm.reserved = estimations_per_block, 0
         prm.threshold, prm.sprt_delta, prm.sprt_ratio, prm.seed = float(threshold), sprt_delta, sprt_ratio, seed
         si = None
         if sample_idx is not None:
-            si = np.ascontiguousarray(sample_idx, np.uint32).reshape(-1, 3 if p3p else 8)
+            si = np.ascontiguousarray(sample_idx, np.uint32).reshape(-1, 3 if p3p else (5 if five else 8))
             prm.n_hypotheses = len(si)
         pose = np.empty((3, 4), np.float64); best = C.c_uint32(); ninl = C.c_uint32()
         inl = np.empty(max(n, 1), np.uint32)
@@ -104,7 +139,8 @@ class EssentialConsensus:
 
     @staticmethod
     def arrsac_samples(seed, n, n_hypotheses, sample_size=8):
-        """The minimal samples rs_essential_arrsac (8) / rs_p3p_arrsac (3) draw on the device for (seed, n)."""
+        """The minimal samples rs_essential_arrsac (8; 5 with the five-point estimator) / rs_p3p_arrsac (3) draw on the
+        device for (seed, n)."""
         out = np.empty((n_hypotheses, sample_size), np.uint32)
         check(_lib.lib().rs_arrsac_samples(seed, n, n_hypotheses, sample_size, out.ctypes.data), "rs_arrsac_samples")
         return out
@@ -135,12 +171,12 @@ class EssentialConsensus:
 
     @staticmethod
     def make_params(threshold, n_hypotheses=8192, seed=0, block_size=64, init_blocks=4, max_candidates=1024, bound=True,
-                    sprt=True, sprt_delta=0.05, sprt_ratio=1e3, estimations_per_block=0, halve=False):
+                    sprt=True, sprt_delta=0.05, sprt_ratio=1e3, estimations_per_block=0, halve=False, estimator="eight_point"):
         prm = _lib.ArrsacParams()
         prm.struct_size = C.sizeof(_lib.ArrsacParams)
         prm.n_hypotheses, prm.block_size, prm.init_blocks, prm.max_candidates = n_hypotheses, block_size, init_blocks, max_candidates
         prm.flags = ((_lib.RS_PRUNE_BOUND if bound else 0) | (_lib.RS_PRUNE_SPRT if sprt else 0)
-                     | (_lib.RS_PRUNE_HALVE if halve else 0))
+                     | (_lib.RS_PRUNE_HALVE if halve else 0) | _estimator_flag(estimator))
         prm.estimations_per_block, prm.reserved = estimations_per_block, 0
         prm.threshold, prm.sprt_delta, prm.sprt_ratio, prm.seed = float(threshold), sprt_delta, sprt_ratio, seed
         return prm

@@ -388,6 +388,7 @@ inline std::vector<std::array<std::size_t, 2>> match_descriptors(Matcher& m, con
 //   cv_core::FeatureMatch(a, b) / FeatureWorldMatch(bearing, world)        cv-core/src/matches.rs
 //   cv_pinhole::CameraIntrinsics::calibrate                                 cv-pinhole/src/lib.rs:108-117
 //   eight_point::EightPoint, lambda_twist::LambdaTwist (Estimator)          eight-point/src/lib.rs:60-83, lambda-twist/src/lib.rs:330-347
+//   nister_stewenius::NisterStewenius (Estimator)                           nister-stewenius/src/lib.rs:283-330
 //   arrsac::Arrsac::{new, initialization_hypotheses, max_candidate_hypotheses, estimations_per_block, block_size,
 //                    likelihood_ratio_threshold} + Consensus::{model, model_inliers}
 //                                                                           call sites akaze/tests/estimate_pose.rs:63-75,
@@ -438,6 +439,13 @@ struct LambdaTwist {
     static constexpr std::size_t MIN_SAMPLES = 3;   // lambda-twist/src/lib.rs:333
 };
 }  // namespace lambda_twist
+namespace nister_stewenius {
+// The five-point minimal solver for calibrated cameras.  What runs is include/akz_five_point_math.h: the reference's
+// algorithm with rows 6..9 of the action matrix's eigenvector (rows 5..8 as written at lib.rs:230 do not solve the problem).
+struct NisterStewenius {
+    static constexpr std::size_t MIN_SAMPLES = 5;   // nister-stewenius/src/lib.rs:308
+};
+}  // namespace nister_stewenius
 
 namespace arrsac {
 
@@ -492,10 +500,33 @@ public:
             }
         cv_core::CameraToCamera pose{};
         std::vector<std::size_t> inl;
-        if (!run(false, a.data(), b.data(), (uint32_t)data.size(), pose.rt.data(), &inl)) return std::nullopt;
+        if (!run(kEightPoint, a.data(), b.data(), (uint32_t)data.size(), pose.rt.data(), &inl)) return std::nullopt;
         return std::make_pair(pose, std::move(inl));
     }
     std::optional<cv_core::CameraToCamera> model(const eight_point::EightPoint& e, const std::vector<cv_core::FeatureMatch>& data)
+    {
+        auto r = model_inliers(e, data);
+        if (!r) return std::nullopt;
+        return r->first;
+    }
+    // Consensus<NisterStewenius, FeatureMatch>::model_inliers (nister-stewenius/src/lib.rs:303-330 estimates): the builder's
+    // hypothesis counts are five-match samples, each with up to ten essential matrices (include/akz.h RS_ESTIMATOR_FIVE_POINT)
+    std::optional<std::pair<cv_core::CameraToCamera, std::vector<std::size_t>>> model_inliers(const nister_stewenius::NisterStewenius&,
+                                                                                              const std::vector<cv_core::FeatureMatch>& data)
+    {
+        if (data.size() < nister_stewenius::NisterStewenius::MIN_SAMPLES) return std::nullopt;
+        std::vector<double> a(3 * data.size()), b(3 * data.size());
+        for (std::size_t i = 0; i < data.size(); ++i)
+            for (int k = 0; k < 3; ++k) {
+                a[3 * i + k] = data[i].a[k];
+                b[3 * i + k] = data[i].b[k];
+            }
+        cv_core::CameraToCamera pose{};
+        std::vector<std::size_t> inl;
+        if (!run(kFivePoint, a.data(), b.data(), (uint32_t)data.size(), pose.rt.data(), &inl)) return std::nullopt;
+        return std::make_pair(pose, std::move(inl));
+    }
+    std::optional<cv_core::CameraToCamera> model(const nister_stewenius::NisterStewenius& e, const std::vector<cv_core::FeatureMatch>& data)
     {
         auto r = model_inliers(e, data);
         if (!r) return std::nullopt;
@@ -513,15 +544,20 @@ public:
         }
         cv_core::WorldToCamera pose{};
         std::vector<std::size_t> inl;
-        if (!run(true, a.data(), w.data(), (uint32_t)data.size(), pose.rt.data(), &inl)) return std::nullopt;
+        if (!run(kP3P, a.data(), w.data(), (uint32_t)data.size(), pose.rt.data(), &inl)) return std::nullopt;
         return std::make_pair(pose, std::move(inl));
     }
 
 private:
-    bool run(bool p3p, const double* a, const double* b, uint32_t n, double* pose, std::vector<std::size_t>* inl)
+    enum Estimator { kEightPoint, kP3P, kFivePoint };
+    bool run(Estimator est, const double* a, const double* b, uint32_t n, double* pose, std::vector<std::size_t>* inl)
     {
+        const bool p3p = est == kP3P;
         const uint32_t blocks = (n + p_.block_size - 1) / p_.block_size;
-        const uint32_t need_h = p_.n_hypotheses + p_.estimations_per_block * blocks;
+        // (a five-point sample takes ten hypothesis slots of the context)
+        const uint32_t need_h = (p_.n_hypotheses + p_.estimations_per_block * blocks) * (est == kFivePoint ? 10u : 1u);
+        rs_arrsac_params prm = p_;
+        if (est == kFivePoint) prm.flags |= RS_ESTIMATOR_FIVE_POINT;
         if (!ctx_ || n > cap_m_ || need_h > cap_h_) {
             if (ctx_) rs_destroy(ctx_);
             ctx_ = nullptr;
@@ -532,8 +568,8 @@ private:
         }
         std::vector<uint32_t> idx(n);
         uint32_t best = 0, ninl = 0;
-        const int32_t st = p3p ? rs_p3p_arrsac(ctx_, a, b, n, nullptr, &p_, pose, &best, idx.data(), n, &ninl, nullptr)
-                               : rs_essential_arrsac(ctx_, a, b, n, nullptr, &p_, pose, &best, idx.data(), n, &ninl, nullptr);
+        const int32_t st = p3p ? rs_p3p_arrsac(ctx_, a, b, n, nullptr, &prm, pose, &best, idx.data(), n, &ninl, nullptr)
+                               : rs_essential_arrsac(ctx_, a, b, n, nullptr, &prm, pose, &best, idx.data(), n, &ninl, nullptr);
         akaze::check(st, p3p ? "rs_p3p_arrsac" : "rs_essential_arrsac");
         if (best == 0xFFFFFFFFu) return false;     // Consensus::model_inliers returned None
         inl->assign(idx.begin(), idx.begin() + ninl);

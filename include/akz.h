@@ -452,6 +452,17 @@ int32_t rs_calibrate(const double* intrinsics, int32_t use_k1, double k1, const 
 int32_t rs_essential_batch(rs_ctx* ctx, const double* bearings_a, const double* bearings_b, uint32_t n,
                            const uint32_t* sample_idx, uint32_t n_hyp, double thresh, double* best_pose,
                            uint32_t* best_id, uint32_t* inlier_idx, uint32_t cap, uint32_t* n_inliers);
+/* Consensus::model_inliers(&NisterStewenius::new(), matches): the same with the five-point minimal solver for calibrated
+ * cameras (nister-stewenius/src/lib.rs:50-330).  sample_idx [n_samples][5]; a sample has up to ten essential matrices
+ * (include/akz_five_point_math.h: the reference's algorithm with rows 6..9 of the action matrix's eigenvector — rows 5..8 as
+ * written at lib.rs:230 do not solve the problem), in ascending order of the action matrix's eigenvalue;
+ * sample h owns the hypothesis slots 10 h .. 10 h + 9, unused ones hold no model, and each solution goes through the
+ * eight-point path's E -> four poses -> residual.  best_id = (10 sample + solution) 4 + pose.  The context needs
+ * 10 x n_samples hypothesis slots (rs_create's max_hypotheses), else AKZ_E_INVALID; n < 5 gives no model
+ * (best_id 0xFFFFFFFF, AKZ_OK). */
+int32_t rs_five_point_batch(rs_ctx* ctx, const double* bearings_a, const double* bearings_b, uint32_t n,
+                            const uint32_t* sample_idx, uint32_t n_samples, double thresh, double* best_pose,
+                            uint32_t* best_id, uint32_t* inlier_idx, uint32_t cap, uint32_t* n_inliers);
 /* The same consensus in arrsac's shape (arrsac::Arrsac::model_inliers; parameters as its builder exposes them at
  * vslam-sandbox/src/main.rs:105-117: initialization_hypotheses, max_candidate_hypotheses, block_size,
  * likelihood_ratio_threshold): the hypotheses are scored breadth-first, `block_size` matches at a time, and after
@@ -471,15 +482,20 @@ int32_t rs_essential_batch(rs_ctx* ctx, const double* bearings_a, const double* 
  * `seed` (rs_arrsac_samples reproduces them on the host).  The arrsac crate is not vendored in the reference: the
  * sampler, the retirement rules and their order are this library's, specified by oracle/arrsac_oracle.c and held to
  * it bit for bit (parity with the crate unpinned beyond the count pin of akaze/tests/estimate_pose.rs:75).
- * best_id / best_pose / inlier_idx as for rs_essential_batch. */
-enum { RS_PRUNE_BOUND = 1u << 0, RS_PRUNE_SPRT = 1u << 1, RS_PRUNE_HALVE = 1u << 2 };
+ * best_id / best_pose / inlier_idx as for rs_essential_batch.
+ *
+ * RS_ESTIMATOR_FIVE_POINT (rs_essential_arrsac and rs_essential_arrsac_batch_device only; the P3P entry points refuse it):
+ * the estimator is NisterStewenius instead of EightPoint.  n_hypotheses and estimations_per_block then count five-match
+ * SAMPLES, each of which takes ten hypothesis slots of the context (see rs_five_point_batch; sample_idx is [n][5]);
+ * max_candidates and stats.poses keep counting poses, best_id = (10 sample + solution) 4 + pose. */
+enum { RS_PRUNE_BOUND = 1u << 0, RS_PRUNE_SPRT = 1u << 1, RS_PRUNE_HALVE = 1u << 2, RS_ESTIMATOR_FIVE_POINT = 1u << 3 };
 typedef struct rs_arrsac_params {
     uint32_t struct_size;      /* sizeof(rs_arrsac_params) */
     uint32_t n_hypotheses;     /* initialization_hypotheses */
     uint32_t block_size;       /* matches per scoring block */
     uint32_t init_blocks;      /* blocks scored before max_candidates applies */
     uint32_t max_candidates;   /* max_candidate_hypotheses (poses kept); 0 = no cap */
-    uint32_t flags;            /* RS_PRUNE_* */
+    uint32_t flags;            /* RS_PRUNE_*, RS_ESTIMATOR_FIVE_POINT */
     double threshold;          /* inlier threshold on CameraToCamera::residual */
     double sprt_delta;         /* P(inlier | wrong model), e.g. 0.05 */
     double sprt_ratio;         /* likelihood ratio threshold, arrsac default 1e3 */
@@ -505,7 +521,8 @@ int32_t rs_p3p_arrsac(rs_ctx* ctx, const double* bearings, const double* world, 
                       const uint32_t* sample_idx, const rs_arrsac_params* params, double* best_pose,
                       uint32_t* best_id, uint32_t* inlier_idx, uint32_t cap, uint32_t* n_inliers,
                       rs_arrsac_stats* stats);
-/* The minimal samples the two functions draw on the device for (seed, n): sample_size 8 (eight-point) or 3 (P3P). */
+/* The minimal samples the two functions draw on the device for (seed, n): sample_size 8 (eight-point), 5 (five-point) or
+ * 3 (P3P). */
 int32_t rs_arrsac_samples(uint64_t seed, uint32_t n, uint32_t n_hyp, uint32_t sample_size, uint32_t* sample_idx);
 /* Consensus::model_inliers(&LambdaTwist::new(), matches) for 3D-2D registration (cv-sfm/src/lib.rs:1619-1622,
  * lambda-twist/tests/consensus.rs:59-61), sampler factored out as above: n_hyp sample triples; each gives up
@@ -521,6 +538,10 @@ int32_t rs_debug_counts(rs_ctx* ctx, uint32_t* counts, uint32_t cap);
  * what EightPoint::estimate / LambdaTwist::estimate returned for each minimal sample (eight-point/src/lib.rs:70-83,
  * lambda-twist/src/lib.rs:330-347) */
 int32_t rs_debug_poses(rs_ctx* ctx, double* poses, uint32_t* ok, uint32_t n_hyp);
+/* parity tap: the essential matrices E [n_samples][10][9] (row-major, b^T E a = 0; slots beyond a sample's count are
+ * zero-filled) and the solution counts [n_samples] of the last single-scene five-point call (rs_five_point_batch, or
+ * rs_essential_arrsac with RS_ESTIMATOR_FIVE_POINT).  rs_debug_poses / rs_debug_counts see n_hyp = 10 x n_samples. */
+int32_t rs_debug_essentials(rs_ctx* ctx, double* E, uint32_t* n_solutions, uint32_t n_samples);
 
 /* parity tap: CameraToCamera::residual (cv-core/src/pose.rs:249-295) of every (pose, match) as the device evaluates it.
  * poses [n_pose][12] row-major [R | t], bearings [n][3], host buffers.  paired == 0: out [n_pose][n].  paired != 0: out
@@ -697,7 +718,7 @@ const char* akz_version(void);
 /* The ABI number: raised whenever a declared signature, struct layout or enum value of this header changes (additions
  * included).  A binding compares akz_abi_version() of the library it loaded with the AKZ_ABI_VERSION it was written against
  * and refuses to run on a mismatch (cv_amd/_lib.py, rust/akaze-mi355x/src/lib.rs, include/akaze.hpp do). */
-#define AKZ_ABI_VERSION 9u
+#define AKZ_ABI_VERSION 10u
 uint32_t akz_abi_version(void);
 
 /* HIP-event timing of the kernel families of a batch (bench.py's roofline objects).  Kernel families (every id but the

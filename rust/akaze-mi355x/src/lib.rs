@@ -236,7 +236,7 @@ static ARITH: std::sync::atomic::AtomicU32 = std::sync::atomic::AtomicU32::new(0
 
 /// The thread's matcher context, grown to hold `n` descriptors a side.
 /// include/akz.h AKZ_ABI_VERSION these bindings were written against; the loaded library must export the same number.
-const AKZ_ABI_VERSION: u32 = 9;
+const AKZ_ABI_VERSION: u32 = 10;
 fn require_abi() {
     let got = unsafe { akz_abi_version() };
     assert_eq!(got, AKZ_ABI_VERSION, "libakz exports ABI {got}, akaze-mi355x was written against {AKZ_ABI_VERSION}");
@@ -618,9 +618,10 @@ impl Arrsac {
     pub fn initialization_blocks(mut self, n: usize) -> Self { self.params.init_blocks = n as u32; self }
     pub fn likelihood_ratio_threshold(mut self, r: f64) -> Self { self.params.sprt_ratio = r; self }
 
-    fn context(&mut self, n: u32) -> *mut c_void {
+    /// `per`: hypothesis slots a sample takes (ten for the five-point estimator, one otherwise)
+    fn context(&mut self, n: u32, per: u32) -> *mut c_void {
         let blocks = (n + self.params.block_size - 1) / self.params.block_size;
-        let need_h = self.params.n_hypotheses + self.params.estimations_per_block * blocks;
+        let need_h = (self.params.n_hypotheses + self.params.estimations_per_block * blocks) * per;
         if self.ctx.map_or(true, |(m, h, _)| m < n || h < need_h) {
             if let Some((_, _, old)) = self.ctx.take() {
                 unsafe { rs_destroy(old) };
@@ -634,16 +635,24 @@ impl Arrsac {
     }
     /// (row-major 3x4 `[R | t]`, inlier indices) or `None`
     fn run(&mut self, p3p: bool, a: &[f64], b: &[f64], n: u32) -> Option<([f64; 12], Vec<usize>)> {
-        let ctx = self.context(n);
+        self.run_with(p3p, false, a, b, n)
+    }
+    /// `five_point`: RS_ESTIMATOR_FIVE_POINT (include/akz.h) — the hypothesis counts are five-match samples, ten slots each
+    fn run_with(&mut self, p3p: bool, five_point: bool, a: &[f64], b: &[f64], n: u32) -> Option<([f64; 12], Vec<usize>)> {
+        let ctx = self.context(n, if five_point { 10 } else { 1 });
+        let mut params = self.params;
+        if five_point {
+            params.flags |= 8; // RS_ESTIMATOR_FIVE_POINT
+        }
         let mut pose = [0f64; 12];
         let (mut best, mut n_inl) = (0u32, 0u32);
         let mut inl = vec![0u32; n as usize];
         let st = unsafe {
             if p3p {
-                rs_p3p_arrsac(ctx, a.as_ptr(), b.as_ptr(), n, ptr::null(), &self.params, pose.as_mut_ptr(), &mut best,
+                rs_p3p_arrsac(ctx, a.as_ptr(), b.as_ptr(), n, ptr::null(), &params, pose.as_mut_ptr(), &mut best,
                               inl.as_mut_ptr(), n, &mut n_inl, ptr::null_mut())
             } else {
-                rs_essential_arrsac(ctx, a.as_ptr(), b.as_ptr(), n, ptr::null(), &self.params, pose.as_mut_ptr(), &mut best,
+                rs_essential_arrsac(ctx, a.as_ptr(), b.as_ptr(), n, ptr::null(), &params, pose.as_mut_ptr(), &mut best,
                                     inl.as_mut_ptr(), n, &mut n_inl, ptr::null_mut())
             }
         };
@@ -684,6 +693,30 @@ impl Consensus<eight_point::EightPoint, FeatureMatch> for Arrsac {
             return None;
         }
         self.run(false, &a, &b, n).map(|(rt, inl)| (CameraToCamera(isometry(&rt)), inl))
+    }
+}
+/// `Consensus<NisterStewenius, FeatureMatch>` — the five-point minimal solver for calibrated cameras
+/// (nister-stewenius/src/lib.rs:303-330).  What runs is include/akz_five_point_math.h: the reference's algorithm with rows
+/// 6..9 of the action matrix's eigenvector (rows 5..8 as written at lib.rs:230 do not solve the problem); the builder's
+/// hypothesis counts are five-match samples, each with up to ten essential matrices.
+impl Consensus<nister_stewenius::NisterStewenius, FeatureMatch> for Arrsac {
+    type Inliers = Vec<usize>;
+    fn model<I>(&mut self, estimator: &nister_stewenius::NisterStewenius, data: I) -> Option<CameraToCamera>
+    where I: Iterator<Item = FeatureMatch> + Clone {
+        self.model_inliers(estimator, data).map(|(m, _)| m)
+    }
+    fn model_inliers<I>(&mut self, _estimator: &nister_stewenius::NisterStewenius, data: I) -> Option<(CameraToCamera, Vec<usize>)>
+    where I: Iterator<Item = FeatureMatch> + Clone {
+        let (mut a, mut b) = (Vec::new(), Vec::new());
+        for FeatureMatch(fa, fb) in data {
+            a.extend_from_slice(fa.as_ref().as_slice());
+            b.extend_from_slice(fb.as_ref().as_slice());
+        }
+        let n = (a.len() / 3) as u32;
+        if (n as usize) < <nister_stewenius::NisterStewenius as Estimator<FeatureMatch>>::MIN_SAMPLES {
+            return None;
+        }
+        self.run_with(false, true, &a, &b, n).map(|(rt, inl)| (CameraToCamera(isometry(&rt)), inl))
     }
 }
 /// `Consensus<LambdaTwist, FeatureWorldMatch>` — lambda-twist/src/lib.rs:330-347 estimates, cv-core/src/pose.rs:194-201 scores.

@@ -4,7 +4,11 @@ consensus (GPU box): random scene counts and sizes, outlier fractions, cameras, 
 rs_essential_arrsac_batch_device / rs_p3p_arrsac_batch_device vs oracle/arrsac_oracle.c (orc_arrsac_pairs /
 orc_p3p_arrsac_pairs): bearings, scoring order, winner id, pose bits, inlier list, survivors / blocks / poses /
 residuals evaluated must all be equal.  The oracle runs in a process pool.
-usage: python tools/stress_verify.py [--rounds 12] [--seed 1] [--procs 32]"""
+--estimator five_point: the two-view rounds with RS_ESTIMATOR_FIVE_POINT.  oracle/ has no five-point statement (its
+specification is the host build of include/akz_five_point_math.h, tests/test_gpu_five_point.py): every scene of the
+batched call is compared with the single-scene rs_essential_arrsac on that scene's bearings in its scoring order, with
+the scene's seed — winner id, pose bits, inlier list.
+usage: python tools/stress_verify.py [--rounds 12] [--seed 1] [--procs 32] [--estimator eight_point|five_point]"""
 import argparse
 import multiprocessing as mp
 import os
@@ -79,14 +83,88 @@ def oracle_scene(args):
     return r, s, w
 
 
+def five_point_rounds(a):
+    """The two-view rounds with the five-point estimator: batched call == single-scene calls."""
+    import torch
+    from oracle import oracle as O
+    from cv_amd import build
+    build.build()
+    from cv_amd.ransac import EssentialConsensus
+    dev = torch.device("cuda", 0)
+    bad = models = scenes = 0
+    for r in range(a.rounds):
+        R = make_round(r, a.seed)
+        if R["reg"] is not None:
+            continue
+        cap, kw, S = R["cap"], R["kw"], len(R["scenes"])
+        n_smp = min(R["n_hyp"], 500)
+        pairs = np.zeros((S, cap, 2), np.uint32)
+        for s, sc in enumerate(R["scenes"]):
+            pairs[s, :len(sc[2])] = sc[2]
+        npairs = np.array([len(sc[2]) for sc in R["scenes"]], np.uint32)
+        d_ka = torch.from_numpy(np.stack([sc[0] for sc in R["scenes"]]).view(np.uint8).reshape(S, cap, 28)).to(dev)
+        d_kb = torch.from_numpy(np.stack([sc[1] for sc in R["scenes"]]).view(np.uint8).reshape(S, cap, 28)).to(dev)
+        d_pairs = torch.from_numpy(pairs.view(np.int32)).to(dev)
+        d_np = torch.from_numpy(npairs.view(np.int32)).to(dev)
+        d_pose = torch.zeros((S, 12), dtype=torch.float64, device=dev)
+        d_best = torch.zeros((S,), dtype=torch.int32, device=dev)
+        d_inl = torch.zeros((S, cap), dtype=torch.int32, device=dev)
+        d_ninl = torch.zeros((S,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        blocks_max = (cap + kw["block_size"] - 1) // kw["block_size"]
+        slots = 10 * (n_smp + kw["estimations_per_block"] * blocks_max)
+        cons = EssentialConsensus(cap, slots)
+        cons.reserve(S)
+        single = EssentialConsensus(cap, slots)
+        prm = cons.make_params(R["thr"], n_hypotheses=n_smp, seed=R["seed"], estimator="five_point", **kw)
+        ia = list(range(S))
+        cons.model_inliers_batch_device(d_ka.data_ptr(), d_kb.data_ptr(), cap, ia, ia, d_pairs.data_ptr(), d_np.data_ptr(),
+                                        cons.camera(R["cam_a"]), cons.camera(R["cam_b"]), prm, d_pose.data_ptr(), d_best.data_ptr(),
+                                        d_inl.data_ptr(), d_ninl.data_ptr(), None, shuffle=R["shuffle"])
+        cons.sync()
+        pose = d_pose.cpu().numpy(); best = d_best.cpu().numpy().view(np.uint32)
+        inl = d_inl.cpu().numpy().view(np.uint32); ninl = d_ninl.cpu().numpy().view(np.uint32)
+        rbad = 0
+        for s in range(S):
+            n = int(npairs[s])
+            scenes += 1
+            if n < 5:
+                ok = best[s] == 0xFFFFFFFF and ninl[s] == 0
+            else:
+                ga, gb, order = cons.scene(s, cap)
+                order = order.astype(np.int64) if R["shuffle"] else np.arange(n)
+                inv = np.empty(n, np.int64); inv[order] = np.arange(n)
+                sseed = O.scene_seed(R["seed"], s)
+                smp = inv[EssentialConsensus.arrsac_samples(sseed, n, n_smp, sample_size=5).astype(np.int64)].astype(np.uint32)
+                w = single.arrsac_model_inliers(ga[order], gb[order], R["thr"], sample_idx=smp, seed=sseed, estimator="five_point", **kw)
+                if w is None:
+                    ok = best[s] == 0xFFFFFFFF and ninl[s] == 0
+                else:
+                    models += 1
+                    ok = (best[s] == w[2] and pose[s].tobytes() == np.ascontiguousarray(w[0]).tobytes()
+                          and inl[s, :ninl[s]].tolist() == sorted(order[w[1].astype(np.int64)].tolist()))
+            if not ok:
+                rbad += 1
+                print(f"MISMATCH round {r} scene {s}: n {n} best {best[s]} inliers {ninl[s]}", flush=True)
+        bad += rbad
+        cons.close(); single.close()
+        print(f"round {r} (five-point): {S} scenes cap {cap} samples {n_smp} thr {R['thr']:g} shuffle {int(R['shuffle'])} {kw} -> "
+              f"{'ok' if not rbad else str(rbad) + ' BAD'}", flush=True)
+    print(f"stress_verify five_point seed {a.seed}: {scenes} scenes, {models} with a model, {bad} mismatches")
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--procs", type=int, default=32)
+    ap.add_argument("--estimator", choices=("eight_point", "five_point"), default="eight_point")
     a = ap.parse_args()
     from oracle import oracle as O
     O.build()
+    if a.estimator == "five_point":
+        return five_point_rounds(a)
     rounds = [make_round(r, a.seed) for r in range(a.rounds)]
     jobs = [(r, a.seed, s) for r, R in enumerate(rounds) for s in range(len(R["scenes"]))]
     with mp.get_context("spawn").Pool(a.procs) as pool:
