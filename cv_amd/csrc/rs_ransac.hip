@@ -514,9 +514,13 @@ __global__ __launch_bounds__(1024) void k_rsb_alive_init(RsB B, uint32_t n_pose)
 // cv-sfm/src/lib.rs:1394-1412) scores its hypotheses breadth-first, block of matches by block of matches, and drops
 // the ones that can no longer win.  The same shape on the device, every kernel over all scenes of the call:
 //   k_rsb_prepare      (micro-batch entry) calibrate the matcher's pairs into bearings, optional seeded shuffle order
-//   k_rsb_sample       xoshiro256++ minimal samples drawn on the device (the caller need not ship n_hyp x 8 indices)
-//   k_rsb_hypotheses   one lane per minimal sample: essential matrix + four poses, registers only
-//   k_rsb_score        every live pose against the next `block` matches (2^lg lanes per pose; k_rsb_score_p3p: a lane per pose)
+//   k_rsb_sample       xoshiro256++ minimal samples drawn on the device (the caller need not ship n_hyp x K indices)
+//   hypotheses         samples -> hypothesis slots of four poses each, by the estimator (host side: the RsEstimator table):
+//                        eight-point   k_rsb_hypotheses: a lane per sample, essential matrix + four poses, registers only
+//                        five-point    k_rsb_five_point_nullspace, _solve, _hypotheses: ten slots per sample
+//                        Lambda Twist  k_rsb_p3p_hypotheses: a lane per sample
+//   k_rsb_score        every live pose against the next `block` matches, by the estimator's residual family: two-view
+//                      (2^lg lanes per pose; block 0: k_rsb_score_first) or world-to-camera (k_rsb_score_p3p: a lane per pose)
 //   k_rsb_prune        after each block: the best count so far B, then a pose is retired when
 //                        (bound)  count + matches_left < B            — it cannot reach the best: exact, always on
 //                        (cap)    it is not among the max_candidates best after the initialisation blocks
@@ -1480,47 +1484,37 @@ struct rs_ctx : RsArena {
     hipEvent_t ev = nullptr;
     uint32_t max_matches = 0, max_hyp = 0;
     double* d_logtab = nullptr;                                        // ln(k), k = 0 .. max_matches (host libm values)
-    uint32_t last_hyp = 0;
-    uint32_t last_five_samples = 0;                                    // samples of the last single-scene five-point call
+    uint32_t last_hyp = 0, last_five_samples = 0;                      // what the debug taps may read (rs_note_call)
 };
 
 // (akz_common.h) what rs_triangulate.hip enqueues with
 RsHandles rs_internal_handles(rs_ctx* c) { return RsHandles{c->device, c->stream, c->ev, c->d_frames, c->max_scenes}; }
 
+// Every device array of an arena, once: where its pointer lives and its bytes per scene (n matches, H hypothesis slots).
+struct RsSlot {
+    void** p;
+    size_t bytes;
+};
+static std::vector<RsSlot> rs_arena_slots(RsArena* A, size_t n, size_t H)
+{
+    const size_t u = sizeof(uint32_t), d = sizeof(double);
+    auto at = [](auto** p, size_t bytes) { return RsSlot{(void**)p, bytes}; };
+    return {at(&A->d_n, u), at(&A->d_nalive, u), at(&A->d_ninl, u), at(&A->d_first, u), at(&A->d_enable, u), at(&A->d_frames, 2 * u),
+            at(&A->d_a, 3 * n * d), at(&A->d_b, 4 * n * d), at(&A->d_order, n * u), at(&A->d_inl, n * u),
+            at(&A->d_samples, 8 * H * u), at(&A->d_poses, 48 * H * d), at(&A->d_ok, 4 * H * u), at(&A->d_counts, 4 * H * u), at(&A->d_alive, 4 * H * u),
+            at(&A->d_neval, sizeof(unsigned long long)), at(&A->d_best, 4 * u), at(&A->d_best_pose, 12 * d), at(&A->d_stats, sizeof(rs_arrsac_stats)),
+            at(&A->d_fp_basis, 4 * H * d), at(&A->d_fp_E, 9 * H * d), at(&A->d_fp_nsol, H * u)};
+}
+
 static void rs_free_arena(RsArena* c)
 {
-    hipFree(c->d_n); hipFree(c->d_a); hipFree(c->d_b); hipFree(c->d_poses); hipFree(c->d_best_pose); hipFree(c->d_order);
-    hipFree(c->d_samples); hipFree(c->d_ok); hipFree(c->d_counts); hipFree(c->d_alive); hipFree(c->d_nalive); hipFree(c->d_best);
-    hipFree(c->d_inl); hipFree(c->d_ninl); hipFree(c->d_first); hipFree(c->d_enable); hipFree(c->d_frames); hipFree(c->d_neval);
-    hipFree(c->d_stats); hipFree(c->d_fp_basis); hipFree(c->d_fp_E); hipFree(c->d_fp_nsol);
+    for (const RsSlot& e : rs_arena_slots(c, 0, 0)) hipFree(*e.p);
     *c = RsArena();
 }
 
 static int32_t rs_alloc_arena_into(RsArena* A, size_t n, size_t H, uint32_t S)
 {
-    const size_t s = S;
-    AKZ_HIP(hipMalloc(&A->d_n, sizeof(uint32_t) * s));
-    AKZ_HIP(hipMalloc(&A->d_a, sizeof(double) * 3 * n * s));
-    AKZ_HIP(hipMalloc(&A->d_b, sizeof(double) * 4 * n * s));
-    AKZ_HIP(hipMalloc(&A->d_order, sizeof(uint32_t) * n * s));
-    AKZ_HIP(hipMalloc(&A->d_samples, sizeof(uint32_t) * 8 * H * s));
-    AKZ_HIP(hipMalloc(&A->d_poses, sizeof(double) * 48 * H * s));
-    AKZ_HIP(hipMalloc(&A->d_ok, sizeof(uint32_t) * 4 * H * s));
-    AKZ_HIP(hipMalloc(&A->d_counts, sizeof(uint32_t) * 4 * H * s));
-    AKZ_HIP(hipMalloc(&A->d_alive, sizeof(uint32_t) * 4 * H * s));
-    AKZ_HIP(hipMalloc(&A->d_nalive, sizeof(uint32_t) * s));
-    AKZ_HIP(hipMalloc(&A->d_neval, sizeof(unsigned long long) * s));
-    AKZ_HIP(hipMalloc(&A->d_best, sizeof(uint32_t) * 4 * s));
-    AKZ_HIP(hipMalloc(&A->d_inl, sizeof(uint32_t) * n * s));
-    AKZ_HIP(hipMalloc(&A->d_ninl, sizeof(uint32_t) * s));
-    AKZ_HIP(hipMalloc(&A->d_best_pose, sizeof(double) * 12 * s));
-    AKZ_HIP(hipMalloc(&A->d_first, sizeof(uint32_t) * s));
-    AKZ_HIP(hipMalloc(&A->d_enable, sizeof(uint32_t) * s));
-    AKZ_HIP(hipMalloc(&A->d_frames, sizeof(uint32_t) * 2 * s));
-    AKZ_HIP(hipMalloc(&A->d_stats, sizeof(rs_arrsac_stats) * s));
-    AKZ_HIP(hipMalloc(&A->d_fp_basis, sizeof(double) * 4 * H * s));
-    AKZ_HIP(hipMalloc(&A->d_fp_E, sizeof(double) * 9 * H * s));
-    AKZ_HIP(hipMalloc(&A->d_fp_nsol, sizeof(uint32_t) * H * s));
+    for (const RsSlot& e : rs_arena_slots(A, n, H)) AKZ_HIP(hipMalloc(e.p, e.bytes * S));
     A->max_scenes = S;
     return AKZ_OK;
 }
@@ -1701,68 +1695,131 @@ static int32_t rs_fetch_single(rs_ctx* c, double* best_pose, uint32_t* best_id, 
     return ninl > cap ? AKZ_E_CAPACITY : AKZ_OK;
 }
 
-// five-point hypotheses of the samples [h0, h0 + nh) of S scenes -> the slots [10 h0, 10 (h0 + nh))
-static int32_t rs_five_point_launch(hipStream_t s, const RsB& B, uint32_t S, uint32_t h0, uint32_t nh, const uint32_t* gate)
+// The templated kernels, named once in the order the code object has carried them since they were written: implicit
+// instantiations are emitted in the order of their first mention, so with this list a host-side edit below leaves the device
+// code byte for byte what it was (the check for "same kernels": compare the device assembly of two commits).
+[[maybe_unused]] static const void* const kKernelOrder[] = {
+    (const void*)k_rs_inliers<false>, (const void*)k_rs_inliers<true>, (const void*)k_rsb_prepare<false>, (const void*)k_rsb_sample<5>,
+    (const void*)k_rsb_sample<8>, (const void*)k_rsb_best_inliers<false>, (const void*)k_rsb_resample<5>, (const void*)k_rsb_resample<8>,
+    (const void*)k_rsb_prepare<true>, (const void*)k_rsb_sample<3>, (const void*)k_rsb_best_inliers<true>, (const void*)k_rsb_resample<3>};
+
+// ---- the estimators ------------------------------------------------------------------------------------------------
+// Everything the host code knows about an estimator is stated here.  The host counts minimal SAMPLES (n_hypotheses,
+// estimations_per_block, the three launchers below); sample h owns the hypothesis slots [per h, per (h + 1)), and from the
+// hypothesis kernels on the consensus sees slots and nothing else.
+struct RsEstimator {
+    uint32_t K;      // matches per minimal sample
+    uint32_t per;    // hypothesis slots per sample
+    uint32_t BW;     // doubles per element of the second input: bearings of view b, or homogeneous world points
+    bool world;      // residual family: world-to-camera (k_rsb_score_p3p; exhaustive: k_p3p_score), else two-view (k_rsb_score, k_rsb_score_first)
+    bool keeps_E;    // the hypothesis launcher leaves every sample's essential matrices in fp_E / fp_nsol (rs_debug_essentials)
+    bool lenient;    // the exhaustive entry answers as rs_five_point_batch documents: too few slots AKZ_E_INVALID, n < K "no model"
+    decltype(&k_rsb_prepare<false>) prepare;            // the family's instantiations
+    decltype(&k_rsb_best_inliers<false>) best_inliers;
+    decltype(&k_rs_inliers<false>) inliers;
+    int32_t (*draw)(hipStream_t s, const RsB& B, uint32_t S, unsigned long long seed, uint32_t n);                   // samples [0, n)
+    int32_t (*redraw)(hipStream_t s, const RsB& B, uint32_t S, unsigned long long seed, uint32_t smp0, uint32_t n);  // [smp0, smp0 + n) among the best inliers
+    int32_t (*hypotheses)(hipStream_t s, const RsB& B, uint32_t S, uint32_t smp0, uint32_t n, const uint32_t* gate); // samples [smp0, smp0 + n) -> their slots
+};
+
+template <int K>
+static int32_t rs_draw(hipStream_t s, const RsB& B, uint32_t S, unsigned long long seed, uint32_t n)
 {
-    hipLaunchKernelGGL(k_rsb_five_point_nullspace, dim3((nh + 63) / 64, S), dim3(64), 0, s, B, h0, nh, gate);
+    hipLaunchKernelGGL((k_rsb_sample<K>), dim3((n + 255) / 256, S), dim3(256), 0, s, B, seed, n);
     AKZ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_rsb_five_point_solve, dim3((nh + 63) / 64, S), dim3(64), 0, s, B, h0, nh);
+    return AKZ_OK;
+}
+template <int K>
+static int32_t rs_redraw(hipStream_t s, const RsB& B, uint32_t S, unsigned long long seed, uint32_t smp0, uint32_t n)
+{
+    hipLaunchKernelGGL((k_rsb_resample<K>), dim3((n + 255) / 256, S), dim3(256), 0, s, B, seed, smp0, n);
     AKZ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_rsb_five_point_hypotheses, dim3((10 * nh + 63) / 64, S), dim3(64), 0, s, B, 10 * h0, 10 * nh);
+    return AKZ_OK;
+}
+// one slot per sample, one kernel, one lane per sample
+template <void (*Kernel)(RsB, uint32_t, uint32_t, const uint32_t*)>
+static int32_t rs_hypotheses(hipStream_t s, const RsB& B, uint32_t S, uint32_t smp0, uint32_t n, const uint32_t* gate)
+{
+    hipLaunchKernelGGL(Kernel, dim3((n + 63) / 64, S), dim3(64), 0, s, B, smp0, n, gate);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+// ten slots per sample: null space and solutions a lane per sample, then E -> four poses a lane per slot
+static int32_t rs_five_point_hypotheses(hipStream_t s, const RsB& B, uint32_t S, uint32_t smp0, uint32_t n, const uint32_t* gate)
+{
+    hipLaunchKernelGGL(k_rsb_five_point_nullspace, dim3((n + 63) / 64, S), dim3(64), 0, s, B, smp0, n, gate);
+    AKZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_rsb_five_point_solve, dim3((n + 63) / 64, S), dim3(64), 0, s, B, smp0, n);
+    AKZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_rsb_five_point_hypotheses, dim3((10 * n + 63) / 64, S), dim3(64), 0, s, B, 10 * smp0, 10 * n);
     AKZ_LAUNCH_CHECK();
     return AKZ_OK;
 }
 
-// exhaustive scoring of caller-provided minimal samples, one scene (slot 0 of the arena).  five (two-view only): the
-// samples are five-point ones, n_smp of them, ten hypothesis slots each.
-template <bool P3P>
-static int32_t exhaustive_run(rs_ctx* c, const double* in_a, const double* in_b, uint32_t n, const uint32_t* sample_idx,
-                              uint32_t n_smp, double thresh, double* best_pose, uint32_t* best_id, uint32_t* inlier_idx,
-                              uint32_t cap, uint32_t* n_inliers, bool five = false)
+//                                    K  per BW  world  keeps_E lenient
+static const RsEstimator kEightPoint = {8, 1, 3, false, false, false, k_rsb_prepare<false>, k_rsb_best_inliers<false>, k_rs_inliers<false>,
+                                        rs_draw<8>, rs_redraw<8>, rs_hypotheses<k_rsb_hypotheses>};
+static const RsEstimator kFivePoint = {5, 10, 3, false, true, true, k_rsb_prepare<false>, k_rsb_best_inliers<false>, k_rs_inliers<false>,
+                                       rs_draw<5>, rs_redraw<5>, rs_five_point_hypotheses};
+static const RsEstimator kLambdaTwist = {3, 1, 4, true, false, false, k_rsb_prepare<true>, k_rsb_best_inliers<true>, k_rs_inliers<true>,
+                                         rs_draw<3>, rs_redraw<3>, rs_hypotheses<k_rsb_p3p_hypotheses>};
+
+// The estimator that rs_arrsac_params::flags selects at an entry point of the two-view or the world-to-camera family;
+// nullptr: the family has none such (the P3P entry points refuse RS_ESTIMATOR_FIVE_POINT).
+static const RsEstimator* rs_estimator(uint32_t flags, bool world)
 {
-    const uint32_t K = P3P ? 3u : (five ? 5u : 8u);
-    constexpr uint32_t BW = P3P ? 4u : 3u;
+    const bool nister = (flags & RS_ESTIMATOR_FIVE_POINT) != 0;
+    if (world) return nister ? nullptr : &kLambdaTwist;
+    return nister ? &kFivePoint : &kEightPoint;
+}
+
+// What the last call was, for the debug taps: its hypothesis slots, and its samples where rs_debug_essentials may read them
+// (a single-scene call of an estimator that keeps its essential matrices).  Every entry point that runs a consensus ends here.
+static void rs_note_call(rs_ctx* c, const RsEstimator& est, uint32_t samples, bool single_scene)
+{
+    c->last_hyp = samples * est.per;
+    c->last_five_samples = single_scene && est.keeps_E ? samples : 0u;
+}
+
+// exhaustive scoring of n_smp caller-provided minimal samples, one scene (slot 0 of the arena)
+static int32_t exhaustive_run(rs_ctx* c, const RsEstimator& est, const double* in_a, const double* in_b, uint32_t n,
+                              const uint32_t* sample_idx, uint32_t n_smp, double thresh, double* best_pose, uint32_t* best_id,
+                              uint32_t* inlier_idx, uint32_t cap, uint32_t* n_inliers)
+{
     if (!c || !in_a || !in_b || !sample_idx || !best_pose || !best_id || !n_inliers || (cap && !inlier_idx)) return AKZ_E_INVALID;
     RS_NEED_ARENA(c);
-    if (five) {
-        if (n_smp == 0 || (uint64_t)n_smp * 10u > c->max_hyp) return AKZ_E_INVALID;   // ten slots per sample
-        if (n < K) {                                                                    // MIN_SAMPLES (nister-stewenius/src/lib.rs:308): no model
-            *best_id = 0xFFFFFFFFu;
-            *n_inliers = 0;
-            return AKZ_OK;
-        }
+    const bool room = (uint64_t)n_smp * est.per <= c->max_hyp;
+    if (n_smp == 0 || (est.lenient && !room)) return AKZ_E_INVALID;
+    if (n < est.K) {   // MIN_SAMPLES (eight-point/src/lib.rs:73, lambda-twist/src/lib.rs:333, nister-stewenius/src/lib.rs:308)
+        if (!est.lenient) return AKZ_E_INVALID;
+        *best_id = 0xFFFFFFFFu;   // no model
+        *n_inliers = 0;
+        return AKZ_OK;
     }
-    const uint32_t n_hyp = five ? n_smp * 10u : n_smp;
-    if (n < K || n_hyp == 0) return AKZ_E_INVALID;  // MIN_SAMPLES (eight-point/src/lib.rs:73, lambda-twist/src/lib.rs:333)
-    if (n > c->max_matches || n_hyp > c->max_hyp) return AKZ_E_TOO_LARGE;
-    for (size_t i = 0; i < (size_t)n_smp * K; ++i)
+    if (n > c->max_matches || !room) return AKZ_E_TOO_LARGE;
+    const uint32_t n_hyp = n_smp * est.per;
+    for (size_t i = 0; i < (size_t)n_smp * est.K; ++i)
         if (sample_idx[i] >= n) return AKZ_E_INVALID;
     AKZ_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     AKZ_HIP(hipMemcpyAsync(c->d_a, in_a, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s));
-    AKZ_HIP(hipMemcpyAsync(c->d_b, in_b, sizeof(double) * BW * (size_t)n, hipMemcpyHostToDevice, s));
-    AKZ_HIP(hipMemcpyAsync(c->d_samples, sample_idx, sizeof(uint32_t) * K * (size_t)n_smp, hipMemcpyHostToDevice, s));
+    AKZ_HIP(hipMemcpyAsync(c->d_b, in_b, sizeof(double) * est.BW * (size_t)n, hipMemcpyHostToDevice, s));
+    AKZ_HIP(hipMemcpyAsync(c->d_samples, sample_idx, sizeof(uint32_t) * est.K * (size_t)n_smp, hipMemcpyHostToDevice, s));
     AKZ_HIP(hipMemsetD32Async((hipDeviceptr_t)c->d_n, (int)n, 1, s));
     AKZ_HIP(hipMemsetAsync(c->d_counts, 0, sizeof(uint32_t) * 4 * (size_t)n_hyp, s));
     AKZ_HIP(hipMemsetAsync(c->d_neval, 0, sizeof(unsigned long long), s));
     const RsB B = rs_view(c, false);
-    if (P3P)
-        hipLaunchKernelGGL(k_rsb_p3p_hypotheses, dim3((n_hyp + 63) / 64, 1), dim3(64), 0, s, B, 0u, n_hyp, (const uint32_t*)nullptr);
-    else if (five)
-        AKZ_TRY(rs_five_point_launch(s, B, 1, 0u, n_smp, nullptr));
-    else
-        hipLaunchKernelGGL(k_rsb_hypotheses, dim3((n_hyp + 63) / 64, 1), dim3(64), 0, s, B, 0u, n_hyp, (const uint32_t*)nullptr);
-    AKZ_LAUNCH_CHECK();
-    // grid.y is limited to 65535: score the poses in slabs
+    AKZ_TRY(est.hypotheses(s, B, 1, 0u, n_smp, nullptr));
     const uint32_t n_pose = n_hyp * 4;
-    for (uint32_t p0 = 0; P3P && p0 < n_pose; p0 += 65532) {
-        uint32_t np = n_pose - p0 < 65532 ? n_pose - p0 : 65532;     // (65532: whole hypotheses per slab)
-        if (P3P)
+    if (est.world) {
+        // grid.y is limited to 65535: score the poses in slabs
+        for (uint32_t p0 = 0; p0 < n_pose; p0 += 65532) {
+            uint32_t np = n_pose - p0 < 65532 ? n_pose - p0 : 65532;     // (65532: whole hypotheses per slab)
             hipLaunchKernelGGL(k_p3p_score, dim3((n + 255) / 256, np), dim3(256), 0, s, c->d_a, c->d_b, n,
                                c->d_poses + (size_t)p0 * 12, c->d_ok + p0, thresh, c->d_counts + p0);
-        AKZ_LAUNCH_CHECK();
-    }
-    if (!P3P) {
+            AKZ_LAUNCH_CHECK();
+        }
+    } else {
         // the first-block kernel of the ARRSAC-shaped loop over ALL matches: far pairs are discarded by the bound, the rest
         // are dealt to full waves; blockIdx.y splits the match list so that one scene still fills the chip
         AKZ_HIP(hipMemsetAsync(c->d_nalive, 0, sizeof(uint32_t), s));   // (no residual count is kept here)
@@ -1774,11 +1831,10 @@ static int32_t exhaustive_run(rs_ctx* c, const double* in_a, const double* in_b,
     }
     hipLaunchKernelGGL(k_rs_best, dim3(1), dim3(1024), 0, s, c->d_counts, c->d_ok, n_pose, c->d_best);
     AKZ_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_rs_inliers<P3P>), dim3(1), dim3(1024), 0, s, c->d_a, c->d_b, n, c->d_poses, c->d_best, thresh,
-                       c->d_inl, n, c->d_ninl, c->d_best_pose);
+    hipLaunchKernelGGL(est.inliers, dim3(1), dim3(1024), 0, s, c->d_a, c->d_b, n, c->d_poses, c->d_best, thresh, c->d_inl, n, c->d_ninl,
+                       c->d_best_pose);
     AKZ_LAUNCH_CHECK();
-    c->last_hyp = n_hyp;
-    c->last_five_samples = five ? n_smp : 0u;
+    rs_note_call(c, est, n_smp, true);
     return rs_fetch_single(c, best_pose, best_id, inlier_idx, cap, n_inliers, nullptr, nullptr);
 }
 
@@ -1787,20 +1843,18 @@ extern "C" int32_t rs_essential_batch(rs_ctx* c, const double* bearings_a, const
                                       uint32_t* best_id, uint32_t* inlier_idx, uint32_t cap, uint32_t* n_inliers)
 {
     return akz_guard([&]() -> int32_t {
-        return exhaustive_run<false>(c, bearings_a, bearings_b, n, sample_idx, n_hyp, thresh, best_pose, best_id, inlier_idx, cap,
-                                     n_inliers);
+        return exhaustive_run(c, kEightPoint, bearings_a, bearings_b, n, sample_idx, n_hyp, thresh, best_pose, best_id, inlier_idx, cap, n_inliers);
     });
 }
 
-// Consensus::model_inliers(&NisterStewenius::new(), matches) with the sampler factored out: n_samples minimal samples of
-// five matches, up to ten essential matrices each; best_id = (10 sample + solution) 4 + pose
+// Consensus::model_inliers(&NisterStewenius::new(), matches) with the sampler factored out: n_samples minimal samples, up to
+// ten essential matrices each; best_id = (10 sample + solution) 4 + pose
 extern "C" int32_t rs_five_point_batch(rs_ctx* c, const double* bearings_a, const double* bearings_b, uint32_t n,
                                        const uint32_t* sample_idx, uint32_t n_samples, double thresh, double* best_pose,
                                        uint32_t* best_id, uint32_t* inlier_idx, uint32_t cap, uint32_t* n_inliers)
 {
     return akz_guard([&]() -> int32_t {
-        return exhaustive_run<false>(c, bearings_a, bearings_b, n, sample_idx, n_samples, thresh, best_pose, best_id, inlier_idx, cap,
-                                     n_inliers, true);
+        return exhaustive_run(c, kFivePoint, bearings_a, bearings_b, n, sample_idx, n_samples, thresh, best_pose, best_id, inlier_idx, cap, n_inliers);
     });
 }
 
@@ -1811,63 +1865,50 @@ extern "C" int32_t rs_p3p_batch(rs_ctx* c, const double* bearings, const double*
                                 uint32_t* best_id, uint32_t* inlier_idx, uint32_t cap, uint32_t* n_inliers)
 {
     return akz_guard([&]() -> int32_t {
-        return exhaustive_run<true>(c, bearings, world, n, sample_idx, n_hyp, thresh, best_pose, best_id, inlier_idx, cap, n_inliers);
+        return exhaustive_run(c, kLambdaTwist, bearings, world, n, sample_idx, n_hyp, thresh, best_pose, best_id, inlier_idx, cap, n_inliers);
     });
 }
 
-// two_view: the entry point has a choice of estimator (RS_ESTIMATOR_FIVE_POINT is refused by the P3P ones)
-static int32_t rs_check_params(const rs_ctx* c, const rs_arrsac_params* prm, uint32_t n_max, uint32_t* blocks_max, bool two_view)
+static int32_t rs_check_params(const rs_ctx* c, const RsEstimator& est, const rs_arrsac_params* prm, uint32_t n_max)
 {
     if (prm->struct_size != sizeof(rs_arrsac_params)) return AKZ_E_INVALID;
     if (prm->n_hypotheses == 0 || prm->block_size == 0) return AKZ_E_INVALID;
-    const uint32_t known = RS_PRUNE_BOUND | RS_PRUNE_SPRT | RS_PRUNE_HALVE | (two_view ? (uint32_t)RS_ESTIMATOR_FIVE_POINT : 0u);
+    const uint32_t known = RS_PRUNE_BOUND | RS_PRUNE_SPRT | RS_PRUNE_HALVE | RS_ESTIMATOR_FIVE_POINT;   // (the estimator bit: rs_estimator)
     if (prm->reserved != 0 || (prm->flags & ~known)) return AKZ_E_INVALID;
-    // every block but the last may add E hypotheses: they need room in the context's pose arrays (a five-point sample
-    // takes ten slots: n_hypotheses and estimations_per_block count samples)
-    const uint64_t per = (prm->flags & RS_ESTIMATOR_FIVE_POINT) ? 10u : 1u;
+    // every block but the last may add estimations_per_block samples: their slots need room in the context's pose arrays
     const uint64_t n_blocks_max = ((uint64_t)n_max + prm->block_size - 1) / prm->block_size;
-    if (n_max > c->max_matches || per * prm->n_hypotheses > c->max_hyp ||
-        per * ((uint64_t)prm->n_hypotheses + (uint64_t)prm->estimations_per_block * n_blocks_max) > c->max_hyp)
+    if (n_max > c->max_matches || (uint64_t)est.per * prm->n_hypotheses > c->max_hyp ||
+        est.per * ((uint64_t)prm->n_hypotheses + (uint64_t)prm->estimations_per_block * n_blocks_max) > c->max_hyp)
         return AKZ_E_TOO_LARGE;
     if ((prm->flags & RS_PRUNE_SPRT) && !(prm->sprt_delta > 0.0 && prm->sprt_delta < 1.0 && prm->sprt_ratio > 1.0))
         return AKZ_E_INVALID;
-    *blocks_max = (uint32_t)n_blocks_max;
     return AKZ_OK;
+}
+
+// where a call's results go, the per-call figures still to be filled in by the engine
+static RsOut rs_out(void* best_id, void* pose, void* inl, void* ninl, void* stats, uint32_t inl_stride)
+{
+    return RsOut{(uint32_t*)best_id, (double*)pose, (uint32_t*)inl, (uint32_t*)ninl, (rs_arrsac_stats*)stats, inl_stride, 0, 0, 0, 0, 0, 0};
 }
 
 // The ARRSAC-shaped loop over S scenes whose matches (and d_n) are already in the arena; enqueues everything on the
 // context's stream and returns.  n_max: the host's upper bound of the scenes' match counts (sizes the block loop).
 // have_samples: the minimal samples are already in the arena (single-scene calls with caller samples).
-template <bool P3P>
-static int32_t arrsac_engine(rs_ctx* c, uint32_t S, uint32_t n_max, const rs_arrsac_params* prm, bool have_samples, bool with_order,
-                             const RsOut& out_in, uint32_t* blocks_run, uint32_t* hyp_made)
+// *smp_made: the samples the call had room for, the initial ones and every re-sampling round's.
+static int32_t arrsac_engine(rs_ctx* c, const RsEstimator& est, uint32_t S, uint32_t n_max, const rs_arrsac_params* prm, bool have_samples,
+                             bool with_order, const RsOut& out_in, uint32_t* blocks_run, uint32_t* smp_made)
 {
-    // five-point (two-view only): n_hypotheses and estimations_per_block count SAMPLES, ten hypothesis slots each; from the
-    // hypothesis kernels on, the loop below sees slots and nothing else changes
-    const bool five = !P3P && (prm->flags & RS_ESTIMATOR_FIVE_POINT) != 0;
-    const uint32_t K = P3P ? 3u : (five ? 5u : 8u), per = five ? 10u : 1u;
     hipStream_t s = c->stream;
     const RsB B = rs_view(c, with_order);
-    const uint32_t n_smp = prm->n_hypotheses, E_smp = prm->estimations_per_block;
-    const uint32_t n_hyp = n_smp * per, E = E_smp * per;
-    if (!have_samples) {
-        if (five)
-            hipLaunchKernelGGL((k_rsb_sample<5>), dim3((n_smp + 255) / 256, S), dim3(256), 0, s, B, (unsigned long long)prm->seed, n_smp);
-        else
-            hipLaunchKernelGGL((k_rsb_sample<(P3P ? 3 : 8)>), dim3((n_smp + 255) / 256, S), dim3(256), 0, s, B, (unsigned long long)prm->seed, n_smp);
-        AKZ_LAUNCH_CHECK();
-    }
+    const unsigned long long seed = prm->seed;
+    const uint32_t n_smp = prm->n_hypotheses, E_smp = prm->estimations_per_block;   // samples ...
+    const uint32_t n_hyp = n_smp * est.per, E = E_smp * est.per;                    // ... and their hypothesis slots
+    if (!have_samples) AKZ_TRY(est.draw(s, B, S, seed, n_smp));
     // counters of the initial poses (re-sampled poses zero theirs when they join); slot stride 4 H
     if (S == 1) AKZ_HIP(hipMemsetAsync(c->d_counts, 0, sizeof(uint32_t) * 4 * (size_t)n_hyp, s));
     else AKZ_HIP(hipMemsetAsync(c->d_counts, 0, sizeof(uint32_t) * 4 * (size_t)c->max_hyp * S, s));
     AKZ_HIP(hipMemsetAsync(c->d_neval, 0, sizeof(unsigned long long) * S, s));
-    if (P3P)
-        hipLaunchKernelGGL(k_rsb_p3p_hypotheses, dim3((n_hyp + 63) / 64, S), dim3(64), 0, s, B, 0u, n_hyp, (const uint32_t*)nullptr);
-    else if (five)
-        AKZ_TRY(rs_five_point_launch(s, B, S, 0u, n_smp, nullptr));
-    else
-        hipLaunchKernelGGL(k_rsb_hypotheses, dim3((n_hyp + 63) / 64, S), dim3(64), 0, s, B, 0u, n_hyp, (const uint32_t*)nullptr);
-    AKZ_LAUNCH_CHECK();
+    AKZ_TRY(est.hypotheses(s, B, S, 0u, n_smp, nullptr));
     const uint32_t n_pose = n_hyp * 4;
     hipLaunchKernelGGL(k_rsb_alive_init, dim3(S), dim3(1024), 0, s, B, n_pose);
     AKZ_LAUNCH_CHECK();
@@ -1875,10 +1916,10 @@ static int32_t arrsac_engine(rs_ctx* c, uint32_t S, uint32_t n_max, const rs_arr
     // the live count is known to the host only as an upper bound: n_pose before the cap applies, the cap after
     uint32_t live_bound = n_pose;
     const bool prune = (prm->flags & (RS_PRUNE_BOUND | RS_PRUNE_SPRT)) != 0 || prm->max_candidates != 0 || E != 0;
-    uint32_t next_h = n_hyp;                                  // first hypothesis slot of the next re-sampling round
+    uint32_t next_smp = n_smp;                                // first sample of the next re-sampling round
     auto score = [&](uint32_t m_lo, uint32_t m_hi, uint32_t slots, uint32_t from_first) -> int32_t {
         const uint32_t range = m_hi - m_lo;
-        if constexpr (P3P) {
+        if (est.world) {
             uint32_t gy = range / 64;
             gy = gy < 1 ? 1 : (gy > 16 ? 16 : gy);
             hipLaunchKernelGGL(k_rsb_score_p3p, dim3((slots + 255) / 256, gy, S), dim3(256), 0, s, B, m_lo, m_hi, from_first, prm->threshold);
@@ -1906,7 +1947,7 @@ static int32_t arrsac_engine(rs_ctx* c, uint32_t S, uint32_t n_max, const rs_arr
         // without pruning there is nothing to decide between blocks: one block = all matches
         const uint32_t bs = prune ? prm->block_size : n_max;
         const uint32_t m_hi = m_lo + bs < n_max ? m_lo + bs : n_max;
-        if (!P3P && m_lo == 0) AKZ_TRY(score_first(m_hi));
+        if (!est.world && m_lo == 0) AKZ_TRY(score_first(m_hi));
         else AKZ_TRY(score(m_lo, m_hi, live_bound, 0u));
         ++blocks;
         m_lo = m_hi;
@@ -1934,28 +1975,16 @@ static int32_t arrsac_engine(rs_ctx* c, uint32_t S, uint32_t n_max, const rs_arr
             // a single survivor cannot be overtaken when nothing is re-sampled: the block loop ends (the specification's rule)
             if (P.cap == 1 && E == 0 && (prm->flags & RS_PRUNE_HALVE)) break;
             if (E && blocks >= prm->init_blocks) {
-                // inlier-guided re-sampling: list the inliers (matches seen so far) of the best survivor, draw E minimal
+                // inlier-guided re-sampling: list the inliers (matches seen so far) of the best survivor, draw E_smp minimal
                 // samples among them, estimate, and let the valid poses join the live list after catching up on [0, seen)
-                hipLaunchKernelGGL((k_rsb_best_inliers<P3P>), dim3(S), dim3(kChainNT), 0, s, B, m_lo, 0u, prm->threshold, out_in);
+                hipLaunchKernelGGL(est.best_inliers, dim3(S), dim3(kChainNT), 0, s, B, m_lo, 0u, prm->threshold, out_in);
                 AKZ_LAUNCH_CHECK();
-                if (five)
-                    hipLaunchKernelGGL((k_rsb_resample<5>), dim3((E_smp + 255) / 256, S), dim3(256), 0, s, B, (unsigned long long)prm->seed,
-                                       next_h / 10u, E_smp);
-                else
-                    hipLaunchKernelGGL((k_rsb_resample<(P3P ? 3 : 8)>), dim3((E + 255) / 256, S), dim3(256), 0, s, B,
-                                       (unsigned long long)prm->seed, next_h, E);
-                AKZ_LAUNCH_CHECK();
-                if (P3P)
-                    hipLaunchKernelGGL(k_rsb_p3p_hypotheses, dim3((E + 63) / 64, S), dim3(64), 0, s, B, next_h, E, (const uint32_t*)c->d_enable);
-                else if (five)
-                    AKZ_TRY(rs_five_point_launch(s, B, S, next_h / 10u, E_smp, (const uint32_t*)c->d_enable));
-                else
-                    hipLaunchKernelGGL(k_rsb_hypotheses, dim3((E + 63) / 64, S), dim3(64), 0, s, B, next_h, E, (const uint32_t*)c->d_enable);
-                AKZ_LAUNCH_CHECK();
-                hipLaunchKernelGGL(k_rsb_alive_append, dim3(S), dim3(kChainNT), 0, s, B, next_h * 4, E * 4);
+                AKZ_TRY(est.redraw(s, B, S, seed, next_smp, E_smp));
+                AKZ_TRY(est.hypotheses(s, B, S, next_smp, E_smp, (const uint32_t*)c->d_enable));
+                hipLaunchKernelGGL(k_rsb_alive_append, dim3(S), dim3(kChainNT), 0, s, B, next_smp * est.per * 4, E * 4);
                 AKZ_LAUNCH_CHECK();
                 AKZ_TRY(score(0u, m_lo, 4 * E, 1u));
-                next_h += E;
+                next_smp += E_smp;
                 live_bound += 4 * E;
             }
         }
@@ -1966,54 +1995,44 @@ static int32_t arrsac_engine(rs_ctx* c, uint32_t S, uint32_t n_max, const rs_arr
     O.init_blocks = prm->init_blocks;
     O.blocks_run = blocks;
     O.block_size = prune ? prm->block_size : 0u;
-    O.min_samples = K;
-    hipLaunchKernelGGL((k_rsb_best_inliers<P3P>), dim3(S), dim3(kChainNT), 0, s, B, 0u, 1u, prm->threshold, O);
+    O.min_samples = est.K;
+    hipLaunchKernelGGL(est.best_inliers, dim3(S), dim3(kChainNT), 0, s, B, 0u, 1u, prm->threshold, O);
     AKZ_LAUNCH_CHECK();
     *blocks_run = blocks;
-    *hyp_made = next_h;
+    *smp_made = next_smp;
     return AKZ_OK;
 }
 
-// Consensus::model_inliers in ARRSAC's shape for one scene with host buffers: EightPoint (two bearing sets, 8-match
-// samples) or LambdaTwist (bearings + world points, 3-match samples).  sample_idx == NULL draws the samples on the device.
-template <bool P3P>
-static int32_t arrsac_run(rs_ctx* c, const double* in_a, const double* in_b, uint32_t n, const uint32_t* sample_idx,
+// Consensus::model_inliers in ARRSAC's shape for one scene with host buffers: two bearing sets (EightPoint, or NisterStewenius
+// with RS_ESTIMATOR_FIVE_POINT), or world: bearings + world points (LambdaTwist).  sample_idx == NULL draws the samples on the device.
+static int32_t arrsac_run(rs_ctx* c, bool world, const double* in_a, const double* in_b, uint32_t n, const uint32_t* sample_idx,
                           const rs_arrsac_params* prm, double* best_pose, uint32_t* best_id, uint32_t* inlier_idx,
                           uint32_t cap, uint32_t* n_inliers, rs_arrsac_stats* stats)
 {
-    constexpr uint32_t BW = P3P ? 4u : 3u;                      // doubles per element of the second input
     if (!c || !in_a || !in_b || !prm || !best_pose || !best_id || !n_inliers || (cap && !inlier_idx)) return AKZ_E_INVALID;
     RS_NEED_ARENA(c);
-    const bool five = !P3P && (prm->flags & RS_ESTIMATOR_FIVE_POINT) != 0;
-    const uint32_t K = P3P ? 3u : (five ? 5u : 8u);             // sample size
-    if (n < K) return AKZ_E_INVALID;   // MIN_SAMPLES (eight-point/src/lib.rs:73, lambda-twist/src/lib.rs:333, nister-stewenius/src/lib.rs:308)
-    uint32_t blocks_max = 0;
-    AKZ_TRY(rs_check_params(c, prm, n, &blocks_max, !P3P));
+    const RsEstimator* est = rs_estimator(prm->flags, world);
+    if (!est || n < est->K) return AKZ_E_INVALID;   // MIN_SAMPLES (eight-point/src/lib.rs:73, lambda-twist/src/lib.rs:333, nister-stewenius/src/lib.rs:308)
+    AKZ_TRY(rs_check_params(c, *est, prm, n));
     if (sample_idx)
-        for (size_t i = 0; i < (size_t)prm->n_hypotheses * K; ++i)
+        for (size_t i = 0; i < (size_t)prm->n_hypotheses * est->K; ++i)
             if (sample_idx[i] >= n) return AKZ_E_INVALID;
     AKZ_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     AKZ_HIP(hipMemcpyAsync(c->d_a, in_a, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s));
-    AKZ_HIP(hipMemcpyAsync(c->d_b, in_b, sizeof(double) * BW * (size_t)n, hipMemcpyHostToDevice, s));
+    AKZ_HIP(hipMemcpyAsync(c->d_b, in_b, sizeof(double) * est->BW * (size_t)n, hipMemcpyHostToDevice, s));
     AKZ_HIP(hipMemsetD32Async((hipDeviceptr_t)c->d_n, (int)n, 1, s));
     if (sample_idx)
-        AKZ_HIP(hipMemcpyAsync(c->d_samples, sample_idx, sizeof(uint32_t) * K * (size_t)prm->n_hypotheses, hipMemcpyHostToDevice, s));
-    RsOut O;
-    O.best_id = c->d_best + 3;      // (slot 3 of scene 0's best[4]: the final kernel also fills slots 0..2)
-    O.pose = c->d_best_pose;
-    O.inl = c->d_inl;
-    O.ninl = c->d_ninl;
-    O.stats = nullptr;
-    O.inl_stride = c->max_matches;
-    O.n_hyp = O.resample = O.init_blocks = O.blocks_run = O.block_size = O.min_samples = 0;
-    uint32_t blocks = 0, made = 0;
-    AKZ_TRY((arrsac_engine<P3P>(c, 1, n, prm, sample_idx != nullptr, false, O, &blocks, &made)));
+        AKZ_HIP(hipMemcpyAsync(c->d_samples, sample_idx, sizeof(uint32_t) * est->K * (size_t)prm->n_hypotheses, hipMemcpyHostToDevice, s));
+    // (best id: slot 3 of scene 0's best[4]: the final kernel also fills slots 0..2)
+    const RsOut O = rs_out(c->d_best + 3, c->d_best_pose, c->d_inl, c->d_ninl, nullptr, c->max_matches);
+    uint32_t blocks = 0, smp_made = 0;
+    AKZ_TRY(arrsac_engine(c, *est, 1, n, prm, sample_idx != nullptr, false, O, &blocks, &smp_made));
     uint32_t survivors = 0;
     unsigned long long neval = 0;
     const int32_t st = rs_fetch_single(c, best_pose, best_id, inlier_idx, cap, n_inliers, &survivors, &neval);
-    c->last_hyp = made;
-    c->last_five_samples = five ? made / 10u : 0u;
+    rs_note_call(c, *est, smp_made, true);
+    const uint32_t made = smp_made * est->per;   // hypothesis slots
     if (stats) {
         stats->poses = made * 4;
         stats->survivors = survivors;
@@ -2031,7 +2050,7 @@ extern "C" int32_t rs_essential_arrsac(rs_ctx* c, const double* bearings_a, cons
                                        rs_arrsac_stats* stats)
 {
     return akz_guard([&]() -> int32_t {
-        return arrsac_run<false>(c, bearings_a, bearings_b, n, sample_idx, prm, best_pose, best_id, inlier_idx, cap, n_inliers, stats);
+        return arrsac_run(c, false, bearings_a, bearings_b, n, sample_idx, prm, best_pose, best_id, inlier_idx, cap, n_inliers, stats);
     });
 }
 
@@ -2043,8 +2062,49 @@ extern "C" int32_t rs_p3p_arrsac(rs_ctx* c, const double* bearings, const double
                                  rs_arrsac_stats* stats)
 {
     return akz_guard([&]() -> int32_t {
-        return arrsac_run<true>(c, bearings, world, n, sample_idx, prm, best_pose, best_id, inlier_idx, cap, n_inliers, stats);
+        return arrsac_run(c, true, bearings, world, n, sample_idx, prm, best_pose, best_id, inlier_idx, cap, n_inliers, stats);
     });
+}
+
+static RsCam rs_cam(const rs_camera* k)
+{
+    RsCam r;
+    r.intr[0] = k->fx; r.intr[1] = k->fy; r.intr[2] = k->cx; r.intr[3] = k->cy; r.intr[4] = k->skew;
+    r.k1 = k->k1;
+    r.use_k1 = k->use_k1 ? 1 : 0;
+    r.pad = 0;
+    return r;
+}
+
+// What the two batched device entries share, from the argument checks they have in common to the consensus itself.
+// prepare(stream, B, shuffle) is the entry's own part: it uploads the frame indices and launches its k_rsb_prepare.
+template <class Prepare>
+static int32_t arrsac_batch_device(rs_ctx* c, bool world, uint32_t cap_per_img, uint32_t n_scenes, const rs_arrsac_params* prm, uint32_t flags,
+                                   void* d_pose, void* d_best_id, void* d_inliers, void* d_n_inliers, void* d_stats, void* stream_to_wait,
+                                   Prepare&& prepare)
+{
+    if (cap_per_img == 0 || (flags & ~(uint32_t)RS_BATCH_SHUFFLE)) return AKZ_E_INVALID;
+    if (n_scenes == 0) return AKZ_OK;
+    RS_NEED_ARENA(c);
+    if (n_scenes > c->max_scenes) return AKZ_E_TOO_LARGE;
+    const uint32_t n_max = cap_per_img < c->max_matches ? cap_per_img : c->max_matches;
+    const RsEstimator* est = rs_estimator(prm->flags, world);
+    if (!est || n_max < est->K) return AKZ_E_INVALID;
+    const bool shuffle = (flags & RS_BATCH_SHUFFLE) != 0;
+    if (shuffle && n_max > kRadixSortMax) return AKZ_E_TOO_LARGE;   // the shuffle sorts a scene's keys in LDS
+    AKZ_TRY(rs_check_params(c, *est, prm, n_max));
+    AKZ_HIP(hipSetDevice(c->device));
+    if (stream_to_wait) {
+        AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
+        AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
+    }
+    if (shuffle) AKZ_HIP(hipFuncSetAttribute((const void*)est->prepare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRadixSortLdsBytes));
+    AKZ_TRY(prepare(c->stream, rs_view(c, shuffle), shuffle));
+    uint32_t blocks = 0, smp_made = 0;
+    AKZ_TRY(arrsac_engine(c, *est, n_scenes, n_max, prm, false, shuffle, rs_out(d_best_id, d_pose, d_inliers, d_n_inliers, d_stats, cap_per_img),
+                          &blocks, &smp_made));
+    rs_note_call(c, *est, smp_made, false);
+    return AKZ_OK;
 }
 
 // Two-view verification of a whole micro-batch, device-resident end to end (cv-sfm/src/lib.rs:1385-1412 for every
@@ -2061,53 +2121,19 @@ extern "C" int32_t rs_essential_arrsac_batch_device(rs_ctx* c, const void* d_kps
         if (!c || !d_kps_a || !d_kps_b || !ia || !ib || !d_pairs || !d_npairs || !cam_a || !cam_b || !prm || !d_pose || !d_best_id ||
             !d_inliers || !d_n_inliers)
             return AKZ_E_INVALID;
-        if (cap_per_img == 0 || (flags & ~(uint32_t)RS_BATCH_SHUFFLE) || cam_a->reserved != 0 || cam_b->reserved != 0) return AKZ_E_INVALID;
-        if (n_scenes == 0) return AKZ_OK;
-        RS_NEED_ARENA(c);
-        if (n_scenes > c->max_scenes) return AKZ_E_TOO_LARGE;
-        const uint32_t n_max = cap_per_img < c->max_matches ? cap_per_img : c->max_matches;
-        if (n_max < ((prm->flags & RS_ESTIMATOR_FIVE_POINT) ? 5u : 8u)) return AKZ_E_INVALID;
-        if ((flags & RS_BATCH_SHUFFLE) && n_max > kRadixSortMax) return AKZ_E_TOO_LARGE;   // the shuffle sorts a scene's keys in LDS
-        uint32_t blocks_max = 0;
-        AKZ_TRY(rs_check_params(c, prm, n_max, &blocks_max, true));
-        AKZ_HIP(hipSetDevice(c->device));
-        hipStream_t s = c->stream;
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(s, c->ev, 0));
-        }
-        AKZ_HIP(hipMemcpyAsync(c->d_frames, ia, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, s));
-        AKZ_HIP(hipMemcpyAsync(c->d_frames + c->max_scenes, ib, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, s));
-        auto cam = [](const rs_camera* k) {
-            RsCam r;
-            r.intr[0] = k->fx; r.intr[1] = k->fy; r.intr[2] = k->cx; r.intr[3] = k->cy; r.intr[4] = k->skew;
-            r.k1 = k->k1;
-            r.use_k1 = k->use_k1 ? 1 : 0;
-            r.pad = 0;
-            return r;
-        };
-        const bool shuffle = (flags & RS_BATCH_SHUFFLE) != 0;
-        const RsB B = rs_view(c, shuffle);
-        if (shuffle)
-            AKZ_HIP(hipFuncSetAttribute((const void*)k_rsb_prepare<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRadixSortLdsBytes));
-        hipLaunchKernelGGL(k_rsb_prepare<false>, dim3(n_scenes), dim3(1024), shuffle ? kRadixSortLdsBytes : 0, s, B, (const akz_keypoint*)d_kps_a,
-                           d_kps_b, cap_per_img, (const uint32_t*)c->d_frames,
-                           (const uint32_t*)(c->d_frames + c->max_scenes), (const uint32_t*)d_pairs, (const uint32_t*)d_npairs, cam(cam_a),
-                           cam(cam_b), c->d_n, c->d_a, c->d_b, c->d_order, shuffle ? 1u : 0u, (unsigned long long)prm->seed, cap_per_img);
-        AKZ_LAUNCH_CHECK();
-        RsOut O;
-        O.best_id = (uint32_t*)d_best_id;
-        O.pose = (double*)d_pose;
-        O.inl = (uint32_t*)d_inliers;
-        O.ninl = (uint32_t*)d_n_inliers;
-        O.stats = (rs_arrsac_stats*)d_stats;
-        O.inl_stride = cap_per_img;
-        O.n_hyp = O.resample = O.init_blocks = O.blocks_run = O.block_size = O.min_samples = 0;
-        uint32_t blocks = 0, made = 0;
-        AKZ_TRY((arrsac_engine<false>(c, n_scenes, n_max, prm, false, shuffle, O, &blocks, &made)));
-        c->last_hyp = made;
-        c->last_five_samples = 0;
-        return AKZ_OK;
+        if (cam_a->reserved != 0 || cam_b->reserved != 0) return AKZ_E_INVALID;
+        return arrsac_batch_device(c, false, cap_per_img, n_scenes, prm, flags, d_pose, d_best_id, d_inliers, d_n_inliers, d_stats, stream_to_wait,
+                                   [&](hipStream_t s, const RsB& B, bool shuffle) -> int32_t {
+            uint32_t* d_ia = c->d_frames, *d_ib = c->d_frames + c->max_scenes;
+            AKZ_HIP(hipMemcpyAsync(d_ia, ia, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, s));
+            AKZ_HIP(hipMemcpyAsync(d_ib, ib, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_rsb_prepare<false>, dim3(n_scenes), dim3(1024), shuffle ? kRadixSortLdsBytes : 0, s, B, (const akz_keypoint*)d_kps_a,
+                               d_kps_b, cap_per_img, (const uint32_t*)d_ia, (const uint32_t*)d_ib, (const uint32_t*)d_pairs, (const uint32_t*)d_npairs,
+                               rs_cam(cam_a), rs_cam(cam_b), c->d_n, c->d_a, c->d_b, c->d_order, shuffle ? 1u : 0u, (unsigned long long)prm->seed,
+                               cap_per_img);
+            AKZ_LAUNCH_CHECK();
+            return AKZ_OK;
+        });
     });
 }
 
@@ -2123,49 +2149,18 @@ extern "C" int32_t rs_p3p_arrsac_batch_device(rs_ctx* c, const void* d_kps, uint
     return akz_guard([&]() -> int32_t {
         if (!c || !d_kps || !ik || !d_pairs || !d_npairs || !d_world || !cam || !prm || !d_pose || !d_best_id || !d_inliers || !d_n_inliers)
             return AKZ_E_INVALID;
-        if (n_world == 0) return AKZ_E_INVALID;
-        if (cap_per_img == 0 || (flags & ~(uint32_t)RS_BATCH_SHUFFLE) || cam->reserved != 0) return AKZ_E_INVALID;
-        if (n_scenes == 0) return AKZ_OK;
-        RS_NEED_ARENA(c);
-        if (n_scenes > c->max_scenes) return AKZ_E_TOO_LARGE;
-        const uint32_t n_max = cap_per_img < c->max_matches ? cap_per_img : c->max_matches;
-        if (n_max < 3) return AKZ_E_INVALID;
-        if ((flags & RS_BATCH_SHUFFLE) && n_max > kRadixSortMax) return AKZ_E_TOO_LARGE;
-        uint32_t blocks_max = 0;
-        AKZ_TRY(rs_check_params(c, prm, n_max, &blocks_max, false));
-        AKZ_HIP(hipSetDevice(c->device));
-        hipStream_t s = c->stream;
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(s, c->ev, 0));
-        }
-        AKZ_HIP(hipMemcpyAsync(c->d_frames, ik, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, s));
-        RsCam k;
-        k.intr[0] = cam->fx; k.intr[1] = cam->fy; k.intr[2] = cam->cx; k.intr[3] = cam->cy; k.intr[4] = cam->skew;
-        k.k1 = cam->k1;
-        k.use_k1 = cam->use_k1 ? 1 : 0;
-        k.pad = 0;
-        const bool shuffle = (flags & RS_BATCH_SHUFFLE) != 0;
-        const RsB B = rs_view(c, shuffle);
-        if (shuffle)
-            AKZ_HIP(hipFuncSetAttribute((const void*)k_rsb_prepare<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRadixSortLdsBytes));
-        hipLaunchKernelGGL(k_rsb_prepare<true>, dim3(n_scenes), dim3(1024), shuffle ? kRadixSortLdsBytes : 0, s, B, (const akz_keypoint*)d_kps,
-                           d_world, cap_per_img, (const uint32_t*)c->d_frames, (const uint32_t*)c->d_frames, (const uint32_t*)d_pairs,
-                           (const uint32_t*)d_npairs, k, k, c->d_n, c->d_a, c->d_b, c->d_order, shuffle ? 1u : 0u,
-                           (unsigned long long)prm->seed, n_world);
-        AKZ_LAUNCH_CHECK();
-        RsOut O;
-        O.best_id = (uint32_t*)d_best_id;
-        O.pose = (double*)d_pose;
-        O.inl = (uint32_t*)d_inliers;
-        O.ninl = (uint32_t*)d_n_inliers;
-        O.stats = (rs_arrsac_stats*)d_stats;
-        O.inl_stride = cap_per_img;
-        O.n_hyp = O.resample = O.init_blocks = O.blocks_run = O.block_size = O.min_samples = 0;
-        uint32_t blocks = 0, made = 0;
-        AKZ_TRY((arrsac_engine<true>(c, n_scenes, n_max, prm, false, shuffle, O, &blocks, &made)));
-        c->last_hyp = made;
-        return AKZ_OK;
+        if (n_world == 0 || cam->reserved != 0) return AKZ_E_INVALID;
+        return arrsac_batch_device(c, true, cap_per_img, n_scenes, prm, flags, d_pose, d_best_id, d_inliers, d_n_inliers, d_stats, stream_to_wait,
+                                   [&](hipStream_t s, const RsB& B, bool shuffle) -> int32_t {
+            AKZ_HIP(hipMemcpyAsync(c->d_frames, ik, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, s));
+            const RsCam k = rs_cam(cam);
+            hipLaunchKernelGGL(k_rsb_prepare<true>, dim3(n_scenes), dim3(1024), shuffle ? kRadixSortLdsBytes : 0, s, B, (const akz_keypoint*)d_kps,
+                               d_world, cap_per_img, (const uint32_t*)c->d_frames, (const uint32_t*)c->d_frames, (const uint32_t*)d_pairs,
+                               (const uint32_t*)d_npairs, k, k, c->d_n, c->d_a, c->d_b, c->d_order, shuffle ? 1u : 0u,
+                               (unsigned long long)prm->seed, n_world);
+            AKZ_LAUNCH_CHECK();
+            return AKZ_OK;
+        });
     });
 }
 

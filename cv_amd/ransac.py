@@ -59,35 +59,28 @@ class EssentialConsensus:
         except Exception:
             pass
 
-    def model_inliers(self, bearings_a, bearings_b, sample_idx, threshold):
-        """Returns (pose [3,4] = [R | t], inlier indices, best_id) or None when no sample gave a model."""
-        a = np.ascontiguousarray(bearings_a, np.float64); b = np.ascontiguousarray(bearings_b, np.float64)
-        si = np.ascontiguousarray(sample_idx, np.uint32).reshape(-1, 8)
+    def _exhaustive(self, fn, width, first, second, sample_idx, threshold):
+        """The exhaustive single-scene call `fn` of include/akz.h on samples of `width` matches: (pose, inliers, best_id) or None."""
+        a = np.ascontiguousarray(first, np.float64); b = np.ascontiguousarray(second, np.float64)
+        si = np.ascontiguousarray(sample_idx, np.uint32).reshape(-1, width)
         n = len(a)
         pose = np.empty((3, 4), np.float64); best = C.c_uint32(); ninl = C.c_uint32()
         inl = np.empty(max(n, 1), np.uint32)
-        check(_lib.lib().rs_essential_batch(self._h, a.ctypes.data, b.ctypes.data, n, si.ctypes.data, len(si),
-                                            float(threshold), pose.ctypes.data, C.byref(best), inl.ctypes.data, n,
-                                            C.byref(ninl)), "rs_essential_batch")
+        check(getattr(_lib.lib(), fn)(self._h, a.ctypes.data, b.ctypes.data, n, si.ctypes.data, len(si), float(threshold),
+                                      pose.ctypes.data, C.byref(best), inl.ctypes.data, n, C.byref(ninl)), fn)
         if best.value == 0xFFFFFFFF:
             return None
         return pose, inl[:ninl.value].copy(), best.value
+
+    def model_inliers(self, bearings_a, bearings_b, sample_idx, threshold):
+        """Returns (pose [3,4] = [R | t], inlier indices, best_id) or None when no sample gave a model."""
+        return self._exhaustive("rs_essential_batch", 8, bearings_a, bearings_b, sample_idx, threshold)
 
     def five_point_model_inliers(self, bearings_a, bearings_b, sample_idx, threshold):
         """Consensus::model_inliers(&NisterStewenius::new(), ...) with the sampler factored out (rs_five_point_batch):
         sample_idx [n_samples, 5]; the context needs 10 x n_samples hypothesis slots.  Returns (pose [3,4], inlier indices,
         best_id = (10 sample + solution) 4 + pose) or None when no sample gave a model."""
-        a = np.ascontiguousarray(bearings_a, np.float64); b = np.ascontiguousarray(bearings_b, np.float64)
-        si = np.ascontiguousarray(sample_idx, np.uint32).reshape(-1, 5)
-        n = len(a)
-        pose = np.empty((3, 4), np.float64); best = C.c_uint32(); ninl = C.c_uint32()
-        inl = np.empty(max(n, 1), np.uint32)
-        check(_lib.lib().rs_five_point_batch(self._h, a.ctypes.data, b.ctypes.data, n, si.ctypes.data, len(si),
-                                             float(threshold), pose.ctypes.data, C.byref(best), inl.ctypes.data, n,
-                                             C.byref(ninl)), "rs_five_point_batch")
-        if best.value == 0xFFFFFFFF:
-            return None
-        return pose, inl[:ninl.value].copy(), best.value
+        return self._exhaustive("rs_five_point_batch", 5, bearings_a, bearings_b, sample_idx, threshold)
 
     def essentials(self, n_samples):
         """(E [n_samples, 10, 3, 3] with b^T E a = 0, unused slots zero; n_solutions [n_samples]) of the last single-scene
@@ -108,18 +101,13 @@ class EssentialConsensus:
         estimator="five_point": NisterStewenius instead of EightPoint (RS_ESTIMATOR_FIVE_POINT): n_hypotheses and
         estimations_per_block count 5-match samples, ten hypothesis slots each; sample_idx is [n, 5].
         Returns (pose, inliers, best_id, stats dict) or None."""
-        five = _estimator_flag(estimator)
+        prm = self.make_params(threshold, n_hypotheses, seed, block_size, init_blocks, max_candidates, bound, sprt, sprt_delta,
+                               sprt_ratio, estimations_per_block, halve, estimator)
+        five = prm.flags & _lib.RS_ESTIMATOR_FIVE_POINT
         if five and p3p:
             raise ValueError("estimator applies to the two-view consensus")
         a = np.ascontiguousarray(bearings_a, np.float64); b = np.ascontiguousarray(bearings_b, np.float64)
         n = len(a)
-        prm = _lib.ArrsacParams()
-        prm.struct_size = C.sizeof(_lib.ArrsacParams)
-        prm.n_hypotheses, prm.block_size, prm.init_blocks, prm.max_candidates = n_hypotheses, block_size, init_blocks, max_candidates
-        prm.flags = ((_lib.RS_PRUNE_BOUND if bound else 0) | (_lib.RS_PRUNE_SPRT if sprt else 0)
-                     | (_lib.RS_PRUNE_HALVE if halve else 0) | five)
-        prm.estimations_per_block, prm.reserved = estimations_per_block, 0
-        prm.threshold, prm.sprt_delta, prm.sprt_ratio, prm.seed = float(threshold), sprt_delta, sprt_ratio, seed
         si = None
         if sample_idx is not None:
             si = np.ascontiguousarray(sample_idx, np.uint32).reshape(-1, 3 if p3p else (5 if five else 8))
@@ -148,16 +136,7 @@ class EssentialConsensus:
     def p3p_model_inliers(self, bearings, world, sample_idx, threshold):
         """Consensus::model_inliers(&LambdaTwist::new(), ...): bearings [n,3], world [n,4] homogeneous
         (Projective form), sample_idx [n_hyp,3].  Returns (pose [3,4], inliers, best_id) or None."""
-        b = np.ascontiguousarray(bearings, np.float64); w = np.ascontiguousarray(world, np.float64)
-        si = np.ascontiguousarray(sample_idx, np.uint32).reshape(-1, 3)
-        n = len(b)
-        pose = np.empty((3, 4), np.float64); best = C.c_uint32(); ninl = C.c_uint32()
-        inl = np.empty(max(n, 1), np.uint32)
-        check(_lib.lib().rs_p3p_batch(self._h, b.ctypes.data, w.ctypes.data, n, si.ctypes.data, len(si), float(threshold),
-                                      pose.ctypes.data, C.byref(best), inl.ctypes.data, n, C.byref(ninl)), "rs_p3p_batch")
-        if best.value == 0xFFFFFFFF:
-            return None
-        return pose, inl[:ninl.value].copy(), best.value
+        return self._exhaustive("rs_p3p_batch", 3, bearings, world, sample_idx, threshold)
 
     def poses(self, n_hyp):
         """(poses [n_hyp,4,3,4], ok [n_hyp,4]) of the last single-scene call (rs_debug_poses)."""

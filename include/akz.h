@@ -540,7 +540,9 @@ int32_t rs_debug_counts(rs_ctx* ctx, uint32_t* counts, uint32_t cap);
 int32_t rs_debug_poses(rs_ctx* ctx, double* poses, uint32_t* ok, uint32_t n_hyp);
 /* parity tap: the essential matrices E [n_samples][10][9] (row-major, b^T E a = 0; slots beyond a sample's count are
  * zero-filled) and the solution counts [n_samples] of the last single-scene five-point call (rs_five_point_batch, or
- * rs_essential_arrsac with RS_ESTIMATOR_FIVE_POINT).  rs_debug_poses / rs_debug_counts see n_hyp = 10 x n_samples. */
+ * rs_essential_arrsac with RS_ESTIMATOR_FIVE_POINT).  rs_debug_poses / rs_debug_counts see n_hyp = 10 x n_samples.
+ * Any other consensus call on the context since — another estimator, or a batched device entry — leaves nothing to read:
+ * AKZ_E_INVALID for n_samples >= 1. */
 int32_t rs_debug_essentials(rs_ctx* ctx, double* E, uint32_t* n_solutions, uint32_t n_samples);
 
 /* parity tap: CameraToCamera::residual (cv-core/src/pose.rs:249-295) of every (pose, match) as the device evaluates it.

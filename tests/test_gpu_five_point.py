@@ -323,3 +323,49 @@ def test_an_exact_scene_recovers_the_motion(gpu):
     assert np.linalg.norm(pose[:, :3] - r) < 10 * TOL_E
     d = pose[:, 3] / np.linalg.norm(pose[:, 3])
     assert np.linalg.norm(d - t / np.linalg.norm(t)) < 10 * TOL_E
+
+
+@pytest.mark.parametrize("then", ["batched p3p", "eight point"])
+def test_essentials_tap_answers_only_for_the_last_five_point_call(gpu, then):
+    """rs_debug_essentials reads the matrices of the last single-scene five-point call: after any other consensus call on the
+    context — a valid one-scene rs_p3p_arrsac_batch_device, or rs_essential_batch — it refuses (AKZ_E_INVALID = -1) instead of
+    returning the earlier call's matrices."""
+    import torch
+    from cv_amd import _lib
+    from test_oracle_arrsac import _registration_scene
+    rng = np.random.default_rng(0xE8AC7)
+    a, b, r, t, _ = st.scene(rng, n=60)
+    samples = np.stack([rng.choice(60, 5, replace=False) for _ in range(16)]).astype(np.uint32)
+    cons = gpu.EssentialConsensus(64, 160)
+    cons.reserve(1)
+    assert cons.five_point_model_inliers(a, b, samples, 1e-12) is not None
+    E, n = cons.essentials(16)
+    assert n.max() >= 1
+    if then == "batched p3p":
+        cap, n_world = 64, 80
+        cam = (950.0, 955.0, 640.0, 250.0, 0.0, None)
+        kps, world, pr, *_ = _registration_scene(rng, cap, n_world, 48, 0.3, cam)
+        pairs = np.zeros((1, cap, 2), np.uint32)
+        pairs[0, :len(pr)] = pr
+        dev = torch.device("cuda", 0)
+        d_k = torch.from_numpy(kps.view(np.uint8).reshape(1, cap, 28)).to(dev)
+        d_pairs = torch.from_numpy(pairs.view(np.int32)).to(dev)
+        d_np = torch.from_numpy(np.array([len(pr)], np.uint32).view(np.int32)).to(dev)
+        d_world = torch.from_numpy(world).to(dev)
+        d_pose = torch.zeros((1, 12), dtype=torch.float64, device=dev)
+        d_best = torch.zeros((1,), dtype=torch.int32, device=dev)
+        d_inl = torch.zeros((1, cap), dtype=torch.int32, device=dev)
+        d_ninl = torch.zeros((1,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        prm = cons.make_params(1e-6, n_hypotheses=16, seed=5)
+        cons.p3p_model_inliers_batch_device(d_k.data_ptr(), cap, [0], d_pairs.data_ptr(), d_np.data_ptr(), d_world.data_ptr(), n_world,
+                                            cons.camera(cam), prm, d_pose.data_ptr(), d_best.data_ptr(), d_inl.data_ptr(),
+                                            d_ninl.data_ptr(), shuffle=False)
+        cons.sync()
+        assert int(d_ninl.cpu().numpy().view(np.uint32)[0]) <= len(pr)
+    else:
+        eight = np.stack([rng.choice(60, 8, replace=False) for _ in range(16)]).astype(np.uint32)
+        assert cons.model_inliers(a, b, eight, 1e-12) is not None
+    out_E = np.zeros((1, 10, 9), np.float64); out_n = np.zeros(1, np.uint32)
+    assert _lib.lib().rs_debug_essentials(cons._h, out_E.ctypes.data, out_n.ctypes.data, 1) == -1
+    cons.close()
