@@ -113,6 +113,22 @@ class TriangulateParams(C.Structure):
                 ("incidence_minimum_cosine_distance", C.c_double)]
 
 
+class ThreeViewParams(C.Structure):
+    """rs_three_view_params (include/akz.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("robust_view_num_robust_bearing_pair", C.c_uint32),
+                ("maximum_cosine_distance", C.c_double), ("maximum_sine_distance", C.c_double),
+                ("robust_observation_incidence_minimum_cosine_distance", C.c_double),
+                ("robust_view_bearing_pair_minimum_cosine_distance", C.c_double), ("optimization_rate", C.c_double),
+                ("three_view_minimum_relative_scales", C.c_uint32), ("three_view_filter_loop_iterations", C.c_uint32),
+                ("three_view_optimization_landmarks", C.c_uint32), ("three_view_patience", C.c_uint32),
+                ("three_view_minimum_robust_matches", C.c_uint32), ("hard_minimum_matches", C.c_uint32),
+                ("triangulate", TriangulateParams)]
+
+
+RS_TV_OK, RS_TV_FEW_SCALES, RS_TV_FEW_BEARING_PAIRS, RS_TV_FEW_MATCHES, RS_TV_LOST_HALF, RS_TV_FEW_ROBUST, RS_TV_BAD_INDEX = range(7)
+RS_TV_MAX_LANDMARKS, RS_TV_MAX_RUNS, RS_TV_MAX_ITERATIONS, RS_TV_MAX_COMMON, RS_TV_STATS = 1024, 9, 1 << 20, 9216, 24
+RS_TV_S_SCALES, RS_TV_S_MEDIAN, RS_TV_S_PAIRS, RS_TV_S_RUN_MATCHES, RS_TV_S_RUN_STOP, RS_TV_S_ROBUST, RS_TV_S_STAGE = 0, 1, 3, 4, 13, 22, 23
+
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
 
@@ -135,7 +151,7 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("size", "
 NB_DTYPE = np.dtype([("index", "<u4"), ("distance", "<u4")])
 assert KP_DTYPE.itemsize == 28 and NB_DTYPE.itemsize == 8
 
-ABI_VERSION = 10         # include/akz.h AKZ_ABI_VERSION this file's argtypes were written against
+ABI_VERSION = 11         # include/akz.h AKZ_ABI_VERSION this file's argtypes were written against
 
 # every symbol include/akz.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
@@ -151,7 +167,7 @@ ABI_SYMBOLS = [
     "rs_p3p_batch", "rs_debug_counts", "rs_debug_poses", "rs_batch_reserve", "rs_essential_arrsac_batch_device", "rs_sync",
     "rs_stream", "rs_debug_scene", "rs_debug_residuals", "rs_p3p_arrsac_batch_device", "hm_landmark_pairs_batch_device", "hm_landmark_matches_batch_device", "hm_landmark_matches_ordered_batch_device", "hm_set_targets", "hm_targets_generation", "hm_knn_targets", "rs_debug_scene_world", "rs_debug_far",
     "rs_triangulate_params_default", "rs_triangulate_observations", "rs_triangulate_landmarks_device", "rs_triangulate_merged_device",
-    "rs_triangulate_pairs_batch_device",
+    "rs_triangulate_pairs_batch_device", "rs_three_view_params_default", "rs_three_view_init_batch_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -278,6 +294,9 @@ def lib():
                                                vp, vp, vp]
     L.rs_triangulate_pairs_batch_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, C.POINTER(Camera), C.POINTER(Camera),
                                                     vp, vp, vp, vp, tp, vp, vp, vp]
+    L.rs_three_view_params_default.argtypes = [C.POINTER(ThreeViewParams)]
+    L.rs_three_view_init_batch_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, C.POINTER(Camera), vp, vp, vp, vp, vp, vp, vp, vp, u32,
+                                                  C.POINTER(ThreeViewParams), vp, vp, vp, vp, vp, vp, vp]
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

@@ -126,7 +126,7 @@ static inline int32_t akz_guard(F&& f) noexcept
 }
 
 // What rs_triangulate.hip needs of an rs_ctx (defined in rs_ransac.hip): its device, its stream and wait event, and the
-// per-scene frame lists of the batch arena ([2][max_scenes] u32; max_scenes == 0: no arena).
+// per-scene frame lists of the batch arena ([3][max_scenes] u32; max_scenes == 0: no arena).
 struct RsHandles {
     int device;
     hipStream_t stream;

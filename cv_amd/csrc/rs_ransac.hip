@@ -1499,7 +1499,7 @@ static std::vector<RsSlot> rs_arena_slots(RsArena* A, size_t n, size_t H)
 {
     const size_t u = sizeof(uint32_t), d = sizeof(double);
     auto at = [](auto** p, size_t bytes) { return RsSlot{(void**)p, bytes}; };
-    return {at(&A->d_n, u), at(&A->d_nalive, u), at(&A->d_ninl, u), at(&A->d_first, u), at(&A->d_enable, u), at(&A->d_frames, 2 * u),
+    return {at(&A->d_n, u), at(&A->d_nalive, u), at(&A->d_ninl, u), at(&A->d_first, u), at(&A->d_enable, u), at(&A->d_frames, 3 * u),
             at(&A->d_a, 3 * n * d), at(&A->d_b, 4 * n * d), at(&A->d_order, n * u), at(&A->d_inl, n * u),
             at(&A->d_samples, 8 * H * u), at(&A->d_poses, 48 * H * d), at(&A->d_ok, 4 * H * u), at(&A->d_counts, 4 * H * u), at(&A->d_alive, 4 * H * u),
             at(&A->d_neval, sizeof(unsigned long long)), at(&A->d_best, 4 * u), at(&A->d_best_pose, 12 * d), at(&A->d_stats, sizeof(rs_arrsac_stats)),

@@ -1,0 +1,125 @@
+"""Host-side mirror of cv-sfm's three-view bootstrap over rs_three_view_init_batch_device of include/akz.h.
+
+  VSlam::init_reconstruction, from the common matches on     cv-sfm/src/lib.rs:1002-1300
+  three_view_simple_optimize_l2                               cv-optimize/src/three_view_optimizer.rs:126-200
+  the join of the two pair lists (stays with the caller)     cv-sfm/src/lib.rs:992-998, 1190-1191, 1216, 1234
+
+Every triple is worked by one persistent workgroup on the device (cv_amd/csrc/rs_three_view.hip); there is no CPU fallback.
+The join and the shuffle of the common matches use the caller's HashMap and RNG in the reference and stay on the host here:
+`join_pairs` builds the three index lists in the reference's order.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+
+VERDICTS = ("ok", "few_scales", "few_bearing_pairs", "few_matches", "lost_half", "few_robust", "bad_index")
+
+
+def join_pairs(first_pairs, second_pairs, permutation=None):
+    """(triples [n][3] {centre, first, second}, first_only [m][2], second_only [k][2]) u32 from the inlier lists
+    [(centre, first)] and [(centre, second)] of two consensuses.  As the reference: a HashMap centre -> other feature per
+    list (a centre feature that occurs twice keeps its LAST entry), triples in the order of first_pairs, the one-pair lists in
+    the order of their own pair list.  `permutation` (of range(n)) is the shuffle of lib.rs:999, the caller's RNG."""
+    fp = np.asarray(first_pairs, np.int64).reshape(-1, 2)
+    sp = np.asarray(second_pairs, np.int64).reshape(-1, 2)
+    second_map = {int(c): int(s) for c, s in sp}
+    first_map = {int(c): int(f) for c, f in fp}
+    triples = np.array([(c, f, second_map[c]) for c, f in fp.tolist() if c in second_map], np.uint32).reshape(-1, 3)
+    if permutation is not None:
+        perm = np.asarray(permutation, np.int64)
+        if sorted(perm.tolist()) != list(range(len(triples))):
+            raise ValueError("permutation must be a permutation of the common matches")
+        triples = triples[perm]
+    first_only = np.array([(c, f) for c, f in fp.tolist() if c not in second_map], np.uint32).reshape(-1, 2)
+    second_only = np.array([(c, s) for c, s in sp.tolist() if c not in first_map], np.uint32).reshape(-1, 2)
+    return triples, first_only, second_only
+
+
+@dataclass
+class ThreeViewResult:
+    verdict: int
+    poses: np.ndarray        # [2][3][4] CameraToCamera centre -> first / second, or None
+    combined: np.ndarray     # bool per common match, or None
+    first_ok: np.ndarray
+    second_ok: np.ndarray
+    stats: np.ndarray        # [RS_TV_STATS] u32
+
+    @property
+    def verdict_name(self):
+        return VERDICTS[self.verdict]
+
+    @property
+    def median_scale(self):
+        return float(self.stats[_lib.RS_TV_S_MEDIAN:_lib.RS_TV_S_MEDIAN + 2].copy().view(np.float64)[0])
+
+
+class ThreeViewInit:
+    """The three-view bootstrap on the context (and stream) of an EssentialConsensus, so that it queues behind that
+    object's consensus calls."""
+
+    def __init__(self, consensus):
+        self._cons = consensus
+
+    @staticmethod
+    def params(**kw):
+        """rs_three_view_params: the reference's defaults (cv-sfm/src/settings.rs:320-427) with `kw` on top; `triangulate`
+        takes an rs_triangulate_params (cv_amd.triangulation.make_params)."""
+        p = _lib.ThreeViewParams()
+        check(_lib.lib().rs_three_view_params_default(C.byref(p)), "rs_three_view_params_default")
+        for k, v in kw.items():
+            if k == "struct_size" or not hasattr(p, k):
+                raise TypeError(f"rs_three_view_params has no setting {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def init_batch_device(self, d_kps, cap_per_img, n_blocks, ic, i_first, i_second, cam, d_pose_first, d_pose_second, d_triples,
+                          d_ntriples, d_first_only, d_nfirst, d_second_only, d_nsecond, params, d_pose_out, d_verdict, d_combined,
+                          d_first_ok, d_second_ok, d_stats, stream_to_wait=None):
+        """rs_three_view_init_batch_device: arguments named d_* are device pointers (ints), ic / i_first / i_second host lists of
+        keypoint-block indices, one per scene.  Enqueues on the consensus' stream and returns; its sync() waits."""
+        n = len(ic)
+        if len(i_first) != n or len(i_second) != n:
+            raise ValueError("one centre, first and second block per scene")
+        a, b, c = ((C.c_uint32 * n)(*x) for x in (ic, i_first, i_second))
+        check(_lib.lib().rs_three_view_init_batch_device(
+            self._cons._h, d_kps, cap_per_img, n_blocks, a, b, c, C.byref(cam), d_pose_first, d_pose_second, d_triples, d_ntriples,
+            d_first_only, d_nfirst, d_second_only, d_nsecond, n, C.byref(params), d_pose_out, d_verdict, d_combined, d_first_ok,
+            d_second_ok, d_stats, stream_to_wait), "rs_three_view_init_batch_device")
+
+    def init(self, torch, keypoints, cam, pose_first, pose_second, first_pairs, second_pairs, params=None, permutation=None, device=0):
+        """One triple from host arrays: keypoints = (centre, first, second) KP_DTYPE arrays, the two CameraToCamera poses
+        [3][4] and inlier pair lists of the consensuses.  Copies, runs the device call, waits.  -> ThreeViewResult."""
+        triples, first_only, second_only = join_pairs(first_pairs, second_pairs, permutation)
+        cap = max(1, max(len(k) for k in keypoints), len(triples), len(first_only), len(second_only))
+        kps = np.zeros((3, cap), _lib.KP_DTYPE)
+        for k in range(3):
+            kps[k, :len(keypoints[k])] = np.asarray(keypoints[k], _lib.KP_DTYPE)
+        dev = torch.device("cuda", device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+
+        def padded(a, w):
+            out = np.zeros((cap, w), np.uint32)
+            out[:len(a)] = a
+            return out
+
+        d_kps, d_t, d_f, d_s = up(kps), up(padded(triples, 3)), up(padded(first_only, 2)), up(padded(second_only, 2))
+        d_n = up(np.array([len(triples), len(first_only), len(second_only)], np.uint32))
+        d_pf, d_ps = up(np.asarray(pose_first, np.float64).reshape(12)), up(np.asarray(pose_second, np.float64).reshape(12))
+        d_pose = torch.zeros(24, dtype=torch.float64, device=dev)
+        d_masks = torch.zeros((3, cap), dtype=torch.uint8, device=dev)
+        d_out = torch.zeros(1 + _lib.RS_TV_STATS, dtype=torch.int32, device=dev)
+        self.init_batch_device(d_kps.data_ptr(), cap, 3, [0], [1], [2], cam, d_pf.data_ptr(), d_ps.data_ptr(), d_t.data_ptr(),
+                               d_n.data_ptr(), d_f.data_ptr(), d_n.data_ptr() + 4, d_s.data_ptr(), d_n.data_ptr() + 8,
+                               params or self.params(), d_pose.data_ptr(), d_out.data_ptr(), d_masks[0].data_ptr(), d_masks[1].data_ptr(),
+                               d_masks[2].data_ptr(), d_out.data_ptr() + 4, _lib.wait_handle(torch.cuda.current_stream(dev)))
+        self._cons.sync()
+        out = d_out.cpu().numpy().view(np.uint32)
+        ok = int(out[0]) == _lib.RS_TV_OK
+        masks = d_masks.cpu().numpy().astype(bool)
+        return ThreeViewResult(int(out[0]), d_pose.cpu().numpy().reshape(2, 3, 4) if ok else None,
+                               masks[0, :len(triples)] if ok else None, masks[1, :len(first_only)] if ok else None,
+                               masks[2, :len(second_only)] if ok else None, out[1:].copy())

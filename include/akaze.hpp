@@ -646,6 +646,53 @@ private:
 };
 }  // namespace cv_geom
 
+// cv-sfm's three-view bootstrap (VSlam::init_reconstruction from its common matches on, cv-sfm/src/lib.rs:1002-1300) over
+// rs_three_view_init_batch_device: every argument named d_* is device memory the caller owns (the layouts are include/akz.h's),
+// the call enqueues on stream() and returns.  The join of the two pair lists and the shuffle stay with the caller.
+namespace cv_sfm {
+class ThreeViewInit {
+public:
+    // room for `max_scenes` triples per call
+    explicit ThreeViewInit(uint32_t max_scenes = 1, int device = 0)
+    {
+        akaze::require_abi();
+        rs_three_view_params_default(&p_);
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+        const int32_t st = rs_batch_reserve(ctx_, max_scenes);
+        if (st != AKZ_OK) {
+            rs_destroy(ctx_);
+            akaze::check(st, "rs_batch_reserve");
+        }
+    }
+    ~ThreeViewInit() { if (ctx_) rs_destroy(ctx_); }
+    ThreeViewInit(const ThreeViewInit&) = delete;
+    ThreeViewInit& operator=(const ThreeViewInit&) = delete;
+    rs_three_view_params& params() { return p_; }   // the reference's defaults (cv-sfm/src/settings.rs:320-427) to begin with
+    const rs_three_view_params& params() const { return p_; }
+    // one block index per scene in ic / i_first / i_second; outputs as include/akz.h documents them
+    void init_batch_device(const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks, const std::vector<uint32_t>& ic,
+                           const std::vector<uint32_t>& i_first, const std::vector<uint32_t>& i_second, const rs_camera& cam,
+                           const void* d_pose_first, const void* d_pose_second, const void* d_triples, const void* d_ntriples,
+                           const void* d_first_only, const void* d_nfirst, const void* d_second_only, const void* d_nsecond,
+                           void* d_pose_out, void* d_verdict, void* d_combined, void* d_first_ok, void* d_second_ok, void* d_stats,
+                           void* stream_to_wait = nullptr)
+    {
+        if (i_first.size() != ic.size() || i_second.size() != ic.size()) throw std::invalid_argument("one centre, first and second block per scene");
+        akaze::check(rs_three_view_init_batch_device(ctx_, d_kps, cap_per_img, n_blocks, ic.data(), i_first.data(), i_second.data(), &cam,
+                                                     d_pose_first, d_pose_second, d_triples, d_ntriples, d_first_only, d_nfirst, d_second_only,
+                                                     d_nsecond, (uint32_t)ic.size(), &p_, d_pose_out, d_verdict, d_combined, d_first_ok,
+                                                     d_second_ok, d_stats, stream_to_wait),
+                     "rs_three_view_init_batch_device");
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_three_view_params p_;
+    rs_ctx* ctx_ = nullptr;
+};
+}  // namespace cv_sfm
+
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over
 // hm_hash_bag / hm_hash_knn.  The hashing crate is not vendored in the reference: see oracle/lsh_oracle.c for what
 // is restated (nearest-codeword bag hash, one bit per codeword).

@@ -671,6 +671,80 @@ int32_t rs_triangulate_pairs_batch_device(rs_ctx* ctx, const void* d_kps_a, cons
                                           uint32_t n_scenes, const rs_camera* cam_a, const rs_camera* cam_b, const void* d_pose,
                                           const void* d_best_id, const void* d_inliers, const void* d_n_inliers,
                                           const rs_triangulate_params* params, void* d_points, void* d_reason, void* stream_to_wait);
+/* ---- the three-view bootstrap of a reconstruction on the device ----
+ * What cv-sfm's VSlam::init_reconstruction does for ONE combination of two two-view consensuses of a centre frame
+ * (cv-sfm/src/lib.rs:1002-1300), for n_scenes combinations side by side: the depth ratios of the common matches and their
+ * median as the scale of the second pose, the optimisation matches (the first three_view_optimization_landmarks that pass
+ * is_tri_landmark_robust, in list order), the robust bearing pairs, three_view_filter_loop_iterations + 1 runs of
+ * three_view_simple_optimize_l2 (cv-optimize/src/three_view_optimizer.rs:126-200) with the filter between them, and the
+ * final masks and counts.  One persistent workgroup per triple, one launch.  The arithmetic is
+ * include/akz_three_view_math.h (compiled for the device and, by the tests, for the host: equal bit for bit); its head
+ * lists what is unpinned against the reference — nalgebra's from_scaled_axis, and the order of the sum over landmarks,
+ * which is fixed there.  The HashMap join of the two pair lists and the shuffle (lib.rs:992-999) use the caller's RNG and
+ * stay with the caller.
+ * Verdicts.  The reference `continue`s to the next combination on every one of them but RS_TV_FEW_BEARING_PAIRS, where it
+ * `return`s None: a caller that mirrors it ends its whole search there. */
+enum {
+    RS_TV_OK = 0,
+    RS_TV_FEW_SCALES = 1,         /* fewer than three_view_minimum_relative_scales depth ratios (lib.rs:1039): continue */
+    RS_TV_FEW_BEARING_PAIRS = 2,  /* fewer than robust_view_num_robust_bearing_pair (lib.rs:1100): return None */
+    RS_TV_FEW_MATCHES = 3,        /* fewer than hard_minimum_matches entering a run (lib.rs:1118, 1167): continue */
+    RS_TV_LOST_HALF = 4,          /* no more than half of the first optimisation matches left (lib.rs:1126, 1175, 1281): continue */
+    RS_TV_FEW_ROBUST = 5,         /* num_robust_matches < three_view_minimum_robust_matches (lib.rs:1286): continue */
+    RS_TV_BAD_INDEX = 6           /* a feature >= cap_per_img or a block >= n_blocks: the scene is refused, nothing read out of bounds */
+};
+enum {
+    RS_TV_MAX_LANDMARKS = 1024,       /* three_view_optimization_landmarks at the most (they live in one workgroup's LDS) */
+    RS_TV_MAX_RUNS = 9,               /* three_view_filter_loop_iterations + 1 at the most */
+    RS_TV_MAX_ITERATIONS = 1 << 20,   /* a larger three_view_patience counts as this: the bound that ends every run */
+    RS_TV_MAX_COMMON = 9216,          /* cap_per_img at the most (the depth ratios of the first pass wait in LDS for their median) */
+    /* d_stats words (u32) of a scene: */
+    RS_TV_S_SCALES = 0,               /* depth ratios found */
+    RS_TV_S_MEDIAN = 1,               /* [2] median_scale (after the sqrt) as the bits of its f64, low word first */
+    RS_TV_S_PAIRS = 3,                /* robust bearing pairs */
+    RS_TV_S_RUN_MATCHES = 4,          /* [9] optimisation matches entering run r; 0xFFFFFFFF: not reached */
+    RS_TV_S_RUN_STOP = 13,            /* [9] the iteration run r left its loop at (patience - 1: the last one; less: 50 iterations
+                                       * without improvement); 0xFFFFFFFF: not run */
+    RS_TV_S_ROBUST = 22,              /* num_robust_matches */
+    RS_TV_S_STAGE = 23,               /* where the verdict fell: 0 indices, 1 scales, 2 bearing pairs, 3 + r entering run r, 12 the end */
+    RS_TV_STATS = 24
+};
+typedef struct rs_three_view_params {
+    uint32_t struct_size;                                         /* sizeof(rs_three_view_params) */
+    uint32_t robust_view_num_robust_bearing_pair;                 /* 3 */
+    double maximum_cosine_distance;                               /* 1e-5 */
+    double maximum_sine_distance;                                 /* 1e-1 */
+    double robust_observation_incidence_minimum_cosine_distance;  /* 1e-3 */
+    double robust_view_bearing_pair_minimum_cosine_distance;      /* 1e-2 */
+    double optimization_rate;                                     /* 0.001, the literal of lib.rs:1133 */
+    uint32_t three_view_minimum_relative_scales;                  /* 16 */
+    uint32_t three_view_filter_loop_iterations;                   /* 8; more than RS_TV_MAX_RUNS - 1: AKZ_E_INVALID */
+    uint32_t three_view_optimization_landmarks;                   /* 1024; more than RS_TV_MAX_LANDMARKS: AKZ_E_TOO_LARGE */
+    uint32_t three_view_patience;                                 /* 65536: the optimiser's iteration limit */
+    uint32_t three_view_minimum_robust_matches;                   /* 32 */
+    uint32_t hard_minimum_matches;                                /* 32, the literal of lib.rs:1118, 1167 */
+    rs_triangulate_params triangulate;                            /* the eigen-solver's settings */
+} rs_three_view_params;
+/* the reference's defaults (cv-sfm/src/settings.rs:320-427) */
+int32_t rs_three_view_params_default(rs_three_view_params* params);
+/* Scene s: centre block ic[s], first i_first[s], second i_second[s] of d_kps ([n_blocks][cap_per_img] akz_keypoint as
+ * akz_extract_batch_device leaves them; bearing = CameraIntrinsics::calibrate); d_pose_first / d_pose_second [n_scenes][12]
+ * the CameraToCamera poses centre -> first / second as rs_essential_arrsac_batch_device writes them; d_triples
+ * [n_scenes][cap_per_img][3] u32 {centre, first, second feature} the common matches in the caller's (shuffled) order,
+ * d_ntriples [n_scenes]; d_first_only / d_second_only [n_scenes][cap_per_img][2] u32 {centre, other feature} the matches of
+ * one pair whose centre feature the other pair does not have, with their counts.  Counts above cap_per_img count as it.
+ * Outputs: d_verdict [n_scenes] u32 (RS_TV_*), d_stats [n_scenes][RS_TV_STATS] u32 — always written; and for RS_TV_OK only
+ * d_pose_out [n_scenes][2][12] the optimised poses, d_combined [n_scenes][cap_per_img] u8 (lib.rs:1193-1210, one byte per
+ * common match), d_first_ok / d_second_ok [n_scenes][cap_per_img] u8 (lib.rs:1212-1246) — a rejected scene's are left as
+ * they were.  n_scenes within rs_batch_reserve's room (AKZ_E_TOO_LARGE beyond it).  The parameters are checked before
+ * anything else.  One launch on rs_stream() after stream_to_wait (may be NULL); returns after enqueueing. */
+int32_t rs_three_view_init_batch_device(rs_ctx* ctx, const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks, const uint32_t* ic,
+                                        const uint32_t* i_first, const uint32_t* i_second, const rs_camera* cam,
+                                        const void* d_pose_first, const void* d_pose_second, const void* d_triples,
+                                        const void* d_ntriples, const void* d_first_only, const void* d_nfirst,
+                                        const void* d_second_only, const void* d_nsecond, uint32_t n_scenes,
+                                        const rs_three_view_params* params, void* d_pose_out, void* d_verdict, void* d_combined,
+                                        void* d_first_ok, void* d_second_ok, void* d_stats, void* stream_to_wait);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched
@@ -720,7 +794,7 @@ const char* akz_version(void);
 /* The ABI number: raised whenever a declared signature, struct layout or enum value of this header changes (additions
  * included).  A binding compares akz_abi_version() of the library it loaded with the AKZ_ABI_VERSION it was written against
  * and refuses to run on a mismatch (cv_amd/_lib.py, rust/akaze-mi355x/src/lib.rs, include/akaze.hpp do). */
-#define AKZ_ABI_VERSION 10u
+#define AKZ_ABI_VERSION 11u
 uint32_t akz_abi_version(void);
 
 /* HIP-event timing of the kernel families of a batch (bench.py's roofline objects).  Kernel families (every id but the

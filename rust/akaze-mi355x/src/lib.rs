@@ -102,6 +102,17 @@ extern "C" {
     fn rs_triangulate_params_default(params: *mut RsTriangulateParams) -> i32;
     fn rs_triangulate_observations(ctx: *mut c_void, poses: *const f64, bearings: *const f64, n: u32,
                                    params: *const RsTriangulateParams, point: *mut f64, reason: *mut u8) -> i32;
+    fn rs_batch_reserve(ctx: *mut c_void, max_scenes: u32) -> i32;
+    fn rs_sync(ctx: *mut c_void) -> i32;
+    fn rs_stream(ctx: *mut c_void) -> *mut c_void;
+    fn rs_three_view_params_default(params: *mut RsThreeViewParams) -> i32;
+    fn rs_three_view_init_batch_device(ctx: *mut c_void, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, ic: *const u32,
+                                       i_first: *const u32, i_second: *const u32, cam: *const RsCamera, d_pose_first: *const c_void,
+                                       d_pose_second: *const c_void, d_triples: *const c_void, d_ntriples: *const c_void,
+                                       d_first_only: *const c_void, d_nfirst: *const c_void, d_second_only: *const c_void,
+                                       d_nsecond: *const c_void, n_scenes: u32, params: *const RsThreeViewParams,
+                                       d_pose_out: *mut c_void, d_verdict: *mut c_void, d_combined: *mut c_void, d_first_ok: *mut c_void,
+                                       d_second_ok: *mut c_void, d_stats: *mut c_void, stream_to_wait: *mut c_void) -> i32;
     fn hm_create(device: i32, max_q: u32, max_t: u32, out: *mut *mut c_void) -> i32;
     fn hm_destroy(ctx: *mut c_void) -> i32;
     fn hm_knn2(ctx: *mut c_void, q: *const [u8; 64], nq: u32, t: *const [u8; 64], nt: u32, out: *mut AkzNeighbor) -> i32;
@@ -236,7 +247,7 @@ static ARITH: std::sync::atomic::AtomicU32 = std::sync::atomic::AtomicU32::new(0
 
 /// The thread's matcher context, grown to hold `n` descriptors a side.
 /// include/akz.h AKZ_ABI_VERSION these bindings were written against; the loaded library must export the same number.
-const AKZ_ABI_VERSION: u32 = 10;
+const AKZ_ABI_VERSION: u32 = 11;
 fn require_abi() {
     let got = unsafe { akz_abi_version() };
     assert_eq!(got, AKZ_ABI_VERSION, "libakz exports ABI {got}, akaze-mi355x was written against {AKZ_ABI_VERSION}");
@@ -825,5 +836,104 @@ impl TriangulatorObservations for LinearEigenTriangulator {
         assert_eq!(st, 0, "rs_triangulate_observations");
         // (the device has already normalised xyz: from_homogeneous_unchecked would do; from_homogeneous is idempotent on it)
         (reason == 0).then(|| WorldPoint::from_homogeneous(Vector4::new(point[0], point[1], point[2], point[3])))
+    }
+}
+
+/// `rs_camera` (include/akz.h).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsCamera {
+    pub fx: f64,
+    pub fy: f64,
+    pub cx: f64,
+    pub cy: f64,
+    pub skew: f64,
+    pub k1: f64,
+    pub use_k1: i32,
+    pub reserved: i32,
+}
+
+/// `rs_three_view_params` (include/akz.h): cv-sfm's settings of the three-view bootstrap (cv-sfm/src/settings.rs:320-427).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsThreeViewParams {
+    struct_size: u32,
+    pub robust_view_num_robust_bearing_pair: u32,
+    pub maximum_cosine_distance: f64,
+    pub maximum_sine_distance: f64,
+    pub robust_observation_incidence_minimum_cosine_distance: f64,
+    pub robust_view_bearing_pair_minimum_cosine_distance: f64,
+    pub optimization_rate: f64,
+    pub three_view_minimum_relative_scales: u32,
+    pub three_view_filter_loop_iterations: u32,
+    pub three_view_optimization_landmarks: u32,
+    pub three_view_patience: u32,
+    pub three_view_minimum_robust_matches: u32,
+    pub hard_minimum_matches: u32,
+    pub triangulate: RsTriangulateParams,
+}
+
+/// The verdict of one triple (`RS_TV_*`).  The reference `continue`s to the next combination on every one of them but
+/// `FewBearingPairs`, where `init_reconstruction` returns `None` (cv-sfm/src/lib.rs:1100-1106).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ThreeViewVerdict {
+    Ok = 0,
+    FewScales = 1,
+    FewBearingPairs = 2,
+    FewMatches = 3,
+    LostHalf = 4,
+    FewRobust = 5,
+    BadIndex = 6,
+}
+
+/// Words of a scene's `d_stats` row (`RS_TV_S_*`).
+pub const RS_TV_STATS: usize = 24;
+
+/// `VSlam::init_reconstruction` from its common matches on (cv-sfm/src/lib.rs:1002-1300) for many triples side by side
+/// (`rs_three_view_init_batch_device`).  Every `d_*` argument is device memory the caller owns, laid out as include/akz.h
+/// documents; the call enqueues on `stream()` and returns.  The HashMap join and the shuffle of lib.rs:992-999 stay with
+/// the caller, who owns the RNG.
+pub struct ThreeViewInit {
+    pub params: RsThreeViewParams,
+    ctx: *mut c_void,
+}
+impl ThreeViewInit {
+    /// Room for `max_scenes` triples per call.
+    pub fn new(max_scenes: u32) -> Self {
+        require_abi();
+        let mut params: RsThreeViewParams = unsafe { std::mem::zeroed() };
+        assert_eq!(unsafe { rs_three_view_params_default(&mut params) }, 0, "rs_three_view_params_default");
+        let mut ctx = ptr::null_mut();
+        assert_eq!(unsafe { rs_create(0, 8, 1, &mut ctx) }, 0, "rs_create");
+        assert_eq!(unsafe { rs_batch_reserve(ctx, max_scenes) }, 0, "rs_batch_reserve");
+        Self { params, ctx }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until `sync()` returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn init_batch_device(&self, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, ic: &[u32], i_first: &[u32], i_second: &[u32],
+                                    cam: &RsCamera, d_pose_first: *const c_void, d_pose_second: *const c_void, d_triples: *const c_void,
+                                    d_ntriples: *const c_void, d_first_only: *const c_void, d_nfirst: *const c_void,
+                                    d_second_only: *const c_void, d_nsecond: *const c_void, d_pose_out: *mut c_void, d_verdict: *mut c_void,
+                                    d_combined: *mut c_void, d_first_ok: *mut c_void, d_second_ok: *mut c_void, d_stats: *mut c_void,
+                                    stream_to_wait: *mut c_void) -> Result<(), i32> {
+        assert!(i_first.len() == ic.len() && i_second.len() == ic.len(), "one centre, first and second block per scene");
+        let st = rs_three_view_init_batch_device(self.ctx, d_kps, cap_per_img, n_blocks, ic.as_ptr(), i_first.as_ptr(), i_second.as_ptr(), cam,
+                                                 d_pose_first, d_pose_second, d_triples, d_ntriples, d_first_only, d_nfirst, d_second_only,
+                                                 d_nsecond, ic.len() as u32, &self.params, d_pose_out, d_verdict, d_combined, d_first_ok,
+                                                 d_second_ok, d_stats, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    pub fn sync(&self) {
+        assert_eq!(unsafe { rs_sync(self.ctx) }, 0, "rs_sync");
+    }
+    pub fn stream(&self) -> *mut c_void {
+        unsafe { rs_stream(self.ctx) }
+    }
+}
+impl Drop for ThreeViewInit {
+    fn drop(&mut self) {
+        unsafe { rs_destroy(self.ctx) };
     }
 }
