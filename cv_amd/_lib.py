@@ -129,6 +129,19 @@ RS_TV_OK, RS_TV_FEW_SCALES, RS_TV_FEW_BEARING_PAIRS, RS_TV_FEW_MATCHES, RS_TV_LO
 RS_TV_MAX_LANDMARKS, RS_TV_MAX_RUNS, RS_TV_MAX_ITERATIONS, RS_TV_MAX_COMMON, RS_TV_STATS = 1024, 9, 1 << 20, 9216, 24
 RS_TV_S_SCALES, RS_TV_S_MEDIAN, RS_TV_S_PAIRS, RS_TV_S_RUN_MATCHES, RS_TV_S_RUN_STOP, RS_TV_S_ROBUST, RS_TV_S_STAGE = 0, 1, 3, 4, 13, 22, 23
 
+
+class ThreeViewConstraintParams(C.Structure):
+    """rs_three_view_constraint_params (include/akz.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("optimization_minimum_landmarks", C.c_uint32),
+                ("optimization_maximum_landmarks", C.c_uint32), ("constraint_patience", C.c_uint32),
+                ("robust_view_num_robust_bearing_pair", C.c_uint32),
+                ("robust_view_bearing_pair_minimum_cosine_distance", C.c_double)]
+
+
+RS_TVC_OK, RS_TVC_FEW_LANDMARKS, RS_TVC_FEW_BEARING_PAIRS, RS_TVC_BAD_INDEX = range(4)
+RS_TVC_MAX_LANDMARKS, RS_TVC_MAX_ITERATIONS, RS_TVC_STATS = 256, 1 << 20, 8
+RS_TVC_S_LANDMARKS, RS_TVC_S_USED, RS_TVC_S_PAIRS, RS_TVC_S_ORIGINAL_SCALE, RS_TVC_S_FINAL_SCALE, RS_TVC_S_STAGE = 0, 1, 2, 3, 5, 7
+
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
 
@@ -168,6 +181,7 @@ ABI_SYMBOLS = [
     "rs_stream", "rs_debug_scene", "rs_debug_residuals", "rs_p3p_arrsac_batch_device", "hm_landmark_pairs_batch_device", "hm_landmark_matches_batch_device", "hm_landmark_matches_ordered_batch_device", "hm_set_targets", "hm_targets_generation", "hm_knn_targets", "rs_debug_scene_world", "rs_debug_far",
     "rs_triangulate_params_default", "rs_triangulate_observations", "rs_triangulate_landmarks_device", "rs_triangulate_merged_device",
     "rs_triangulate_pairs_batch_device", "rs_three_view_params_default", "rs_three_view_init_batch_device",
+    "rs_three_view_constraint_params_default", "rs_three_view_constraint_batch_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -297,6 +311,9 @@ def lib():
     L.rs_three_view_params_default.argtypes = [C.POINTER(ThreeViewParams)]
     L.rs_three_view_init_batch_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, C.POINTER(Camera), vp, vp, vp, vp, vp, vp, vp, vp, u32,
                                                   C.POINTER(ThreeViewParams), vp, vp, vp, vp, vp, vp, vp]
+    L.rs_three_view_constraint_params_default.argtypes = [C.POINTER(ThreeViewConstraintParams)]
+    L.rs_three_view_constraint_batch_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(Camera), vp, vp, vp, u32, u32,
+                                                        C.POINTER(ThreeViewConstraintParams), vp, vp, vp, vp]
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

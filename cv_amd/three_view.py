@@ -7,6 +7,15 @@
 Every triple is worked by one persistent workgroup on the device (cv_amd/csrc/rs_three_view.hip); there is no CPU fallback.
 The join and the shuffle of the common matches use the caller's HashMap and RNG in the reference and stay on the host here:
 `join_pairs` builds the three index lists in the reference's order.
+
+And of the pose graph's three-view constraints over rs_three_view_constraint_batch_device:
+
+  VSlam::optimize_three_view behind its shuffle and sort     cv-sfm/src/lib.rs:1939-2062
+  three_view_adaptive_optimize_l2                             cv-optimize/src/three_view_optimizer.rs:203-272
+
+One wavefront per constraint (cv_amd/csrc/rs_three_view_constraint.hip).  The shuffle and the unstable sort by observation
+count use the caller's RNG and Rust's tie order in the reference and stay on the host: `order_landmarks` builds one
+admissible order.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -123,3 +132,77 @@ class ThreeViewInit:
         return ThreeViewResult(int(out[0]), d_pose.cpu().numpy().reshape(2, 3, 4) if ok else None,
                                masks[0, :len(triples)] if ok else None, masks[1, :len(first_only)] if ok else None,
                                masks[2, :len(second_only)] if ok else None, out[1:].copy())
+
+
+CONSTRAINT_VERDICTS = ("ok", "few_landmarks", "few_bearing_pairs", "bad_index")
+
+
+def order_landmarks(obs_counts, permutation=None):
+    """The positions of a constraint's landmarks in the order optimize_three_view walks them in: `permutation` (of
+    range(n), the shuffle of lib.rs:1968, the caller's RNG; default none), then a STABLE descending sort by observation count.
+    The reference sorts with sort_unstable_by_key, which fixes no order among landmarks with equal counts: this is one
+    admissible order, not the one a given Rust build produces."""
+    counts = np.asarray(obs_counts, np.int64).reshape(-1)
+    perm = np.arange(len(counts)) if permutation is None else np.asarray(permutation, np.int64)
+    if sorted(perm.tolist()) != list(range(len(counts))):
+        raise ValueError("permutation must be a permutation of the landmarks")
+    return perm[np.argsort(-counts[perm], kind="stable")]
+
+
+@dataclass
+class ThreeViewConstraintResult:
+    verdicts: np.ndarray     # [n] u32 (RS_TVC_*)
+    poses: np.ndarray        # [n][2][3][4] CameraToCamera first view -> second / third; rows of refused constraints are zero
+    stats: np.ndarray        # [n][RS_TVC_STATS] u32
+
+    def scale(self, i, which=_lib.RS_TVC_S_FINAL_SCALE):
+        return float(self.stats[i, which:which + 2].copy().view(np.float64)[0])
+
+
+class ThreeViewConstraints:
+    """The three-view constraints on the context (and stream) of an EssentialConsensus, so that a batch queues behind that
+    object's other calls."""
+
+    def __init__(self, consensus):
+        self._cons = consensus
+
+    @staticmethod
+    def params(**kw):
+        """rs_three_view_constraint_params: the reference's defaults (cv-sfm/src/settings.rs:332-338, 465-483) with `kw` on top."""
+        p = _lib.ThreeViewConstraintParams()
+        check(_lib.lib().rs_three_view_constraint_params_default(C.byref(p)), "rs_three_view_constraint_params_default")
+        for k, v in kw.items():
+            if k == "struct_size" or not hasattr(p, k):
+                raise TypeError(f"rs_three_view_constraint_params has no setting {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def batch_device(self, d_kps, cap_per_img, n_blocks, d_poses, cam, d_views, d_lm_start, d_lm, n_lm, n_constraints, params,
+                     d_pose_out, d_verdict, d_stats, stream_to_wait=None):
+        """rs_three_view_constraint_batch_device: arguments named d_* are device pointers (ints).  Enqueues on the consensus'
+        stream and returns; its sync() waits."""
+        check(_lib.lib().rs_three_view_constraint_batch_device(
+            self._cons._h, d_kps, cap_per_img, n_blocks, d_poses, C.byref(cam), d_views, d_lm_start, d_lm, n_lm, n_constraints,
+            C.byref(params), d_pose_out, d_verdict, d_stats, stream_to_wait), "rs_three_view_constraint_batch_device")
+
+    def run(self, torch, kps, poses, cam, views, lm_start, lm, params=None):
+        """One batch from torch tensors on the device: kps [n_blocks][cap] keypoints (uint8 [n_blocks][cap][28] as
+        akz_extract_batch_device leaves them), poses [n_blocks][12] float64, views [n][3], lm_start [n + 1] and lm [n_lm][3]
+        int32 (read as u32).  Runs the device call, waits.  -> ThreeViewConstraintResult (host arrays)."""
+        n, n_blocks, n_lm = int(views.shape[0]), int(kps.shape[0]), int(lm.shape[0])
+        if lm_start.numel() != n + 1 or poses.numel() != 12 * n_blocks or poses.dtype != torch.float64:
+            raise ValueError("lm_start is [n + 1], poses [n_blocks][12] float64")
+        for t in (kps, poses, views, lm_start, lm):
+            if not (t.is_cuda and t.is_contiguous()):
+                raise ValueError("contiguous device tensors only")
+        cap = kps.numel() * kps.element_size() // (28 * n_blocks)
+        dev = kps.device
+        d_pose = torch.zeros((max(n, 1), 24), dtype=torch.float64, device=dev)
+        d_out = torch.zeros((max(n, 1), 1 + _lib.RS_TVC_STATS), dtype=torch.int32, device=dev)
+        d_verdict, d_stats = d_out[:, 0].contiguous(), d_out[:, 1:].contiguous()
+        self.batch_device(kps.data_ptr(), cap, n_blocks, poses.data_ptr(), cam, views.data_ptr(), lm_start.data_ptr(),
+                          lm.data_ptr() if n_lm else None, n_lm, n, params or self.params(), d_pose.data_ptr(), d_verdict.data_ptr(),
+                          d_stats.data_ptr(), _lib.wait_handle(torch.cuda.current_stream(dev)))
+        self._cons.sync()
+        return ThreeViewConstraintResult(d_verdict.cpu().numpy().view(np.uint32)[:n], d_pose.cpu().numpy().reshape(-1, 2, 3, 4)[:n],
+                                         d_stats.cpu().numpy().view(np.uint32)[:n])

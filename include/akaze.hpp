@@ -691,6 +691,39 @@ private:
     rs_three_view_params p_;
     rs_ctx* ctx_ = nullptr;
 };
+
+// cv-sfm's three-view constraints of the pose graph (VSlam::optimize_three_view behind its shuffle and sort,
+// cv-sfm/src/lib.rs:1939-2062) over rs_three_view_constraint_batch_device, one wavefront per constraint: every argument named
+// d_* is device memory the caller owns (the layouts are include/akz.h's), the call enqueues on stream() and returns.  The
+// shuffle and the unstable sort by observation count stay with the caller.
+class ThreeViewConstraints {
+public:
+    explicit ThreeViewConstraints(int device = 0)
+    {
+        akaze::require_abi();
+        rs_three_view_constraint_params_default(&p_);
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+    }
+    ~ThreeViewConstraints() { if (ctx_) rs_destroy(ctx_); }
+    ThreeViewConstraints(const ThreeViewConstraints&) = delete;
+    ThreeViewConstraints& operator=(const ThreeViewConstraints&) = delete;
+    rs_three_view_constraint_params& params() { return p_; }   // the reference's defaults (cv-sfm/src/settings.rs:332-338, 465-483)
+    const rs_three_view_constraint_params& params() const { return p_; }
+    void batch_device(const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks, const void* d_poses, const rs_camera& cam,
+                      const void* d_views, const void* d_lm_start, const void* d_lm, uint32_t n_lm, uint32_t n_constraints,
+                      void* d_pose_out, void* d_verdict, void* d_stats, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_three_view_constraint_batch_device(ctx_, d_kps, cap_per_img, n_blocks, d_poses, &cam, d_views, d_lm_start, d_lm, n_lm,
+                                                           n_constraints, &p_, d_pose_out, d_verdict, d_stats, stream_to_wait),
+                     "rs_three_view_constraint_batch_device");
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_three_view_constraint_params p_;
+    rs_ctx* ctx_ = nullptr;
+};
 }  // namespace cv_sfm
 
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over

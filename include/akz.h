@@ -745,6 +745,60 @@ int32_t rs_three_view_init_batch_device(rs_ctx* ctx, const void* d_kps, uint32_t
                                         const void* d_second_only, const void* d_nsecond, uint32_t n_scenes,
                                         const rs_three_view_params* params, void* d_pose_out, void* d_verdict, void* d_combined,
                                         void* d_first_ok, void* d_second_ok, void* d_stats, void* stream_to_wait);
+/* ---- the three-view constraints of the pose graph on the device ----
+ * What cv-sfm's VSlam::optimize_three_view does for ONE covisible view triple of an existing reconstruction
+ * (cv-sfm/src/lib.rs:1939-2062), for n_constraints triples side by side: the minimum-landmarks test on the whole list, the
+ * relative poses first = pose[v1] * pose[v0]^-1 and second = pose[v2] * pose[v0]^-1, take(optimization_maximum_landmarks),
+ * the robust bearing pairs among the taken landmarks, constraint_patience iterations of three_view_adaptive_optimize_l2
+ * (cv-optimize/src/three_view_optimizer.rs:203-272; it has no early exit) and the return to the original scale.  One
+ * wavefront per constraint, one launch.  The arithmetic is include/akz_three_view_constraint_math.h (compiled for the device
+ * and, by the tests, for the host: equal bit for bit); its head lists what is unpinned against the reference — what
+ * akz_three_view_math.h lists, the product of two isometries, and the order of the sum over landmarks, which is fixed there.
+ * landmarks.shuffle (lib.rs:1968, the caller's RNG) and sort_unstable_by_key (lib.rs:1970, Rust's order among equal
+ * observation counts) stay with the caller: a list arrives in the order the reference would walk it in. */
+enum {
+    RS_TVC_OK = 0,
+    RS_TVC_FEW_LANDMARKS = 1,         /* fewer than optimization_minimum_landmarks in the list (lib.rs:1949) */
+    RS_TVC_FEW_BEARING_PAIRS = 2,     /* fewer than robust_view_num_robust_bearing_pair (lib.rs:2026) */
+    RS_TVC_BAD_INDEX = 3              /* a block >= n_blocks, a feature >= cap_per_img anywhere in the list, or a list range that
+                                       * leaves [0, n_lm]: this constraint alone is refused, nothing is read out of bounds */
+};
+enum {
+    RS_TVC_MAX_LANDMARKS = 256,       /* optimization_maximum_landmarks at the most (beyond 64 a wave keeps them in LDS) */
+    RS_TVC_MAX_ITERATIONS = 1 << 20,  /* a larger constraint_patience counts as this: the bound that ends every constraint */
+    /* d_stats words (u32) of a constraint; a word behind the stage its verdict fell at is 0: */
+    RS_TVC_S_LANDMARKS = 0,           /* the length of the list */
+    RS_TVC_S_USED = 1,                /* min(length, optimization_maximum_landmarks) */
+    RS_TVC_S_PAIRS = 2,               /* robust bearing pairs */
+    RS_TVC_S_ORIGINAL_SCALE = 3,      /* [2] |t_first| + |t_second| before the optimiser: the bits of its f64, low word first */
+    RS_TVC_S_FINAL_SCALE = 5,         /* [2] the same behind it */
+    RS_TVC_S_STAGE = 7,               /* where the verdict fell: 0 indices, 1 minimum landmarks, 2 bearing pairs, 3 the end */
+    RS_TVC_STATS = 8
+};
+typedef struct rs_three_view_constraint_params {
+    uint32_t struct_size;                                      /* sizeof(rs_three_view_constraint_params) */
+    uint32_t optimization_minimum_landmarks;                   /* 24 */
+    uint32_t optimization_maximum_landmarks;                   /* 64; more than RS_TVC_MAX_LANDMARKS: AKZ_E_TOO_LARGE */
+    uint32_t constraint_patience;                              /* 4096: the optimiser's iterations, all of which run */
+    uint32_t robust_view_num_robust_bearing_pair;              /* 3 */
+    double robust_view_bearing_pair_minimum_cosine_distance;   /* 1e-2 */
+} rs_three_view_constraint_params;
+/* the reference's defaults (cv-sfm/src/settings.rs:332-338, 465-483) */
+int32_t rs_three_view_constraint_params_default(rs_three_view_constraint_params* params);
+/* Constraint s: views d_views[s] ([n_constraints][3] u32 keypoint blocks of d_kps, [n_blocks][cap_per_img] akz_keypoint as
+ * akz_extract_batch_device leaves them; bearing = CameraIntrinsics::calibrate) under the poses d_poses ([n_blocks][12] f64
+ * WorldToCamera, as rs_triangulate_landmarks_device reads them); its landmarks are entries d_lm_start[s] .. d_lm_start[s + 1]
+ * (d_lm_start [n_constraints + 1] u32, ascending) of d_lm ([n_lm][3] u32, a landmark's feature in each of the three views), in
+ * the caller's order.  Every list is a device array: n_constraints is not bound by rs_batch_reserve.
+ * Outputs: d_verdict [n_constraints] u32 (RS_TVC_*) and d_stats [n_constraints][RS_TVC_STATS] u32 — always written; d_pose_out
+ * [n_constraints][2][12] f64 the two CameraToCamera poses of the constraint — for RS_TVC_OK only, a refused constraint's are
+ * left as they were.  The parameters are checked before anything else (a NaN threshold: AKZ_E_INVALID).  One launch on
+ * rs_stream() after stream_to_wait (may be NULL); returns after enqueueing. */
+int32_t rs_three_view_constraint_batch_device(rs_ctx* ctx, const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks,
+                                              const void* d_poses, const rs_camera* cam, const void* d_views, const void* d_lm_start,
+                                              const void* d_lm, uint32_t n_lm, uint32_t n_constraints,
+                                              const rs_three_view_constraint_params* params, void* d_pose_out, void* d_verdict,
+                                              void* d_stats, void* stream_to_wait);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched
@@ -791,9 +845,11 @@ const char* akz_strerror(int32_t status);
 int32_t akz_last_hip_error(void);
 const char* akz_last_hip_error_string(void);
 const char* akz_version(void);
-/* The ABI number: raised whenever a declared signature, struct layout or enum value of this header changes (additions
- * included).  A binding compares akz_abi_version() of the library it loaded with the AKZ_ABI_VERSION it was written against
- * and refuses to run on a mismatch (cv_amd/_lib.py, rust/akaze-mi355x/src/lib.rs, include/akaze.hpp do). */
+/* The ABI number: raised whenever an existing declaration, struct layout or enum value of this header changes.  A pure
+ * addition (a new function, struct or enum that leaves every existing one as it was) does not raise it: a binding written
+ * against the same number still finds everything it declares.  A binding compares akz_abi_version() of the library it
+ * loaded with the AKZ_ABI_VERSION it was written against and refuses to run on a mismatch (cv_amd/_lib.py,
+ * rust/akaze-mi355x/src/lib.rs, include/akaze.hpp do). */
 #define AKZ_ABI_VERSION 11u
 uint32_t akz_abi_version(void);
 

@@ -113,6 +113,12 @@ extern "C" {
                                        d_nsecond: *const c_void, n_scenes: u32, params: *const RsThreeViewParams,
                                        d_pose_out: *mut c_void, d_verdict: *mut c_void, d_combined: *mut c_void, d_first_ok: *mut c_void,
                                        d_second_ok: *mut c_void, d_stats: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_three_view_constraint_params_default(params: *mut RsThreeViewConstraintParams) -> i32;
+    fn rs_three_view_constraint_batch_device(ctx: *mut c_void, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, d_poses: *const c_void,
+                                             cam: *const RsCamera, d_views: *const c_void, d_lm_start: *const c_void, d_lm: *const c_void,
+                                             n_lm: u32, n_constraints: u32, params: *const RsThreeViewConstraintParams,
+                                             d_pose_out: *mut c_void, d_verdict: *mut c_void, d_stats: *mut c_void,
+                                             stream_to_wait: *mut c_void) -> i32;
     fn hm_create(device: i32, max_q: u32, max_t: u32, out: *mut *mut c_void) -> i32;
     fn hm_destroy(ctx: *mut c_void) -> i32;
     fn hm_knn2(ctx: *mut c_void, q: *const [u8; 64], nq: u32, t: *const [u8; 64], nt: u32, out: *mut AkzNeighbor) -> i32;
@@ -933,6 +939,79 @@ impl ThreeViewInit {
     }
 }
 impl Drop for ThreeViewInit {
+    fn drop(&mut self) {
+        unsafe { rs_destroy(self.ctx) };
+    }
+}
+
+/// `rs_three_view_constraint_params` (include/akz.h): cv-sfm's settings of a three-view constraint
+/// (cv-sfm/src/settings.rs:332-338, 465-483).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsThreeViewConstraintParams {
+    struct_size: u32,
+    pub optimization_minimum_landmarks: u32,
+    pub optimization_maximum_landmarks: u32,
+    pub constraint_patience: u32,
+    pub robust_view_num_robust_bearing_pair: u32,
+    pub robust_view_bearing_pair_minimum_cosine_distance: f64,
+}
+
+/// The verdict of one constraint (`RS_TVC_*`): `optimize_three_view` returns `None` on the two in the middle
+/// (cv-sfm/src/lib.rs:1949, 2026).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ThreeViewConstraintVerdict {
+    Ok = 0,
+    FewLandmarks = 1,
+    FewBearingPairs = 2,
+    BadIndex = 3,
+}
+
+/// Words of a constraint's `d_stats` row (`RS_TVC_S_*`).
+pub const RS_TVC_STATS: usize = 8;
+
+/// `VSlam::optimize_three_view` behind its shuffle and sort (cv-sfm/src/lib.rs:1939-2062) for many view triples side by
+/// side (`rs_three_view_constraint_batch_device`), one wavefront per constraint.  Every `d_*` argument is device memory
+/// the caller owns, laid out as include/akz.h documents; the call enqueues on `stream()` and returns.  The shuffle and the
+/// unstable sort by observation count (lib.rs:1968-1977) stay with the caller, who owns the RNG.
+pub struct ThreeViewConstraints {
+    pub params: RsThreeViewConstraintParams,
+    ctx: *mut c_void,
+}
+impl ThreeViewConstraints {
+    pub fn new() -> Self {
+        require_abi();
+        let mut params: RsThreeViewConstraintParams = unsafe { std::mem::zeroed() };
+        assert_eq!(unsafe { rs_three_view_constraint_params_default(&mut params) }, 0, "rs_three_view_constraint_params_default");
+        let mut ctx = ptr::null_mut();
+        assert_eq!(unsafe { rs_create(0, 8, 1, &mut ctx) }, 0, "rs_create");
+        Self { params, ctx }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until `sync()` returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn batch_device(&self, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, d_poses: *const c_void, cam: &RsCamera,
+                               d_views: *const c_void, d_lm_start: *const c_void, d_lm: *const c_void, n_lm: u32, n_constraints: u32,
+                               d_pose_out: *mut c_void, d_verdict: *mut c_void, d_stats: *mut c_void,
+                               stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_three_view_constraint_batch_device(self.ctx, d_kps, cap_per_img, n_blocks, d_poses, cam, d_views, d_lm_start, d_lm, n_lm,
+                                                       n_constraints, &self.params, d_pose_out, d_verdict, d_stats, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    pub fn sync(&self) {
+        assert_eq!(unsafe { rs_sync(self.ctx) }, 0, "rs_sync");
+    }
+    pub fn stream(&self) -> *mut c_void {
+        unsafe { rs_stream(self.ctx) }
+    }
+}
+impl Default for ThreeViewConstraints {
+    fn default() -> Self {
+        Self::new()
+    }
+}
+impl Drop for ThreeViewConstraints {
     fn drop(&mut self) {
         unsafe { rs_destroy(self.ctx) };
     }

@@ -12,6 +12,10 @@ build of the same header on one core.
                   against the device's single-triple result (bit equality expected; the tolerance is that of
                   tests/test_three_view_math.py)
   python tools/bench_three_view.py --step probe|batch|host [--out DIR]     one step alone
+  python tools/bench_three_view.py --constraints [--out DIR]
+        the three-view constraints of the pose graph (cv_amd/csrc/rs_three_view_constraint.hip) at the reference's default
+        settings (64 landmarks, 4 096 iterations), one child process under `timeout`: microseconds per iteration of one
+        constraint alone and of batches of 256, 2 048 and 8 192, and the host build's time for one (bit equality expected)
 Prints one JSON line per step.
 """
 import argparse
@@ -148,6 +152,57 @@ def step_host(out):
     return 0 if res.get("within_tolerance", True) else 1
 
 
+def step_constraints(out):
+    import three_view_constraint_checker as T
+    from cv_amd import _lib
+    from cv_amd.three_view import ThreeViewConstraints
+    torch, cons = gpu()
+    cap, n_lm, patience = 64, 64, 4096
+    pool = [T.scene(9100 + k, n_lm) for k in range(16)]
+    dev = torch.device("cuda", 0)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    cam = _lib.Camera(T.K.CAM["fx"], T.K.CAM["fy"], T.K.CAM["cx"], T.K.CAM["cy"], 0.0, 0.0, 0, 0)
+    tvc = ThreeViewConstraints(cons)
+
+    def call(n, prm):
+        rng = np.random.default_rng(n)
+        arrays = T.device_arrays(pool, cap, [(i % len(pool), rng.permutation(n_lm)) for i in range(n)])
+        kps, poses, views, lm_start, lm = arrays
+        d = [up(a) for a in arrays]
+        d_pose = torch.zeros((n, 24), dtype=torch.float64, device=dev)
+        d_verdict = torch.zeros((n,), dtype=torch.int32, device=dev)
+        d_stats = torch.zeros((n, _lib.RS_TVC_STATS), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tvc.batch_device(d[0].data_ptr(), cap, len(kps), d[1].data_ptr(), cam, d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(), len(lm), n,
+                         prm, d_pose.data_ptr(), d_verdict.data_ptr(), d_stats.data_ptr())
+        cons.sync()
+        sec = time.perf_counter() - t0
+        return sec, arrays, d_verdict.cpu().numpy().view(np.uint32), d_stats.cpu().numpy().view(np.uint32), d_pose.cpu().numpy()
+
+    call(1, ThreeViewConstraints.params(constraint_patience=8))                 # warm-up: module load
+    prm = ThreeViewConstraints.params()
+    res = {"step": "constraints", "landmarks": n_lm, "patience": patience, "batches": {}}
+    for n in (1, 256, 2048, 8192):
+        sec = min(call(n, prm)[0] for _ in range(3))
+        _, arrays, verdict, stats, pose = call(n, prm)
+        assert np.all(verdict == 0), np.bincount(verdict)
+        res["batches"][str(n)] = {"call_ms": round(sec * 1e3, 3), "us_per_iteration": round(sec * 1e6 / patience, 3),
+                                  "us_per_constraint_iteration": round(sec * 1e6 / patience / n, 5)}
+        if n == 1:
+            t0 = time.perf_counter()
+            h = T.constraint_scene(arrays[0], arrays[1], T.K.rig_camera(), arrays[2], arrays[3], arrays[4], 0, T.settings())
+            hsec = time.perf_counter() - t0
+            res["host"] = {"what": "tests/cpp/three_view_constraint_host.c, gcc -O2 -ffp-contract=off, one core", "seconds": round(hsec, 4),
+                           "us_per_iteration": round(hsec * 1e6 / patience, 3), "verdict": h["verdict"],
+                           "stats_equal": bool(np.array_equal(stats[0], h["stats"])), "poses_bit_equal": bool(pose[0].tobytes() == h["pose_out"].tobytes())}
+    with open(os.path.join(out, "constraints.json"), "w") as f:
+        json.dump(res, f)
+    print(json.dumps(res))
+    cons.close()
+    return 0 if res["host"]["stats_equal"] and res["host"]["poses_bit_equal"] else 1
+
+
 def child(step, out, limit):
     cmd = ["timeout", "-k", "10", str(int(limit)), sys.executable, os.path.abspath(__file__), "--step", step, "--out", out]
     print("#", " ".join(cmd), flush=True)
@@ -156,12 +211,15 @@ def child(step, out, limit):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=["probe", "batch", "host"])
+    ap.add_argument("--step", choices=["probe", "batch", "host", "constraints"])
+    ap.add_argument("--constraints", action="store_true", help="time the three-view constraints instead of the bootstrap")
     ap.add_argument("--out", default=os.path.join(tempfile.gettempdir(), "bench_three_view"), help="where the steps leave their files")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     if a.step:
-        return {"probe": step_probe, "batch": step_batch, "host": step_host}[a.step](a.out) or 0
+        return {"probe": step_probe, "batch": step_batch, "host": step_host, "constraints": step_constraints}[a.step](a.out) or 0
+    if a.constraints:
+        return child("constraints", a.out, 300)
     rc = child("probe", a.out, 120)
     if rc:
         return rc
