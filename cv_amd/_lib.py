@@ -142,6 +142,17 @@ RS_TVC_OK, RS_TVC_FEW_LANDMARKS, RS_TVC_FEW_BEARING_PAIRS, RS_TVC_BAD_INDEX = ra
 RS_TVC_MAX_LANDMARKS, RS_TVC_MAX_ITERATIONS, RS_TVC_STATS = 256, 1 << 20, 8
 RS_TVC_S_LANDMARKS, RS_TVC_S_USED, RS_TVC_S_PAIRS, RS_TVC_S_ORIGINAL_SCALE, RS_TVC_S_FINAL_SCALE, RS_TVC_S_STAGE = 0, 1, 2, 3, 5, 7
 
+
+class PoseGraphParams(C.Structure):
+    """rs_pose_graph_params (include/akz.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("optimization_iterations", C.c_uint32), ("graph_optimization_rate", C.c_double)]
+
+
+RS_PG_OK, RS_PG_FEW_VIEWS, RS_PG_NONFINITE, RS_PG_BAD_INDEX = range(4)
+RS_PG_VIEW_UPDATED, RS_PG_VIEW_NO_CONSTRAINT, RS_PG_VIEW_NONFINITE = range(3)
+RS_PG_RESIDENT_VIEWS, RS_PG_DEFAULT_RESIDENT_VIEWS, RS_PG_MAX_ITERATIONS, RS_PG_STATS = 256, 8, 1 << 20, 8
+RS_PG_S_VIEWS, RS_PG_S_UPDATED, RS_PG_S_EDGES, RS_PG_S_ROUNDS, RS_PG_S_STAGE, RS_PG_S_FIRST_BAD_VIEW = range(6)
+
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
 
@@ -182,6 +193,7 @@ ABI_SYMBOLS = [
     "rs_triangulate_params_default", "rs_triangulate_observations", "rs_triangulate_landmarks_device", "rs_triangulate_merged_device",
     "rs_triangulate_pairs_batch_device", "rs_three_view_params_default", "rs_three_view_init_batch_device",
     "rs_three_view_constraint_params_default", "rs_three_view_constraint_batch_device",
+    "rs_pose_graph_params_default", "rs_pose_graph_edges_device", "rs_pose_graph_relax_batch_device", "rs_pose_graph_debug_resident_views",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -314,6 +326,11 @@ def lib():
     L.rs_three_view_constraint_params_default.argtypes = [C.POINTER(ThreeViewConstraintParams)]
     L.rs_three_view_constraint_batch_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(Camera), vp, vp, vp, u32, u32,
                                                         C.POINTER(ThreeViewConstraintParams), vp, vp, vp, vp]
+    L.rs_pose_graph_params_default.argtypes = [C.POINTER(PoseGraphParams)]
+    L.rs_pose_graph_edges_device.argtypes = [vp, vp, vp, vp, u32, vp, vp]
+    L.rs_pose_graph_relax_batch_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, u32, C.POINTER(PoseGraphParams),
+                                                   vp, vp, vp, vp]
+    L.rs_pose_graph_debug_resident_views.argtypes = [vp, u32]
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

@@ -135,6 +135,14 @@ struct RsHandles {
     uint32_t max_scenes;
 };
 RsHandles rs_internal_handles(rs_ctx* c);
+// What rs_pose_graph.hip keeps in an rs_ctx: its scratch (the second pose table of the swept form and the words the kernels
+// of one call hand each other), grown on demand and freed by rs_destroy, and the largest graph the resident form takes.
+struct RsPoseGraphState {
+    void* d_scratch = nullptr;
+    size_t bytes = 0;
+    uint32_t resident_views = RS_PG_DEFAULT_RESIDENT_VIEWS;
+};
+RsPoseGraphState* rs_internal_pose_graph(rs_ctx* c);
 
 static inline int akz_div_up(int a, int b) { return (a + b - 1) / b; }
 static inline size_t akz_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }

@@ -1485,10 +1485,12 @@ struct rs_ctx : RsArena {
     uint32_t max_matches = 0, max_hyp = 0;
     double* d_logtab = nullptr;                                        // ln(k), k = 0 .. max_matches (host libm values)
     uint32_t last_hyp = 0, last_five_samples = 0;                      // what the debug taps may read (rs_note_call)
+    RsPoseGraphState pose_graph;                                       // rs_pose_graph.hip's (akz_common.h)
 };
 
 // (akz_common.h) what rs_triangulate.hip enqueues with
 RsHandles rs_internal_handles(rs_ctx* c) { return RsHandles{c->device, c->stream, c->ev, c->d_frames, c->max_scenes}; }
+RsPoseGraphState* rs_internal_pose_graph(rs_ctx* c) { return &c->pose_graph; }
 
 // Every device array of an arena, once: where its pointer lives and its bytes per scene (n matches, H hypothesis slots).
 struct RsSlot {
@@ -1611,6 +1613,7 @@ extern "C" int32_t rs_destroy(rs_ctx* c)
         if (c->stream) hipStreamSynchronize(c->stream);
         rs_free_arena(static_cast<RsArena*>(c));
         hipFree(c->d_logtab);
+        hipFree(c->pose_graph.d_scratch);
         if (c->ev) hipEventDestroy(c->ev);
         if (c->stream) hipStreamDestroy(c->stream);
         delete c;

@@ -185,10 +185,12 @@ class ThreeViewConstraints:
             self._cons._h, d_kps, cap_per_img, n_blocks, d_poses, C.byref(cam), d_views, d_lm_start, d_lm, n_lm, n_constraints,
             C.byref(params), d_pose_out, d_verdict, d_stats, stream_to_wait), "rs_three_view_constraint_batch_device")
 
-    def run(self, torch, kps, poses, cam, views, lm_start, lm, params=None):
+    def run_tensors(self, torch, kps, poses, cam, views, lm_start, lm, params=None):
         """One batch from torch tensors on the device: kps [n_blocks][cap] keypoints (uint8 [n_blocks][cap][28] as
         akz_extract_batch_device leaves them), poses [n_blocks][12] float64, views [n][3], lm_start [n + 1] and lm [n_lm][3]
-        int32 (read as u32).  Runs the device call, waits.  -> ThreeViewConstraintResult (host arrays)."""
+        int32 (read as u32).  Enqueues the device call and returns without waiting -> (verdicts [n] int32, poses [n][24]
+        float64, stats [n][RS_TVC_STATS] int32) on the device, complete on the consensus' stream: what
+        pose_graph.PoseGraph.edges takes."""
         n, n_blocks, n_lm = int(views.shape[0]), int(kps.shape[0]), int(lm.shape[0])
         if lm_start.numel() != n + 1 or poses.numel() != 12 * n_blocks or poses.dtype != torch.float64:
             raise ValueError("lm_start is [n + 1], poses [n_blocks][12] float64")
@@ -203,6 +205,11 @@ class ThreeViewConstraints:
         self.batch_device(kps.data_ptr(), cap, n_blocks, poses.data_ptr(), cam, views.data_ptr(), lm_start.data_ptr(),
                           lm.data_ptr() if n_lm else None, n_lm, n, params or self.params(), d_pose.data_ptr(), d_verdict.data_ptr(),
                           d_stats.data_ptr(), _lib.wait_handle(torch.cuda.current_stream(dev)))
+        return d_verdict[:n], d_pose[:n], d_stats[:n]
+
+    def run(self, torch, kps, poses, cam, views, lm_start, lm, params=None):
+        """run_tensors, waits.  -> ThreeViewConstraintResult (host arrays)."""
+        d_verdict, d_pose, d_stats = self.run_tensors(torch, kps, poses, cam, views, lm_start, lm, params)
         self._cons.sync()
-        return ThreeViewConstraintResult(d_verdict.cpu().numpy().view(np.uint32)[:n], d_pose.cpu().numpy().reshape(-1, 2, 3, 4)[:n],
-                                         d_stats.cpu().numpy().view(np.uint32)[:n])
+        return ThreeViewConstraintResult(d_verdict.cpu().numpy().view(np.uint32), d_pose.cpu().numpy().reshape(-1, 2, 3, 4),
+                                         d_stats.cpu().numpy().view(np.uint32))

