@@ -364,3 +364,29 @@ def wait_handle(stream):
     synchronise with the default stream by themselves)."""
     h = stream.cuda_stream
     return h if h else STREAM_LEGACY
+
+
+def params(struct_type, default_symbol, **kw):
+    """A parameter struct of the ABI with the defaults its `*_params_default` symbol gives and `kw` on top; struct_size or
+    an unknown name raises TypeError."""
+    p = struct_type()
+    check(getattr(lib(), default_symbol)(C.byref(p)), default_symbol)
+    c_name = default_symbol[:-len("_default")]
+    for k, v in kw.items():
+        if k == "struct_size" or not hasattr(p, k):
+            raise TypeError(f"{c_name} has no setting {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def stat_f64(stats, at):
+    """the float64 that the two u32 stats words at `at` (low, high) hold"""
+    return float(stats[at:at + 2].copy().view(np.float64)[0])
+
+
+def device_bytes(torch, a, dev):
+    """A host array as a flat uint8 tensor on `dev`; an empty one as 8 zero bytes, so that it still has an address."""
+    a = np.ascontiguousarray(a)
+    if a.size == 0:
+        return torch.zeros(8, dtype=torch.uint8, device=dev)
+    return torch.from_numpy(a.view(np.uint8).reshape(-1)).to(dev)

@@ -229,11 +229,7 @@ static void comm_resolve(akz_comm* c, size_t keep)
 }
 static int32_t comm_begin(akz_comm* c, void* stream_to_wait, hipEvent_t* e0, hipEvent_t* e1)
 {
-    AKZ_HIP(hipSetDevice(c->device));
-    if (stream_to_wait) {
-        AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-        AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-    }
+    AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
     *e0 = *e1 = nullptr;
     if (c->timing) {
         if (c->pending.size() >= kCommMaxPending) comm_resolve(c, kCommMaxPending / 2);

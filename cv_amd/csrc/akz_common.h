@@ -31,6 +31,17 @@ extern thread_local int g_akz_last_hip;
 // `stream_to_wait` arguments of the ABI: NULL = nothing to wait for; AKZ_STREAM_LEGACY (include/akz.h, the value of
 // hipStreamLegacy) = the legacy default stream, whose own handle is NULL too and could not be told from "none".
 inline hipStream_t akz_wait_stream(void* h) { return h == (void*)1 ? (hipStream_t)nullptr : (hipStream_t)h; }
+// The prologue of every entry point that enqueues on a context's own stream: make the context's device current and, when
+// the caller names a stream, order `stream` behind what that stream holds now (through the context's event `ev`).
+inline int32_t akz_enqueue_behind(int device, hipStream_t stream, hipEvent_t ev, void* stream_to_wait)
+{
+    AKZ_HIP(hipSetDevice(device));
+    if (stream_to_wait) {
+        AKZ_HIP(hipEventRecord(ev, akz_wait_stream(stream_to_wait)));
+        AKZ_HIP(hipStreamWaitEvent(stream, ev, 0));
+    }
+    return AKZ_OK;
+}
 
 // Slots per frame in every per-(frame, level) table (candidate counts and lists, the keypoint kernels' level
 // table).  A configuration whose pyramid has more levels is refused at akz_create (AKZ_E_INVALID).
@@ -135,6 +146,10 @@ struct RsHandles {
     uint32_t max_scenes;
 };
 RsHandles rs_internal_handles(rs_ctx* c);
+inline int32_t akz_enqueue_behind(const RsHandles& h, void* stream_to_wait)
+{
+    return akz_enqueue_behind(h.device, h.stream, h.ev, stream_to_wait);
+}
 // What rs_pose_graph.hip keeps in an rs_ctx: its scratch (the second pose table of the swept form and the words the kernels
 // of one call hand each other), grown on demand and freed by rs_destroy, and the largest graph the resident form takes.
 struct RsPoseGraphState {
@@ -213,6 +228,25 @@ __device__ __forceinline__ uint32_t* lds_radix_sort_ids(const uint32_t* rk, uint
 
 // ---- device helpers ---------------------------------------------------------------------------
 #if defined(__HIPCC__)
+// Sums over the 64 lanes of a wave by the xor butterfly m = 32, 16, ..., 1; every lane ends with the same bits.  For doubles
+// the order of the additions is part of the bit-for-bit contract with the host builds: part[k] = part[k] + (lane ^ m)'s
+// part[k], k ascending inside m — what akz_tv_sum_tree (include/akz_three_view_math.h), akz_tvc_sum_wave
+// (include/akz_three_view_constraint_math.h) and akz_pg_sum_wave (include/akz_pose_graph_math.h) state for the host.
+__device__ __forceinline__ uint32_t akz_wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+template <int N>
+__device__ __forceinline__ void akz_wave_sum(double (&part)[N])
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) part[k] = part[k] + __shfl_xor(part[k], m, 64);
+    }
+}
 // Ascending bitonic sort of np2 (a power of two) 64-bit keys in LDS by one block of NT threads (NT a multiple of
 // 64, all threads call it; the keys must be complete and a barrier passed before).  Work item t owns the pair
 // (i, i | j) with i = t with a zero inserted at bit log2(j), so every thread compares one pair per item.  The

@@ -1274,11 +1274,7 @@ extern "C" int32_t hm_knn_views_device(hm_ctx* c, const void* d_q, const void* d
         if (!c || !d_q || !d_nq || !d_views || !d_nviews || !view_idx || !d_out || k < 1 || k > 3) return AKZ_E_INVALID;
         if (cap_per_img == 0 || cap_per_img >= (1u << (kIdxBits - 1))) return AKZ_E_INVALID;
         if (n_views == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         AKZ_TRY(hm_ensure_probs(c, knn_stage_bytes(n_views)));
         std::vector<HmProb> hp(n_views);
         for (uint32_t v = 0; v < n_views; ++v)
@@ -1301,11 +1297,7 @@ extern "C" int32_t hm_knn_batch_device(hm_ctx* c, const void* d_q, const void* d
         if (!c || !d_q || !d_nq || !d_t || !d_nt || !iq || !it || !d_out || k < 1 || k > 3) return AKZ_E_INVALID;
         if (cap_per_img == 0 || cap_per_img >= (1u << (kIdxBits - 1)) || n_probs > 65535u) return AKZ_E_INVALID;
         if (n_probs == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         AKZ_TRY(hm_ensure_probs(c, knn_stage_bytes(n_probs)));
         std::vector<HmProb> hp(n_probs);
         for (uint32_t p = 0; p < n_probs; ++p)
@@ -1384,11 +1376,7 @@ extern "C" int32_t hm_best_of_views_device(hm_ctx* c, const void* d_knn, const v
     return akz_guard([&]() -> int32_t {
         if (!c || !d_knn || !d_nq || !view_idx || !d_landmarks || !d_nviews || !d_best || !d_decision) return AKZ_E_INVALID;
         if (k < 1 || k > 3 || n_views == 0 || n_views > 64 || cap_per_img == 0) return AKZ_E_INVALID;
-        AKZ_HIP(hipSetDevice(c->device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         AKZ_TRY(hm_ensure_probs(c, 256));
         AKZ_TRY(hm_push_probs(c, 0, view_idx, sizeof(uint32_t) * n_views));
         hipLaunchKernelGGL(k_best_of_views, dim3((cap_per_img + 255) / 256), dim3(256), 0, c->stream, (const akz_neighbor*)d_knn,
@@ -1412,11 +1400,7 @@ extern "C" int32_t hm_best_of_views_batch_device(hm_ctx* c, const void* d_knn, c
         if (!c || !d_knn || !d_nq || !iq || !view_idx || !d_landmarks || !d_nviews || !d_best || !d_decision) return AKZ_E_INVALID;
         if (k < 1 || k > 3 || n_views == 0 || n_views > 64 || cap_per_img == 0 || n_frames > 65535u) return AKZ_E_INVALID;
         if (n_frames == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         const size_t vi_bytes = akz_align_up(sizeof(uint32_t) * (size_t)n_frames * n_views, 64);
         AKZ_TRY(hm_ensure_probs(c, vi_bytes + sizeof(uint32_t) * n_frames + 64));
         AKZ_TRY(hm_push_probs(c, 0, view_idx, sizeof(uint32_t) * (size_t)n_frames * n_views));
@@ -1591,11 +1575,7 @@ extern "C" int32_t hm_landmark_matches_ordered_batch_device(hm_ctx* c, const voi
         if (cap_per_img > kLmSlots / 4) return AKZ_E_TOO_LARGE;           // 2 keys per feature at a load factor <= 1/2
         if (d_merge_ok && (uint64_t)n_world + (uint64_t)n_frames * cap_per_img > 0xFFFFFFFFull) return AKZ_E_TOO_LARGE;
         if (n_frames == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         AKZ_TRY(hm_ensure_probs(c, sizeof(uint32_t) * n_frames + 64));
         AKZ_TRY(hm_push_probs(c, 0, iq, sizeof(uint32_t) * n_frames));
         AKZ_HIP(hipFuncSetAttribute((const void*)k_landmark_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLmLdsBytes));
@@ -1710,11 +1690,7 @@ extern "C" int32_t hm_match_batch_device(hm_ctx* c, const void* d_a, const void*
         if (!c || !d_a || !d_na || !d_b || !d_nb || !ia || !ib || !d_pairs || !d_n_out) return AKZ_E_INVALID;
         if (rule < 0 || rule > 2 || cap_per_img == 0 || cap_per_img >= (1u << (kIdxBits - 1))) return AKZ_E_INVALID;
         if (n_pairs == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         const uint32_t ndir = symmetric ? 2u : 1u;
         size_t need = (size_t)n_pairs * cap_per_img * 2;
         if (need > c->bscratch_elems) {
@@ -1805,11 +1781,7 @@ extern "C" int32_t hm_hash_bag_device(hm_ctx* c, const void* d_descs, const void
         if (n_codewords == 0 || (n_codewords & 31u) || n_codewords >= (1u << (kIdxBits - 1))) return AKZ_E_INVALID;
         if (cap_per_img == 0 || cap_per_img >= (1u << (kIdxBits - 1)) || n_frames > 65535u) return AKZ_E_INVALID;
         if (n_frames == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         return hash_bag_launch(c, (const uint4*)d_descs, (const uint32_t*)d_counts, cap_per_img, n_frames,
                                (const uint4*)d_codewords, n_codewords, (uint32_t*)d_hash, (akz_neighbor*)d_words);
     });
@@ -1864,8 +1836,7 @@ __global__ __launch_bounds__(256) void k_hash_dist(const uint32_t* __restrict__ 
     const uint32_t* h = hashes + (size_t)i * words;
     uint32_t acc = 0;
     for (uint32_t w = lane; w < words; w += 64u) acc += (uint32_t)__popc(q[w] ^ h[w]);
-#pragma unroll
-    for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = akz_wave_sum(acc);
     if (lane == 0) dist[i] = acc;
 }
 

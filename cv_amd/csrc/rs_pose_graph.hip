@@ -44,6 +44,7 @@
 namespace {
 
 constexpr int kPgWave = AKZ_PG_WAVE;
+static_assert(AKZ_PG_WAVE == 64, "akz_wave_sum adds over 64 lanes");
 constexpr int kPgWaves = 4;                                   // of k_pg_prepare, k_pg_relax_sweep and k_pg_finish
 constexpr int kPgBlock = kPgWave * kPgWaves;
 constexpr int kPgResidentBlock = kPgWave * RS_PG_RESIDENT_WAVES;
@@ -80,13 +81,6 @@ struct PgCall {
     uint32_t n_views, n_graphs, n_rows, n_constraints, iterations, resident_views;
     double rate;
 };
-
-__device__ __forceinline__ uint32_t pg_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = kPgWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kPgWave);
-    return v;
-}
 
 __global__ __launch_bounds__(kPgBlock) void k_pg_edges(const double* __restrict__ cposes, const uint32_t* __restrict__ cverdict,
                                                        uint32_t n_constraints, double* __restrict__ edges)
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_prepare(PgCall a)
                     bad |= r < 0;
                     has += r > 0 ? 1u : 0u;
                 }
-            has = pg_wave_sum(has);
+            has = akz_wave_sum(has);
             bad = __any(bad);
             if (lane == 0) {
                 a.view_graph[v] = has;
@@ -196,11 +190,7 @@ __device__ __forceinline__ int pg_view_round(const PgCall& a, const double* src,
 #pragma unroll
         for (int k = 0; k < 6; ++k) part[k] = part[k] + q[k];
     }
-#pragma unroll
-    for (int m = kPgWave / 2; m >= 1; m >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) part[k] = part[k] + __shfl_xor(part[k], m, kPgWave);
-    }
+    akz_wave_sum(part);
     const int ok = akz_pg_view_update(part, a.rate, cur, out);
     if (lane == 0) {
 #pragma unroll
@@ -287,16 +277,6 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_finish(PgCall a)
     }
 }
 
-int32_t pg_wait(const RsHandles& h, void* stream_to_wait)
-{
-    AKZ_HIP(hipSetDevice(h.device));
-    if (stream_to_wait) {
-        AKZ_HIP(hipEventRecord(h.ev, akz_wait_stream(stream_to_wait)));
-        AKZ_HIP(hipStreamWaitEvent(h.stream, h.ev, 0));
-    }
-    return AKZ_OK;
-}
-
 }   // namespace
 
 extern "C" int32_t rs_pose_graph_params_default(rs_pose_graph_params* prm)
@@ -322,7 +302,7 @@ extern "C" int32_t rs_pose_graph_edges_device(rs_ctx* c, const void* d_views, co
         if (!c || !d_views || !d_constraint_poses || !d_constraint_verdict || !d_edges) return AKZ_E_INVALID;
         if (n_constraints == 0) return AKZ_OK;
         const RsHandles h = rs_internal_handles(c);
-        AKZ_TRY(pg_wait(h, stream_to_wait));
+        AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         hipLaunchKernelGGL(k_pg_edges, dim3((n_constraints + kPgBlock - 1) / kPgBlock), dim3(kPgBlock), 0, h.stream,
                            (const double*)d_constraint_poses, (const uint32_t*)d_constraint_verdict, n_constraints, (double*)d_edges);
         AKZ_LAUNCH_CHECK();
@@ -345,7 +325,7 @@ extern "C" int32_t rs_pose_graph_relax_batch_device(rs_ctx* c, void* d_poses, ui
         if (n_graphs == 0) return AKZ_OK;
         const RsHandles h = rs_internal_handles(c);
         RsPoseGraphState* pg = rs_internal_pose_graph(c);
-        AKZ_TRY(pg_wait(h, stream_to_wait));
+        AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         // the context's scratch: the second pose table, a word per view, two per graph
         const size_t table_bytes = akz_align_up(sizeof(double) * 12 * (size_t)n_views, 256);
         const size_t view_bytes = akz_align_up(sizeof(uint32_t) * (size_t)n_views, 256);

@@ -2096,11 +2096,7 @@ static int32_t arrsac_batch_device(rs_ctx* c, bool world, uint32_t cap_per_img, 
     const bool shuffle = (flags & RS_BATCH_SHUFFLE) != 0;
     if (shuffle && n_max > kRadixSortMax) return AKZ_E_TOO_LARGE;   // the shuffle sorts a scene's keys in LDS
     AKZ_TRY(rs_check_params(c, *est, prm, n_max));
-    AKZ_HIP(hipSetDevice(c->device));
-    if (stream_to_wait) {
-        AKZ_HIP(hipEventRecord(c->ev, akz_wait_stream(stream_to_wait)));
-        AKZ_HIP(hipStreamWaitEvent(c->stream, c->ev, 0));
-    }
+    AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
     if (shuffle) AKZ_HIP(hipFuncSetAttribute((const void*)est->prepare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRadixSortLdsBytes));
     AKZ_TRY(prepare(c->stream, rs_view(c, shuffle), shuffle));
     uint32_t blocks = 0, smp_made = 0;

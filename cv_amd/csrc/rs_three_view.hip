@@ -23,6 +23,7 @@ namespace {
 
 constexpr int kTvBlock = AKZ_TV_THREADS;
 constexpr int kTvWaves = AKZ_TV_THREADS / AKZ_TV_WAVE;
+static_assert(AKZ_TV_WAVE == 64, "akz_wave_sum adds over 64 lanes");
 static_assert(RS_TV_STATS == AKZ_TV_STATS && RS_TV_MAX_COMMON * sizeof(unsigned long long) <= 9 * AKZ_TV_MAX_LANDMARKS * sizeof(double),
               "the ratio keys of the first pass live where the landmarks go afterwards");
 static_assert(RS_TV_OK == AKZ_TV_OK && RS_TV_FEW_SCALES == AKZ_TV_FEW_SCALES && RS_TV_FEW_BEARING_PAIRS == AKZ_TV_FEW_BEARING_PAIRS &&
@@ -62,8 +63,7 @@ __device__ __forceinline__ uint32_t tv_block_sum(TvShared& sh, uint32_t& tick, u
 {
     const uint32_t lane = threadIdx.x & (AKZ_TV_WAVE - 1), w = threadIdx.x / AKZ_TV_WAVE, buf = tick & 1u;
     ++tick;
-#pragma unroll
-    for (int m = AKZ_TV_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    v = akz_wave_sum(v);
     if (lane == 0) sh.cnt[buf][w] = v;
     __syncthreads();
     uint32_t all = 0;
@@ -147,11 +147,7 @@ __device__ uint32_t tv_optimize(TvShared& sh, double* poses, double rate, uint32
 #pragma unroll
             for (int k = 0; k < 12; ++k) part[k] = part[k] + g[k];
         }
-#pragma unroll
-        for (int m = AKZ_TV_WAVE / 2; m >= 1; m >>= 1) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) part[k] = part[k] + __shfl_xor(part[k], m);
-        }
+        akz_wave_sum(part);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) sh.red[it & 1u][w][k] = part[k];
@@ -415,11 +411,7 @@ extern "C" int32_t rs_three_view_init_batch_device(rs_ctx* c, const void* d_kps,
         const RsHandles h = rs_internal_handles(c);
         if (h.max_scenes == 0) return AKZ_E_INVALID;              // a context without its batch arena (rs_batch_reserve failed)
         if (n_scenes > h.max_scenes) return AKZ_E_TOO_LARGE;
-        AKZ_HIP(hipSetDevice(h.device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(h.ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(h.stream, h.ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         // the frame lists go where the consensus keeps its own: stream order puts the copies behind that call's last reader
         AKZ_HIP(hipMemcpyAsync(h.d_frames, ic, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, h.stream));
         AKZ_HIP(hipMemcpyAsync(h.d_frames + h.max_scenes, i_first, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, h.stream));

@@ -27,6 +27,7 @@
 namespace {
 
 constexpr int kTvcWave = AKZ_TVC_WAVE;
+static_assert(AKZ_TVC_WAVE == 64, "akz_wave_sum adds over 64 lanes");
 constexpr int kTvcBlock = AKZ_TVC_WAVE * RS_TVC_BLOCK_WAVES;
 static_assert(RS_TVC_OK == AKZ_TVC_OK && RS_TVC_FEW_LANDMARKS == AKZ_TVC_FEW_LANDMARKS && RS_TVC_FEW_BEARING_PAIRS == AKZ_TVC_FEW_BEARING_PAIRS &&
               RS_TVC_BAD_INDEX == AKZ_TVC_BAD_INDEX, "verdict values");
@@ -35,12 +36,6 @@ static_assert(RS_TVC_STATS == AKZ_TVC_STATS && RS_TVC_S_LANDMARKS == AKZ_TVC_S_L
               RS_TVC_S_FINAL_SCALE == AKZ_TVC_S_FINAL_SCALE && RS_TVC_S_STAGE == AKZ_TVC_S_STAGE, "stats words");
 static_assert(RS_TVC_MAX_LANDMARKS == AKZ_TVC_MAX_LANDMARKS && RS_TVC_MAX_ITERATIONS == AKZ_TVC_MAX_ITERATIONS, "limits");
 
-__device__ __forceinline__ uint32_t tvc_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = kTvcWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kTvcWave);
-    return v;
-}
 // all of a constraint's stats words and its verdict, by one lane at the point the verdict falls
 __device__ __forceinline__ void tvc_finish(uint32_t* stats, uint32_t* verdict, uint32_t v, uint32_t stage, uint32_t n_list, uint32_t used,
                                            uint32_t pairs, double original_scale, double final_scale)
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(kTvcBlock, 2) void k_tv_constraints(const akz_keypo
             mine += akz_tv_bearing_pair_robust(a, a + 3, a + 6, b, b + 3, b + 6, st.robust_view_bearing_pair_minimum_cosine_distance) ? 1u : 0u;
         }
     }
-    const uint32_t pairs = tvc_wave_sum(mine);
+    const uint32_t pairs = akz_wave_sum(mine);
     if (pairs < st.robust_view_num_robust_bearing_pair) {
         if (lane == 0) tvc_finish(stats, verdict + s, AKZ_TVC_FEW_BEARING_PAIRS, AKZ_TVC_STAGE_PAIRS, n_list, used, pairs, original_scale, 0.0);
         return;
@@ -168,11 +163,7 @@ __global__ __launch_bounds__(kTvcBlock, 2) void k_tv_constraints(const akz_keypo
                 for (int k = 0; k < 9; ++k) b[k] = sh[k * stride + i];
                 akz_tvc_accumulate(inv, b, b + 3, b + 6, part);
             }
-#pragma unroll
-            for (int m = kTvcWave / 2; m >= 1; m >>= 1) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) part[k] = part[k] + __shfl_xor(part[k], m, kTvcWave);
-            }
+            akz_wave_sum(part);
             akz_tvc_adaptive_step(part, inv_len, inv);
         }
         akz_tv_pose_inverse(inv, rel);
@@ -233,11 +224,7 @@ extern "C" int32_t rs_three_view_constraint_batch_device(rs_ctx* c, const void* 
         if (cap_per_img == 0 || n_blocks == 0 || cam->reserved != 0) return AKZ_E_INVALID;
         if (n_constraints == 0) return AKZ_OK;
         const RsHandles h = rs_internal_handles(c);
-        AKZ_HIP(hipSetDevice(h.device));
-        if (stream_to_wait) {
-            AKZ_HIP(hipEventRecord(h.ev, akz_wait_stream(stream_to_wait)));
-            AKZ_HIP(hipStreamWaitEvent(h.stream, h.ev, 0));
-        }
+        AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         const uint32_t stride = st.optimization_maximum_landmarks <= (uint32_t)kTvcWave ? (uint32_t)kTvcWave : (uint32_t)RS_TVC_MAX_LANDMARKS;
         const size_t lds = sizeof(double) * 9 * stride * RS_TVC_BLOCK_WAVES;
         const uint32_t grid = (n_constraints + RS_TVC_BLOCK_WAVES - 1) / RS_TVC_BLOCK_WAVES;

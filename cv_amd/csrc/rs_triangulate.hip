@@ -201,16 +201,6 @@ int32_t tri_settings(const rs_triangulate_params* prm, akz_tri_settings* st)
     return AKZ_OK;
 }
 
-int32_t tri_wait(const RsHandles& h, void* stream_to_wait)
-{
-    AKZ_HIP(hipSetDevice(h.device));
-    if (stream_to_wait) {
-        AKZ_HIP(hipEventRecord(h.ev, akz_wait_stream(stream_to_wait)));
-        AKZ_HIP(hipStreamWaitEvent(h.stream, h.ev, 0));
-    }
-    return AKZ_OK;
-}
-
 }   // namespace
 
 extern "C" int32_t rs_triangulate_params_default(rs_triangulate_params* prm)
@@ -270,7 +260,7 @@ extern "C" int32_t rs_triangulate_landmarks_device(rs_ctx* c, const void* d_kps,
         AKZ_TRY(tri_settings(prm, &st));
         if (n_landmarks == 0) return AKZ_OK;
         const RsHandles h = rs_internal_handles(c);
-        AKZ_TRY(tri_wait(h, stream_to_wait));
+        AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         hipLaunchKernelGGL(k_tri_landmarks, dim3((n_landmarks + kTriBlock - 1) / kTriBlock), dim3(kTriBlock), 0, h.stream,
                            (const akz_keypoint*)d_kps, cap_per_img, n_blocks, (const double*)d_poses, *cam, (const uint32_t*)d_obs_start,
                            (const uint32_t*)d_obs, n_obs, n_landmarks, st, (double*)d_world, (unsigned char*)d_reason);
@@ -293,7 +283,7 @@ extern "C" int32_t rs_triangulate_merged_device(rs_ctx* c, const void* d_kps, ui
         AKZ_TRY(tri_settings(prm, &st));
         if (n_frames == 0) return AKZ_OK;
         const RsHandles h = rs_internal_handles(c);
-        AKZ_TRY(tri_wait(h, stream_to_wait));
+        AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         hipLaunchKernelGGL(k_tri_merged, dim3((cap_per_img + kTriBlock - 1) / kTriBlock, n_frames), dim3(kTriBlock), 0, h.stream,
                            (const akz_keypoint*)d_kps, cap_per_img, n_blocks, (const double*)d_poses, *cam, (const uint32_t*)d_obs_start,
                            (const uint32_t*)d_obs, n_obs, n_landmarks, st, (const uint2*)d_best, (const uint32_t*)d_decision,
@@ -320,7 +310,7 @@ extern "C" int32_t rs_triangulate_pairs_batch_device(rs_ctx* c, const void* d_kp
         const RsHandles h = rs_internal_handles(c);
         if (h.max_scenes == 0) return AKZ_E_INVALID;              // a context without its batch arena (rs_batch_reserve failed)
         if (n_scenes > h.max_scenes) return AKZ_E_TOO_LARGE;
-        AKZ_TRY(tri_wait(h, stream_to_wait));
+        AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         // the frame lists go where the consensus keeps its own: stream order puts the copy behind that call's last reader
         AKZ_HIP(hipMemcpyAsync(h.d_frames, ia, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, h.stream));
         AKZ_HIP(hipMemcpyAsync(h.d_frames + h.max_scenes, ib, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, h.stream));

@@ -68,13 +68,7 @@ class PoseGraph:
     @staticmethod
     def params(**kw):
         """rs_pose_graph_params: the reference's defaults (cv-sfm/src/settings.rs:461-463, 477-479) with `kw` on top."""
-        p = _lib.PoseGraphParams()
-        check(_lib.lib().rs_pose_graph_params_default(C.byref(p)), "rs_pose_graph_params_default")
-        for k, v in kw.items():
-            if k == "struct_size" or not hasattr(p, k):
-                raise TypeError(f"rs_pose_graph_params has no setting {k!r}")
-            setattr(p, k, v)
-        return p
+        return _lib.params(_lib.PoseGraphParams, "rs_pose_graph_params_default", **kw)
 
     def resident_views(self, views=_lib.RS_PG_DEFAULT_RESIDENT_VIEWS):
         """parity tap: graphs of more than `views` views (at most RS_PG_RESIDENT_VIEWS) take the swept form from now on (0:
@@ -102,10 +96,7 @@ class PoseGraph:
             if not (a.is_cuda and a.is_contiguous() and a.element_size() == np.dtype(dtype).itemsize):
                 raise ValueError("contiguous device tensors of the documented element type only")
             return a
-        host = np.ascontiguousarray(a, dtype)
-        if host.size == 0:
-            return torch.zeros(8, dtype=torch.uint8, device=dev)
-        return torch.from_numpy(host.view(np.uint8).reshape(-1)).to(dev)
+        return _lib.device_bytes(torch, np.ascontiguousarray(a, dtype), dev)
 
     def edges(self, torch, views, constraints, device=0):
         """The edge table [n][6][12] float64 on the device of the constraints (views [n][3], and `constraints`: a

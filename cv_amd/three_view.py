@@ -63,7 +63,7 @@ class ThreeViewResult:
 
     @property
     def median_scale(self):
-        return float(self.stats[_lib.RS_TV_S_MEDIAN:_lib.RS_TV_S_MEDIAN + 2].copy().view(np.float64)[0])
+        return _lib.stat_f64(self.stats, _lib.RS_TV_S_MEDIAN)
 
 
 class ThreeViewInit:
@@ -77,13 +77,7 @@ class ThreeViewInit:
     def params(**kw):
         """rs_three_view_params: the reference's defaults (cv-sfm/src/settings.rs:320-427) with `kw` on top; `triangulate`
         takes an rs_triangulate_params (cv_amd.triangulation.make_params)."""
-        p = _lib.ThreeViewParams()
-        check(_lib.lib().rs_three_view_params_default(C.byref(p)), "rs_three_view_params_default")
-        for k, v in kw.items():
-            if k == "struct_size" or not hasattr(p, k):
-                raise TypeError(f"rs_three_view_params has no setting {k!r}")
-            setattr(p, k, v)
-        return p
+        return _lib.params(_lib.ThreeViewParams, "rs_three_view_params_default", **kw)
 
     def init_batch_device(self, d_kps, cap_per_img, n_blocks, ic, i_first, i_second, cam, d_pose_first, d_pose_second, d_triples,
                           d_ntriples, d_first_only, d_nfirst, d_second_only, d_nsecond, params, d_pose_out, d_verdict, d_combined,
@@ -108,7 +102,7 @@ class ThreeViewInit:
         for k in range(3):
             kps[k, :len(keypoints[k])] = np.asarray(keypoints[k], _lib.KP_DTYPE)
         dev = torch.device("cuda", device)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+        up = lambda a: _lib.device_bytes(torch, a, dev)
 
         def padded(a, w):
             out = np.zeros((cap, w), np.uint32)
@@ -156,7 +150,7 @@ class ThreeViewConstraintResult:
     stats: np.ndarray        # [n][RS_TVC_STATS] u32
 
     def scale(self, i, which=_lib.RS_TVC_S_FINAL_SCALE):
-        return float(self.stats[i, which:which + 2].copy().view(np.float64)[0])
+        return _lib.stat_f64(self.stats[i], which)
 
 
 class ThreeViewConstraints:
@@ -169,13 +163,7 @@ class ThreeViewConstraints:
     @staticmethod
     def params(**kw):
         """rs_three_view_constraint_params: the reference's defaults (cv-sfm/src/settings.rs:332-338, 465-483) with `kw` on top."""
-        p = _lib.ThreeViewConstraintParams()
-        check(_lib.lib().rs_three_view_constraint_params_default(C.byref(p)), "rs_three_view_constraint_params_default")
-        for k, v in kw.items():
-            if k == "struct_size" or not hasattr(p, k):
-                raise TypeError(f"rs_three_view_constraint_params has no setting {k!r}")
-            setattr(p, k, v)
-        return p
+        return _lib.params(_lib.ThreeViewConstraintParams, "rs_three_view_constraint_params_default", **kw)
 
     def batch_device(self, d_kps, cap_per_img, n_blocks, d_poses, cam, d_views, d_lm_start, d_lm, n_lm, n_constraints, params,
                      d_pose_out, d_verdict, d_stats, stream_to_wait=None):

@@ -1,6 +1,6 @@
 /* The CPU checker of the five-point kernels: thin exported wrappers around include/akz_five_point_math.h, the text
- * cv_amd/csrc/rs_ransac.hip compiles for the device.  tests/five_point_checker.py builds this with the host compiler
- * (-O2 -ffp-contract=off) into a shared object and loads it with ctypes. */
+ * cv_amd/csrc/rs_ransac.hip compiles for the device.  tests/five_point_checker.py has tests/host_build.py build this with
+ * the host compiler (its `load`: -O2, no contraction to FMA) into a shared object and loads it with ctypes. */
 #include <stddef.h>
 #include <stdint.h>
 

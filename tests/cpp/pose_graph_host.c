@@ -1,7 +1,7 @@
 /* The CPU checker of the pose-graph relaxation: thin exported wrappers around include/akz_pose_graph_math.h, the text
- * cv_amd/csrc/rs_pose_graph.hip compiles for the device.  tests/pose_graph_checker.py builds this with the host compiler
- * (-O2 -ffp-contract=off) into a shared object and loads it with ctypes.  The arithmetic and the control flow of a graph are
- * the header's. */
+ * cv_amd/csrc/rs_pose_graph.hip compiles for the device.  tests/pose_graph_checker.py has tests/host_build.py build this
+ * with the host compiler (its `load`: -O2, no contraction to FMA) into a shared object and loads it with ctypes.  The
+ * arithmetic and the control flow of a graph are the header's. */
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>

@@ -1,7 +1,7 @@
 /* The CPU checker of the three-view bootstrap: thin exported wrappers around include/akz_three_view_math.h, the text
- * cv_amd/csrc/rs_three_view.hip compiles for the device.  tests/three_view_checker.py builds this with the host compiler
- * (-O2 -ffp-contract=off) into a shared object and loads it with ctypes.  The gather around the header (keypoint ->
- * bearing, the index checks) restates the kernel's; the arithmetic is the header's. */
+ * cv_amd/csrc/rs_three_view.hip compiles for the device.  tests/three_view_checker.py has tests/host_build.py build this
+ * with the host compiler (its `load`: -O2, no contraction to FMA) into a shared object and loads it with ctypes.  The
+ * gather around the header (keypoint -> bearing, the index checks) restates the kernel's; the arithmetic is the header's. */
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>

@@ -1,6 +1,6 @@
 /* The CPU checker of the triangulation kernels: thin exported wrappers around include/akz_triangulate_math.h, the text
- * cv_amd/csrc/rs_triangulate.hip compiles for the device.  tests/test_triangulate_math.py and tests/test_gpu_triangulate.py
- * build this with the host compiler (-O2 -ffp-contract=off) into a shared object and load it with ctypes.  The loops
+ * cv_amd/csrc/rs_triangulate.hip compiles for the device.  tests/triangulate_checker.py has tests/host_build.py build this
+ * with the host compiler (its `load`: -O2, no contraction to FMA) into a shared object and loads it with ctypes.  The loops
  * around the header (which list belongs to which row) restate the kernels'; the arithmetic is the header's. */
 #include <stddef.h>
 #include <stdint.h>

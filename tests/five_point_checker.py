@@ -1,32 +1,22 @@
 """The CPU checker of the five-point kernels for the tests: tests/cpp/five_point_host.c (thin wrappers around
-include/akz_five_point_math.h) compiled with the host compiler, flags -O2 -ffp-contract=off, into a shared object in a
-temporary directory and loaded with ctypes."""
+include/akz_five_point_math.h) as host_build.load compiles it — the host compiler, no contraction to FMA, as the kernels —
+loaded with ctypes."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 EPS, MAX_SWEEPS = 1e-16, 1000        # AKZ_FP_JACOBI_EPS, AKZ_FP_JACOBI_SWEEPS of include/akz_five_point_math.h
 
-_dir = None
 _lib = None
 
 
 def lib():
-    global _dir, _lib
+    global _lib
     if _lib is not None:
         return _lib
-    cc = shutil.which("gcc") or shutil.which("cc")
-    assert cc, "the CPU checker needs a host C compiler"
-    _dir = tempfile.TemporaryDirectory(prefix="akz_fp_host_")
-    so = os.path.join(_dir.name, "libfp_host.so")
-    subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-std=c11", "-shared", "-fPIC", "-Wall",
-                           os.path.join(ROOT, "tests", "cpp", "five_point_host.c"), "-o", so, "-lm"])
-    L = C.CDLL(so)
+    L = host_build.load("five_point_host.c")
     vp, u32 = C.c_void_p, C.c_uint32
     L.fp_essentials.argtypes = [vp, vp, vp, u32, C.c_double, C.c_int, vp, vp]
     L.fp_essentials.restype = None

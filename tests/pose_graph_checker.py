@@ -1,17 +1,13 @@
 """The CPU checker of the pose-graph kernels for the tests: tests/cpp/pose_graph_host.c (thin wrappers around
-include/akz_pose_graph_math.h) compiled with the host compiler, flags -O2 -ffp-contract=off, into a shared object in a
-temporary directory and loaded with ctypes; plus the synthetic graphs the test files use."""
+include/akz_pose_graph_math.h) as host_build.load compiles it — the host compiler, no contraction to FMA, as the kernels —
+loaded with ctypes; plus the synthetic graphs the test files use."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
+import host_build
 import pose_graph_statement as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATS = 8
 S_VIEWS, S_UPDATED, S_EDGES, S_ROUNDS, S_STAGE, S_FIRST_BAD_VIEW = range(6)
 OK, FEW_VIEWS, NONFINITE, BAD_INDEX = range(4)
@@ -32,21 +28,14 @@ def settings(iterations=1024, rate=1e-3):
     return Settings(rate, iterations)
 
 
-_dir = None
 _lib = None
 
 
 def lib():
-    global _dir, _lib
+    global _lib
     if _lib is not None:
         return _lib
-    cc = shutil.which("gcc") or shutil.which("cc")
-    assert cc, "the CPU checker needs a host C compiler"
-    _dir = tempfile.TemporaryDirectory(prefix="akz_pg_host_")
-    so = os.path.join(_dir.name, "libpg_host.so")
-    subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-std=gnu11", "-shared", "-fPIC", "-Wall",
-                           os.path.join(ROOT, "tests", "cpp", "pose_graph_host.c"), "-o", so, "-lm"])
-    L = C.CDLL(so)
+    L = host_build.load("pose_graph_host.c")
     vp, u32, dbl = C.c_void_p, C.c_uint32, C.c_double
     L.pg_acos.argtypes = [dbl]
     L.pg_acos.restype = dbl

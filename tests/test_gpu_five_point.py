@@ -2,12 +2,12 @@
 device == host build of include/akz_five_point_math.h bit for bit, the E -> poses -> residual path == the oracle's on the
 device's own matrices, and the consensus entry points agree with one another.  Run with -m gpu."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import five_point_checker as ck
 import five_point_statement as st
 
@@ -287,12 +287,7 @@ def test_cpp_host_mirror_five_point(gpu, noisy, tmp_path):
     """arrsac::Arrsac::model_inliers(NisterStewenius) of include/akaze.hpp from a native process (tests/cpp/five_point.cpp):
     its output file == the ctypes path's bytes."""
     a, b, samples, thr = noisy
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "five_point"
-    lib_dir = os.path.join(root, "cv_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "five_point.cpp"), "-o", str(exe),
-                           "-L", lib_dir, "-lakz", f"-Wl,-rpath,{lib_dir}"])
+    exe = host_build.native(tmp_path, "five_point.cpp", hip=False)
     np.concatenate([a, b], axis=1).tofile(tmp_path / "matches.bin")
     n_hyp, seed, block = 64, 4242, 100
     r = subprocess.run([str(exe), str(tmp_path / "matches.bin"), str(tmp_path / "out.bin"), repr(thr), str(seed), str(n_hyp), str(block)],

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import synth_frame
+import host_build
 
 pytestmark = pytest.mark.gpu
 
@@ -776,12 +777,7 @@ def test_cpp_host_mirror_estimate_pose(gpu, kitti, tmp_path):
     consensus -> 11 inliers) restated in C++ against include/akaze.hpp — the twin of the Rust shim — and run as a separate
     native process linked to libakz.so; plus the context cache, list growth and the colour arm from a native caller."""
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "estimate_pose"
-    lib_dir = os.path.join(root, "cv_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "estimate_pose.cpp"), "-o", str(exe),
-                           "-L", lib_dir, "-lakz", f"-Wl,-rpath,{lib_dir}"])
+    exe = host_build.native(tmp_path, "estimate_pose.cpp", hip=False)
     f0, f1 = tmp_path / "f0.raw", tmp_path / "f14.raw"
     kitti[0].tofile(f0); kitti[1].tofile(f1)
     h, w = kitti[0].shape
@@ -798,14 +794,7 @@ def test_native_host_drives_the_device_pipeline(gpu, kitti, tmp_path):
     nothing copied back in between: 399 / 343 descriptors, 11 matches, 11 inliers, and the device API's keypoints and
     descriptors byte-equal to the host API's."""
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "device_pipeline"
-    lib_dir = os.path.join(root, "cv_amd", "lib")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
-                           "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "device_pipeline.cpp"),
-                           "-o", str(exe), "-L", lib_dir, "-lakz", "-L", os.path.join(rocm, "lib"), "-lamdhip64",
-                           f"-Wl,-rpath,{lib_dir}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}"])
+    exe = host_build.native(tmp_path, "device_pipeline.cpp", hip=True)
     f0, f1 = tmp_path / "f0.raw", tmp_path / "f14.raw"
     kitti[0].tofile(f0); kitti[1].tofile(f1)
     h, w = kitti[0].shape

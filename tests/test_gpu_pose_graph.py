@@ -6,12 +6,12 @@ Forms: the resident form (one persistent workgroup a graph) can take RS_PG_RESID
 graphs of at most 8, the others go through a launch per round; PoseGraph.resident_views moves the limit, so that both forms
 are tested at every size up to 256 and 257."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import pose_graph_checker as P
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +44,7 @@ def run(torch, cons, A, st, resident=None, n_rows=None, n_constraints=None):
     from cv_amd import _lib
     from cv_amd.pose_graph import PoseGraph
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev) if a.size else torch.zeros(8, dtype=torch.uint8, device=dev)
+    up = lambda a: _lib.device_bytes(torch, a, dev)
     n_views, n_graphs, n_c = len(A["poses"]), len(A["graph_start"]) - 1, len(A["views"])
     d_poses, d_gs, d_rs, d_re, d_views, d_cposes, d_cverdict = (up(A[k]) for k in ("poses", "graph_start", "row_start", "row_edges", "views", "cposes", "cverdict"))
     d_edges = torch.full((n_c * 72 * 8,), FILL, dtype=torch.uint8, device=dev)
@@ -213,7 +213,7 @@ def test_the_parameters_are_checked_with_a_live_context(gpu, cons):
     torch = gpu
     A = P.batch([P.Graph(400, 6)])
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    up = lambda a: _lib.device_bytes(torch, a, dev)
     d = {k: up(A[k]) for k in ("poses", "graph_start", "row_start", "row_edges", "views", "cverdict", "edges")}
     d_out = torch.full((4 * (1 + P.STATS + 6),), FILL, dtype=torch.uint8, device=dev)
     L = _lib.lib()
@@ -300,14 +300,7 @@ def test_the_chain_stays_on_the_device(gpu, cons):
 def test_cpp_host_mirror_pose_graph(gpu, cons, tmp_path):
     """cv_sfm::PoseGraph of include/akaze.hpp from a native process (tests/cpp/pose_graph.cpp): its flatten and its printed
     verdicts, states, stats and poses equal the ctypes path's."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "pose_graph"
-    lib_dir = os.path.join(root, "cv_amd", "lib")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
-                           "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "pose_graph.cpp"),
-                           "-o", str(exe), "-L", lib_dir, "-lakz", "-L", os.path.join(rocm, "lib"), "-lamdhip64",
-                           f"-Wl,-rpath,{lib_dir}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}"])
+    exe = host_build.native(tmp_path, "pose_graph.cpp", hip=True)
     A = P.batch(small_graphs() + [P.Graph(9, 4, triples=[(0, 1, 2)], refused=[0])])
     rounds = 7
     with open(tmp_path / "batch.bin", "wb") as f:

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
 import three_view_checker as K
 
 pytestmark = pytest.mark.gpu
@@ -47,10 +48,11 @@ def device_params(st):
 def run(torch, cons, scenes, st, blocks_override=None):
     """The device call on `scenes` (scene s owns keypoint blocks 3s .. 3s + 2) and the host build on each; everything the call
     may write is compared in bytes.  -> the host results."""
+    from cv_amd import _lib
     from cv_amd.three_view import ThreeViewInit
     S, cap = len(scenes), scenes[0]["kps"].shape[1]
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    up = lambda a: _lib.device_bytes(torch, a, dev)
     kps = np.concatenate([s["kps"] for s in scenes])
     blocks = [list(range(3 * s, 3 * s + 3)) for s in range(S)]
     for s, b in (blocks_override or {}).items():
@@ -257,9 +259,10 @@ def test_default_settings_scene(gpu, cons):
     kps = np.ascontiguousarray(g["kps"]).view(K.KP_DTYPE).reshape(3, cap)
     n, nf, ns = (int(x) for x in g["counts"])
     sc = dict(kps=kps, triples=g["triples"], n=n, fo=g["first_only"], nf=nf, so=g["second_only"], ns=ns, pose_in=g["pose_in"])
+    from cv_amd import _lib
     from cv_amd.three_view import ThreeViewInit
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    up = lambda a: _lib.device_bytes(torch, a, dev)
     d_kps, d_p, d_t, d_f, d_s = up(kps), up(sc["pose_in"]), up(sc["triples"]), up(sc["fo"]), up(sc["so"])
     d_n = up(g["counts"])
     d_pose = torch.zeros(24, dtype=torch.float64, device=dev)
@@ -299,14 +302,7 @@ def test_default_settings_scene(gpu, cons):
 def test_cpp_host_mirror_three_view(gpu, cons, tmp_path):
     """cv_sfm::ThreeViewInit of include/akaze.hpp from a native process (tests/cpp/three_view.cpp): its printed verdict, poses
     and stats equal the ctypes path's."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "three_view"
-    lib_dir = os.path.join(root, "cv_amd", "lib")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
-                           "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "three_view.cpp"),
-                           "-o", str(exe), "-L", lib_dir, "-lakz", "-L", os.path.join(rocm, "lib"), "-lamdhip64",
-                           f"-Wl,-rpath,{lib_dir}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}"])
+    exe = host_build.native(tmp_path, "three_view.cpp", hip=True)
     cap = 256
     rig = K.Rig(71, 150, noise=0.5, perturb=2e-3, n_first=11, n_second=13, outliers=9)
     sc = scene_of(rig, cap, shuffle_seed=2)

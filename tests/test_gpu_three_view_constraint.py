@@ -4,12 +4,12 @@ compared).  Poses a constraint does not write keep the pattern they were filled 
 
 Residency: the kernel takes 230 VGPRs, two waves per SIMD, 2 048 constraints at once on the 256 CUs; the batch of 1 025 is
 beyond one wave per SIMD (1 024), the batch of 2 305 beyond what is resident at all."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import three_view_constraint_checker as T
 
 pytestmark = pytest.mark.gpu
@@ -49,17 +49,17 @@ def camera():
 def run(torch, cons, arrays, st, n_lm=None):
     """The device call on `arrays` (T.device_arrays) and the host build on each constraint; everything the call may write is
     compared in bytes.  -> the host results."""
+    from cv_amd import _lib
     from cv_amd.three_view import ThreeViewConstraints
     kps, poses, views, lm_start, lm = arrays
     n = len(views)
     n_lm = len(lm) if n_lm is None else n_lm
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev) if a.size else torch.zeros(8, dtype=torch.uint8, device=dev)
+    up = lambda a: _lib.device_bytes(torch, a, dev)
     d_kps, d_poses, d_views, d_start, d_lm = up(kps), up(poses), up(views), up(lm_start), up(lm)
     d_pose = torch.full((n * 24 * 8,), FILL, dtype=torch.uint8, device=dev)
     d_verdict = torch.full((n * 4,), FILL, dtype=torch.uint8, device=dev)
     d_stats = torch.full((n * T.STATS * 4,), FILL, dtype=torch.uint8, device=dev)
-    from cv_amd import _lib
     ThreeViewConstraints(cons).batch_device(d_kps.data_ptr(), kps.shape[1], kps.shape[0], d_poses.data_ptr(), camera(), d_views.data_ptr(),
                                             d_start.data_ptr(), d_lm.data_ptr(), n_lm, n, ThreeViewConstraints.params(**T.settings_dict(st)),
                                             d_pose.data_ptr(), d_verdict.data_ptr(), d_stats.data_ptr(),
@@ -203,14 +203,7 @@ def test_run_takes_torch_tensors(gpu, cons, scenes):
 def test_cpp_host_mirror_three_view_constraint(gpu, cons, scenes, tmp_path):
     """cv_sfm::ThreeViewConstraints of include/akaze.hpp from a native process (tests/cpp/three_view_constraint.cpp): its
     printed verdicts, poses and stats equal the ctypes path's."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "three_view_constraint"
-    lib_dir = os.path.join(root, "cv_amd", "lib")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
-                           "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "three_view_constraint.cpp"),
-                           "-o", str(exe), "-L", lib_dir, "-lakz", "-L", os.path.join(rocm, "lib"), "-lamdhip64",
-                           f"-Wl,-rpath,{lib_dir}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}"])
+    exe = host_build.native(tmp_path, "three_view_constraint.cpp", hip=True)
     arrays = T.device_arrays(scenes[1:3] + scenes[8:], CAP, [(0, np.arange(64)), (1, np.arange(12)), (1, np.arange(130)), (2, None)])
     kps, poses, views, lm_start, lm = arrays
     patience, maximum = 24, 100

@@ -2,11 +2,11 @@
 (tests/triangulate_checker.py), bit for bit, and the registration loop closed on the device: poses and observation lists in,
 registered poses out, the world table never on the host."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import host_build
 import triangulate_checker as tc
 
 pytestmark = pytest.mark.gpu
@@ -465,12 +465,7 @@ def test_cpp_host_mirror_triangulate(gpu, tmp_path):
     """cv_geom::LinearEigenTriangulator of include/akaze.hpp from a native process (tests/cpp/triangulate.cpp): the
     reference's doc-test and its None cases."""
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "triangulate"
-    lib_dir = os.path.join(root, "cv_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "triangulate.cpp"), "-o", str(exe),
-                           "-L", lib_dir, "-lakz", f"-Wl,-rpath,{lib_dir}"])
+    exe = host_build.native(tmp_path, "triangulate.cpp", hip=False)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "doc-test distance" in r.stdout and "none cases ok" in r.stdout and "triangulate ok" in r.stdout

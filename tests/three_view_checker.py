@@ -1,18 +1,14 @@
 """The CPU checker of the three-view kernel for the tests: tests/cpp/three_view_host.c (thin wrappers around
-include/akz_three_view_math.h) compiled with the host compiler, flags -O2 -ffp-contract=off, into a shared object in a
-temporary directory and loaded with ctypes; plus the synthetic rigs both test files use."""
+include/akz_three_view_math.h) as host_build.load compiles it — the host compiler, no contraction to FMA, as the kernel —
+loaded with ctypes; plus the synthetic rigs both test files use."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
+import host_build
 from triangulate_checker import KP_DTYPE, Camera, camera
 from triangulate_checker import Settings as TriSettings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATS = 24
 S_SCALES, S_MEDIAN, S_PAIRS, S_RUN_MATCHES, S_RUN_STOP, S_ROBUST, S_STAGE = 0, 1, 3, 4, 13, 22, 23
 FOCAL = 1000.0
@@ -42,21 +38,14 @@ def settings_dict(st):
     return {n: getattr(st, n) for n, _ in Settings._fields_ if n != "tri"}
 
 
-_dir = None
 _lib = None
 
 
 def lib():
-    global _dir, _lib
+    global _lib
     if _lib is not None:
         return _lib
-    cc = shutil.which("gcc") or shutil.which("cc")
-    assert cc, "the CPU checker needs a host C compiler"
-    _dir = tempfile.TemporaryDirectory(prefix="akz_tv_host_")
-    so = os.path.join(_dir.name, "libtv_host.so")
-    subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-std=gnu11", "-shared", "-fPIC", "-Wall",
-                           os.path.join(ROOT, "tests", "cpp", "three_view_host.c"), "-o", so, "-lm"])
-    L = C.CDLL(so)
+    L = host_build.load("three_view_host.c")
     vp, u32, dbl = C.c_void_p, C.c_uint32, C.c_double
     sp, cp = C.POINTER(Settings), C.POINTER(Camera)
     L.tv_gradients.argtypes = [vp] * 5

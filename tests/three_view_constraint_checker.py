@@ -1,19 +1,15 @@
 """The CPU checker of the three-view constraint kernel for the tests: tests/cpp/three_view_constraint_host.c (thin wrappers
-around include/akz_three_view_constraint_math.h) compiled with the host compiler, flags -O2 -ffp-contract=off, into a shared
-object in a temporary directory and loaded with ctypes; plus the synthetic scenes both test files use."""
+around include/akz_three_view_constraint_math.h) as host_build.load compiles it — the host compiler, no contraction to FMA,
+as the kernel — loaded with ctypes; plus the synthetic scenes both test files use."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
+import host_build
 import three_view_checker as K
 import three_view_constraint_statement as S
 from triangulate_checker import KP_DTYPE, Camera
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATS = 8
 S_LANDMARKS, S_USED, S_PAIRS, S_ORIGINAL_SCALE, S_FINAL_SCALE, S_STAGE = 0, 1, 2, 3, 5, 7
 OK, FEW_LANDMARKS, FEW_BEARING_PAIRS, BAD_INDEX = range(4)
@@ -40,21 +36,14 @@ def settings_dict(st):
     return {n: getattr(st, n) for n, _ in Settings._fields_}
 
 
-_dir = None
 _lib = None
 
 
 def lib():
-    global _dir, _lib
+    global _lib
     if _lib is not None:
         return _lib
-    cc = shutil.which("gcc") or shutil.which("cc")
-    assert cc, "the CPU checker needs a host C compiler"
-    _dir = tempfile.TemporaryDirectory(prefix="akz_tvc_host_")
-    so = os.path.join(_dir.name, "libtvc_host.so")
-    subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-std=gnu11", "-shared", "-fPIC", "-Wall",
-                           os.path.join(ROOT, "tests", "cpp", "three_view_constraint_host.c"), "-o", so, "-lm"])
-    L = C.CDLL(so)
+    L = host_build.load("three_view_constraint_host.c")
     vp, u32, dbl = C.c_void_p, C.c_uint32, C.c_double
     sp = C.POINTER(Settings)
     L.tvc_pose_mul.argtypes = [vp, vp, vp]

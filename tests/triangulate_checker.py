@@ -1,15 +1,12 @@
 """The CPU checker of the triangulation kernels for the tests: tests/cpp/triangulate_host.c (thin wrappers around
-include/akz_triangulate_math.h) compiled with the host compiler, flags -O2 -ffp-contract=off, into a shared object in a
-temporary directory and loaded with ctypes; plus the synthetic maps both test files use."""
+include/akz_triangulate_math.h) as host_build.load compiles it — the host compiler, no contraction to FMA, as the kernels —
+loaded with ctypes; plus the synthetic maps both test files use."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("octave", "<u4"),
                      ("class_id", "<u4")])
 NONE = np.array([0.0, 0.0, 0.0, -1.0])
@@ -34,21 +31,14 @@ def camera(fx, fy, cx, cy, skew=0.0, k1=None):
     return Camera(fx, fy, cx, cy, skew, k1 or 0.0, int(k1 is not None), 0)
 
 
-_dir = None
 _lib = None
 
 
 def lib():
-    global _dir, _lib
+    global _lib
     if _lib is not None:
         return _lib
-    cc = shutil.which("gcc") or shutil.which("cc")
-    assert cc, "the CPU checker needs a host C compiler"
-    _dir = tempfile.TemporaryDirectory(prefix="akz_tri_host_")
-    so = os.path.join(_dir.name, "libtri_host.so")
-    subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-std=c11", "-shared", "-fPIC", "-Wall",
-                           os.path.join(ROOT, "tests", "cpp", "triangulate_host.c"), "-o", so, "-lm"])
-    L = C.CDLL(so)
+    L = host_build.load("triangulate_host.c")
     vp, u32 = C.c_void_p, C.c_uint32
     sp, cp = C.POINTER(Settings), C.POINTER(Camera)
     L.tri_observations.argtypes = [vp, vp, u32, C.c_int, sp, vp]

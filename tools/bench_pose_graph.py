@@ -36,7 +36,7 @@ def step(views, graphs, rounds):
     pg = PoseGraph(cons)
     dev = torch.device("cuda", 0)
     stream = torch.cuda.ExternalStream(cons.stream(), device=dev)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    up = lambda a: _lib.device_bytes(torch, a, dev)
     prm = PoseGraph.params(optimization_iterations=rounds)
     res = {"rounds": rounds, "rate": prm.graph_optimization_rate, "graphs_per_call": graphs, "edges_per_view": 18, "sizes": {}}
     ok = True

@@ -53,7 +53,7 @@ def device_call(torch, cons, sc, prm):
     from cv_amd.three_view import ThreeViewInit
     S = len(sc)
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    up = lambda a: _lib.device_bytes(torch, a, dev)
     d_kps = up(np.concatenate([s["kps"] for s in sc]))
     d_pf, d_ps = up(np.stack([s["pose_in"][0] for s in sc])), up(np.stack([s["pose_in"][1] for s in sc]))
     d_t, d_f, d_s = (up(np.stack([s[k] for s in sc])) for k in ("triples", "fo", "so"))
@@ -160,7 +160,7 @@ def step_constraints(out):
     cap, n_lm, patience = 64, 64, 4096
     pool = [T.scene(9100 + k, n_lm) for k in range(16)]
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    up = lambda a: _lib.device_bytes(torch, a, dev)
     cam = _lib.Camera(T.K.CAM["fx"], T.K.CAM["fy"], T.K.CAM["cx"], T.K.CAM["cy"], 0.0, 0.0, 0, 0)
     tvc = ThreeViewConstraints(cons)
 
