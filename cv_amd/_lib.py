@@ -153,6 +153,19 @@ RS_PG_VIEW_UPDATED, RS_PG_VIEW_NO_CONSTRAINT, RS_PG_VIEW_NONFINITE = range(3)
 RS_PG_RESIDENT_VIEWS, RS_PG_DEFAULT_RESIDENT_VIEWS, RS_PG_MAX_ITERATIONS, RS_PG_STATS = 256, 8, 1 << 20, 8
 RS_PG_S_VIEWS, RS_PG_S_UPDATED, RS_PG_S_EDGES, RS_PG_S_ROUNDS, RS_PG_S_STAGE, RS_PG_S_FIRST_BAD_VIEW = range(6)
 
+class ObservationFilterParams(C.Structure):
+    """rs_observation_filter_params (include/akz.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("minimum_robust_landmarks", C.c_uint32), ("maximum_cosine_distance", C.c_double),
+                ("maximum_sine_distance", C.c_double), ("reconstruction_optimization_iterations", C.c_uint32),
+                ("reserved", C.c_uint32), ("triangulate", TriangulateParams)]
+
+
+RS_OF_KEPT, RS_OF_SINGLE, RS_OF_PAIR_SPLIT, RS_OF_NO_POINT, RS_OF_KICKED, RS_OF_BAD_INDEX, RS_OF_SKIPPED = range(7)
+RS_OF_OK, RS_OF_FEW_LANDMARKS, RS_OF_BAD_RANGE, RS_OF_RECON_SKIPPED = range(4)
+RS_OF_NO_SOLVE, RS_OF_ROBUST_BEFORE, RS_OF_ROBUST_AFTER, RS_OF_STATS, RS_OF_MAX_ITERATIONS = 255, 1, 2, 8, 64
+RS_OF_S_LANDMARKS, RS_OF_S_ROBUST_BEFORE, RS_OF_S_ROBUST_AFTER, RS_OF_S_OBS_SPLIT, RS_OF_S_PAIR_SPLIT, RS_OF_S_NO_POINT, RS_OF_S_KICKED = range(7)
+RS_OR_OK, RS_OR_STAGE_RELAX, RS_OR_STAGE_FILTER, RS_OR_STOPPED = 0, 1, 2, 1 << 30
+
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
 
@@ -194,6 +207,7 @@ ABI_SYMBOLS = [
     "rs_triangulate_pairs_batch_device", "rs_three_view_params_default", "rs_three_view_init_batch_device",
     "rs_three_view_constraint_params_default", "rs_three_view_constraint_batch_device",
     "rs_pose_graph_params_default", "rs_pose_graph_edges_device", "rs_pose_graph_relax_batch_device", "rs_pose_graph_debug_resident_views",
+    "rs_observation_filter_params_default", "rs_filter_observations_device", "rs_optimize_reconstruction_batch_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -331,6 +345,11 @@ def lib():
     L.rs_pose_graph_relax_batch_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, u32, C.POINTER(PoseGraphParams),
                                                    vp, vp, vp, vp]
     L.rs_pose_graph_debug_resident_views.argtypes = [vp, u32]
+    ofp = C.POINTER(ObservationFilterParams)
+    L.rs_observation_filter_params_default.argtypes = [ofp]
+    L.rs_filter_observations_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(Camera), vp, vp, u32, u32, vp, vp, u32, vp, ofp] + [vp] * 11
+    L.rs_optimize_reconstruction_batch_device.argtypes = ([vp, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, u32, C.POINTER(PoseGraphParams),
+                                                           vp, u32, C.POINTER(Camera), vp, vp, u32, u32, vp, ofp] + [vp] * 17)
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

@@ -158,6 +158,23 @@ struct RsPoseGraphState {
     uint32_t resident_views = RS_PG_DEFAULT_RESIDENT_VIEWS;
 };
 RsPoseGraphState* rs_internal_pose_graph(rs_ctx* c);
+// rs_pose_graph_relax_batch_device with d_skip ([n_graphs] u32 or null): a graph whose word is not zero is not run and none
+// of its outputs (poses, verdict, view states, stats) is written (rs_pose_graph.hip; rs_observation_filter.hip's chain)
+int32_t rs_internal_pose_graph_relax(rs_ctx* c, void* d_poses, uint32_t n_views, const void* d_graph_start, uint32_t n_graphs,
+                                     const void* d_row_start, const void* d_row_edges, uint32_t n_rows, const void* d_views,
+                                     const void* d_constraint_verdict, const void* d_edges, uint32_t n_constraints,
+                                     const rs_pose_graph_params* prm, void* d_graph_verdict, void* d_view_state, void* d_stats,
+                                     const void* d_skip, void* stream_to_wait);
+// What rs_observation_filter.hip keeps in an rs_ctx, grown on demand and freed by rs_destroy: the scratch of one filter pass
+// (a word per landmark, per reconstruction, per observation and per scan tile) and that of the chain (a word per
+// reconstruction and the landmark tables between its rounds).
+struct RsObsFilterState {
+    void* d_scratch = nullptr;
+    size_t bytes = 0;
+    void* d_chain = nullptr;
+    size_t chain_bytes = 0;
+};
+RsObsFilterState* rs_internal_obs_filter(rs_ctx* c);
 
 static inline int akz_div_up(int a, int b) { return (a + b - 1) / b; }
 static inline size_t akz_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }

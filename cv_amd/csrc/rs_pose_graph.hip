@@ -78,6 +78,7 @@ struct PgCall {
     uint32_t* view_graph;        // [n_views] scratch: the swept graph a view belongs to, kPgNone for every other view
     uint32_t* form;              // [n_graphs] scratch
     uint32_t* stop;              // [n_graphs] scratch: the round a swept graph stopped in, kPgNone while it runs
+    const uint32_t* skip;        // [n_graphs] or null: nonzero = the graph is not run and none of its outputs is written
     uint32_t n_views, n_graphs, n_rows, n_constraints, iterations, resident_views;
     double rate;
 };
@@ -106,6 +107,10 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_prepare(PgCall a)
 {
     __shared__ uint32_t s_bad, s_updated, s_edges, s_before;
     const uint32_t g = blockIdx.x, lane = threadIdx.x & (kPgWave - 1), w = threadIdx.x / kPgWave;
+    if (a.skip && a.skip[g] != 0u) {                  // (rs_internal_pose_graph_relax) the whole workgroup leaves together
+        if (threadIdx.x == 0) { a.form[g] = kPgDone; a.stop[g] = kPgNone; }
+        return;
+    }
     if (threadIdx.x == 0) { s_bad = 0u; s_updated = 0u; s_edges = 0u; s_before = 0u; }
     __syncthreads();
     const uint32_t gs = a.graph_start[g], ge = a.graph_start[g + 1];
@@ -310,11 +315,12 @@ extern "C" int32_t rs_pose_graph_edges_device(rs_ctx* c, const void* d_views, co
     });
 }
 
-extern "C" int32_t rs_pose_graph_relax_batch_device(rs_ctx* c, void* d_poses, uint32_t n_views, const void* d_graph_start, uint32_t n_graphs,
-                                                    const void* d_row_start, const void* d_row_edges, uint32_t n_rows, const void* d_views,
-                                                    const void* d_constraint_verdict, const void* d_edges, uint32_t n_constraints,
-                                                    const rs_pose_graph_params* prm, void* d_graph_verdict, void* d_view_state, void* d_stats,
-                                                    void* stream_to_wait)
+// (akz_common.h) rs_pose_graph_relax_batch_device with a list of graphs to leave alone
+int32_t rs_internal_pose_graph_relax(rs_ctx* c, void* d_poses, uint32_t n_views, const void* d_graph_start, uint32_t n_graphs,
+                                     const void* d_row_start, const void* d_row_edges, uint32_t n_rows, const void* d_views,
+                                     const void* d_constraint_verdict, const void* d_edges, uint32_t n_constraints,
+                                     const rs_pose_graph_params* prm, void* d_graph_verdict, void* d_view_state, void* d_stats,
+                                     const void* d_skip, void* stream_to_wait)
 {
     return akz_guard([&]() -> int32_t {
         if (!prm || prm->struct_size != sizeof(rs_pose_graph_params)) return AKZ_E_INVALID;
@@ -355,6 +361,7 @@ extern "C" int32_t rs_pose_graph_relax_batch_device(rs_ctx* c, void* d_poses, ui
         a.graph_verdict = (uint32_t*)d_graph_verdict;
         a.view_state = (uint32_t*)d_view_state;
         a.stats = (uint32_t*)d_stats;
+        a.skip = (const uint32_t*)d_skip;
         a.n_views = n_views; a.n_graphs = n_graphs; a.n_rows = n_rows; a.n_constraints = n_constraints;
         // the bound that makes the running time finite: more iterations than RS_PG_MAX_ITERATIONS count as that
         a.iterations = prm->optimization_iterations < (uint32_t)RS_PG_MAX_ITERATIONS ? prm->optimization_iterations : (uint32_t)RS_PG_MAX_ITERATIONS;
@@ -383,4 +390,15 @@ extern "C" int32_t rs_pose_graph_relax_batch_device(rs_ctx* c, void* d_poses, ui
         }
         return AKZ_OK;
     });
+}
+
+extern "C" int32_t rs_pose_graph_relax_batch_device(rs_ctx* c, void* d_poses, uint32_t n_views, const void* d_graph_start, uint32_t n_graphs,
+                                                    const void* d_row_start, const void* d_row_edges, uint32_t n_rows, const void* d_views,
+                                                    const void* d_constraint_verdict, const void* d_edges, uint32_t n_constraints,
+                                                    const rs_pose_graph_params* prm, void* d_graph_verdict, void* d_view_state, void* d_stats,
+                                                    void* stream_to_wait)
+{
+    return rs_internal_pose_graph_relax(c, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views,
+                                        d_constraint_verdict, d_edges, n_constraints, prm, d_graph_verdict, d_view_state, d_stats, nullptr,
+                                        stream_to_wait);
 }

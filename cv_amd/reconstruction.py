@@ -1,0 +1,216 @@
+"""Host-side mirror of cv-sfm's optimize_reconstruction over rs_filter_observations_device and
+rs_optimize_reconstruction_batch_device of include/akz.h.
+
+  VSlam::optimize_reconstruction            cv-sfm/src/lib.rs:2343-2355
+  VSlam::filter_non_robust_observations     cv-sfm/src/lib.rs:2657-2757
+  split_landmark / split_observation        cv-sfm/src/lib.rs:2559-2568, 552-588
+
+One lane per landmark decides and an exclusive scan over the observations compacts the table on the device
+(cv_amd/csrc/rs_observation_filter.hip); there is no CPU fallback.  ObservationFilter is one pass; ReconstructionOptimizer
+chains reconstruction_optimization_iterations rounds of PoseGraph's relaxation and the filter and closes with the world table
+of the filtered lists.  The run_tensors methods enqueue and return device tensors — a chain that must not stop at the host
+goes on from them (the filtered table as a triangulation.LandmarkTable) —, the run methods wait and copy to the host.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .pose_graph import PoseGraph
+from .triangulation import LandmarkTable
+
+LANDMARK_STATES = ("kept", "single", "pair_split", "no_point", "kicked", "bad_index", "skipped")
+VERDICTS = ("ok", "few_landmarks", "bad_range", "skipped")
+
+
+def stopped_at(verdict):
+    """A word of ReconstructionOptimizer's verdicts -> None for a reconstruction that went through, else (round, "relax" or
+    "filter", the stage's own verdict: RS_PG_* or RS_OF_*)."""
+    v = int(verdict)
+    if v == _lib.RS_OR_OK:
+        return None
+    return (v >> 16) & 0x3FFF, "relax" if (v >> 8) & 0xFF == _lib.RS_OR_STAGE_RELAX else "filter", v & 0xFF
+
+
+@dataclass
+class ObservationFilterTensors:
+    """What one pass wrote, on the device (rs_filter_observations_device's outputs by their names without d_)."""
+    keep: object            # [n_obs] uint8
+    lm_state: object        # [n_landmarks] uint8 (RS_OF_*)
+    tri_reason: object      # [n_landmarks] uint8
+    robust: object          # [n_landmarks] uint8, bits RS_OF_ROBUST_BEFORE / _AFTER
+    obs_start_out: object   # [n_landmarks + 1] int32
+    obs_out: object         # [n_obs][2] int32, rows [0, counts[0]) written
+    split_out: object       # [n_obs][2] int32, rows [0, counts[1]) written
+    counts: object          # [2] int32 {kept, split off}
+    recon_verdict: object   # [n_recons] int32 (RS_OF_OK ...)
+    stats: object           # [n_recons][RS_OF_STATS] int32
+    n_landmarks: int
+    n_obs: int
+
+    def table(self, torch):
+        """the filtered lists as a LandmarkTable over these tensors"""
+        return LandmarkTable.from_device(torch, self.obs_start_out, self.obs_out, self.n_landmarks, self.n_obs)
+
+
+@dataclass
+class ObservationFilterResult:
+    keep: np.ndarray
+    lm_state: np.ndarray
+    tri_reason: np.ndarray
+    robust: np.ndarray
+    obs_start: np.ndarray     # [n_landmarks + 1] the filtered table
+    obs: np.ndarray           # [kept][2]
+    split: np.ndarray         # [split off][2]: row k is the new single-observation landmark n_landmarks + k
+    verdicts: np.ndarray      # [n_recons] u32
+    stats: np.ndarray         # [n_recons][RS_OF_STATS] u32
+    tensors: object           # the ObservationFilterTensors it was read from
+
+
+def _tensor(torch, a, dtype, dev):
+    return PoseGraph._tensor(torch, a, dtype, dev)
+
+
+class ObservationFilter:
+    """The filter on the context (and stream) of an EssentialConsensus, so that it queues behind that object's other calls."""
+
+    def __init__(self, consensus):
+        self._cons = consensus
+
+    @staticmethod
+    def params(**kw):
+        """rs_observation_filter_params: the reference's defaults (cv-sfm/src/settings.rs:324-350, 429-431) with `kw` on top;
+        `triangulate` takes a whole rs_triangulate_params (triangulation.make_params)."""
+        return _lib.params(_lib.ObservationFilterParams, "rs_observation_filter_params_default", **kw)
+
+    def filter_device(self, d_kps, cap, n_blocks, d_poses, cam, d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start, d_view_start, n_recons,
+                      d_skip, params, d_keep, d_lm_state, d_tri_reason, d_robust, d_obs_start_out, d_obs_out, d_split_out, d_counts,
+                      d_recon_verdict, d_stats, stream_to_wait=None):
+        """rs_filter_observations_device: arguments named d_* are device pointers (ints).  Enqueues and returns."""
+        check(_lib.lib().rs_filter_observations_device(
+            self._cons._h, d_kps, cap, n_blocks, d_poses, C.byref(cam), d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start, d_view_start,
+            n_recons, d_skip, C.byref(params), d_keep, d_lm_state, d_tri_reason, d_robust, d_obs_start_out, d_obs_out, d_split_out, d_counts,
+            d_recon_verdict, d_stats, stream_to_wait), "rs_filter_observations_device")
+
+    @staticmethod
+    def _outputs(torch, dev, n_obs, n_landmarks, n_recons, rounds=1):
+        z8 = lambda n: torch.zeros((max(n, 1),), dtype=torch.uint8, device=dev)
+        z32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        return ObservationFilterTensors(z8(n_obs), z8(n_landmarks), z8(n_landmarks), z8(n_landmarks), z32(n_landmarks + 1), z32(max(n_obs, 1), 2),
+                                        z32(rounds * max(n_obs, 1), 2), z32(rounds * 2), z32(rounds * max(n_recons, 1)),
+                                        z32(rounds * max(n_recons, 1), _lib.RS_OF_STATS), n_landmarks, n_obs)
+
+    def run_tensors(self, torch, table, d_kps, cap, n_blocks, d_poses, cam, recon_start, view_start, skip=None, params=None):
+        """One pass over `table` (a LandmarkTable) under d_poses ([n_blocks][12] float64 device tensor): recon_start, view_start
+        [n_recons + 1] and skip [n_recons] as numpy arrays or 4-byte device tensors.  Enqueued behind the current torch stream;
+        no wait -> ObservationFilterTensors."""
+        dev = table.dev
+        n_recons = int(np.prod(recon_start.shape)) - 1
+        if n_recons < 0 or int(np.prod(view_start.shape)) != n_recons + 1:
+            raise ValueError("recon_start and view_start are [n_recons + 1]")
+        d_rs, d_vs = _tensor(torch, recon_start, np.uint32, dev), _tensor(torch, view_start, np.uint32, dev)
+        d_skip = None if skip is None else _tensor(torch, skip, np.uint32, dev)
+        o = self._outputs(torch, dev, table.n_obs, table.n_landmarks, n_recons)
+        self.filter_device(d_kps.data_ptr(), cap, n_blocks, d_poses.data_ptr(), cam, table.d_start.data_ptr(), table.d_obs.data_ptr(),
+                           table.n_obs, table.n_landmarks, d_rs.data_ptr(), d_vs.data_ptr(), n_recons,
+                           None if d_skip is None else d_skip.data_ptr(), params or self.params(), o.keep.data_ptr(), o.lm_state.data_ptr(),
+                           o.tri_reason.data_ptr(), o.robust.data_ptr(), o.obs_start_out.data_ptr(), o.obs_out.data_ptr(),
+                           o.split_out.data_ptr(), o.counts.data_ptr(), o.recon_verdict.data_ptr(), o.stats.data_ptr(),
+                           _lib.wait_handle(torch.cuda.current_stream(dev)))
+        o._inputs = (d_rs, d_vs, d_skip)          # alive until the stream has run
+        return o
+
+    def run(self, torch, table, d_kps, cap, n_blocks, d_poses, cam, recon_start, view_start, skip=None, params=None):
+        """run_tensors, then WAITS and copies to the host -> ObservationFilterResult."""
+        o = self.run_tensors(torch, table, d_kps, cap, n_blocks, d_poses, cam, recon_start, view_start, skip, params)
+        self._cons.sync()
+        return _to_host(o, int(np.prod(recon_start.shape)) - 1)
+
+
+def _to_host(o, n_recons, rnd=0):
+    u32 = lambda t: t.cpu().numpy().view(np.uint32)
+    counts = u32(o.counts).reshape(-1, 2)[rnd]
+    room = max(o.n_obs, 1)
+    return ObservationFilterResult(
+        o.keep.cpu().numpy()[:o.n_obs], o.lm_state.cpu().numpy()[:o.n_landmarks], o.tri_reason.cpu().numpy()[:o.n_landmarks],
+        o.robust.cpu().numpy()[:o.n_landmarks], u32(o.obs_start_out), u32(o.obs_out)[:counts[0]],
+        u32(o.split_out)[rnd * room:rnd * room + counts[1]], u32(o.recon_verdict)[rnd * max(n_recons, 1):][:n_recons],
+        u32(o.stats).reshape(-1, max(n_recons, 1), _lib.RS_OF_STATS)[rnd][:n_recons], o)
+
+
+@dataclass
+class ReconstructionResult:
+    verdicts: np.ndarray      # [n_graphs] u32: RS_OR_OK or where a reconstruction stopped (stopped_at)
+    pose_graph: object        # pose_graph.PoseGraphResult of the last round each reconstruction was relaxed in
+    filter: object            # ObservationFilterResult of the last round (verdicts and stats: that round's)
+    world: object             # device tensor [n_landmarks][4] float64 of the final table, or None
+    world_reason: object      # device tensor [n_landmarks] uint8, or None
+    tensors: object           # ObservationFilterTensors holding every round's verdicts, stats, counts and split lists
+
+
+class ReconstructionOptimizer:
+    """optimize_reconstruction for many reconstructions at once, chained on top of a PoseGraph (and on its context)."""
+
+    def __init__(self, pose_graph):
+        self._pg = pose_graph
+        self._cons = pose_graph._cons
+
+    params = staticmethod(ObservationFilter.params)
+
+    def optimize_device(self, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views, d_constraint_verdict,
+                        d_edges, n_constraints, pg_params, d_kps, cap, cam, d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start, params,
+                        d_verdict, d_graph_verdict, d_view_state, d_pg_stats, d_keep, d_lm_state, d_tri_reason, d_robust, d_obs_start_out,
+                        d_obs_out, d_split_out, d_counts, d_recon_verdict, d_of_stats, d_world=None, d_world_reason=None, stream_to_wait=None):
+        """rs_optimize_reconstruction_batch_device: arguments named d_* are device pointers (ints).  Enqueues and returns."""
+        check(_lib.lib().rs_optimize_reconstruction_batch_device(
+            self._cons._h, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views, d_constraint_verdict, d_edges,
+            n_constraints, C.byref(pg_params), d_kps, cap, C.byref(cam), d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start,
+            C.byref(params), d_verdict, d_graph_verdict, d_view_state, d_pg_stats, d_keep, d_lm_state, d_tri_reason, d_robust,
+            d_obs_start_out, d_obs_out, d_split_out, d_counts, d_recon_verdict, d_of_stats, d_world, d_world_reason, stream_to_wait),
+            "rs_optimize_reconstruction_batch_device")
+
+    def run_tensors(self, torch, poses, graph_start, row_start, row_edges, edges, table, d_kps, cap, cam, recon_start, pg_params=None,
+                    params=None, world=True):
+        """poses [n_views][12] float64 device tensor (relaxed in place), graph_start / row_start / row_edges as PoseGraph.relax
+        takes them, `edges` what PoseGraph.edges returned, `table` the LandmarkTable over the same views' keypoint blocks d_kps.
+        Enqueued behind the current torch stream; no wait -> (d_verdict, pose-graph outputs (d_graph_verdict, d_view_state,
+        d_pg_stats), ObservationFilterTensors, d_world, d_world_reason)."""
+        d_edges, (d_views, d_verdicts, n_constraints) = edges
+        dev = d_edges.device
+        params, pg_params = params or self.params(), pg_params or PoseGraph.params()
+        rounds = max(int(params.reconstruction_optimization_iterations), 1)
+        n_views = int(np.prod(poses.shape)) // 12
+        n_graphs, n_rows = int(np.prod(graph_start.shape)) - 1, int(np.prod(row_edges.shape))
+        d_gs, d_rs, d_re, d_recon = (_tensor(torch, a, np.uint32, dev) for a in (graph_start, row_start, row_edges, recon_start))
+        i32 = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device=dev)
+        d_verdict, d_gv, d_state, d_pg_stats = i32(max(n_graphs, 1)), i32(max(n_graphs, 1)), i32(max(n_views, 1)), i32(max(n_graphs, 1), _lib.RS_PG_STATS)
+        o = ObservationFilter._outputs(torch, dev, table.n_obs, table.n_landmarks, n_graphs, rounds)
+        d_world = table.new_world() if world else None
+        d_reason = torch.zeros((max(table.n_landmarks, 1),), dtype=torch.uint8, device=dev) if world else None
+        self.optimize_device(poses.data_ptr(), n_views, d_gs.data_ptr(), n_graphs, d_rs.data_ptr(), d_re.data_ptr(), n_rows, d_views.data_ptr(),
+                             d_verdicts.data_ptr(), d_edges.data_ptr(), n_constraints, pg_params, d_kps.data_ptr(), cap, cam,
+                             table.d_start.data_ptr(), table.d_obs.data_ptr(), table.n_obs, table.n_landmarks, d_recon.data_ptr(), params,
+                             d_verdict.data_ptr(), d_gv.data_ptr(), d_state.data_ptr(), d_pg_stats.data_ptr(), o.keep.data_ptr(),
+                             o.lm_state.data_ptr(), o.tri_reason.data_ptr(), o.robust.data_ptr(), o.obs_start_out.data_ptr(),
+                             o.obs_out.data_ptr(), o.split_out.data_ptr(), o.counts.data_ptr(), o.recon_verdict.data_ptr(), o.stats.data_ptr(),
+                             None if d_world is None else d_world.data_ptr(), None if d_reason is None else d_reason.data_ptr(),
+                             _lib.wait_handle(torch.cuda.current_stream(dev)))
+        o._inputs = (d_gs, d_rs, d_re, d_recon)
+        return d_verdict, (d_gv, d_state, d_pg_stats), o, d_world, d_reason
+
+    def run(self, torch, poses, graph_start, row_start, row_edges, edges, table, d_kps, cap, cam, recon_start, pg_params=None, params=None,
+            world=True):
+        """run_tensors, then WAITS and copies verdicts, states and stats to the host -> ReconstructionResult (the world table
+        stays on the device, where the registration chain reads it)."""
+        from .pose_graph import PoseGraphResult
+        params = params or self.params()
+        d_verdict, (d_gv, d_state, d_pg_stats), o, d_world, d_reason = self.run_tensors(
+            torch, poses, graph_start, row_start, row_edges, edges, table, d_kps, cap, cam, recon_start, pg_params, params, world)
+        self._cons.sync()
+        n_graphs, n_views = int(np.prod(graph_start.shape)) - 1, int(np.prod(poses.shape)) // 12
+        u32 = lambda t: t.cpu().numpy().view(np.uint32)
+        last = max(int(params.reconstruction_optimization_iterations), 1) - 1
+        return ReconstructionResult(u32(d_verdict)[:n_graphs], PoseGraphResult(u32(d_gv)[:n_graphs], u32(d_state)[:n_views], u32(d_pg_stats)[:n_graphs], poses),
+                                    _to_host(o, n_graphs, last), d_world, d_reason, o)

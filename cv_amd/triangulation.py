@@ -112,6 +112,21 @@ class LandmarkTable:
         self.d_obs_counts = torch.from_numpy(np.diff(start).astype(np.uint32).view(np.int32)).to(dev)
         self.dev = dev
 
+    @classmethod
+    def from_device(cls, torch, d_start, d_obs, n_landmarks, n_obs):
+        """A table over arrays that are on the device already (reconstruction.ObservationFilter's filtered table): d_start
+        [n_landmarks + 1] and d_obs [n_obs][2], 4-byte integer tensors that are kept, not copied.  n_obs is the room of d_obs; how
+        many rows the table fills is d_start[n_landmarks], known on the device.  Nothing is brought to the host, so nothing is
+        validated here: the kernels refuse a list that leaves [0, n_obs]."""
+        if not (d_start.is_cuda and d_obs.is_cuda and d_start.is_contiguous() and d_obs.is_contiguous() and d_start.element_size() == 4 and
+                d_obs.element_size() == 4 and d_start.numel() >= n_landmarks + 1 and d_obs.numel() >= 2 * n_obs):
+            raise ValueError("contiguous 4-byte device tensors of [n_landmarks + 1] and [n_obs][2]")
+        t = cls.__new__(cls)
+        t.torch, t.n_landmarks, t.n_obs, t.dev = torch, int(n_landmarks), int(n_obs), d_start.device
+        t.d_start, t.d_obs = d_start, d_obs
+        t.d_obs_counts = (d_start.view(torch.int32)[1:n_landmarks + 1] - d_start.view(torch.int32)[:n_landmarks]).contiguous()
+        return t
+
     def new_world(self, extra_rows=0):
         """A world table of n_landmarks + extra_rows rows, every row "None"."""
         w = self.torch.zeros((self.n_landmarks + extra_rows, 4), dtype=self.torch.float64, device=self.dev)

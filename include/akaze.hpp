@@ -786,6 +786,64 @@ private:
     rs_pose_graph_params p_;
     rs_ctx* ctx_ = nullptr;
 };
+
+// cv-sfm's filter of a reconstruction's observations behind a relaxation (VSlam::filter_non_robust_observations,
+// cv-sfm/src/lib.rs:2657-2757) over rs_filter_observations_device: one lane per landmark decides, an exclusive scan over the
+// observations compacts the table.  Every argument named d_* is device memory the caller owns (the layouts are
+// include/akz.h's); the calls enqueue on stream() and return.
+class ObservationFilter {
+public:
+    explicit ObservationFilter(int device = 0)
+    {
+        akaze::require_abi();
+        rs_observation_filter_params_default(&p_);
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+    }
+    ~ObservationFilter() { if (ctx_) rs_destroy(ctx_); }
+    ObservationFilter(const ObservationFilter&) = delete;
+    ObservationFilter& operator=(const ObservationFilter&) = delete;
+    rs_observation_filter_params& params() { return p_; }   // the reference's defaults (cv-sfm/src/settings.rs:324-350, 429-431)
+    const rs_observation_filter_params& params() const { return p_; }
+    void filter_device(const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks, const void* d_poses, const rs_camera& cam,
+                       const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks, const void* d_recon_start,
+                       const void* d_view_start, uint32_t n_recons, const void* d_skip, void* d_keep, void* d_lm_state, void* d_tri_reason,
+                       void* d_robust, void* d_obs_start_out, void* d_obs_out, void* d_split_out, void* d_counts, void* d_recon_verdict,
+                       void* d_stats, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_filter_observations_device(ctx_, d_kps, cap_per_img, n_blocks, d_poses, &cam, d_obs_start, d_obs, n_obs, n_landmarks,
+                                                   d_recon_start, d_view_start, n_recons, d_skip, &p_, d_keep, d_lm_state, d_tri_reason, d_robust,
+                                                   d_obs_start_out, d_obs_out, d_split_out, d_counts, d_recon_verdict, d_stats, stream_to_wait),
+                     "rs_filter_observations_device");
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+    rs_ctx* context() { return ctx_; }
+
+private:
+    rs_observation_filter_params p_;
+    rs_ctx* ctx_ = nullptr;
+};
+
+// VSlam::optimize_reconstruction (cv-sfm/src/lib.rs:2343-2355) over rs_optimize_reconstruction_batch_device, on the filter's
+// context: filter.params().reconstruction_optimization_iterations rounds of the relaxation (under `pg`) and the filter, then
+// the world table of the final lists into d_world (may be null).  Where a reconstruction stopped is d_verdict's word (RS_OR_*).
+inline void optimize_reconstruction(ObservationFilter& filter, const rs_pose_graph_params& pg, void* d_poses, uint32_t n_views,
+                                    const void* d_graph_start, uint32_t n_graphs, const void* d_row_start, const void* d_row_edges, uint32_t n_rows,
+                                    const void* d_views, const void* d_constraint_verdict, const void* d_edges, uint32_t n_constraints,
+                                    const void* d_kps, uint32_t cap_per_img, const rs_camera& cam, const void* d_obs_start, const void* d_obs,
+                                    uint32_t n_obs, uint32_t n_landmarks, const void* d_recon_start, void* d_verdict, void* d_graph_verdict,
+                                    void* d_view_state, void* d_pg_stats, void* d_keep, void* d_lm_state, void* d_tri_reason, void* d_robust,
+                                    void* d_obs_start_out, void* d_obs_out, void* d_split_out, void* d_counts, void* d_recon_verdict,
+                                    void* d_of_stats, void* d_world = nullptr, void* d_world_reason = nullptr, void* stream_to_wait = nullptr)
+{
+    akaze::check(rs_optimize_reconstruction_batch_device(filter.context(), d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows,
+                                                         d_views, d_constraint_verdict, d_edges, n_constraints, &pg, d_kps, cap_per_img, &cam,
+                                                         d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start, &filter.params(), d_verdict,
+                                                         d_graph_verdict, d_view_state, d_pg_stats, d_keep, d_lm_state, d_tri_reason, d_robust,
+                                                         d_obs_start_out, d_obs_out, d_split_out, d_counts, d_recon_verdict, d_of_stats, d_world,
+                                                         d_world_reason, stream_to_wait),
+                 "rs_optimize_reconstruction_batch_device");
+}
 }  // namespace cv_sfm
 
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over

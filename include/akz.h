@@ -886,6 +886,126 @@ int32_t rs_pose_graph_relax_batch_device(rs_ctx* ctx, void* d_poses, uint32_t n_
  * called) take the swept form in the calls that follow on this context — 0 sends every graph through it; with a limit of
  * at most 8 a call of more views than the limit is swept as a whole */
 int32_t rs_pose_graph_debug_resident_views(rs_ctx* ctx, uint32_t views);
+/* ---- the observation filter behind a relaxation, and optimize_reconstruction as a whole, on the device ----
+ * What cv-sfm's VSlam::filter_non_robust_observations does (cv-sfm/src/lib.rs:2657-2757) for n_recons reconstructions side by
+ * side: every landmark is triangulated again under the poses as they are now, the observations that no longer agree with
+ * their landmark are split off, landmarks that no longer triangulate are split whole, and a reconstruction that keeps fewer
+ * than minimum_robust_landmarks robust landmarks is rejected.  One lane per landmark decides (the design matrix and the
+ * eigenvectors in registers, one keep flag per observation in memory); an exclusive scan of the keep flags over the
+ * observations of the call — tile sums, a scan of the tile sums by one workgroup, a scatter; no workgroup waits for another —
+ * builds the filtered table and the list of the split-off observations.  The arithmetic is
+ * include/akz_observation_filter_math.h (compiled for the device and, by the tests, for the host: equal bit for bit); its
+ * head lists what is unpinned against the reference — above all the order of a landmark's observations, which decides which
+ * observation a split leaves behind. */
+enum {                                /* d_lm_state: what became of a landmark */
+    RS_OF_KEPT = 0,                   /* two or more observations, all stayed */
+    RS_OF_SINGLE = 1,                 /* one observation or none: nothing happens (lib.rs:2686-2687) */
+    RS_OF_PAIR_SPLIT = 2,             /* two observations that failed is_bi_landmark_robust: the second was split off */
+    RS_OF_NO_POINT = 3,               /* three or more and no point (d_tri_reason says why): all but the first were split off */
+    RS_OF_KICKED = 4,                 /* three or more, a point, at least one observation split off */
+    RS_OF_BAD_INDEX = 5,              /* an observation names a block >= n_blocks or a feature >= cap_per_img: the landmark is left
+                                       * as it is and is not robust, nothing is read out of bounds */
+    RS_OF_SKIPPED = 6                 /* the landmark belongs to no reconstruction that ran (d_skip, a refused range, or no range
+                                       * at all): left as it is, nothing computed */
+};
+enum {                                /* d_recon_verdict */
+    RS_OF_OK = 0,
+    RS_OF_FEW_LANDMARKS = 1,          /* fewer than minimum_robust_landmarks robust after the filter (lib.rs:2747-2753): the reference
+                                       * removes the reconstruction; here its filtered table is still written */
+    RS_OF_BAD_RANGE = 2,              /* d_recon_start, d_view_start or the part of d_obs_start the reconstruction owns is not
+                                       * ascending inside its bounds ([0, n_landmarks], [0, n_blocks], [0, n_obs]), or a start in
+                                       * front of the range lies above its first (as RS_PG_BAD_INDEX reaches back): this
+                                       * reconstruction alone is refused and passes through, so the ones that run never share an
+                                       * observation */
+    RS_OF_RECON_SKIPPED = 3           /* d_skip[r] != 0: passed through */
+};
+enum {
+    RS_OF_NO_SOLVE = 255,             /* d_tri_reason of a landmark whose filter ran no triangulation */
+    RS_OF_ROBUST_BEFORE = 1,          /* d_robust bit 0: is_landmark_robust before the filter */
+    RS_OF_ROBUST_AFTER = 2,           /* d_robust bit 1: after it */
+    /* d_stats words (u32) of a reconstruction; all 0 for RS_OF_BAD_RANGE, all but the first 0 for RS_OF_RECON_SKIPPED: */
+    RS_OF_S_LANDMARKS = 0,            /* rows of the table it owns */
+    RS_OF_S_ROBUST_BEFORE = 1,        /* initial_num_landmarks (lib.rs:2670-2676) */
+    RS_OF_S_ROBUST_AFTER = 2,         /* final_num_landmarks (lib.rs:2738-2744) */
+    RS_OF_S_OBS_SPLIT = 3,            /* observations split off */
+    RS_OF_S_PAIR_SPLIT = 4,           /* landmarks RS_OF_PAIR_SPLIT */
+    RS_OF_S_NO_POINT = 5,             /* landmarks RS_OF_NO_POINT */
+    RS_OF_S_KICKED = 6,               /* landmarks RS_OF_KICKED */
+    RS_OF_STATS = 8,                  /* word 7 is 0 */
+    RS_OF_MAX_ITERATIONS = 64,        /* a larger reconstruction_optimization_iterations: AKZ_E_TOO_LARGE */
+    /* d_verdict of rs_optimize_reconstruction_batch_device: 0, or RS_OR_STOPPED | round << 16 | stage << 8 | the verdict the
+     * stage gave (RS_PG_* or RS_OF_*) */
+    RS_OR_OK = 0,
+    RS_OR_STAGE_RELAX = 1,
+    RS_OR_STAGE_FILTER = 2,
+    RS_OR_STOPPED = 1 << 30
+};
+typedef struct rs_observation_filter_params {
+    uint32_t struct_size;                                /* sizeof(rs_observation_filter_params) */
+    uint32_t minimum_robust_landmarks;                   /* 32 */
+    double maximum_cosine_distance;                      /* 1e-5; NaN: AKZ_E_INVALID */
+    double maximum_sine_distance;                        /* 1e-1; NaN: AKZ_E_INVALID */
+    uint32_t reconstruction_optimization_iterations;     /* 1: the rounds of rs_optimize_reconstruction_batch_device */
+    uint32_t reserved;                                   /* 0 */
+    rs_triangulate_params triangulate;                   /* the eigen-solver's settings, robust_minimum_observations and the incidence
+                                                          * distance; its n_views is used by the closing triangulation of
+                                                          * rs_optimize_reconstruction_batch_device only: the filter takes every
+                                                          * reconstruction's own from d_view_start */
+} rs_observation_filter_params;
+/* the reference's defaults (cv-sfm/src/settings.rs:324-350, 429-431) */
+int32_t rs_observation_filter_params_default(rs_observation_filter_params* params);
+/* One pass of the filter.  The landmark table as rs_triangulate_landmarks_device takes it (d_kps, cap_per_img, n_blocks,
+ * d_poses, cam, d_obs_start [n_landmarks + 1], d_obs [n_obs][2]; a block is a view); only the first min(d_obs_start[n_landmarks],
+ * n_obs) observations are the table's, so n_obs may be the capacity of an array whose fill is known on the device only.
+ * Reconstruction r owns landmarks d_recon_start[r] .. d_recon_start[r + 1] (u32 [n_recons + 1]) and has d_view_start[r + 1] -
+ * d_view_start[r] views (u32 [n_recons + 1], the d_graph_start of rs_pose_graph_relax_batch_device).  d_skip (optional)
+ * [n_recons] u32: nonzero = pass the reconstruction through.
+ * Outputs, all written by every call: d_keep [n_obs] u8 (1 = the observation stays; everything outside a running
+ * reconstruction is 1), d_lm_state [n_landmarks] u8 (RS_OF_*), d_tri_reason [n_landmarks] u8 (RS_TRI_* of
+ * triangulate_landmark where it ran, 6 for a bad index, RS_OF_NO_SOLVE otherwise), d_robust [n_landmarks] u8 (bits
+ * RS_OF_ROBUST_*), d_recon_verdict [n_recons] u32, d_stats [n_recons][RS_OF_STATS] u32, d_counts [2] u32 {observations kept,
+ * observations split off}, and the two compacted lists: the filtered table d_obs_start_out [n_landmarks + 1] / d_obs_out
+ * (room for [n_obs][2]; rows [0, kept) are written: the kept observations of every landmark in their order) and d_split_out
+ * (room for [n_obs][2]; rows [0, split) are written: the split-off observations in (landmark, position) order — the k-th of
+ * them is by definition the new single-observation landmark n_landmarks + k).  The input table is const: an output that
+ * overlaps d_obs_start or d_obs is refused with AKZ_E_INVALID before anything is enqueued.  The parameters are checked before
+ * anything else.  Enqueues on rs_stream() after stream_to_wait (may be NULL) and returns; allocates nothing beyond growing the
+ * context's scratch. */
+int32_t rs_filter_observations_device(rs_ctx* ctx, const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks, const void* d_poses,
+                                      const rs_camera* cam, const void* d_obs_start, const void* d_obs, uint32_t n_obs,
+                                      uint32_t n_landmarks, const void* d_recon_start, const void* d_view_start, uint32_t n_recons,
+                                      const void* d_skip, const rs_observation_filter_params* params, void* d_keep, void* d_lm_state,
+                                      void* d_tri_reason, void* d_robust, void* d_obs_start_out, void* d_obs_out, void* d_split_out,
+                                      void* d_counts, void* d_recon_verdict, void* d_stats, void* stream_to_wait);
+/* VSlam::optimize_reconstruction (cv-sfm/src/lib.rs:2343-2355) for n_graphs reconstructions side by side:
+ * reconstruction_optimization_iterations rounds of rs_pose_graph_relax_batch_device (its arguments, d_poses ... pg_params, with
+ * n_views == the n_blocks of the landmark table and d_graph_start as the filter's d_view_start) followed by
+ * rs_filter_observations_device on the table the round before wrote, without a host step between them.  A reconstruction
+ * whose graph verdict is not RS_PG_OK, or which the filter rejects, stops there: d_verdict [n_graphs] u32 says which round
+ * and which stage (RS_OR_*), its poses are not relaxed again and the filters of later rounds pass its part of the table
+ * through.  (The reference removes such a reconstruction; and it lets a graph whose view was removed in the LAST round of a
+ * relaxation through to the filter — DESIGN.md §7 —, which this call does not follow: RS_PG_NONFINITE stops a reconstruction
+ * in whichever round it falls.)
+ * Outputs: d_graph_verdict, d_view_state, d_pg_stats as the relaxation writes them, of the last round a reconstruction was
+ * relaxed in; d_recon_verdict [iterations][n_graphs] and d_of_stats [iterations][n_graphs][RS_OF_STATS] of every round's
+ * filter; d_split_out [iterations][n_obs][2] and d_counts [iterations][2] likewise (round k's split-off observations are
+ * the single-observation landmarks the later rounds do not see: they can never become robust again); d_keep, d_lm_state,
+ * d_tri_reason, d_robust of the LAST round, d_keep indexing the table that round read; d_obs_start_out / d_obs_out the final
+ * table.  The tables between the rounds live in scratch of the context (two of them at the most, grown on demand); with one
+ * iteration there is none.  d_world (optional) [n_landmarks][4] f64 and d_world_reason (optional) [n_landmarks] u8:
+ * rs_triangulate_landmarks_device on the final table, so that the world table the registration chain reads is the filtered
+ * one.  iterations == 0 copies the table to the outputs and triangulates it. */
+int32_t rs_optimize_reconstruction_batch_device(rs_ctx* ctx, void* d_poses, uint32_t n_views, const void* d_graph_start, uint32_t n_graphs,
+                                                const void* d_row_start, const void* d_row_edges, uint32_t n_rows, const void* d_views,
+                                                const void* d_constraint_verdict, const void* d_edges, uint32_t n_constraints,
+                                                const rs_pose_graph_params* pg_params, const void* d_kps, uint32_t cap_per_img,
+                                                const rs_camera* cam, const void* d_obs_start, const void* d_obs, uint32_t n_obs,
+                                                uint32_t n_landmarks, const void* d_recon_start,
+                                                const rs_observation_filter_params* params, void* d_verdict, void* d_graph_verdict,
+                                                void* d_view_state, void* d_pg_stats, void* d_keep, void* d_lm_state, void* d_tri_reason,
+                                                void* d_robust, void* d_obs_start_out, void* d_obs_out, void* d_split_out, void* d_counts,
+                                                void* d_recon_verdict, void* d_of_stats, void* d_world, void* d_world_reason,
+                                                void* stream_to_wait);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched

@@ -129,6 +129,25 @@ extern "C" {
                                         params: *const RsPoseGraphParams, d_graph_verdict: *mut c_void, d_view_state: *mut c_void,
                                         d_stats: *mut c_void, stream_to_wait: *mut c_void) -> i32;
     fn rs_pose_graph_debug_resident_views(ctx: *mut c_void, views: u32) -> i32;
+    fn rs_observation_filter_params_default(params: *mut RsObservationFilterParams) -> i32;
+    fn rs_filter_observations_device(ctx: *mut c_void, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, d_poses: *const c_void,
+                                     cam: *const RsCamera, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32,
+                                     d_recon_start: *const c_void, d_view_start: *const c_void, n_recons: u32, d_skip: *const c_void,
+                                     params: *const RsObservationFilterParams, d_keep: *mut c_void, d_lm_state: *mut c_void,
+                                     d_tri_reason: *mut c_void, d_robust: *mut c_void, d_obs_start_out: *mut c_void, d_obs_out: *mut c_void,
+                                     d_split_out: *mut c_void, d_counts: *mut c_void, d_recon_verdict: *mut c_void, d_stats: *mut c_void,
+                                     stream_to_wait: *mut c_void) -> i32;
+    fn rs_optimize_reconstruction_batch_device(ctx: *mut c_void, d_poses: *mut c_void, n_views: u32, d_graph_start: *const c_void, n_graphs: u32,
+                                               d_row_start: *const c_void, d_row_edges: *const c_void, n_rows: u32, d_views: *const c_void,
+                                               d_constraint_verdict: *const c_void, d_edges: *const c_void, n_constraints: u32,
+                                               pg_params: *const RsPoseGraphParams, d_kps: *const c_void, cap_per_img: u32, cam: *const RsCamera,
+                                               d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32,
+                                               d_recon_start: *const c_void, params: *const RsObservationFilterParams, d_verdict: *mut c_void,
+                                               d_graph_verdict: *mut c_void, d_view_state: *mut c_void, d_pg_stats: *mut c_void,
+                                               d_keep: *mut c_void, d_lm_state: *mut c_void, d_tri_reason: *mut c_void, d_robust: *mut c_void,
+                                               d_obs_start_out: *mut c_void, d_obs_out: *mut c_void, d_split_out: *mut c_void,
+                                               d_counts: *mut c_void, d_recon_verdict: *mut c_void, d_of_stats: *mut c_void, d_world: *mut c_void,
+                                               d_world_reason: *mut c_void, stream_to_wait: *mut c_void) -> i32;
     fn hm_create(device: i32, max_q: u32, max_t: u32, out: *mut *mut c_void) -> i32;
     fn hm_destroy(ctx: *mut c_void) -> i32;
     fn hm_knn2(ctx: *mut c_void, q: *const [u8; 64], nq: u32, t: *const [u8; 64], nt: u32, out: *mut AkzNeighbor) -> i32;
@@ -1140,6 +1159,130 @@ impl Default for PoseGraph {
     }
 }
 impl Drop for PoseGraph {
+    fn drop(&mut self) {
+        unsafe { rs_destroy(self.ctx) };
+    }
+}
+
+/// `rs_observation_filter_params` (include/akz.h): cv-sfm's settings of `filter_non_robust_observations` and
+/// `optimize_reconstruction` (cv-sfm/src/settings.rs:324-350, 429-431).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsObservationFilterParams {
+    struct_size: u32,
+    pub minimum_robust_landmarks: u32,
+    pub maximum_cosine_distance: f64,
+    pub maximum_sine_distance: f64,
+    pub reconstruction_optimization_iterations: u32,
+    reserved: u32,
+    pub triangulate: RsTriangulateParams,
+}
+
+/// What became of a landmark (`RS_OF_*`, one byte of `d_lm_state`).
+#[repr(u8)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum LandmarkState {
+    Kept = 0,
+    Single = 1,
+    PairSplit = 2,
+    NoPoint = 3,
+    Kicked = 4,
+    BadIndex = 5,
+    Skipped = 6,
+}
+
+/// The filter's verdict on a reconstruction (`RS_OF_OK` ...): the reference removes it on `FewLandmarks`
+/// (cv-sfm/src/lib.rs:2747-2753).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ObservationFilterVerdict {
+    Ok = 0,
+    FewLandmarks = 1,
+    BadRange = 2,
+    Skipped = 3,
+}
+
+/// Words of a reconstruction's `d_stats` row (`RS_OF_STATS`); `d_tri_reason` of a landmark without a solve
+/// (`RS_OF_NO_SOLVE`); the bits of `d_robust`.
+pub const RS_OF_STATS: usize = 8;
+pub const RS_OF_NO_SOLVE: u8 = 255;
+pub const RS_OF_ROBUST_BEFORE: u8 = 1;
+pub const RS_OF_ROBUST_AFTER: u8 = 2;
+/// A word of `optimize_reconstruction`'s `d_verdict`: 0, or `RS_OR_STOPPED | round << 16 | stage << 8 | the stage's verdict`.
+pub const RS_OR_STOPPED: u32 = 1 << 30;
+pub const RS_OR_STAGE_RELAX: u32 = 1;
+pub const RS_OR_STAGE_FILTER: u32 = 2;
+
+/// `VSlam::filter_non_robust_observations` (cv-sfm/src/lib.rs:2657-2757) for many reconstructions side by side
+/// (`rs_filter_observations_device`) and `VSlam::optimize_reconstruction` (lib.rs:2343-2355) as a whole
+/// (`rs_optimize_reconstruction_batch_device`).  Every `d_*` argument is device memory the caller owns, laid out as
+/// include/akz.h documents; the calls enqueue on `stream()` and return.
+pub struct ObservationFilter {
+    pub params: RsObservationFilterParams,
+    ctx: *mut c_void,
+}
+impl ObservationFilter {
+    pub fn new() -> Self {
+        require_abi();
+        let mut params: RsObservationFilterParams = unsafe { std::mem::zeroed() };
+        assert_eq!(unsafe { rs_observation_filter_params_default(&mut params) }, 0, "rs_observation_filter_params_default");
+        let mut ctx = ptr::null_mut();
+        assert_eq!(unsafe { rs_create(0, 8, 1, &mut ctx) }, 0, "rs_create");
+        Self { params, ctx }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until `sync()` returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn filter_device(&self, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, d_poses: *const c_void, cam: &RsCamera,
+                                d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32, d_recon_start: *const c_void,
+                                d_view_start: *const c_void, n_recons: u32, d_skip: *const c_void, d_keep: *mut c_void, d_lm_state: *mut c_void,
+                                d_tri_reason: *mut c_void, d_robust: *mut c_void, d_obs_start_out: *mut c_void, d_obs_out: *mut c_void,
+                                d_split_out: *mut c_void, d_counts: *mut c_void, d_recon_verdict: *mut c_void, d_stats: *mut c_void,
+                                stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_filter_observations_device(self.ctx, d_kps, cap_per_img, n_blocks, d_poses, cam, d_obs_start, d_obs, n_obs, n_landmarks,
+                                               d_recon_start, d_view_start, n_recons, d_skip, &self.params, d_keep, d_lm_state, d_tri_reason,
+                                               d_robust, d_obs_start_out, d_obs_out, d_split_out, d_counts, d_recon_verdict, d_stats,
+                                               stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// `optimize_reconstruction`: `self.params.reconstruction_optimization_iterations` rounds of the relaxation (under
+    /// `pg_params`) and the filter, then the world table of the final lists into `d_world` (may be null).
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until `sync()` returns.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn optimize_reconstruction_device(&self, pg_params: &RsPoseGraphParams, d_poses: *mut c_void, n_views: u32,
+                                                 d_graph_start: *const c_void, n_graphs: u32, d_row_start: *const c_void,
+                                                 d_row_edges: *const c_void, n_rows: u32, d_views: *const c_void,
+                                                 d_constraint_verdict: *const c_void, d_edges: *const c_void, n_constraints: u32,
+                                                 d_kps: *const c_void, cap_per_img: u32, cam: &RsCamera, d_obs_start: *const c_void,
+                                                 d_obs: *const c_void, n_obs: u32, n_landmarks: u32, d_recon_start: *const c_void,
+                                                 d_verdict: *mut c_void, d_graph_verdict: *mut c_void, d_view_state: *mut c_void,
+                                                 d_pg_stats: *mut c_void, d_keep: *mut c_void, d_lm_state: *mut c_void, d_tri_reason: *mut c_void,
+                                                 d_robust: *mut c_void, d_obs_start_out: *mut c_void, d_obs_out: *mut c_void,
+                                                 d_split_out: *mut c_void, d_counts: *mut c_void, d_recon_verdict: *mut c_void,
+                                                 d_of_stats: *mut c_void, d_world: *mut c_void, d_world_reason: *mut c_void,
+                                                 stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_optimize_reconstruction_batch_device(self.ctx, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows,
+                                                         d_views, d_constraint_verdict, d_edges, n_constraints, pg_params, d_kps, cap_per_img, cam,
+                                                         d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start, &self.params, d_verdict,
+                                                         d_graph_verdict, d_view_state, d_pg_stats, d_keep, d_lm_state, d_tri_reason, d_robust,
+                                                         d_obs_start_out, d_obs_out, d_split_out, d_counts, d_recon_verdict, d_of_stats, d_world,
+                                                         d_world_reason, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    pub fn sync(&self) {
+        assert_eq!(unsafe { rs_sync(self.ctx) }, 0, "rs_sync");
+    }
+    pub fn stream(&self) -> *mut c_void {
+        unsafe { rs_stream(self.ctx) }
+    }
+}
+impl Default for ObservationFilter {
+    fn default() -> Self {
+        Self::new()
+    }
+}
+impl Drop for ObservationFilter {
     fn drop(&mut self) {
         unsafe { rs_destroy(self.ctx) };
     }
