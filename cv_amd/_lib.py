@@ -166,6 +166,19 @@ RS_OF_NO_SOLVE, RS_OF_ROBUST_BEFORE, RS_OF_ROBUST_AFTER, RS_OF_STATS, RS_OF_MAX_
 RS_OF_S_LANDMARKS, RS_OF_S_ROBUST_BEFORE, RS_OF_S_ROBUST_AFTER, RS_OF_S_OBS_SPLIT, RS_OF_S_PAIR_SPLIT, RS_OF_S_NO_POINT, RS_OF_S_KICKED = range(7)
 RS_OR_OK, RS_OR_STAGE_RELAX, RS_OR_STAGE_FILTER, RS_OR_STOPPED = 0, 1, 2, 1 << 30
 
+class SingleViewParams(C.Structure):
+    """rs_single_view_params (include/akz.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("single_view_optimization_num_matches", C.c_uint32),
+                ("single_view_filter_loop_iterations", C.c_uint32), ("single_view_patience", C.c_uint32),
+                ("single_view_optimization_rate", C.c_double), ("single_view_minimum_landmarks", C.c_uint32),
+                ("single_view_minimum_robust_landmarks", C.c_uint32), ("maximum_cosine_distance", C.c_double),
+                ("maximum_sine_distance", C.c_double), ("triangulate", TriangulateParams)]
+
+
+RS_SV_OK, RS_SV_NO_MODEL, RS_SV_FEW_LANDMARKS, RS_SV_LOST_HALF, RS_SV_FEW_ROBUST, RS_SV_BAD_INDEX = range(6)
+RS_SV_MAX_MATCHES, RS_SV_MAX_RUNS, RS_SV_MAX_ITERATIONS, RS_SV_STATS = 2048, 9, 1 << 20, 24
+RS_SV_S_INLIERS, RS_SV_S_RUN_MATCHES, RS_SV_S_RUN_STOP, RS_SV_S_ROBUST, RS_SV_S_NO_OTHER, RS_SV_S_STAGE = 0, 1, 10, 19, 20, 21
+
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
 
@@ -202,12 +215,13 @@ ABI_SYMBOLS = [
     "hm_timing_get",
     "hm_stream", "rs_create", "rs_destroy", "rs_calibrate", "rs_essential_batch", "rs_five_point_batch", "rs_debug_essentials", "rs_essential_arrsac", "rs_p3p_arrsac", "rs_arrsac_samples",
     "rs_p3p_batch", "rs_debug_counts", "rs_debug_poses", "rs_batch_reserve", "rs_essential_arrsac_batch_device", "rs_sync",
-    "rs_stream", "rs_debug_scene", "rs_debug_residuals", "rs_p3p_arrsac_batch_device", "hm_landmark_pairs_batch_device", "hm_landmark_matches_batch_device", "hm_landmark_matches_ordered_batch_device", "hm_set_targets", "hm_targets_generation", "hm_knn_targets", "rs_debug_scene_world", "rs_debug_far",
+    "rs_stream", "rs_debug_scene", "rs_debug_residuals", "rs_p3p_arrsac_batch_device", "hm_landmark_pairs_batch_device", "hm_landmark_matches_batch_device", "hm_landmark_matches_ordered_batch_device", "hm_landmark_original_matches_batch_device", "hm_set_targets", "hm_targets_generation", "hm_knn_targets", "rs_debug_scene_world", "rs_debug_far",
     "rs_triangulate_params_default", "rs_triangulate_observations", "rs_triangulate_landmarks_device", "rs_triangulate_merged_device",
     "rs_triangulate_pairs_batch_device", "rs_three_view_params_default", "rs_three_view_init_batch_device",
     "rs_three_view_constraint_params_default", "rs_three_view_constraint_batch_device",
     "rs_pose_graph_params_default", "rs_pose_graph_edges_device", "rs_pose_graph_relax_batch_device", "rs_pose_graph_debug_resident_views",
     "rs_observation_filter_params_default", "rs_filter_observations_device", "rs_optimize_reconstruction_batch_device",
+    "rs_single_view_params_default", "rs_refine_poses_batch_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -291,6 +305,7 @@ def lib():
     L.hm_landmark_pairs_batch_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp]
     L.hm_landmark_matches_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp]
     L.hm_landmark_matches_ordered_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp]
+    L.hm_landmark_original_matches_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
     L.hm_match.argtypes = [vp, vp, u32, vp, u32, i32, u32, C.c_float, i32, vp, u32, C.POINTER(u32)]
     L.hm_match_batch_device.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, u32, i32, u32, C.c_float, i32, vp, vp, vp]
     L.hm_sync.argtypes = [vp]
@@ -350,6 +365,10 @@ def lib():
     L.rs_filter_observations_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(Camera), vp, vp, u32, u32, vp, vp, u32, vp, ofp] + [vp] * 11
     L.rs_optimize_reconstruction_batch_device.argtypes = ([vp, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, u32, C.POINTER(PoseGraphParams),
                                                            vp, u32, C.POINTER(Camera), vp, vp, u32, u32, vp, ofp] + [vp] * 17)
+    svp = C.POINTER(SingleViewParams)
+    L.rs_single_view_params_default.argtypes = [svp]
+    L.rs_refine_poses_batch_device.argtypes = ([vp, vp, u32, u32, vp, C.POINTER(Camera), vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                u32, svp] + [vp] * 6)
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

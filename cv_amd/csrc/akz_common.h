@@ -175,6 +175,13 @@ struct RsObsFilterState {
     size_t chain_bytes = 0;
 };
 RsObsFilterState* rs_internal_obs_filter(rs_ctx* c);
+// What rs_single_view.hip keeps in an rs_ctx, grown on demand and freed by rs_destroy: a word per original match of a call
+// (the place of every match with a world point in the list the consensus saw).
+struct RsSingleViewState {
+    void* d_scratch = nullptr;
+    size_t bytes = 0;
+};
+RsSingleViewState* rs_internal_single_view(rs_ctx* c);
 
 static inline int akz_div_up(int a, int b) { return (a + b - 1) / b; }
 static inline size_t akz_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }

@@ -1506,7 +1506,7 @@ __global__ __launch_bounds__(1024) void k_landmark_pairs(const uint2* __restrict
                 on = lm_claimed_once(tab, dup, l0) && lm_claimed_once(tab, dup, l1);
                 row = n_world + f * cap + j;
             }
-            if (on) on = world[(size_t)4 * row + 3] >= 0.0;
+            if (on && world) on = world[(size_t)4 * row + 3] >= 0.0;   // no table: original_matches, nothing dropped
         }
         const unsigned long long bal = __ballot(on);
         if (lane == 0) s_wave[wv] = (uint32_t)__popcll(bal);
@@ -1564,13 +1564,13 @@ __global__ __launch_bounds__(1024) void k_landmark_pairs(const uint2* __restrict
     }
 }
 
-extern "C" int32_t hm_landmark_matches_ordered_batch_device(hm_ctx* c, const void* d_best, const void* d_decision, const void* d_merge_ok,
-                                                            const void* d_obs_counts, const void* d_nq, const uint32_t* iq,
-                                                            uint32_t cap_per_img, uint32_t n_frames, const void* d_world,
-                                                            uint32_t n_world, void* d_pairs, void* d_npairs, void* stream_to_wait)
+// d_world == nullptr: the lists before the drop of the matches without a robust triangulation
+static int32_t lm_matches_enqueue(hm_ctx* c, const void* d_best, const void* d_decision, const void* d_merge_ok, const void* d_obs_counts,
+                                  const void* d_nq, const uint32_t* iq, uint32_t cap_per_img, uint32_t n_frames, const void* d_world,
+                                  uint32_t n_world, void* d_pairs, void* d_npairs, void* stream_to_wait)
 {
     return akz_guard([&]() -> int32_t {
-        if (!c || !d_best || !d_decision || !d_nq || !iq || !d_world || !d_pairs || !d_npairs) return AKZ_E_INVALID;
+        if (!c || !d_best || !d_decision || !d_nq || !iq || !d_pairs || !d_npairs) return AKZ_E_INVALID;
         if (cap_per_img == 0 || n_world == 0 || n_frames > 65535u) return AKZ_E_INVALID;
         if (cap_per_img > kLmSlots / 4) return AKZ_E_TOO_LARGE;           // 2 keys per feature at a load factor <= 1/2
         if (d_merge_ok && (uint64_t)n_world + (uint64_t)n_frames * cap_per_img > 0xFFFFFFFFull) return AKZ_E_TOO_LARGE;
@@ -1586,6 +1586,27 @@ extern "C" int32_t hm_landmark_matches_ordered_batch_device(hm_ctx* c, const voi
         AKZ_LAUNCH_CHECK();
         return AKZ_OK;
     });
+}
+
+extern "C" int32_t hm_landmark_matches_ordered_batch_device(hm_ctx* c, const void* d_best, const void* d_decision, const void* d_merge_ok,
+                                                            const void* d_obs_counts, const void* d_nq, const uint32_t* iq,
+                                                            uint32_t cap_per_img, uint32_t n_frames, const void* d_world,
+                                                            uint32_t n_world, void* d_pairs, void* d_npairs, void* stream_to_wait)
+{
+    if (!d_world) return AKZ_E_INVALID;
+    return lm_matches_enqueue(c, d_best, d_decision, d_merge_ok, d_obs_counts, d_nq, iq, cap_per_img, n_frames, d_world, n_world, d_pairs,
+                              d_npairs, stream_to_wait);
+}
+
+// original_matches (cv-sfm/src/lib.rs:1549-1576) for rs_refine_poses_batch_device: the same kernel, nothing dropped for its
+// world point
+extern "C" int32_t hm_landmark_original_matches_batch_device(hm_ctx* c, const void* d_best, const void* d_decision, const void* d_merge_ok,
+                                                             const void* d_obs_counts, const void* d_nq, const uint32_t* iq,
+                                                             uint32_t cap_per_img, uint32_t n_frames, uint32_t n_world, void* d_pairs,
+                                                             void* d_npairs, void* stream_to_wait)
+{
+    return lm_matches_enqueue(c, d_best, d_decision, d_merge_ok, d_obs_counts, d_nq, iq, cap_per_img, n_frames, nullptr, n_world, d_pairs,
+                              d_npairs, stream_to_wait);
 }
 
 // the same in ascending feature order (no observation counts: the caller orders, or shuffles, the matches itself)

@@ -11,7 +11,8 @@
 
 The reference walks this per feature on the CPU; here one call enqueues, for ALL frames of a micro-batch,
 hm_hash_bag_device -> hm_knn_batch_device (k = 3, frames x views problems) -> hm_best_of_views_batch_device ->
-hm_landmark_matches_batch_device -> rs_p3p_arrsac_batch_device on the blocks where akz_extract_batch_device left them; nothing
+hm_landmark_matches_batch_device -> rs_p3p_arrsac_batch_device (and, with refine(), hm_landmark_original_matches_batch_device ->
+rs_refine_poses_batch_device: the single-view optimiser and consistency filter of cv-sfm/src/lib.rs:1625-1775) on the blocks where akz_extract_batch_device left them; nothing
 returns to the host in between.  What stays with the caller is the reference's control plane: which views a frame is matched
 against, which landmark each stored feature observes (and so which features observe each landmark: a LandmarkTable), and
 for the merge candidates (decision 2) the graph test are_landmarks_sharing_view — handed in as a mask.  The table of
@@ -27,6 +28,7 @@ from . import _lib
 from ._lib import check
 from .knn import Matcher
 from .ransac import EssentialConsensus
+from .single_view import RefineOutputs, SingleViewRefiner
 from . import triangulation
 
 
@@ -71,7 +73,12 @@ class Registration:
         self._sets = [dict(best=z((F, cap, 3, 2), torch.int32), decision=z((F, cap), torch.int32), pairs=z((F, cap, 2), torch.int32),
                            npairs=z((F,), torch.int32), pose=z((F, 12), torch.float64), best_id=z((F,), torch.int32),
                            inliers=z((F, cap), torch.int32), n_inliers=z((F,), torch.int32), stats=z((F, 32), torch.uint8),
+                           originals=z((F, cap, 2), torch.int32), noriginals=z((F,), torch.int32),
+                           refined=RefineOutputs(z((F, 12), torch.float64), z((F,), torch.int32), z((F, cap), torch.uint8),
+                                                 z((F,), torch.int32), z((F, _lib.RS_SV_STATS), torch.int32)),
                            done=torch.cuda.Event(), used=False) for _ in range(2)]
+        self.refiner = SingleViewRefiner(self.cons)
+        self.sv_prm = self.refiner.params()              # the reference's single-view defaults
         self._calls = 0
         self._hm_s = torch.cuda.ExternalStream(self.hm_stream(), device=self.dev)
         self._rs_s = torch.cuda.ExternalStream(self.rs_stream(), device=self.dev)
@@ -189,6 +196,34 @@ class Registration:
                                                  stream_to_wait=self.hm_stream())
         cur["done"].record(self._rs_s)
         cur["used"] = True
+        self._consensus_args = (d_kps, d_counts, d_world, n_world, d_merge_ok, d_obs_counts)
+
+    def refine(self, d_poses, d_obs_start, d_obs, n_landmarks, params=None, stream=None):
+        """What register_frame_subset does behind its consensus (cv-sfm/src/lib.rs:1625-1775) for the frames of the last
+        consensus(): the original matches — that call's lists before the drop of the matches without a world point, in the same
+        order — on the matcher's stream, then the single-view optimiser and consistency filter on rs_stream() behind the
+        consensus, no host step.  The landmark table as triangulate() took it: d_poses [blocks][12] float64 the views' poses,
+        d_obs_start [n_landmarks + 1] / d_obs [n_obs][2] int32 the observations {block, feature} of every landmark key.  stream:
+        the torch stream the table was written on (default: nothing to wait for).  Outputs: self.originals / noriginals and
+        self.refined (a single_view.RefineOutputs: pose, verdict, final, n_final, stats) — the pose for the pose graph and the
+        final_matches map over self.originals."""
+        L = _lib.lib()
+        cur, fb = self._cur, self._fb
+        d_kps, d_counts, d_world, n_world, d_merge_ok, d_obs_counts = self._consensus_args
+        F = len(fb)
+        _, fb_p = _u32(fb)
+        check(L.hm_landmark_original_matches_batch_device(self.matcher.handle, self.best.data_ptr(), self.decision.data_ptr(),
+                                                          None if d_merge_ok is None else d_merge_ok.data_ptr(),
+                                                          None if d_obs_counts is None else d_obs_counts.data_ptr(), d_counts.data_ptr(),
+                                                          fb_p, self.cap, F, n_world, self.originals.data_ptr(), self.noriginals.data_ptr(),
+                                                          None if stream is None else _lib.wait_handle(stream)),
+              "hm_landmark_original_matches_batch_device")
+        self.refiner.refine_tensors(self.torch, d_kps, d_poses, self.cam, d_obs_start, d_obs, n_landmarks, d_world, n_world,
+                                    [int(b) for b in fb], self.originals, self.noriginals, None if d_merge_ok is None else self.best,
+                                    self.pose, self.best_id, self.inliers, self.n_inliers, params or self.sv_prm, out=self.refined,
+                                    stream_to_wait=self.hm_stream())
+        cur["done"].record(self._rs_s)
+        return self.refined
 
     def sync(self):
         check(_lib.lib().hm_sync(self.matcher.handle), "hm_sync")

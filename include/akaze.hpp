@@ -844,6 +844,41 @@ inline void optimize_reconstruction(ObservationFilter& filter, const rs_pose_gra
                                                          d_world_reason, stream_to_wait),
                  "rs_optimize_reconstruction_batch_device");
 }
+
+// What cv-sfm's register_frame_subset does behind its consensus (cv-sfm/src/lib.rs:1625-1775) over
+// rs_refine_poses_batch_device: the single-view L2 optimiser and the consistency filter, one persistent workgroup per new
+// frame.  It works on the context of the consensus that registered the frames (`ctx`, not owned: the call queues behind
+// rs_p3p_arrsac_batch_device on that context's stream, no host step).  Every argument named d_* is device memory the caller
+// owns (the layouts are include/akz.h's); the call enqueues and returns.
+class SingleViewRefiner {
+public:
+    enum Verdict : uint32_t { Ok = RS_SV_OK, NoModel = RS_SV_NO_MODEL, FewLandmarks = RS_SV_FEW_LANDMARKS, LostHalf = RS_SV_LOST_HALF,
+                              FewRobust = RS_SV_FEW_ROBUST, BadIndex = RS_SV_BAD_INDEX };
+    explicit SingleViewRefiner(rs_ctx* ctx) : ctx_(ctx)
+    {
+        akaze::require_abi();
+        rs_single_view_params_default(&p_);
+    }
+    rs_single_view_params& params() { return p_; }   // the reference's defaults (cv-sfm/src/settings.rs:324-383)
+    const rs_single_view_params& params() const { return p_; }
+    void refine_batch_device(const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks, const void* d_poses, const rs_camera& cam,
+                             const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks, const void* d_world,
+                             uint32_t n_world, const std::vector<uint32_t>& ik, const void* d_matches, const void* d_nmatches, const void* d_best,
+                             const void* d_pose, const void* d_best_id, const void* d_inliers, const void* d_n_inliers, void* d_pose_out,
+                             void* d_verdict, void* d_final, void* d_n_final, void* d_stats, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_refine_poses_batch_device(ctx_, d_kps, cap_per_img, n_blocks, d_poses, &cam, d_obs_start, d_obs, n_obs, n_landmarks, d_world,
+                                                  n_world, ik.data(), d_matches, d_nmatches, d_best, d_pose, d_best_id, d_inliers, d_n_inliers,
+                                                  (uint32_t)ik.size(), &p_, d_pose_out, d_verdict, d_final, d_n_final, d_stats, stream_to_wait),
+                     "rs_refine_poses_batch_device");
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_single_view_params p_;
+    rs_ctx* ctx_ = nullptr;
+};
 }  // namespace cv_sfm
 
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over

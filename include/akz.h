@@ -376,6 +376,15 @@ int32_t hm_landmark_matches_ordered_batch_device(hm_ctx* ctx, const void* d_best
                                                  const void* d_obs_counts, const void* d_nq, const uint32_t* iq, uint32_t cap_per_img,
                                                  uint32_t n_frames, const void* d_world, uint32_t n_world, void* d_pairs,
                                                  void* d_npairs, void* stream_to_wait);
+/* original_matches itself (cv-sfm/src/lib.rs:1549-1576), for rs_refine_poses_batch_device: the same lists in the same order
+ * WITHOUT the drop of the matches whose triangulation is None — final_matches (lib.rs:1742-1758) needs them.  The arguments
+ * of hm_landmark_matches_ordered_batch_device without the world table; n_world still numbers the rows (a merged match is row
+ * n_world + f * cap + j, and a unique match on a landmark key >= n_world names no landmark of the table and is left out as
+ * before).  Given a world table without "None" rows the entry point above writes the same bytes. */
+int32_t hm_landmark_original_matches_batch_device(hm_ctx* ctx, const void* d_best, const void* d_decision, const void* d_merge_ok,
+                                                  const void* d_obs_counts, const void* d_nq, const uint32_t* iq, uint32_t cap_per_img,
+                                                  uint32_t n_frames, uint32_t n_world, void* d_pairs, void* d_npairs,
+                                                  void* stream_to_wait);
 /* hm_landmark_matches_batch_device without a merge mask (equals the reference when no decision-2 match passes the graph test). */
 int32_t hm_landmark_pairs_batch_device(hm_ctx* ctx, const void* d_best, const void* d_decision, const void* d_nq, const uint32_t* iq,
                                        uint32_t cap_per_img, uint32_t n_frames, const void* d_world, uint32_t n_world,
@@ -1006,6 +1015,78 @@ int32_t rs_optimize_reconstruction_batch_device(rs_ctx* ctx, void* d_poses, uint
                                                 void* d_robust, void* d_obs_start_out, void* d_obs_out, void* d_split_out, void* d_counts,
                                                 void* d_recon_verdict, void* d_of_stats, void* d_world, void* d_world_reason,
                                                 void* stream_to_wait);
+/* ---- the refinement of registered poses on the device: single-view L2 optimiser and consistency filter ----
+ * What cv-sfm's register_frame_subset does behind its consensus (cv-sfm/src/lib.rs:1625-1775), for the new frames of a
+ * micro-batch side by side — the same scenes as the preceding rs_p3p_arrsac_batch_device call: the first
+ * single_view_optimization_num_matches inliers, single_view_simple_optimize_l2 (cv-optimize/src/single_view_optimizer.rs:
+ * 80-135), the re-selection of the original matches that are is_observation_consistent (lib.rs:2622-2655) under the new pose
+ * and have a robust world point, single_view_filter_loop_iterations times, one more optimisation, and the final counts and
+ * the map of consistent matches.  One persistent workgroup per scene, one launch.  The arithmetic is
+ * include/akz_single_view_math.h (compiled for the device and, by the tests, for the host: equal bit for bit); its head lists
+ * what is unpinned against the reference — the order of the sum over matches, which is fixed there, among it. */
+enum {
+    RS_SV_OK = 0,
+    RS_SV_NO_MODEL = 1,        /* the consensus found no pose (d_best_id == 0xFFFFFFFF): passed through, the pose copied */
+    RS_SV_FEW_LANDMARKS = 2,   /* fewer than single_view_minimum_landmarks matches with a world point (lib.rs:1606) */
+    RS_SV_LOST_HALF = 3,       /* no more than half of the inliers taken are left (lib.rs:1650, 1697, 1737) */
+    RS_SV_FEW_ROBUST = 4,      /* fewer than single_view_minimum_robust_landmarks final matches (lib.rs:1766) */
+    RS_SV_BAD_INDEX = 5        /* a match, a landmark, an observation or an inlier names something outside the caller's arrays:
+                                * the scene is refused, nothing is read out of bounds */
+};
+enum {
+    RS_SV_MAX_MATCHES = 2048,         /* single_view_optimization_num_matches at the most (they live in one workgroup's LDS) */
+    RS_SV_MAX_RUNS = 9,               /* single_view_filter_loop_iterations + 1 at the most */
+    RS_SV_MAX_ITERATIONS = 1 << 20,   /* a larger single_view_patience counts as this: the bound that ends every run */
+    /* d_stats words (u32) of a scene: */
+    RS_SV_S_INLIERS = 0,              /* inliers taken */
+    RS_SV_S_RUN_MATCHES = 1,          /* [9] matches entering run r; 0xFFFFFFFF: not reached */
+    RS_SV_S_RUN_STOP = 10,            /* [9] the iteration run r left its loop at (patience - 1: the last one; less: 50 iterations
+                                       * without improvement); 0xFFFFFFFF: not run */
+    RS_SV_S_ROBUST = 19,              /* final_num_robust_matches */
+    RS_SV_S_NO_OTHER = 20,            /* original matches whose landmarks have no observation ("unreachable" in the reference; never
+                                       * consistent here) */
+    RS_SV_S_STAGE = 21,               /* where the verdict fell: 0 indices, 1 minimum landmarks, 2 the model, 3 + r entering run r,
+                                       * 12 final_num_robust_matches, 13 the final matches (and RS_SV_OK) */
+    RS_SV_STATS = 24
+};
+typedef struct rs_single_view_params {
+    uint32_t struct_size;                              /* sizeof(rs_single_view_params) */
+    uint32_t single_view_optimization_num_matches;     /* 2048; more than RS_SV_MAX_MATCHES: AKZ_E_TOO_LARGE */
+    uint32_t single_view_filter_loop_iterations;       /* 5; more than RS_SV_MAX_RUNS - 1: AKZ_E_TOO_LARGE */
+    uint32_t single_view_patience;                     /* 100000: the optimiser's iteration limit */
+    double single_view_optimization_rate;              /* 1e-3 */
+    uint32_t single_view_minimum_landmarks;            /* 32 */
+    uint32_t single_view_minimum_robust_landmarks;     /* 64 */
+    double maximum_cosine_distance;                    /* 1e-5 */
+    double maximum_sine_distance;                      /* 1e-1 */
+    rs_triangulate_params triangulate;                 /* the eigen-solver's settings (max_sweeps, eps) */
+} rs_single_view_params;
+/* the reference's defaults (cv-sfm/src/settings.rs:324-383) */
+int32_t rs_single_view_params_default(rs_single_view_params* params);
+/* Scene s < n_scenes is the new frame in keypoint block ik[s] of d_kps.  The landmark table as rs_triangulate_landmarks_device
+ * takes it (d_kps, cap_per_img, n_blocks, d_poses of the views, cam, d_obs_start [n_landmarks + 1], d_obs [n_obs][2]) and the
+ * world table d_world / n_world the consensus read (with n_world + n_scenes * cap_per_img rows when d_best is given).
+ * d_matches [n_scenes][cap_per_img][2] u32 {feature, world row} with d_nmatches [n_scenes]: the ORIGINAL matches in their order
+ * (lib.rs:1549-1576; hm_landmark_original_matches_batch_device), those whose world row says "None" (w < 0) included.  A row
+ * < n_world is the landmark of that key; a row n_world + f * cap_per_img + j is the merged match of d_best[f][j][0..1] (d_best
+ * as hm_best_of_views_batch_device leaves it; optional, required only when such a row occurs), whose observations are those
+ * of its first landmark followed by those of its second.  d_pose, d_best_id, d_inliers, d_n_inliers: the consensus' outputs;
+ * inlier index k names the k-th entry of d_matches whose world row has w >= 0, in order — the list
+ * hm_landmark_matches_*_batch_device hands the consensus for the same world table.
+ * Outputs per scene: d_pose_out [12] f64 (written for RS_SV_OK and, as a copy, RS_SV_NO_MODEL), d_verdict u32 (RS_SV_*),
+ * d_final [cap_per_img] u8 (1 where original match i is consistent under the final pose: the final_matches map; written for
+ * the matches of the scene once the final pass is reached), d_n_final u32 (0 before that), d_stats [RS_SV_STATS] u32.
+ * A scene that names a feature, world row, landmark, block or observation range outside the caller's arrays, or an inlier
+ * beyond its robust sub-list, is refused alone (RS_SV_BAD_INDEX).  The parameters are checked before anything else (a NaN
+ * threshold: AKZ_E_INVALID).  n_scenes within rs_batch_reserve's room.  One launch on rs_stream() after stream_to_wait (may
+ * be NULL); returns after enqueueing; allocates nothing beyond growing the context's scratch. */
+int32_t rs_refine_poses_batch_device(rs_ctx* ctx, const void* d_kps, uint32_t cap_per_img, uint32_t n_blocks, const void* d_poses,
+                                     const rs_camera* cam, const void* d_obs_start, const void* d_obs, uint32_t n_obs,
+                                     uint32_t n_landmarks, const void* d_world, uint32_t n_world, const uint32_t* ik,
+                                     const void* d_matches, const void* d_nmatches, const void* d_best, const void* d_pose,
+                                     const void* d_best_id, const void* d_inliers, const void* d_n_inliers, uint32_t n_scenes,
+                                     const rs_single_view_params* params, void* d_pose_out, void* d_verdict, void* d_final,
+                                     void* d_n_final, void* d_stats, void* stream_to_wait);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched

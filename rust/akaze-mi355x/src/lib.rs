@@ -148,6 +148,18 @@ extern "C" {
                                                d_obs_start_out: *mut c_void, d_obs_out: *mut c_void, d_split_out: *mut c_void,
                                                d_counts: *mut c_void, d_recon_verdict: *mut c_void, d_of_stats: *mut c_void, d_world: *mut c_void,
                                                d_world_reason: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_single_view_params_default(params: *mut RsSingleViewParams) -> i32;
+    fn rs_refine_poses_batch_device(ctx: *mut c_void, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, d_poses: *const c_void,
+                                    cam: *const RsCamera, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32,
+                                    d_world: *const c_void, n_world: u32, ik: *const u32, d_matches: *const c_void, d_nmatches: *const c_void,
+                                    d_best: *const c_void, d_pose: *const c_void, d_best_id: *const c_void, d_inliers: *const c_void,
+                                    d_n_inliers: *const c_void, n_scenes: u32, params: *const RsSingleViewParams, d_pose_out: *mut c_void,
+                                    d_verdict: *mut c_void, d_final: *mut c_void, d_n_final: *mut c_void, d_stats: *mut c_void,
+                                    stream_to_wait: *mut c_void) -> i32;
+    fn hm_landmark_original_matches_batch_device(ctx: *mut c_void, d_best: *const c_void, d_decision: *const c_void, d_merge_ok: *const c_void,
+                                                 d_obs_counts: *const c_void, d_nq: *const c_void, iq: *const u32, cap_per_img: u32,
+                                                 n_frames: u32, n_world: u32, d_pairs: *mut c_void, d_npairs: *mut c_void,
+                                                 stream_to_wait: *mut c_void) -> i32;
     fn hm_create(device: i32, max_q: u32, max_t: u32, out: *mut *mut c_void) -> i32;
     fn hm_destroy(ctx: *mut c_void) -> i32;
     fn hm_knn2(ctx: *mut c_void, q: *const [u8; 64], nq: u32, t: *const [u8; 64], nt: u32, out: *mut AkzNeighbor) -> i32;
@@ -1285,5 +1297,77 @@ impl Default for ObservationFilter {
 impl Drop for ObservationFilter {
     fn drop(&mut self) {
         unsafe { rs_destroy(self.ctx) };
+    }
+}
+
+/// `rs_single_view_params` (include/akz.h): cv-sfm's settings of the single-view refinement (cv-sfm/src/settings.rs:324-383).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsSingleViewParams {
+    struct_size: u32,
+    pub single_view_optimization_num_matches: u32,
+    pub single_view_filter_loop_iterations: u32,
+    pub single_view_patience: u32,
+    pub single_view_optimization_rate: f64,
+    pub single_view_minimum_landmarks: u32,
+    pub single_view_minimum_robust_landmarks: u32,
+    pub maximum_cosine_distance: f64,
+    pub maximum_sine_distance: f64,
+    pub triangulate: RsTriangulateParams,
+}
+
+/// The verdict on a new frame (`RS_SV_*`): the reference returns `None` on every one but `Ok`.
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum SingleViewVerdict {
+    Ok = 0,
+    NoModel = 1,
+    FewLandmarks = 2,
+    LostHalf = 3,
+    FewRobust = 4,
+    BadIndex = 5,
+}
+
+/// The limits of the refinement and the words of a scene's `d_stats` row.
+pub const RS_SV_MAX_MATCHES: u32 = 2048;
+pub const RS_SV_MAX_RUNS: u32 = 9;
+pub const RS_SV_MAX_ITERATIONS: u32 = 1 << 20;
+pub const RS_SV_STATS: usize = 24;
+pub const RS_SV_S_INLIERS: usize = 0;
+pub const RS_SV_S_RUN_MATCHES: usize = 1;
+pub const RS_SV_S_RUN_STOP: usize = 10;
+pub const RS_SV_S_ROBUST: usize = 19;
+pub const RS_SV_S_NO_OTHER: usize = 20;
+pub const RS_SV_S_STAGE: usize = 21;
+
+/// What `register_frame_subset` does behind its consensus (cv-sfm/src/lib.rs:1625-1775) for the new frames of a micro-batch
+/// (`rs_refine_poses_batch_device`), on the context of the consensus that registered them (not owned).  Every `d_*`
+/// argument is device memory the caller owns, laid out as include/akz.h documents; the call enqueues and returns.
+pub struct SingleViewRefiner {
+    pub params: RsSingleViewParams,
+    ctx: *mut c_void,
+}
+impl SingleViewRefiner {
+    /// # Safety
+    /// `ctx` is a live `rs_ctx` that outlives this object.
+    pub unsafe fn new(ctx: *mut c_void) -> Self {
+        require_abi();
+        let mut params: RsSingleViewParams = std::mem::zeroed();
+        assert_eq!(rs_single_view_params_default(&mut params), 0, "rs_single_view_params_default");
+        Self { params, ctx }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn refine_batch_device(&self, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, d_poses: *const c_void, cam: &RsCamera,
+                                      d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32, d_world: *const c_void,
+                                      n_world: u32, ik: &[u32], d_matches: *const c_void, d_nmatches: *const c_void, d_best: *const c_void,
+                                      d_pose: *const c_void, d_best_id: *const c_void, d_inliers: *const c_void, d_n_inliers: *const c_void,
+                                      d_pose_out: *mut c_void, d_verdict: *mut c_void, d_final: *mut c_void, d_n_final: *mut c_void,
+                                      d_stats: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_refine_poses_batch_device(self.ctx, d_kps, cap_per_img, n_blocks, d_poses, cam, d_obs_start, d_obs, n_obs, n_landmarks, d_world,
+                                              n_world, ik.as_ptr(), d_matches, d_nmatches, d_best, d_pose, d_best_id, d_inliers, d_n_inliers,
+                                              ik.len() as u32, &self.params, d_pose_out, d_verdict, d_final, d_n_final, d_stats, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
     }
 }
