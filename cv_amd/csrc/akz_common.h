@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/akz.h"
+#include "../../include/akz_triangulate_math.h"
 
 // ---- error plumbing -------------------------------------------------------------------------
 extern thread_local int g_akz_last_hip;
@@ -183,6 +184,34 @@ struct RsSingleViewState {
 };
 RsSingleViewState* rs_internal_single_view(rs_ctx* c);
 
+// A context's scratch, grown on demand: *d holds at least `need` bytes afterwards (what it held before is not kept).
+inline int32_t akz_grow_scratch(hipStream_t stream, void** d, size_t* have, size_t need)
+{
+    if (*have >= need) return AKZ_OK;
+    AKZ_HIP(hipStreamSynchronize(stream));                       // an earlier call may still use the smaller one
+    if (*d) AKZ_HIP(hipFree(*d));
+    *d = nullptr;
+    *have = 0;
+    AKZ_HIP(hipMalloc(d, need));
+    *have = need;
+    return AKZ_OK;
+}
+// The triangulator's parameters, alone (rs_triangulate) or nested in another stage's: checked (AKZ_E_INVALID) and copied.
+// incidence_minimum_cosine_distance is copied as it is: the stages that read it refuse a non-finite one themselves.
+inline int32_t akz_tri_settings_from(const rs_triangulate_params& t, akz_tri_settings* st)
+{
+    if (t.struct_size != sizeof(rs_triangulate_params) || t.max_sweeps == 0 || t.max_sweeps > 0x7FFFFFFFu) return AKZ_E_INVALID;
+    if (!(t.eps >= 0.0) || !AKZ_TRI_FINITE(t.eps)) return AKZ_E_INVALID;
+    st->eps = t.eps;
+    // A 4 x 4 cyclic Jacobi iteration converges in fewer than 20 sweeps; "no limit" is not something to hand to a GPU that
+    // others share: more than RS_TRI_MAX_SWEEPS sweeps are not run, a list that needed more ends with reason 3.
+    st->max_sweeps = (int)(t.max_sweeps < (uint32_t)RS_TRI_MAX_SWEEPS ? t.max_sweeps : (uint32_t)RS_TRI_MAX_SWEEPS);
+    st->robust_minimum_observations = t.robust_minimum_observations;
+    st->n_views = t.n_views;
+    st->incidence_minimum_cosine_distance = t.incidence_minimum_cosine_distance;
+    return AKZ_OK;
+}
+
 static inline int akz_div_up(int a, int b) { return (a + b - 1) / b; }
 static inline size_t akz_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
@@ -254,8 +283,7 @@ __device__ __forceinline__ uint32_t* lds_radix_sort_ids(const uint32_t* rk, uint
 #if defined(__HIPCC__)
 // Sums over the 64 lanes of a wave by the xor butterfly m = 32, 16, ..., 1; every lane ends with the same bits.  For doubles
 // the order of the additions is part of the bit-for-bit contract with the host builds: part[k] = part[k] + (lane ^ m)'s
-// part[k], k ascending inside m — what akz_tv_sum_tree (include/akz_three_view_math.h), akz_tvc_sum_wave
-// (include/akz_three_view_constraint_math.h) and akz_pg_sum_wave (include/akz_pose_graph_math.h) state for the host.
+// part[k], k ascending inside m — step 2 of include/akz_sum_order.h, akz_sum_wave there.
 __device__ __forceinline__ uint32_t akz_wave_sum(uint32_t v)
 {
 #pragma unroll
@@ -269,6 +297,67 @@ __device__ __forceinline__ void akz_wave_sum(double (&part)[N])
     for (int m = 32; m >= 1; m >>= 1) {
 #pragma unroll
         for (int k = 0; k < N; ++k) part[k] = part[k] + __shfl_xor(part[k], m, 64);
+    }
+}
+// One step of an ordered compaction / a block-wide count over a block of W waves: this thread's place among the set flags of
+// the block (list order = thread order), *total = how many are set.  One barrier; `tick` alternates the two count buffers so
+// that a step may begin while a slower wave still reads the previous one.
+template <int W>
+__device__ __forceinline__ uint32_t akz_block_scan(uint32_t (&cnt)[2][W], uint32_t& tick, bool flag, uint32_t* total)
+{
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, buf = tick & 1u;
+    ++tick;
+    const unsigned long long m = __ballot(flag);
+    if (lane == 0) cnt[buf][w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const uint32_t c = cnt[buf][k];
+        before += (uint32_t)k < w ? c : 0u;
+        all += c;
+    }
+    *total = all;
+    return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+// the sum of one u32 per thread over a block of W waves (integers: exact in any order); buffers and barrier as akz_block_scan
+template <int W>
+__device__ __forceinline__ uint32_t akz_block_sum(uint32_t (&cnt)[2][W], uint32_t& tick, uint32_t v)
+{
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, buf = tick & 1u;
+    ++tick;
+    v = akz_wave_sum(v);
+    if (lane == 0) cnt[buf][w] = v;
+    __syncthreads();
+    uint32_t all = 0;
+#pragma unroll
+    for (int k = 0; k < W; ++k) all += cnt[buf][k];
+    return all;
+}
+// The sum of N doubles per thread over a block of W waves, steps 2 and 3 of include/akz_sum_order.h (akz_sum_block there): the
+// wave butterfly, lane 0 of each wave leaves its N sums in red[parity & 1], ONE barrier, and every thread folds the waves from
+// the left in wave order — same bits in every thread, so nothing is broadcast.  `part` is used up.  A caller in a loop hands
+// its iteration count as `parity`: the two buffers alternate, so that an iteration may begin while a slower wave still reads
+// the previous one, and there is no second barrier.  (The buffer is chosen in here and not by the caller: handed
+// red[parity & 1] as a reference the compiler forms one scalar address for the stores and the loads, learns that the sums are
+// uniform, moves the optimiser step behind them to scalar branches, and k_three_view's iteration is 1.8 % slower —
+// docs/EXPERIMENTS.md #66.)
+template <int W, int N>
+__device__ __forceinline__ void akz_block_sum(double (&red)[2][W][N], uint32_t parity, double (&part)[N], double (&net)[N])
+{
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    akz_wave_sum(part);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) red[parity & 1u][w][k] = part[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        double s = red[parity & 1u][0][k];
+#pragma unroll
+        for (int v = 1; v < W; ++v) s = s + red[parity & 1u][v][k];
+        net[k] = s;
     }
 }
 // Ascending bitonic sort of np2 (a power of two) 64-bit keys in LDS by one block of NT threads (NT a multiple of

@@ -310,18 +310,13 @@ int32_t of_settings(const rs_observation_filter_params* prm, akz_of_settings* st
     if (!prm || prm->struct_size != sizeof(rs_observation_filter_params) || prm->reserved != 0) return AKZ_E_INVALID;
     if (prm->maximum_cosine_distance != prm->maximum_cosine_distance || prm->maximum_sine_distance != prm->maximum_sine_distance)
         return AKZ_E_INVALID;
-    const rs_triangulate_params& t = prm->triangulate;
-    if (t.struct_size != sizeof(rs_triangulate_params) || t.max_sweeps == 0 || t.max_sweeps > 0x7FFFFFFFu) return AKZ_E_INVALID;
-    if (!(t.eps >= 0.0) || !AKZ_TRI_FINITE(t.eps) || !AKZ_TRI_FINITE(t.incidence_minimum_cosine_distance)) return AKZ_E_INVALID;
+    AKZ_TRY(akz_tri_settings_from(prm->triangulate, &st->tri));
+    if (!AKZ_TRI_FINITE(prm->triangulate.incidence_minimum_cosine_distance)) return AKZ_E_INVALID;
     if (prm->reconstruction_optimization_iterations > (uint32_t)RS_OF_MAX_ITERATIONS) return AKZ_E_TOO_LARGE;
     st->maximum_cosine_distance = prm->maximum_cosine_distance;
     st->maximum_sine_distance = prm->maximum_sine_distance;
     st->minimum_robust_landmarks = prm->minimum_robust_landmarks;
-    st->tri.eps = t.eps;
-    st->tri.max_sweeps = (int)(t.max_sweeps < (uint32_t)RS_TRI_MAX_SWEEPS ? t.max_sweeps : (uint32_t)RS_TRI_MAX_SWEEPS);   // as rs_triangulate.hip
-    st->tri.robust_minimum_observations = t.robust_minimum_observations;
     st->tri.n_views = 0u;                                          // every reconstruction's own, in k_of_decide
-    st->tri.incidence_minimum_cosine_distance = t.incidence_minimum_cosine_distance;
     return AKZ_OK;
 }
 
@@ -329,18 +324,6 @@ bool of_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
 {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-int32_t of_grow(hipStream_t stream, void** d, size_t* have, size_t need)
-{
-    if (*have >= need) return AKZ_OK;
-    AKZ_HIP(hipStreamSynchronize(stream));                       // an earlier call may still use the smaller one
-    if (*d) AKZ_HIP(hipFree(*d));
-    *d = nullptr;
-    *have = 0;
-    AKZ_HIP(hipMalloc(d, need));
-    *have = need;
-    return AKZ_OK;
 }
 
 // the tables of one pass and where it writes
@@ -377,7 +360,7 @@ int32_t of_enqueue(rs_ctx* c, const RsHandles& h, const OfArgs& g, const rs_came
     const size_t recon_bytes = akz_align_up(sizeof(uint32_t) * ((size_t)g.n_recons + 1), 256);
     const size_t pos_bytes = akz_align_up(sizeof(uint32_t) * ((size_t)g.n_obs + 1), 256);
     const size_t tile_bytes = akz_align_up(sizeof(uint32_t) * ((size_t)n_tiles + 1), 256);
-    AKZ_TRY(of_grow(h.stream, &fs->d_scratch, &fs->bytes, lm_bytes + recon_bytes + pos_bytes + tile_bytes));
+    AKZ_TRY(akz_grow_scratch(h.stream, &fs->d_scratch, &fs->bytes, lm_bytes + recon_bytes + pos_bytes + tile_bytes));
     char* base = (char*)fs->d_scratch;
     OfCall a;
     a.kps = (const akz_keypoint*)g.d_kps; a.poses = (const double*)g.d_poses;
@@ -480,7 +463,7 @@ extern "C" int32_t rs_optimize_reconstruction_batch_device(
         const size_t start_bytes = akz_align_up(sizeof(uint32_t) * ((size_t)n_landmarks + 1), 256);
         const size_t obs_bytes = akz_align_up(sizeof(uint32_t) * 2 * ((size_t)n_obs + 1), 256);
         const size_t n_tables = rounds <= 1 ? 0 : rounds == 2 ? 1 : 2;
-        AKZ_TRY(of_grow(h.stream, &fs->d_chain, &fs->chain_bytes, stop_bytes + n_tables * (start_bytes + obs_bytes)));
+        AKZ_TRY(akz_grow_scratch(h.stream, &fs->d_chain, &fs->chain_bytes, stop_bytes + n_tables * (start_bytes + obs_bytes)));
         char* base = (char*)fs->d_chain;
         uint32_t* d_stop = (uint32_t*)base;
         void* tab_start[2] = {base + stop_bytes, base + stop_bytes + start_bytes + obs_bytes};

@@ -336,15 +336,7 @@ int32_t rs_internal_pose_graph_relax(rs_ctx* c, void* d_poses, uint32_t n_views,
         const size_t table_bytes = akz_align_up(sizeof(double) * 12 * (size_t)n_views, 256);
         const size_t view_bytes = akz_align_up(sizeof(uint32_t) * (size_t)n_views, 256);
         const size_t graph_bytes = akz_align_up(sizeof(uint32_t) * (size_t)n_graphs, 256);
-        const size_t need = table_bytes + view_bytes + 2 * graph_bytes + 256;
-        if (pg->bytes < need) {
-            AKZ_HIP(hipStreamSynchronize(h.stream));                       // an earlier call may still use the smaller one
-            if (pg->d_scratch) AKZ_HIP(hipFree(pg->d_scratch));
-            pg->d_scratch = nullptr;
-            pg->bytes = 0;
-            AKZ_HIP(hipMalloc(&pg->d_scratch, need));
-            pg->bytes = need;
-        }
+        AKZ_TRY(akz_grow_scratch(h.stream, &pg->d_scratch, &pg->bytes, table_bytes + view_bytes + 2 * graph_bytes + 256));
         char* base = (char*)pg->d_scratch;
         PgCall a;
         a.poses = (double*)d_poses;

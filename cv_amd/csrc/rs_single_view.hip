@@ -63,39 +63,6 @@ struct SvCall {
     uint32_t cap, n_blocks, n_obs, n_landmarks, n_world, n_rows;
 };
 
-// One step of an ordered compaction / a block-wide count (tv_scan of rs_three_view.hip): this thread's place among the set
-// flags of the 256 (list order = thread order), *total = how many are set.  One barrier; `tick` alternates the count buffers.
-__device__ __forceinline__ uint32_t sv_scan(SvShared& sh, uint32_t& tick, bool flag, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & (AKZ_SV_WAVE - 1), w = threadIdx.x / AKZ_SV_WAVE, buf = tick & 1u;
-    ++tick;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) sh.cnt[buf][w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < kSvWaves; ++k) {
-        const uint32_t c = sh.cnt[buf][k];
-        before += (uint32_t)k < w ? c : 0u;
-        all += c;
-    }
-    *total = all;
-    return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-// the sum of one u32 per thread over the block (integers: exact in any order)
-__device__ __forceinline__ uint32_t sv_block_sum(SvShared& sh, uint32_t& tick, uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & (AKZ_SV_WAVE - 1), w = threadIdx.x / AKZ_SV_WAVE, buf = tick & 1u;
-    ++tick;
-    v = akz_wave_sum(v);
-    if (lane == 0) sh.cnt[buf][w] = v;
-    __syncthreads();
-    uint32_t all = 0;
-#pragma unroll
-    for (int k = 0; k < kSvWaves; ++k) all += sh.cnt[buf][k];
-    return all;
-}
-
 // An original match: its feature, its world row and the observation ranges of its one or two landmarks.
 struct SvMatch {
     uint32_t feat, row, s0, n0, s1, n1;
@@ -207,7 +174,7 @@ __device__ uint32_t sv_take(SvShared& sh, uint32_t& tick, const SvCall& a, const
             }
         }
         uint32_t total;
-        const uint32_t slot = m + sv_scan(sh, tick, ok, &total);
+        const uint32_t slot = m + akz_block_scan(sh.cnt, tick, ok, &total);
         if (ok && slot < limit) sv_put(sh, slot, b, w);
         m += total;
     }
@@ -218,7 +185,6 @@ __device__ uint32_t sv_take(SvShared& sh, uint32_t& tick, const SvCall& a, const
 // single_view_simple_optimize_l2 (single_view_optimizer.rs:80-135) on the n matches of sh.lm; pose [12] in and out.
 __device__ uint32_t sv_optimize(SvShared& sh, double* pose, double rate, uint32_t iterations, uint32_t n)
 {
-    const uint32_t lane = threadIdx.x & (AKZ_SV_WAVE - 1), w = threadIdx.x / AKZ_SV_WAVE;
     akz_sv_opt_state os;
     uint32_t it = 0;
     if (n == 0) return 0;
@@ -240,15 +206,8 @@ __device__ uint32_t sv_optimize(SvShared& sh, double* pose, double rate, uint32_
                 for (int k = 0; k < 6; ++k) part[k] = part[k] + g[k];
             }
         }
-        akz_wave_sum(part);
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) sh.red[it & 1u][w][k] = part[k];
-        }
-        __syncthreads();
         double net[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) net[k] = ((sh.red[it & 1u][0][k] + sh.red[it & 1u][1][k]) + sh.red[it & 1u][2][k]) + sh.red[it & 1u][3][k];
+        akz_block_sum(sh.red, it, part, net);
         if (akz_sv_opt_step(&os, net, inv_landmark_len, rate, pose, it, iterations)) break;
     }
     return it;
@@ -290,7 +249,7 @@ __global__ __launch_bounds__(kSvBlock) void k_single_view(SvCall a, rs_camera ca
         return;
     }
     sc.kn = a.kps + (size_t)bn * a.cap;
-    const uint32_t no_other = sv_block_sum(sh, tick, mine);
+    const uint32_t no_other = akz_block_sum(sh.cnt, tick, mine);
 
     // ---- the list the consensus saw: the matches with a world point, in order ----
     uint32_t* place = a.place + (size_t)s * a.cap;
@@ -299,7 +258,7 @@ __global__ __launch_bounds__(kSvBlock) void k_single_view(SvCall a, rs_camera ca
         const uint32_t i = base + tid;
         const bool some = i < sc.n && akz_sv_some(a.world + 4 * (size_t)sc.m[2 * (size_t)i + 1]);
         uint32_t total;
-        const uint32_t slot = n_rob + sv_scan(sh, tick, some, &total);
+        const uint32_t slot = n_rob + akz_block_scan(sh.cnt, tick, some, &total);
         if (some) place[slot] = i;
         n_rob += total;
     }
@@ -374,8 +333,8 @@ __global__ __launch_bounds__(kSvBlock) void k_single_view(SvCall a, rs_camera ca
         n_final += ok ? 1u : 0u;
         robust += ok && akz_sv_some(a.world + 4 * (size_t)mt.row) ? 1u : 0u;
     }
-    robust = sv_block_sum(sh, tick, robust);
-    n_final = sv_block_sum(sh, tick, n_final);
+    robust = akz_block_sum(sh.cnt, tick, robust);
+    n_final = akz_block_sum(sh.cnt, tick, n_final);
     if (tid == 0) {
         unsigned stage;
         const int v = akz_sv_final_verdict(robust, n_final, robust_minimum_matches, st.single_view_minimum_robust_landmarks, &stage);
@@ -393,9 +352,8 @@ __global__ __launch_bounds__(kSvBlock) void k_single_view(SvCall a, rs_camera ca
 int32_t sv_settings(const rs_single_view_params* prm, akz_sv_settings* st)
 {
     if (!prm || prm->struct_size != sizeof(rs_single_view_params)) return AKZ_E_INVALID;
-    const rs_triangulate_params& t = prm->triangulate;
-    if (t.struct_size != sizeof(rs_triangulate_params) || t.max_sweeps == 0 || t.max_sweeps > 0x7FFFFFFFu) return AKZ_E_INVALID;
-    if (!(t.eps >= 0.0) || !AKZ_TRI_FINITE(t.eps)) return AKZ_E_INVALID;
+    // (robust_minimum_observations is copied and not read: the consistency test has no robustness test)
+    AKZ_TRY(akz_tri_settings_from(prm->triangulate, &st->tri));
     if (prm->maximum_cosine_distance != prm->maximum_cosine_distance || prm->maximum_sine_distance != prm->maximum_sine_distance ||
         !AKZ_TRI_FINITE(prm->single_view_optimization_rate))
         return AKZ_E_INVALID;
@@ -410,11 +368,6 @@ int32_t sv_settings(const rs_single_view_params* prm, akz_sv_settings* st)
     st->single_view_patience = prm->single_view_patience < (uint32_t)RS_SV_MAX_ITERATIONS ? prm->single_view_patience : (uint32_t)RS_SV_MAX_ITERATIONS;
     st->single_view_minimum_landmarks = prm->single_view_minimum_landmarks;
     st->single_view_minimum_robust_landmarks = prm->single_view_minimum_robust_landmarks;
-    st->tri.eps = t.eps;
-    st->tri.max_sweeps = (int)(t.max_sweeps < (uint32_t)RS_TRI_MAX_SWEEPS ? t.max_sweeps : (uint32_t)RS_TRI_MAX_SWEEPS);
-    st->tri.robust_minimum_observations = t.robust_minimum_observations;   // not read: the consistency test has no robustness test
-    st->tri.n_views = t.n_views;
-    st->tri.incidence_minimum_cosine_distance = t.incidence_minimum_cosine_distance;
     return AKZ_OK;
 }
 
@@ -458,15 +411,7 @@ extern "C" int32_t rs_refine_poses_batch_device(rs_ctx* c, const void* d_kps, ui
         if (n_scenes > h.max_scenes) return AKZ_E_TOO_LARGE;
         AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         RsSingleViewState* sv = rs_internal_single_view(c);
-        const size_t need = sizeof(uint32_t) * (size_t)n_scenes * cap_per_img;
-        if (sv->bytes < need) {
-            AKZ_HIP(hipStreamSynchronize(h.stream));              // an earlier call may still use the smaller one
-            if (sv->d_scratch) AKZ_HIP(hipFree(sv->d_scratch));
-            sv->d_scratch = nullptr;
-            sv->bytes = 0;
-            AKZ_HIP(hipMalloc(&sv->d_scratch, need));
-            sv->bytes = need;
-        }
+        AKZ_TRY(akz_grow_scratch(h.stream, &sv->d_scratch, &sv->bytes, sizeof(uint32_t) * (size_t)n_scenes * cap_per_img));
         // the frame list goes where the consensus keeps its own: stream order puts the copy behind that call's last reader
         AKZ_HIP(hipMemcpyAsync(h.d_frames, ik, sizeof(uint32_t) * n_scenes, hipMemcpyHostToDevice, h.stream));
         SvCall a;

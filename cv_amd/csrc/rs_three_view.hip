@@ -37,41 +37,6 @@ struct TvShared {
     double median;
 };
 
-// One step of an ordered compaction / a block-wide count: this thread's place among the set flags of the 256 (list order =
-// thread order), *total = how many are set.  One barrier; `tick` alternates the two count buffers so that a step may begin
-// while a slower wave still reads the previous one.
-__device__ __forceinline__ uint32_t tv_scan(TvShared& sh, uint32_t& tick, bool flag, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & (AKZ_TV_WAVE - 1), w = threadIdx.x / AKZ_TV_WAVE, buf = tick & 1u;
-    ++tick;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) sh.cnt[buf][w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < kTvWaves; ++k) {
-        const uint32_t c = sh.cnt[buf][k];
-        before += (uint32_t)k < w ? c : 0u;
-        all += c;
-    }
-    *total = all;
-    return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-
-// the sum of one u32 per thread over the block (integers: exact in any order)
-__device__ __forceinline__ uint32_t tv_block_sum(TvShared& sh, uint32_t& tick, uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & (AKZ_TV_WAVE - 1), w = threadIdx.x / AKZ_TV_WAVE, buf = tick & 1u;
-    ++tick;
-    v = akz_wave_sum(v);
-    if (lane == 0) sh.cnt[buf][w] = v;
-    __syncthreads();
-    uint32_t all = 0;
-#pragma unroll
-    for (int k = 0; k < kTvWaves; ++k) all += sh.cnt[buf][k];
-    return all;
-}
-
 struct TvScene {
     const akz_keypoint *kc, *kf, *ks;   // the three keypoint blocks
     const uint32_t *triples, *first_only, *second_only;
@@ -104,7 +69,7 @@ __device__ uint32_t tv_take(TvShared& sh, uint32_t& tick, const TvScene& sc, con
             ok = akz_tv_tri_landmark_robust(poses, poses + 12, c, f, s, max_cos, st.robust_observation_incidence_minimum_cosine_distance, &st.tri);
         }
         uint32_t total;
-        const uint32_t slot = m + tv_scan(sh, tick, ok, &total);
+        const uint32_t slot = m + akz_block_scan(sh.cnt, tick, ok, &total);
         if (ok && slot < limit) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -122,7 +87,6 @@ __device__ uint32_t tv_take(TvShared& sh, uint32_t& tick, const TvScene& sc, con
 // three_view_simple_optimize_l2 (three_view_optimizer.rs:126-200) on the n landmarks of sh.lm; poses [2][12] in and out.
 __device__ uint32_t tv_optimize(TvShared& sh, double* poses, double rate, uint32_t iterations, uint32_t n)
 {
-    const uint32_t lane = threadIdx.x & (AKZ_TV_WAVE - 1), w = threadIdx.x / AKZ_TV_WAVE;
     double inv[24];
     akz_tv_opt_state os;
     uint32_t it = 0;
@@ -147,15 +111,8 @@ __device__ uint32_t tv_optimize(TvShared& sh, double* poses, double rate, uint32
 #pragma unroll
             for (int k = 0; k < 12; ++k) part[k] = part[k] + g[k];
         }
-        akz_wave_sum(part);
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) sh.red[it & 1u][w][k] = part[k];
-        }
-        __syncthreads();
         double nets[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) nets[k] = ((sh.red[it & 1u][0][k] + sh.red[it & 1u][1][k]) + sh.red[it & 1u][2][k]) + sh.red[it & 1u][3][k];
+        akz_block_sum(sh.red, it, part, nets);
         if (akz_tv_opt_step(&os, nets, scale, inv, it, iterations)) break;
     }
     akz_tv_pose_inverse(inv, poses);
@@ -223,7 +180,7 @@ __global__ __launch_bounds__(kTvBlock) void k_three_view(const akz_keypoint* __r
             ok = akz_tv_relative_scale(poses, poses + 12, c, f, b, &st, &ratio);
         }
         uint32_t total;
-        const uint32_t slot = n_scales + tv_scan(sh, tick, ok, &total);
+        const uint32_t slot = n_scales + akz_block_scan(sh.cnt, tick, ok, &total);
         if (ok) keys[slot] = akz_tri_float_ord(ratio);
         n_scales += total;
     }
@@ -263,7 +220,7 @@ __global__ __launch_bounds__(kTvBlock) void k_three_view(const akz_keypoint* __r
             mine += akz_tv_bearing_pair_robust(a, a + 3, a + 6, b, b + 3, b + 6, st.robust_view_bearing_pair_minimum_cosine_distance) ? 1u : 0u;
         }
     }
-    const uint32_t pairs = tv_block_sum(sh, tick, mine);
+    const uint32_t pairs = akz_block_sum(sh.cnt, tick, mine);
     if (tid == 0) {
         stats[AKZ_TV_S_PAIRS] = pairs;
         stats[AKZ_TV_S_STAGE] = AKZ_TV_STAGE_PAIRS;
@@ -301,7 +258,7 @@ __global__ __launch_bounds__(kTvBlock) void k_three_view(const akz_keypoint* __r
                                             st.robust_observation_incidence_minimum_cosine_distance, &st.tri);
         }
         uint32_t total;
-        tv_scan(sh, tick, ok, &total);
+        akz_block_scan(sh.cnt, tick, ok, &total);
         robust += total;
     }
     if (tid == 0) {
@@ -339,9 +296,7 @@ __global__ __launch_bounds__(kTvBlock) void k_three_view(const akz_keypoint* __r
 int32_t tv_settings(const rs_three_view_params* prm, akz_tv_settings* st)
 {
     if (!prm || prm->struct_size != sizeof(rs_three_view_params)) return AKZ_E_INVALID;
-    const rs_triangulate_params& t = prm->triangulate;
-    if (t.struct_size != sizeof(rs_triangulate_params) || t.max_sweeps == 0 || t.max_sweeps > 0x7FFFFFFFu) return AKZ_E_INVALID;
-    if (!(t.eps >= 0.0) || !AKZ_TRI_FINITE(t.eps)) return AKZ_E_INVALID;
+    AKZ_TRY(akz_tri_settings_from(prm->triangulate, &st->tri));
     const double d[5] = {prm->maximum_cosine_distance, prm->maximum_sine_distance, prm->robust_observation_incidence_minimum_cosine_distance,
                          prm->robust_view_bearing_pair_minimum_cosine_distance, prm->optimization_rate};
     for (double x : d)
@@ -361,11 +316,6 @@ int32_t tv_settings(const rs_three_view_params* prm, akz_tv_settings* st)
     st->three_view_patience = prm->three_view_patience < (uint32_t)RS_TV_MAX_ITERATIONS ? prm->three_view_patience : (uint32_t)RS_TV_MAX_ITERATIONS;
     st->three_view_minimum_robust_matches = prm->three_view_minimum_robust_matches;
     st->hard_minimum_matches = prm->hard_minimum_matches;
-    st->tri.eps = t.eps;
-    st->tri.max_sweeps = (int)(t.max_sweeps < (uint32_t)RS_TRI_MAX_SWEEPS ? t.max_sweeps : (uint32_t)RS_TRI_MAX_SWEEPS);
-    st->tri.robust_minimum_observations = t.robust_minimum_observations;
-    st->tri.n_views = t.n_views;
-    st->tri.incidence_minimum_cosine_distance = t.incidence_minimum_cosine_distance;
     return AKZ_OK;
 }
 

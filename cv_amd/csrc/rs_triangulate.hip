@@ -188,17 +188,9 @@ __global__ void k_tri_observations(const double* __restrict__ poses, const doubl
 
 int32_t tri_settings(const rs_triangulate_params* prm, akz_tri_settings* st)
 {
-    if (!prm || prm->struct_size != sizeof(rs_triangulate_params)) return AKZ_E_INVALID;
-    if (prm->max_sweeps == 0 || prm->max_sweeps > 0x7FFFFFFFu) return AKZ_E_INVALID;
-    if (!(prm->eps >= 0.0) || !AKZ_TRI_FINITE(prm->eps) || !AKZ_TRI_FINITE(prm->incidence_minimum_cosine_distance)) return AKZ_E_INVALID;
-    st->eps = prm->eps;
-    // A 4 x 4 cyclic Jacobi iteration converges in fewer than 20 sweeps; "no limit" is not something to hand to a GPU that
-    // others share: more than RS_TRI_MAX_SWEEPS sweeps are not run, a list that needed more ends with reason 3.
-    st->max_sweeps = (int)(prm->max_sweeps < (uint32_t)RS_TRI_MAX_SWEEPS ? prm->max_sweeps : (uint32_t)RS_TRI_MAX_SWEEPS);
-    st->robust_minimum_observations = prm->robust_minimum_observations;
-    st->n_views = prm->n_views;
-    st->incidence_minimum_cosine_distance = prm->incidence_minimum_cosine_distance;
-    return AKZ_OK;
+    if (!prm) return AKZ_E_INVALID;
+    AKZ_TRY(akz_tri_settings_from(*prm, st));
+    return AKZ_TRI_FINITE(prm->incidence_minimum_cosine_distance) ? AKZ_OK : AKZ_E_INVALID;
 }
 
 }   // namespace

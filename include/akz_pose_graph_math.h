@@ -28,13 +28,9 @@
  *   - the product of isometries: akz_tvc_pose_mul, as it is; the inverse: akz_tv_pose_inverse;
  *   - the order of a view's edges: the reference walks the values of a HashMap and defines none; ours is the caller's row
  *     order;
- *   - THE ORDER OF THE SUM OVER A VIEW'S EDGES.  The reference folds the edges' se3 one after another from zero; a wavefront
- *     cannot.  One order, on both sides, for one wave of AKZ_PG_WAVE = 64 lanes per view and the 6 components q:
- *       1. lane l holds ((0 + q[l]) + q[l + 64]) + q[l + 128] ..., walking its row ascending; an absent edge and an edge of
- *          a refused constraint contribute +0.0;
- *       2. the butterfly v[l] = v[l] + v[l ^ m] for m = 32, 16, 8, 4, 2, 1.
- *     akz_pg_sum_wave executes that order on the host; akz_pg_sum_sequential is the reference's order, kept for the test
- *     that documents what the choice costs.
+ *   - THE ORDER OF THE SUM OVER A VIEW'S EDGES: akz_sum_order.h, one wave's per view; lane l's partial is the 6 se3 components
+ *     of entries l, l + 64, ... of the view's row, an edge of a refused constraint adding nothing.  akz_pg_sum_wave executes
+ *     it on the host; akz_pg_sum_sequential is the reference's order, kept for the test that documents what the choice costs.
  *   - the sign and payload of a NaN: every NaN written is the quiet NaN of akz_tvc_canonical.
  *
  * Findings: a rotation below about 1.5e-8 rad (acos(1 - 2^-53), the smallest angle acos can return; a cosine
@@ -48,7 +44,7 @@
 
 #include "akz_three_view_constraint_math.h"
 
-enum { AKZ_PG_WAVE = 64, AKZ_PG_RESIDENT_VIEWS = 256, AKZ_PG_MAX_ITERATIONS = 1 << 20 };
+enum { AKZ_PG_WAVE = AKZ_SUM_WAVE, AKZ_PG_RESIDENT_VIEWS = 256, AKZ_PG_MAX_ITERATIONS = 1 << 20 };
 
 /* a graph's verdict (RS_PG_* of include/akz.h) */
 enum {
@@ -208,15 +204,7 @@ AKZ_PG_HOST_FN void akz_pg_sum_wave(const double* cur, unsigned v, const unsigne
             for (int k = 0; k < 6; ++k) part[l][k] = part[l][k] + q[k];
         }
     }
-    for (int k = 0; k < 6; ++k) {
-        double tmp[AKZ_PG_WAVE], nxt[AKZ_PG_WAVE];
-        for (int l = 0; l < AKZ_PG_WAVE; ++l) tmp[l] = part[l][k];
-        for (int m = AKZ_PG_WAVE / 2; m >= 1; m >>= 1) {
-            for (int l = 0; l < AKZ_PG_WAVE; ++l) nxt[l] = tmp[l] + tmp[l ^ m];
-            for (int l = 0; l < AKZ_PG_WAVE; ++l) tmp[l] = nxt[l];
-        }
-        sum6[k] = tmp[0];
-    }
+    for (int k = 0; k < 6; ++k) sum6[k] = akz_sum_wave(&part[0][k], 6);
 }
 AKZ_PG_HOST_FN void akz_pg_sum_sequential(const double* cur, unsigned v, const unsigned* row, unsigned n, const unsigned* views,
                                           const unsigned* cverdict, const double* edges, double* sum6)

@@ -18,14 +18,9 @@
  *   register_frame_subset behind its consensus          cv-sfm/src/lib.rs:1625-1775
  *
  * Unpinned against the reference:
- *   - THE ORDER OF THE SUM OVER MATCHES.  The reference adds the matches' gradients one after another; a workgroup cannot.
- *     One order, on both sides, the one akz_three_view_math.h fixes (AKZ_SV_THREADS = 256 partial sums, waves of 64):
- *       1. partial sum t, t < 256, = ((0 + g[t]) + g[t + 256]) + g[t + 512] ..., matches ascending; a match whose
- *          landmark_delta is None adds nothing;
- *       2. inside a wave the butterfly v[l] = v[l] + v[l ^ m] for m = 32, 16, 8, 4, 2, 1;
- *       3. the four waves' sums added in wave order, ((w0 + w1) + w2) + w3.
- *     akz_sv_sum_tree executes that tree on the host; akz_sv_sum_sequential is the reference's order, kept for the test
- *     that documents what the choice costs;
+ *   - THE ORDER OF THE SUM OVER MATCHES: akz_sum_order.h, a workgroup's; thread t's partial is the 6 gradient components of
+ *     matches t, t + 256, ..., a match whose landmark_delta is None adding nothing.  akz_sv_sum_tree executes it on the host;
+ *     akz_sv_sum_sequential is the reference's order, kept for the test that documents what the choice costs;
  *   - Rotation3::from_scaled_axis (akz_tv_from_scaled_axis: Rodrigues with the sine and cosine of akz_portable_math.h);
  *   - the eigen-solver and the product orders of akz_triangulate_math.h's own list;
  *   - the order of a landmark's observations: the reference walks a HashMap; here it is the order of the caller's list.  A
@@ -46,7 +41,7 @@
 
 #include "akz_three_view_constraint_math.h"
 
-enum { AKZ_SV_THREADS = 256, AKZ_SV_WAVE = 64, AKZ_SV_MAX_MATCHES = 2048, AKZ_SV_MAX_RUNS = 9, AKZ_SV_NO_IMPROVE = 50 };
+enum { AKZ_SV_THREADS = AKZ_SUM_THREADS, AKZ_SV_WAVE = AKZ_SUM_WAVE, AKZ_SV_MAX_MATCHES = 2048, AKZ_SV_MAX_RUNS = 9, AKZ_SV_NO_IMPROVE = 50 };
 
 /* verdicts (RS_SV_* of include/akz.h) */
 enum {
@@ -213,7 +208,6 @@ AKZ_RM_FN int akz_sv_final_verdict(unsigned robust, unsigned n_final, unsigned r
 AKZ_SV_HOST_FN void akz_sv_sum_tree(const double* pose, const double* lm, unsigned n, double* net)
 {
     double part[AKZ_SV_THREADS][6];
-    double wave[AKZ_SV_THREADS / AKZ_SV_WAVE][6], tmp[AKZ_SV_WAVE];
     for (unsigned t = 0; t < (unsigned)AKZ_SV_THREADS; ++t) {
         for (int k = 0; k < 6; ++k) part[t][k] = 0.0;
         for (unsigned i = t; i < n; i += (unsigned)AKZ_SV_THREADS) {
@@ -226,17 +220,7 @@ AKZ_SV_HOST_FN void akz_sv_sum_tree(const double* pose, const double* lm, unsign
             for (int k = 0; k < 6; ++k) part[t][k] = part[t][k] + g[k];
         }
     }
-    for (int w = 0; w < AKZ_SV_THREADS / AKZ_SV_WAVE; ++w)
-        for (int k = 0; k < 6; ++k) {
-            for (int l = 0; l < AKZ_SV_WAVE; ++l) tmp[l] = part[w * AKZ_SV_WAVE + l][k];
-            for (int m = AKZ_SV_WAVE / 2; m >= 1; m >>= 1) {
-                double nxt[AKZ_SV_WAVE];
-                for (int l = 0; l < AKZ_SV_WAVE; ++l) nxt[l] = tmp[l] + tmp[l ^ m];
-                for (int l = 0; l < AKZ_SV_WAVE; ++l) tmp[l] = nxt[l];
-            }
-            wave[w][k] = tmp[0];
-        }
-    for (int k = 0; k < 6; ++k) net[k] = ((wave[0][k] + wave[1][k]) + wave[2][k]) + wave[3][k];
+    akz_sum_block(&part[0][0], 6, net);
 }
 AKZ_SV_HOST_FN void akz_sv_sum_sequential(const double* pose, const double* lm, unsigned n, double* net)
 {

@@ -18,15 +18,10 @@
  *   - the sign and payload of a NaN (a pose table with a NaN in it): every NaN written is the quiet NaN of akz_tvc_canonical;
  *   - landmarks.shuffle (the caller's RNG) and sort_unstable_by_key (Rust's order among equal keys): both stay with the
  *     caller, who hands over the list in the order the reference would walk it in;
- *   - THE ORDER OF THE SUM OVER LANDMARKS.  The reference adds the landmarks' gradients and the four norms one after
- *     another; a wavefront cannot.  One order, on both sides, for one wave of AKZ_TVC_WAVE = 64 lanes and all 16 quantities
- *     q (12 gradient components, then the norms of the first translation, first rotation, second translation, second
- *     rotation):
- *       1. lane l holds ((0 + q[l]) + q[l + 64]) + q[l + 128] ..., its landmarks ascending; a lane without a landmark +0.0;
- *       2. the butterfly v[l] = v[l] + v[l ^ m] for m = 32, 16, 8, 4, 2, 1 (IEEE addition commutes, so all 64 lanes end with
- *          the same bits).
- *     There is no step across waves.  akz_tvc_sum_wave below executes that order on the host; akz_tvc_sum_sequential is the
- *     reference's order, kept for the test that documents what the choice costs.
+ *   - THE ORDER OF THE SUM OVER LANDMARKS: akz_sum_order.h, one wave's; lane l's partial is the 16 quantities (12 gradient
+ *     components, then the norms of the first translation, first rotation, second translation, second rotation) of landmarks
+ *     l, l + 64, ...  akz_tvc_sum_wave below executes it on the host; akz_tvc_sum_sequential is the reference's order, kept
+ *     for the test that documents what the choice costs.
  *
  * The finding of akz_three_view_math.h holds here as well: on a well-posed scene every translation gradient is exactly
  * zero, so the translation's rate is 0 / 0, which the reference's is_finite test turns into 0.  The text is shipped as it is.
@@ -36,7 +31,7 @@
 
 #include "akz_three_view_math.h"
 
-enum { AKZ_TVC_WAVE = 64, AKZ_TVC_MAX_LANDMARKS = 256, AKZ_TVC_MAX_ITERATIONS = 1 << 20 };
+enum { AKZ_TVC_WAVE = AKZ_SUM_WAVE, AKZ_TVC_MAX_LANDMARKS = 256, AKZ_TVC_MAX_ITERATIONS = 1 << 20 };
 
 /* verdicts (RS_TVC_* of include/akz.h) */
 enum {
@@ -155,15 +150,7 @@ AKZ_TVC_HOST_FN void akz_tvc_sum_wave(const double* inv, const double* lm9, unsi
         for (int k = 0; k < 16; ++k) part[l][k] = 0.0;
         for (unsigned i = l; i < n; i += (unsigned)AKZ_TVC_WAVE) akz_tvc_accumulate(inv, lm9 + 9 * (size_t)i, lm9 + 9 * (size_t)i + 3, lm9 + 9 * (size_t)i + 6, part[l]);
     }
-    for (int k = 0; k < 16; ++k) {
-        double tmp[AKZ_TVC_WAVE], nxt[AKZ_TVC_WAVE];
-        for (int l = 0; l < AKZ_TVC_WAVE; ++l) tmp[l] = part[l][k];
-        for (int m = AKZ_TVC_WAVE / 2; m >= 1; m >>= 1) {
-            for (int l = 0; l < AKZ_TVC_WAVE; ++l) nxt[l] = tmp[l] + tmp[l ^ m];
-            for (int l = 0; l < AKZ_TVC_WAVE; ++l) tmp[l] = nxt[l];
-        }
-        nets16[k] = tmp[0];
-    }
+    for (int k = 0; k < 16; ++k) nets16[k] = akz_sum_wave(&part[0][k], 16);
 }
 AKZ_TVC_HOST_FN void akz_tvc_sum_sequential(const double* inv, const double* lm9, unsigned n, double* nets16)
 {

@@ -22,14 +22,9 @@
  *     reduction does not cover, gives a matrix of NaN (what sin(inf) gives the reference);
  *   - the eigen-solver and the product orders of akz_triangulate_math.h's own list;
  *   - the order of nalgebra's products, cross products and norms: fixed below, every three-term sum ((x0 + x1) + x2);
- *   - THE ORDER OF THE SUM OVER LANDMARKS.  The reference adds the landmarks' gradients one after another; a workgroup
- *     cannot.  One order, on both sides (AKZ_TV_THREADS = 256 partial sums, waves of AKZ_TV_WAVE = 64):
- *       1. partial sum t, t < 256, = ((0 + g[t]) + g[t + 256]) + g[t + 512] ..., landmarks ascending;
- *       2. inside a wave the butterfly v[l] = v[l] + v[l ^ m] for m = 32, 16, 8, 4, 2, 1 (IEEE addition commutes, so all 64
- *          lanes end with the same bits);
- *       3. the four waves' sums added in wave order, ((w0 + w1) + w2) + w3.
- *     akz_tv_sum_tree below executes that tree on the host; akz_tv_sum_sequential is the reference's order, kept for the
- *     test that documents what the choice costs.
+ *   - THE ORDER OF THE SUM OVER LANDMARKS: akz_sum_order.h, a workgroup's; thread t's partial is the 12 gradient components of
+ *     landmarks t, t + 256, ...  akz_tv_sum_tree below executes it on the host; akz_tv_sum_sequential is the reference's
+ *     order, kept for the test that documents what the choice costs.
  *
  * A finding: three_view_gradients hands two_view_same_space_triangulate_sine_l1 the NEGATED translations
  * (epipolar.rs:118, 128, 139), while that function's w = |z|^2 / z.(t x b) is the inverse depth along `a` for t = the
@@ -42,9 +37,10 @@
 #define AKZ_THREE_VIEW_MATH_H
 
 #include "akz_portable_math.h"
+#include "akz_sum_order.h"
 #include "akz_triangulate_math.h"
 
-enum { AKZ_TV_THREADS = 256, AKZ_TV_WAVE = 64, AKZ_TV_MAX_LANDMARKS = 1024, AKZ_TV_MAX_RUNS = 9, AKZ_TV_NO_IMPROVE = 50 };
+enum { AKZ_TV_THREADS = AKZ_SUM_THREADS, AKZ_TV_WAVE = AKZ_SUM_WAVE, AKZ_TV_MAX_LANDMARKS = 1024, AKZ_TV_MAX_RUNS = 9, AKZ_TV_NO_IMPROVE = 50 };
 
 /* verdicts (RS_TV_* of include/akz.h) */
 enum {
@@ -445,7 +441,6 @@ AKZ_RM_FN void akz_tv_pose_scale(double* pose, double scale)
 AKZ_TV_HOST_FN void akz_tv_sum_tree(const double* inv, const double* lm, unsigned n, double* nets)
 {
     double part[AKZ_TV_THREADS][12];
-    double wave[AKZ_TV_THREADS / AKZ_TV_WAVE][12], tmp[AKZ_TV_WAVE];
     for (unsigned t = 0; t < (unsigned)AKZ_TV_THREADS; ++t) {
         for (int k = 0; k < 12; ++k) part[t][k] = 0.0;
         for (unsigned i = t; i < n; i += (unsigned)AKZ_TV_THREADS) {
@@ -459,17 +454,7 @@ AKZ_TV_HOST_FN void akz_tv_sum_tree(const double* inv, const double* lm, unsigne
             for (int k = 0; k < 12; ++k) part[t][k] = part[t][k] + g[k];
         }
     }
-    for (int w = 0; w < AKZ_TV_THREADS / AKZ_TV_WAVE; ++w)
-        for (int k = 0; k < 12; ++k) {
-            for (int l = 0; l < AKZ_TV_WAVE; ++l) tmp[l] = part[w * AKZ_TV_WAVE + l][k];
-            for (int m = AKZ_TV_WAVE / 2; m >= 1; m >>= 1) {
-                double nxt[AKZ_TV_WAVE];
-                for (int l = 0; l < AKZ_TV_WAVE; ++l) nxt[l] = tmp[l] + tmp[l ^ m];
-                for (int l = 0; l < AKZ_TV_WAVE; ++l) tmp[l] = nxt[l];
-            }
-            wave[w][k] = tmp[0];
-        }
-    for (int k = 0; k < 12; ++k) nets[k] = ((wave[0][k] + wave[1][k]) + wave[2][k]) + wave[3][k];
+    akz_sum_block(&part[0][0], 12, nets);
 }
 AKZ_TV_HOST_FN void akz_tv_sum_sequential(const double* inv, const double* lm, unsigned n, double* nets)
 {

@@ -42,6 +42,18 @@ static void to_soa(const double* lm9, uint32_t n, double* lm)
         for (int k = 0; k < 9; ++k) lm[k * AKZ_TV_MAX_LANDMARKS + i] = lm9[9 * (size_t)i + k];
 }
 
+/* the summed gradients of n landmarks [n][9] {c, f, s}, n <= 1024, in the shipped order or the reference's */
+int tv_sum(const double* inv, const double* lm9, uint32_t n, int sequential, double* nets)
+{
+    double* lm = (double*)calloc(9 * AKZ_TV_MAX_LANDMARKS, sizeof(double));
+    if (!lm || n > AKZ_TV_MAX_LANDMARKS) { free(lm); return -1; }
+    to_soa(lm9, n, lm);
+    if (sequential) akz_tv_sum_sequential(inv, lm, n, nets);
+    else akz_tv_sum_tree(inv, lm, n, nets);
+    free(lm);
+    return 0;
+}
+
 /* one optimiser run: poses [2][12] in and out, landmarks [n][9] {c, f, s}, n <= 1024; returns the stopping iteration */
 uint32_t tv_optimize(double* poses, double rate, uint32_t iterations, const double* lm9, uint32_t n, int sequential)
 {

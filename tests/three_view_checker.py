@@ -60,6 +60,7 @@ def lib():
     L.tv_tri_robust.argtypes = [vp] * 5 + [dbl, dbl, sp]
     L.tv_bi_robust.argtypes = [vp, vp, vp, dbl]
     L.tv_relative_scale.argtypes = [vp] * 5 + [sp, vp]
+    L.tv_sum.argtypes = [vp, vp, u32, C.c_int, vp]
     L.tv_optimize.argtypes = [vp, dbl, u32, vp, u32, C.c_int]
     L.tv_optimize.restype = u32
     L.tv_init_triple.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, u32, sp, C.c_int, vp, vp, vp, vp, vp]
@@ -78,6 +79,13 @@ def gradients(inv, c, f, s):
     g = np.empty(12)
     lib().tv_gradients(inv.ctypes.data, c.ctypes.data, f.ctypes.data, s.ctypes.data, g.ctypes.data)
     return g
+
+
+def gradient_sum(inv, landmarks, sequential=False):
+    """the summed gradients [12] of landmarks [n][3][3] = (c, f, s) under the inverted poses inv [2][3][4]"""
+    inv, lm, nets = _a(inv).reshape(24), _a(landmarks).reshape(-1, 9), np.empty(12)
+    assert lib().tv_sum(inv.ctypes.data, lm.ctypes.data, len(lm), int(sequential), nets.ctypes.data) == 0
+    return nets
 
 
 def optimize(poses, rate, iterations, landmarks, sequential=False):
