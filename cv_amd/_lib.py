@@ -166,6 +166,19 @@ RS_OF_NO_SOLVE, RS_OF_ROBUST_BEFORE, RS_OF_ROBUST_AFTER, RS_OF_STATS, RS_OF_MAX_
 RS_OF_S_LANDMARKS, RS_OF_S_ROBUST_BEFORE, RS_OF_S_ROBUST_AFTER, RS_OF_S_OBS_SPLIT, RS_OF_S_PAIR_SPLIT, RS_OF_S_NO_POINT, RS_OF_S_KICKED = range(7)
 RS_OR_OK, RS_OR_STAGE_RELAX, RS_OR_STAGE_FILTER, RS_OR_STOPPED = 0, 1, 2, 1 << 30
 
+class CovisibilityParams(C.Structure):
+    """rs_covisibility_params (include/akz.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("optimization_robust_covisibility_minimum_landmarks", C.c_uint32),
+                ("optimization_maximum_three_view_constraints", C.c_uint32), ("optimization_minimum_new_constraints", C.c_uint32),
+                ("optimization_minimum_landmarks", C.c_uint32), ("optimization_maximum_landmarks", C.c_uint32),
+                ("candidate_limit", C.c_uint32), ("shuffle_seed", C.c_uint32)]
+
+
+RS_CV_OK, RS_CV_FEW_CONSTRAINTS, RS_CV_BAD_INDEX, RS_CV_NO_GRAPH = range(4)
+RS_CV_NOT_RECORDED, RS_CV_MAX_CANDIDATE_VIEWS, RS_CV_MAX_SLOTS, RS_CV_MAX_FEATURES, RS_CV_STATS = 16, 128, 256, 8192, 8
+RS_CV_S_ROBUST, RS_CV_S_CANDIDATES, RS_CV_S_PAIRS, RS_CV_S_UNIQUE, RS_CV_S_EMITTED, RS_CV_S_FLAGS, RS_CV_S_RECORDED = range(7)
+RS_CV_F_CANDIDATES_CAPPED, RS_CV_F_LIMIT_REACHED = 1, 2
+
 class SingleViewParams(C.Structure):
     """rs_single_view_params (include/akz.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("single_view_optimization_num_matches", C.c_uint32),
@@ -222,6 +235,7 @@ ABI_SYMBOLS = [
     "rs_pose_graph_params_default", "rs_pose_graph_edges_device", "rs_pose_graph_relax_batch_device", "rs_pose_graph_debug_resident_views",
     "rs_observation_filter_params_default", "rs_filter_observations_device", "rs_optimize_reconstruction_batch_device",
     "rs_single_view_params_default", "rs_refine_poses_batch_device",
+    "rs_covisibility_params_default", "rs_covisibility_candidates_device", "rs_covisibility_record_device", "rs_pose_graph_rows_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -369,6 +383,11 @@ def lib():
     L.rs_single_view_params_default.argtypes = [svp]
     L.rs_refine_poses_batch_device.argtypes = ([vp, vp, u32, u32, vp, C.POINTER(Camera), vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp,
                                                 u32, svp] + [vp] * 6)
+    cvp = C.POINTER(CovisibilityParams)
+    L.rs_covisibility_params_default.argtypes = [cvp]
+    L.rs_covisibility_candidates_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, u32, cvp] + [vp] * 7
+    L.rs_covisibility_record_device.argtypes = [vp, vp, vp, u32, vp, u32, cvp, vp, vp, vp, vp]
+    L.rs_pose_graph_rows_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

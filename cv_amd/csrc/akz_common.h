@@ -183,6 +183,14 @@ struct RsSingleViewState {
     size_t bytes = 0;
 };
 RsSingleViewState* rs_internal_single_view(rs_ctx* c);
+// What rs_covisibility.hip keeps in an rs_ctx, grown on demand and freed by rs_destroy: the inverse map {block, feature} ->
+// landmark, a byte per landmark, the rows and counts of the workgroups of one call, a word per slot and per target; and, for
+// rs_pose_graph_rows_device, a cursor per view and a word per row entry.
+struct RsCovisibilityState {
+    void* d_scratch = nullptr;
+    size_t bytes = 0;
+};
+RsCovisibilityState* rs_internal_covisibility(rs_ctx* c);
 
 // A context's scratch, grown on demand: *d holds at least `need` bytes afterwards (what it held before is not kept).
 inline int32_t akz_grow_scratch(hipStream_t stream, void** d, size_t* have, size_t need)
@@ -333,6 +341,30 @@ __device__ __forceinline__ uint32_t akz_block_sum(uint32_t (&cnt)[2][W], uint32_
 #pragma unroll
     for (int k = 0; k < W; ++k) all += cnt[buf][k];
     return all;
+}
+// The exclusive prefix of one u32 per thread over the threads of a block of W waves (thread order), and the block's total; all
+// threads call it.  Two barriers: s_wave is free for the next call when it returns.
+template <int W>
+__device__ __forceinline__ uint32_t akz_block_exclusive(uint32_t v, uint32_t* s_wave, uint32_t* total)
+{
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += t;
+    }
+    if (lane == 63u) s_wave[w] = incl;
+    __syncthreads();
+    uint32_t before = 0u, all = 0u;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        before += (uint32_t)k < w ? s_wave[k] : 0u;
+        all += s_wave[k];
+    }
+    __syncthreads();                              // s_wave is free for the next call
+    *total = all;
+    return incl - v + before;
 }
 // The sum of N doubles per thread over a block of W waves, steps 2 and 3 of include/akz_sum_order.h (akz_sum_block there): the
 // wave butterfly, lane 0 of each wave leaves its N sums in red[parity & 1], ONE barrier, and every thread folds the waves from

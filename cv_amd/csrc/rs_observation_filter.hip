@@ -101,29 +101,6 @@ __device__ __forceinline__ uint32_t of_filled(const OfCall& a)
     return e < a.n_obs ? e : a.n_obs;
 }
 
-// The exclusive prefix of v over the kOfBlock threads of a workgroup, and the workgroup's total; all threads call it.
-__device__ __forceinline__ uint32_t of_block_exclusive(uint32_t v, uint32_t* s_wave, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += t;
-    }
-    if (lane == 63u) s_wave[w] = incl;
-    __syncthreads();
-    uint32_t before = 0u, all = 0u;
-#pragma unroll
-    for (int k = 0; k < kOfWaves; ++k) {
-        before += (uint32_t)k < w ? s_wave[k] : 0u;
-        all += s_wave[k];
-    }
-    __syncthreads();                              // s_wave is free for the next call
-    *total = all;
-    return incl - v + before;
-}
-
 // One workgroup per reconstruction.  A reconstruction runs when (1) no start of d_recon_start in front of its own lies above
 // it and its range ascends inside [0, n_landmarks], (2) its view range ascends inside [0, n_blocks], (3) no start of
 // d_obs_start in front of its first landmark lies above that landmark's and the starts it owns ascend up to n_obs at the
@@ -249,7 +226,7 @@ __global__ __launch_bounds__(kOfBlock) void k_of_scan_sums(OfCall a, uint32_t mi
         const uint32_t t = t0 + threadIdx.x;
         const uint32_t v = t < a.n_tiles ? a.tile[t] : 0u;
         uint32_t total;
-        const uint32_t ex = of_block_exclusive(v, s_wave, &total);
+        const uint32_t ex = akz_block_exclusive<kOfWaves>(v, s_wave, &total);
         if (t < a.n_tiles) a.tile[t] = carry + ex;
         carry += total;
     }
@@ -270,7 +247,7 @@ __global__ __launch_bounds__(kOfBlock) void k_of_scatter(OfCall a)
     const uint32_t filled = of_filled(a);
     uint32_t k[kOfItems], total;
     const uint32_t sum = of_thread_flags(a, blockIdx.x, filled, k);
-    uint32_t kept = a.tile[blockIdx.x] + of_block_exclusive(sum, s_wave, &total);
+    uint32_t kept = a.tile[blockIdx.x] + akz_block_exclusive<kOfWaves>(sum, s_wave, &total);
     const size_t i0 = (size_t)blockIdx.x * kOfTile + (size_t)threadIdx.x * kOfItems;
     const uint2* obs = reinterpret_cast<const uint2*>(a.obs);
 #pragma unroll

@@ -1488,6 +1488,7 @@ struct rs_ctx : RsArena {
     RsPoseGraphState pose_graph;                                       // rs_pose_graph.hip's (akz_common.h)
     RsObsFilterState obs_filter;                                       // rs_observation_filter.hip's (akz_common.h)
     RsSingleViewState single_view;                                     // rs_single_view.hip's (akz_common.h)
+    RsCovisibilityState covisibility;                                  // rs_covisibility.hip's (akz_common.h)
 };
 
 // (akz_common.h) what rs_triangulate.hip enqueues with
@@ -1495,6 +1496,7 @@ RsHandles rs_internal_handles(rs_ctx* c) { return RsHandles{c->device, c->stream
 RsPoseGraphState* rs_internal_pose_graph(rs_ctx* c) { return &c->pose_graph; }
 RsObsFilterState* rs_internal_obs_filter(rs_ctx* c) { return &c->obs_filter; }
 RsSingleViewState* rs_internal_single_view(rs_ctx* c) { return &c->single_view; }
+RsCovisibilityState* rs_internal_covisibility(rs_ctx* c) { return &c->covisibility; }
 
 // Every device array of an arena, once: where its pointer lives and its bytes per scene (n matches, H hypothesis slots).
 struct RsSlot {
@@ -1621,6 +1623,7 @@ extern "C" int32_t rs_destroy(rs_ctx* c)
         hipFree(c->obs_filter.d_scratch);
         hipFree(c->obs_filter.d_chain);
         hipFree(c->single_view.d_scratch);
+        hipFree(c->covisibility.d_scratch);
         if (c->ev) hipEventDestroy(c->ev);
         if (c->stream) hipStreamDestroy(c->stream);
         delete c;

@@ -89,6 +89,25 @@ class PoseGraph:
             self._cons._h, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views, d_constraint_verdict,
             d_edges, n_constraints, C.byref(params), d_graph_verdict, d_view_state, d_stats, stream_to_wait), "rs_pose_graph_relax_batch_device")
 
+    def rows_device(self, d_views, n_constraints, n_views, d_row_start, d_row_edges, d_flags, stream_to_wait=None):
+        """rs_pose_graph_rows_device: `flatten` with order=None on the device; arguments named d_* are device pointers (ints).
+        Enqueues and returns."""
+        check(_lib.lib().rs_pose_graph_rows_device(self._cons._h, d_views, n_constraints, n_views, d_row_start, d_row_edges, d_flags,
+                                                   stream_to_wait), "rs_pose_graph_rows_device")
+
+    def rows(self, torch, views, n_views):
+        """rows_device on a device tensor views [n][3] (4-byte integers).  Enqueued behind the current torch stream; no wait ->
+        (d_row_start [n_views + 1], d_row_edges [6 n], d_flags [1]) int32: d_flags is 1 when a triple named a view >= n_views
+        (it is in no row then)."""
+        dev = views.device
+        n = int(np.prod(views.shape)) // 3
+        d_row_start = torch.zeros((n_views + 1,), dtype=torch.int32, device=dev)
+        d_row_edges = torch.zeros((max(6 * n, 1),), dtype=torch.int32, device=dev)
+        d_flags = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.rows_device(views.data_ptr(), n, n_views, d_row_start.data_ptr(), d_row_edges.data_ptr(), d_flags.data_ptr(),
+                         _lib.wait_handle(torch.cuda.current_stream(dev)))
+        return d_row_start, d_row_edges[:6 * n], d_flags
+
     @staticmethod
     def _tensor(torch, a, dtype, dev):
         """a device tensor as it is (contiguous, of the right width), a host array uploaded"""

@@ -214,3 +214,54 @@ class ReconstructionOptimizer:
         last = max(int(params.reconstruction_optimization_iterations), 1) - 1
         return ReconstructionResult(u32(d_verdict)[:n_graphs], PoseGraphResult(u32(d_gv)[:n_graphs], u32(d_state)[:n_views], u32(d_pg_stats)[:n_graphs], poses),
                                     _to_host(o, n_graphs, last), d_world, d_reason, o)
+
+
+@dataclass
+class RegenerateResult:
+    candidates: object        # covisibility.CovisibilityTensors (target verdicts and stats as the record left them)
+    constraints: tuple        # (d_verdict, d_pose, d_stats) of the constraint stage over the slots
+    recorded: object          # d_recorded [n_slots] int32: the constraints' verdicts the graph saw
+    rows: tuple               # (d_row_start, d_row_edges, d_flags)
+    verdict: object           # d_verdict [n_graphs] int32 (RS_OR_*)
+    pose_graph: tuple         # (d_graph_verdict, d_view_state, d_pg_stats)
+    filter: object            # ObservationFilterTensors
+    world: object             # [n_landmarks][4] float64 of the filtered table
+    world_reason: object      # [n_landmarks] uint8
+
+
+def regenerate(torch, consensus, table, d_kps, cap, cam, poses, graph_start, recon_start, targets=None, reason=None, cv_params=None,
+               tvc_params=None, pg_params=None, params=None):
+    """VSlam::regenerate_reconstruction (cv-sfm/src/lib.rs:2418-2435) for the reconstructions of graph_start side by side, on
+    device tensors: the covisibility candidates of `targets` (default: every view), their three-view constraints, the record,
+    the edges and rows of the pose graph and optimize_reconstruction, each enqueued on the consensus' stream behind the one
+    before.  poses [n_views][12] float64 is relaxed in place.  `reason` [n_landmarks] uint8: the robust triangulation's reason
+    bytes; computed here under `poses` and params.triangulate when not given.  WAITS once, at the end -> RegenerateResult of
+    device tensors."""
+    from .covisibility import Covisibility
+    from .three_view import ThreeViewConstraints
+    from .triangulation import triangulate_landmarks_device
+    n_views = int(np.prod(poses.shape)) // 12
+    dev = table.dev
+    first_world = None
+    pg = PoseGraph(consensus)
+    opt = ReconstructionOptimizer(pg)
+    params = params or opt.params()
+    wait = lambda: _lib.wait_handle(torch.cuda.current_stream(dev))
+    if reason is None:
+        reason = torch.zeros((max(table.n_landmarks, 1),), dtype=torch.uint8, device=dev)
+        first_world = table.new_world()          # the call only enqueues: the table it writes stays referenced until the wait below
+        triangulate_landmarks_device(consensus._h, table, d_kps, cap, n_views, poses, cam, params.triangulate, first_world, reason, wait())
+    targets = np.arange(n_views, dtype=np.uint32) if targets is None else targets
+    cov = Covisibility(consensus)
+    cv_params = cv_params or cov.params()
+    cand = cov.run_tensors(torch, table, cap, n_views, reason, targets, cv_params)
+    kps = d_kps.view(torch.uint8).reshape(n_views, cap, 28)
+    constraints = ThreeViewConstraints(consensus).run_tensors(torch, kps, poses, cam, cand.views, cand.lm_start, cand.lm, tvc_params)
+    recorded = cov.record_tensors(torch, cand, constraints[0], graph_start, cv_params)
+    edges = pg.edges(torch, cand.views, (constraints[1], recorded))
+    rows = pg.rows(torch, cand.views, n_views)
+    d_verdict, pose_graph, o, d_world, d_world_reason = opt.run_tensors(torch, poses, graph_start, rows[0], rows[1], edges, table, d_kps, cap,
+                                                                        cam, recon_start, pg_params, params)
+    consensus.sync()
+    del first_world
+    return RegenerateResult(cand, constraints, recorded, rows, d_verdict, pose_graph, o, d_world, d_world_reason)

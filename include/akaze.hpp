@@ -777,10 +777,19 @@ public:
                                                       stream_to_wait),
                      "rs_pose_graph_relax_batch_device");
     }
+    // flatten() on the device (rs_pose_graph_rows_device): d_row_start [n_views + 1], d_row_edges [6 n], d_flags [1] (1: a triple
+    // named a view >= n_views and is in no row)
+    void rows(const void* d_views, uint32_t n_constraints, uint32_t n_views, void* d_row_start, void* d_row_edges, void* d_flags,
+              void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_pose_graph_rows_device(ctx_, d_views, n_constraints, n_views, d_row_start, d_row_edges, d_flags, stream_to_wait),
+                     "rs_pose_graph_rows_device");
+    }
     // parity tap: graphs of more than `views` views (at most RS_PG_RESIDENT_VIEWS) take the swept form from now on
     void resident_views(uint32_t views) { akaze::check(rs_pose_graph_debug_resident_views(ctx_, views), "rs_pose_graph_debug_resident_views"); }
     void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
     void* stream() { return rs_stream(ctx_); }
+    rs_ctx* context() { return ctx_; }
 
 private:
     rs_pose_graph_params p_;
@@ -844,6 +853,46 @@ inline void optimize_reconstruction(ObservationFilter& filter, const rs_pose_gra
                                                          d_world_reason, stream_to_wait),
                  "rs_optimize_reconstruction_batch_device");
 }
+
+// cv-sfm's covisibility search in front of its three-view constraints (VSlam::generate_view_constraints, cv-sfm/src/lib.rs:
+// 2438-2516) and the verdict of record_view_constraints (lib.rs:2092-2109) over rs_covisibility_candidates_device and
+// rs_covisibility_record_device.  It works on a context it does not own (`ctx`: the one the constraint stage and the pose
+// graph run on, so that the chain queues on one stream).  Every argument named d_* is device memory the caller owns (the
+// layouts are include/akz.h's); the calls enqueue and return.
+class ViewConstraints {
+public:
+    enum Verdict : uint32_t { Ok = RS_CV_OK, FewConstraints = RS_CV_FEW_CONSTRAINTS, BadIndex = RS_CV_BAD_INDEX, NoGraph = RS_CV_NO_GRAPH };
+    explicit ViewConstraints(rs_ctx* ctx) : ctx_(ctx)
+    {
+        akaze::require_abi();
+        rs_covisibility_params_default(&p_);
+    }
+    rs_covisibility_params& params() { return p_; }   // the reference's defaults (cv-sfm/src/settings.rs:453-475)
+    const rs_covisibility_params& params() const { return p_; }
+    uint32_t limit() const { return p_.candidate_limit ? p_.candidate_limit : p_.optimization_maximum_three_view_constraints; }   // slots per target
+    void candidates_device(const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks, uint32_t cap_per_img,
+                           uint32_t n_blocks, const void* d_reason, const void* d_targets, uint32_t n_targets, void* d_views, void* d_lm_start,
+                           void* d_lm, void* d_slot_count, void* d_target_verdict, void* d_stats, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_covisibility_candidates_device(ctx_, d_obs_start, d_obs, n_obs, n_landmarks, cap_per_img, n_blocks, d_reason, d_targets,
+                                                       n_targets, &p_, d_views, d_lm_start, d_lm, d_slot_count, d_target_verdict, d_stats,
+                                                       stream_to_wait),
+                     "rs_covisibility_candidates_device");
+    }
+    void record_device(const void* d_constraint_verdict, const void* d_targets, uint32_t n_targets, const void* d_graph_start, uint32_t n_graphs,
+                       void* d_recorded, void* d_target_verdict, void* d_stats, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_covisibility_record_device(ctx_, d_constraint_verdict, d_targets, n_targets, d_graph_start, n_graphs, &p_, d_recorded,
+                                                   d_target_verdict, d_stats, stream_to_wait),
+                     "rs_covisibility_record_device");
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_covisibility_params p_;
+    rs_ctx* ctx_ = nullptr;
+};
 
 // What cv-sfm's register_frame_subset does behind its consensus (cv-sfm/src/lib.rs:1625-1775) over
 // rs_refine_poses_batch_device: the single-view L2 optimiser and the consistency filter, one persistent workgroup per new

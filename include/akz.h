@@ -1015,6 +1015,88 @@ int32_t rs_optimize_reconstruction_batch_device(rs_ctx* ctx, void* d_poses, uint
                                                 void* d_robust, void* d_obs_start_out, void* d_obs_out, void* d_split_out, void* d_counts,
                                                 void* d_recon_verdict, void* d_of_stats, void* d_world, void* d_world_reason,
                                                 void* stream_to_wait);
+/* ---- the covisibility search in front of the three-view constraints, their record and the rows of the pose graph ----
+ * What cv-sfm's VSlam::generate_view_constraints does up to its call of optimize_three_view (cv-sfm/src/lib.rs:2438-2516, with
+ * view_covisibilities, lib.rs:2535-2556), the verdict of record_view_constraints (lib.rs:2092-2109) and flatten_constraints
+ * (lib.rs:2519-2532), so that landmark table -> candidates -> constraints -> recorded set -> edges -> rows ->
+ * rs_optimize_reconstruction_batch_device runs on rs_stream() without a host step (regenerate_reconstruction, lib.rs:2418-2435).
+ * Integers only.  The decisions are include/akz_covisibility_math.h (compiled for the device and, by the tests, for the host:
+ * equal in every word); its head lists the admissible order it fixes where the reference walks HashMaps and sorts unstably. */
+enum {                                /* d_target_verdict */
+    RS_CV_OK = 0,
+    RS_CV_FEW_CONSTRAINTS = 1,        /* record: fewer than optimization_minimum_new_constraints recorded and recorded + 1 < the
+                                       * views of the target's reconstruction (lib.rs:2098-2102): nothing of the target is recorded */
+    RS_CV_BAD_INDEX = 2,              /* the target is >= n_blocks; a landmark of one of its features names a block >= n_blocks or a
+                                       * feature >= cap_per_img; or some start pair of d_obs_start does not ascend within [0, n_obs]
+                                       * (which refuses every target of the call): no slot is filled, nothing is read out of bounds */
+    RS_CV_NO_GRAPH = 3                /* record: no range of d_graph_start holds the target */
+};
+enum {
+    RS_CV_NOT_RECORDED = 16,          /* d_recorded of a slot the constraint stage accepted and the record did not take */
+    RS_CV_MAX_CANDIDATE_VIEWS = 128,  /* candidate views of a target: 8 128 pairs, whose sort keys are 64 KB of LDS, and 128 bit rows
+                                       * of scratch per workgroup; a target with more keeps the largest counts, ties to the lower
+                                       * block, and says so (RS_CV_F_CANDIDATES_CAPPED) */
+    RS_CV_MAX_SLOTS = 256,            /* candidate_limit at the most: a target's slots are walked by one lane */
+    RS_CV_MAX_FEATURES = 8192,        /* cap_per_img at the most: AKZ_E_TOO_LARGE beyond (a list's sort keys live in LDS) */
+    /* d_stats words (u32) of a target; all 0 for RS_CV_BAD_INDEX: */
+    RS_CV_S_ROBUST = 0,               /* features whose landmark is robust */
+    RS_CV_S_CANDIDATES = 1,           /* candidate views kept */
+    RS_CV_S_PAIRS = 2,                /* triples at or above optimization_robust_covisibility_minimum_landmarks */
+    RS_CV_S_UNIQUE = 3,               /* triples the unique walk took (lib.rs:2490-2495) */
+    RS_CV_S_EMITTED = 4,              /* slots filled */
+    RS_CV_S_FLAGS = 5,                /* RS_CV_F_* */
+    RS_CV_S_RECORDED = 6,             /* constraints recorded: 0 from the candidates call, written by the record */
+    RS_CV_STATS = 8,                  /* word 7 is 0 */
+    RS_CV_F_CANDIDATES_CAPPED = 1,
+    RS_CV_F_LIMIT_REACHED = 2         /* the chain held further admissible triples beyond the limit: the reference would try them
+                                       * after a refusal by the constraint stage; run again with a larger candidate_limit */
+};
+typedef struct rs_covisibility_params {
+    uint32_t struct_size;                                             /* sizeof(rs_covisibility_params) */
+    uint32_t optimization_robust_covisibility_minimum_landmarks;      /* 16 */
+    uint32_t optimization_maximum_three_view_constraints;             /* 64 */
+    uint32_t optimization_minimum_new_constraints;                    /* 4 */
+    uint32_t optimization_minimum_landmarks;                          /* 24; above the maximum: AKZ_E_INVALID */
+    uint32_t optimization_maximum_landmarks;                          /* 64; more than RS_TVC_MAX_LANDMARKS: AKZ_E_TOO_LARGE */
+    uint32_t candidate_limit;                                         /* 0: slots per target; 0 = the maximum of constraints; more
+                                                                       * than RS_CV_MAX_SLOTS either way: AKZ_E_TOO_LARGE */
+    uint32_t shuffle_seed;                                            /* 0: ties of a list's sort by position; else by a mix of
+                                                                       * (seed, landmark), in place of lib.rs:1968's shuffle */
+} rs_covisibility_params;
+/* the reference's defaults (cv-sfm/src/settings.rs:453-475) */
+int32_t rs_covisibility_params_default(rs_covisibility_params* params);
+/* The landmark table as rs_triangulate_landmarks_device takes it (d_obs_start [n_landmarks + 1], d_obs [n_obs][2], cap_per_img,
+ * n_blocks) and d_reason [n_landmarks] u8 as that call writes it: a landmark is robust iff its byte is RS_TRI_OK.  d_targets
+ * [n_targets] u32: the views (keypoint blocks) to generate constraints for.  With limit = candidate_limit, or
+ * optimization_maximum_three_view_constraints when that is 0, target t owns slots t * limit .. (t + 1) * limit of
+ * d_views [n_slots][3], d_lm_start [n_slots + 1] and d_lm [n_slots * optimization_maximum_landmarks][3], the arrays
+ * rs_three_view_constraint_batch_device reads (n_constraints = n_slots, n_lm = n_slots * optimization_maximum_landmarks).  All
+ * outputs are written in full (d_lm behind the last list with zeros).  An unused slot has views {0, 0, 0} and an empty list, which
+ * the constraint stage refuses with RS_TVC_FEW_LANDMARKS.  d_slot_count [n_slots] u32: a slot's covisible landmarks before the
+ * cut to optimization_maximum_landmarks; d_target_verdict [n_targets] u32 (RS_CV_OK or RS_CV_BAD_INDEX); d_stats
+ * [n_targets][RS_CV_STATS] u32.  The parameters are checked before anything else.  Enqueues on rs_stream() after stream_to_wait
+ * (may be NULL) and returns; allocates nothing beyond growing the context's scratch. */
+int32_t rs_covisibility_candidates_device(rs_ctx* ctx, const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks,
+                                          uint32_t cap_per_img, uint32_t n_blocks, const void* d_reason, const void* d_targets,
+                                          uint32_t n_targets, const rs_covisibility_params* params, void* d_views, void* d_lm_start,
+                                          void* d_lm, void* d_slot_count, void* d_target_verdict, void* d_stats, void* stream_to_wait);
+/* Behind rs_three_view_constraint_batch_device on those slots: d_constraint_verdict [n_slots] u32 is its d_verdict.  Per target,
+ * in slot order, the first optimization_maximum_three_view_constraints RS_TVC_OK slots are recorded (lib.rs:2511-2514) unless
+ * record_view_constraints' rule refuses the target; the views of its reconstruction are the length of the first range of
+ * d_graph_start [n_graphs + 1] (rs_pose_graph_relax_batch_device's) that holds it.  d_recorded [n_slots] u32: RS_TVC_OK for a
+ * recorded constraint, else the constraint's own verdict or RS_CV_NOT_RECORDED — what rs_pose_graph_edges_device and the
+ * relaxation take as d_constraint_verdict.  d_target_verdict and d_stats are the candidates call's, updated in place: a target
+ * that is RS_CV_BAD_INDEX stays so and records nothing, the others become RS_CV_OK, RS_CV_FEW_CONSTRAINTS or RS_CV_NO_GRAPH;
+ * word RS_CV_S_RECORDED is written. */
+int32_t rs_covisibility_record_device(rs_ctx* ctx, const void* d_constraint_verdict, const void* d_targets, uint32_t n_targets,
+                                      const void* d_graph_start, uint32_t n_graphs, const rs_covisibility_params* params, void* d_recorded,
+                                      void* d_target_verdict, void* d_stats, void* stream_to_wait);
+/* flatten_constraints: d_row_start [n_views + 1] and d_row_edges [6 * n_constraints] u32 of rs_pose_graph_relax_batch_device from
+ * d_views [n_constraints][3]: view v's row holds the edge ids 6 * constraint + slot whose target is v in ascending order.
+ * Refused constraints stay in the rows.  A triple that names a view >= n_views contributes nothing and sets d_flags [1] u32 to 1
+ * (0 otherwise); d_row_edges behind d_row_start[n_views] is 0. */
+int32_t rs_pose_graph_rows_device(rs_ctx* ctx, const void* d_views, uint32_t n_constraints, uint32_t n_views, void* d_row_start,
+                                  void* d_row_edges, void* d_flags, void* stream_to_wait);
 /* ---- the refinement of registered poses on the device: single-view L2 optimiser and consistency filter ----
  * What cv-sfm's register_frame_subset does behind its consensus (cv-sfm/src/lib.rs:1625-1775), for the new frames of a
  * micro-batch side by side — the same scenes as the preceding rs_p3p_arrsac_batch_device call: the first

@@ -148,6 +148,18 @@ extern "C" {
                                                d_obs_start_out: *mut c_void, d_obs_out: *mut c_void, d_split_out: *mut c_void,
                                                d_counts: *mut c_void, d_recon_verdict: *mut c_void, d_of_stats: *mut c_void, d_world: *mut c_void,
                                                d_world_reason: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_covisibility_params_default(params: *mut RsCovisibilityParams) -> i32;
+    fn rs_covisibility_candidates_device(ctx: *mut c_void, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32,
+                                         cap_per_img: u32, n_blocks: u32, d_reason: *const c_void, d_targets: *const c_void, n_targets: u32,
+                                         params: *const RsCovisibilityParams, d_views: *mut c_void, d_lm_start: *mut c_void,
+                                         d_lm: *mut c_void, d_slot_count: *mut c_void, d_target_verdict: *mut c_void, d_stats: *mut c_void,
+                                         stream_to_wait: *mut c_void) -> i32;
+    fn rs_covisibility_record_device(ctx: *mut c_void, d_constraint_verdict: *const c_void, d_targets: *const c_void, n_targets: u32,
+                                     d_graph_start: *const c_void, n_graphs: u32, params: *const RsCovisibilityParams,
+                                     d_recorded: *mut c_void, d_target_verdict: *mut c_void, d_stats: *mut c_void,
+                                     stream_to_wait: *mut c_void) -> i32;
+    fn rs_pose_graph_rows_device(ctx: *mut c_void, d_views: *const c_void, n_constraints: u32, n_views: u32, d_row_start: *mut c_void,
+                                 d_row_edges: *mut c_void, d_flags: *mut c_void, stream_to_wait: *mut c_void) -> i32;
     fn rs_single_view_params_default(params: *mut RsSingleViewParams) -> i32;
     fn rs_refine_poses_batch_device(ctx: *mut c_void, d_kps: *const c_void, cap_per_img: u32, n_blocks: u32, d_poses: *const c_void,
                                     cam: *const RsCamera, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32,
@@ -1297,6 +1309,94 @@ impl Default for ObservationFilter {
 impl Drop for ObservationFilter {
     fn drop(&mut self) {
         unsafe { rs_destroy(self.ctx) };
+    }
+}
+
+/// `rs_covisibility_params` (include/akz.h): cv-sfm's settings of `generate_view_constraints` and `record_view_constraints`
+/// (cv-sfm/src/settings.rs:453-475), the slots per target and the seed that stands in for the shuffle.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RsCovisibilityParams {
+    struct_size: u32,
+    pub optimization_robust_covisibility_minimum_landmarks: u32,
+    pub optimization_maximum_three_view_constraints: u32,
+    pub optimization_minimum_new_constraints: u32,
+    pub optimization_minimum_landmarks: u32,
+    pub optimization_maximum_landmarks: u32,
+    pub candidate_limit: u32,
+    pub shuffle_seed: u32,
+}
+
+/// A target's verdict (`RS_CV_OK` ...).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum CovisibilityVerdict {
+    Ok = 0,
+    FewConstraints = 1,
+    BadIndex = 2,
+    NoGraph = 3,
+}
+
+/// `d_recorded` of an accepted constraint the record did not take; the capacities; the words of a target's `d_stats` row.
+pub const RS_CV_NOT_RECORDED: u32 = 16;
+pub const RS_CV_MAX_CANDIDATE_VIEWS: u32 = 128;
+pub const RS_CV_MAX_SLOTS: u32 = 256;
+pub const RS_CV_MAX_FEATURES: u32 = 8192;
+pub const RS_CV_STATS: usize = 8;
+pub const RS_CV_F_CANDIDATES_CAPPED: u32 = 1;
+pub const RS_CV_F_LIMIT_REACHED: u32 = 2;
+
+/// `VSlam::generate_view_constraints` up to its call of `optimize_three_view` (cv-sfm/src/lib.rs:2438-2516), the verdict of
+/// `record_view_constraints` (lib.rs:2092-2109) and `flatten_constraints` (lib.rs:2519-2532) on a context the caller owns
+/// (`ctx`: the one the constraint stage and the pose graph run on).  Every `d_*` argument is device memory the caller owns,
+/// laid out as include/akz.h documents; the calls enqueue and return.
+pub struct ViewConstraints {
+    pub params: RsCovisibilityParams,
+    ctx: *mut c_void,
+}
+impl ViewConstraints {
+    /// # Safety
+    /// `ctx` is a live `rs_ctx` that outlives this object.
+    pub unsafe fn new(ctx: *mut c_void) -> Self {
+        require_abi();
+        let mut params: RsCovisibilityParams = std::mem::zeroed();
+        assert_eq!(rs_covisibility_params_default(&mut params), 0, "rs_covisibility_params_default");
+        Self { params, ctx }
+    }
+    /// slots per target
+    pub fn limit(&self) -> u32 {
+        if self.params.candidate_limit != 0 { self.params.candidate_limit } else { self.params.optimization_maximum_three_view_constraints }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn candidates_device(&self, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32, cap_per_img: u32,
+                                    n_blocks: u32, d_reason: *const c_void, d_targets: *const c_void, n_targets: u32, d_views: *mut c_void,
+                                    d_lm_start: *mut c_void, d_lm: *mut c_void, d_slot_count: *mut c_void, d_target_verdict: *mut c_void,
+                                    d_stats: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_covisibility_candidates_device(self.ctx, d_obs_start, d_obs, n_obs, n_landmarks, cap_per_img, n_blocks, d_reason, d_targets,
+                                                   n_targets, &self.params, d_views, d_lm_start, d_lm, d_slot_count, d_target_verdict, d_stats,
+                                                   stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn record_device(&self, d_constraint_verdict: *const c_void, d_targets: *const c_void, n_targets: u32,
+                                d_graph_start: *const c_void, n_graphs: u32, d_recorded: *mut c_void, d_target_verdict: *mut c_void,
+                                d_stats: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_covisibility_record_device(self.ctx, d_constraint_verdict, d_targets, n_targets, d_graph_start, n_graphs, &self.params,
+                                               d_recorded, d_target_verdict, d_stats, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// `flatten_constraints` on the device: `d_row_start` [n_views + 1], `d_row_edges` [6 n], `d_flags` [1].
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn rows_device(&self, d_views: *const c_void, n_constraints: u32, n_views: u32, d_row_start: *mut c_void,
+                              d_row_edges: *mut c_void, d_flags: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_pose_graph_rows_device(self.ctx, d_views, n_constraints, n_views, d_row_start, d_row_edges, d_flags, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
     }
 }
 
