@@ -24,6 +24,7 @@
 // the image is evaluated at its clamped coordinate.  That is exactly what the reference's
 // edge-replicated scratch rows/columns produce stage by stage.
 #include "akz_ctx.h"
+#include <type_traits>
 
 // ---- the three arithmetic orders that live in un-vendored crates of the reference ([3P-unverified]) ----
 // This translation unit is compiled once per combination (-DAKZ_ARITH=0..7, cv_amd/build.py); akz_options.arith selects
@@ -3155,413 +3156,486 @@ static GaussTaps make_taps(float sigma)
     return t;
 }
 
-template <typename InT>
-static int32_t scale_space_impl(akz_ctx* c, const InT* d_imgs, int n)
+// ---------------------------------------------------------------------------------------------
+// The launch schedule of akz_run_scale_space: route_call / route_level decide which kernels run (once per call, once per
+// level) and enqueue nothing; one function per phase enqueues what the route says; scale_space_impl is the loop over them.
+namespace {
+
+// A runtime value as a template argument: `f` is a generic lambda that receives a std::integral_constant.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <typename F> inline void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> inline void with_sigma(uint32_t sg, F&& f)   // the derivative sigmas of the fused kernels (callers admit 2..4 only)
+{
+    switch (sg) { case 2: f(IntC<2>{}); break;   case 3: f(IntC<3>{}); break;   default: f(IntC<4>{}); break; }
+}
+template <typename F> inline void with_steps(int g, F&& f)   // the steps of one k_fed_pair launch: 1..kFedMaxBlock
+{
+    switch (g) {
+    case 1: f(IntC<1>{}); break;   case 2: f(IntC<2>{}); break;   case 3: f(IntC<3>{}); break;   case 4: f(IntC<4>{}); break;
+    case 5: f(IntC<5>{}); break;   case 6: f(IntC<6>{}); break;   case 7: f(IntC<7>{}); break;   case 8: f(IntC<8>{}); break;
+    case 9: f(IntC<9>{}); break;   case 10: f(IntC<10>{}); break; case 11: f(IntC<11>{}); break; case 12: f(IntC<12>{}); break;
+    case 13: f(IntC<13>{}); break; case 14: f(IntC<14>{}); break; case 15: f(IntC<15>{}); break; case 16: f(IntC<16>{}); break;
+    }
+}
+
+// The half-tau values of `count` FED steps of a level from step `first` on, zero-padded (FedTaus: one temporally blocked
+// launch; FedTausN: a whole resident level).
+template <typename Taus> Taus fed_taus(const AkzLevel& L, int first, int count)
+{
+    Taus ft;
+    constexpr int cap = (int)(sizeof(ft.half_tau) / sizeof(ft.half_tau[0]));
+    for (int q = 0; q < cap; ++q) ft.half_tau[q] = q < count ? 0.5f * (float)L.tau[first + q] : 0.0f;
+    return ft;
+}
+
+// Ping-pong between Lt[i] and the scratch plane so that the last of a level's `ng` FED launches lands in Lt[i]: where
+// launch k of ng writes (k = -1: where the first launch reads, which it must not write).
+inline float* fed_dst(const AkzSet& S, int i, int k, int ng) { return ((ng - 1 - k) % 2 == 0) ? S.Lt[i] : S.tmp; }
+
+struct CallRoute {
+    float sigma0 = 0.0f;                        // base_scale_offset
+    int r0 = 0;                                 // ... and its Gaussian radius
+    bool tile0 = false, fused0 = false;         // level 0: the tile kernels' radius; blur + first derivatives in one kernel
+    bool pair0 = false;                         // ... and the input taken two frames per block
+    bool pairc = false, fine = false;           // contrast factor: k_contrast_pair; with the fine histogram
+    int nbands = 0, npairs = 0, seg_rows = 0;   // ... and its cut into waves (pairc only)
+    bool det_side = false;                      // determinant / candidate kernels on the side stream
+};
+
+CallRoute route_call(const akz_ctx* c, int n)
 {
     const AkzPlan& P = c->plan;
-    AkzSet& S = c->S();
-    const int w = P.w, h = P.h;
-    const size_t P0 = (size_t)w * h;
-    const int nlev = (int)P.levels.size();
-    if (nlev == 0) return AKZ_OK;
-    hipStream_t s = c->stream;
-    const int nbins = (int)c->cfg.contrast_factor_num_bins;
-
-    // base_scale_offset and the gradient-histogram scale are config values; the fused tile kernel is
-    // instantiated for the radii the AKAZE path uses (sigma 1.6 -> 4, sigma 1.0 -> 2).
+    const int w = P.w, h = P.h, nbins = (int)c->cfg.contrast_factor_num_bins;
+    CallRoute C;
     // the fused tile kernels are instantiated for the radii of the default configuration (base_scale_offset in
     // (1.5, 2.0] -> radius 4, and the fixed sigma 1.0 -> radius 2); any other base_scale_offset takes the dense
     // stand-alone filter (k_filter1d) for the one blur that depends on it
-    const float sigma0 = (float)c->cfg.base_scale_offset;
-    const int r0 = akz_gaussian_radius(sigma0);
-    const bool tile0 = r0 == 4;
-    GaussTaps t0 = make_taps(tile0 ? sigma0 : 1.6f);
-    GaussTaps t1 = make_taps(1.0f);
-    if (t1.n != 5 || (tile0 && t0.n != 9)) return AKZ_E_INTERNAL;
+    C.sigma0 = (float)c->cfg.base_scale_offset;
+    C.r0 = akz_gaussian_radius(C.sigma0);
+    C.tile0 = C.r0 == 4;
+    C.fused0 = C.tile0 && P.levels[0].deriv_sigma == 2;  // fused blur + first derivatives (default config)
+    C.pair0 = (w & 3) == 0 && c->front_pair;
+    C.pairc = C.pair0 && nbins <= 510;
+    C.fine = C.pairc && c->contrast_fine;
+    if (C.pairc) {
+        // one wave per (frame pair, band, row segment): a batch is cut into kCWavesBatch waves, a few-frame call into
+        // kCSegFew-row segments so that one frame still fills the chip
+        C.nbands = akz_div_up(w, kCBand);
+        C.npairs = (n + 1) / 2;
+        C.seg_rows = n <= kLatencyFrames ? kCSegFew : std::max(akz_div_up(h, akz_div_up(kCWavesBatch, C.npairs * C.nbands)), kCSegFew);
+    }
+    // the side stream shortens the dependency chain of a few-frame call; a batch fills the chip either way (measured:
+    // 6342 vs 6310 frames/s) and its kernels are easier to read in a profile when they do not overlap each other
+    C.det_side = c->det_side_stream && c->stream_det != nullptr && n <= kLatencyFrames;
+    return C;
+}
 
-    akz_timer_begin(c, AKZ_T_SCALE_SPACE, s);
-    // lib.rs:199-201 — Lt[0] = gaussian_blur(image, base_scale_offset); Lsmooth[0] = Lt[0]
-    const bool fused0 = tile0 && P.levels[0].deriv_sigma == 2;  // fused blur + first derivatives (default config)
+struct LevelRoute {
+    // start image and diffusion (levels after the first)
+    int nsteps = 0, nwrites = 0;                 // FED steps; FED launches
+    bool blocked = false, resident = false;      // k_fed_pair; k_level_resident, with its geometry
+    int res_S = 0, res_nw = 0;
+    bool half_in = false, half_out = false;      // the start image is what the previous level's last FED launch wrote (fed_store_half);
+    size_t half_out_fs = 0;                      // this level's last FED launch writes the next octave's, frames half_out_fs apart
+    std::vector<int> groups;                     // the steps of each FED launch (blocked, not resident)
+    bool front_fed = false;                      // front end, first derivatives and the first FED launch in one kernel (k_front_fed)
+    // derivatives and determinant (every level)
+    bool derivs_done = false, pair = false;      // the front end wrote {Lx, Ly}; two-frame kernels
+    bool sigma_fused = false;                    // a sigma the fused front ends and the determinant kernels are specialised (and timed) for
+    bool stream = false;                         // k_det_stream
+};
+
+// Which kernels level i of an n-frame call runs.  `half_handed`: the previous level's route had half_out.
+LevelRoute route_level(const akz_ctx* c, int i, int n, bool fused0, bool half_handed)
+{
+    const AkzPlan& P = c->plan;
+    const int nlev = (int)P.levels.size();
+    const AkzLevel& L = P.levels[i];
+    LevelRoute R;
+    R.sigma_fused = L.deriv_sigma >= 2 && L.deriv_sigma <= 4;
+    if (i > 0) {
+        R.nsteps = (int)L.tau.size();
+        R.blocked = (L.w & 3) == 0 && c->fed_block > 1 && c->front_pair;   // k_fed_pair
+        // steps per launch: the first octave's levels have 3-4 steps; deeper octaves run more steps on smaller
+        // images, where fewer, longer launches win over the smaller useful tile
+        // (measured, 256 x 1080p: 4 / 5 / 6 / 8 steps per launch below the first octave -> 5186 / 5216 / 5259 /
+        // 5299 frames/s; a three-patch halo for up to 12 steps loses again)
+        int fed_block = L.octave == 0 ? (c->fed_block < 4 ? c->fed_block : 4) : c->fed_block;
+        // a call of a few frames is a chain of dependent launches (~5 us each before any work): below the first
+        // octave it runs up to 16 steps per launch (three- and four-patch halos, 40 x 40 / 32 x 32 useful tiles),
+        // which a batch would lose on (see above) and a single frame wins on
+        if (n <= kLatencyFrames && L.octave > 0 && c->fed_block == 8) fed_block = kFedMaxBlock;
+        R.nwrites = R.blocked ? (R.nsteps + fed_block - 1) / fed_block : R.nsteps;  // FED launches
+        // k_level_resident: the whole level (front end + every FED step) in one launch, one workgroup per frame, when
+        // the level is small enough to live on one compute unit (octave 3 of a 1080p pyramid; octaves >= 2 of smaller frames)
+        // One workgroup per frame: a call of few frames leaves most compute units idle under it, and the tile kernels'
+        // many small launches win (1080p, octave 3, serial phase times: 64 frames 5.85 vs 5.78 ms of scale space, 96 frames
+        // a tie, 128 frames 10.74 vs 10.84, 256 frames 20.30 vs 20.82)
+        const int res_min = c->resident_min_frames > 0 ? c->resident_min_frames : (3 * c->n_cu + 7) / 8;
+        R.resident = c->resident_levels && n >= res_min && R.blocked && L.octave > 0 && R.sigma_fused &&
+                     !c->keep_all && R.nsteps >= 1 && R.nsteps <= kResMaxSteps &&
+                     resident_geometry(L.w, L.h, kResR, kResWaves, &R.res_S, &R.res_nw);
+        // The level an octave ends with hands the next octave its half-sized start image straight from the registers of
+        // its last FED launch (fed_store_half) instead of being read back by k_half_size.  The image goes to the plane of
+        // the level AFTER the next one, which nobody touches until that level's own diffusion.
+        R.half_out = !R.resident && R.blocked && R.nsteps > 0 && i + 2 < nlev && P.levels[i + 1].new_octave && P.levels[i + 1].w == (L.w >> 1) &&
+                     P.levels[i + 1].h == (L.h >> 1) && !P.levels[i + 2].new_octave;
+        if (R.half_out) R.half_out_fs = P.levels[i + 1].pixels();
+        R.half_in = L.new_octave && half_handed;
+        // the FED launches of the level: groups of up to fed_block steps, balanced sizes (5 -> 3 + 2)
+        if (R.blocked && !R.resident)
+            for (int left = R.nsteps; left > 0;) {
+                int ngr = (left + fed_block - 1) / fed_block;  // groups still to emit
+                int g = (left + ngr - 1) / ngr;
+                R.groups.push_back(g);
+                left -= g;
+            }
+        // k_front_fed: front end + the first of those launches in one kernel (Lflow stays on chip unless a later
+        // launch of the level needs it: WRITE_FLOW).  The first octave's levels are one or two launches of at most 4
+        // steps (one halo patch, HP = 1); below it the first launch runs up to 8 steps behind a two-patch halo (HP = 2:
+        // rejected in rounds 2-3 at 9636 vs 9781 frames/s, adopted in round 5 at -4.9 % of the scale-space kernel time
+        // once the kernel had lost 17 % of its instructions).  A few-frame call's 9..16-step launches keep the split path.
+        R.front_fed = c->fuse_front_fed && R.blocked && R.sigma_fused && !c->keep_all && !R.groups.empty() &&
+                      R.groups[0] <= (L.octave == 0 ? 4 : 8);
+    }
+    R.derivs_done = i == 0 ? fused0 : R.sigma_fused;
+    R.pair = (L.w & 3) == 0 && c->front_pair;
+    // the streaming kernel wants a few thousand waves (band x 32-row segment x frame); a single frame or the
+    // smallest levels of a small batch keep the tile kernel (single 1080p frame: 1.85 vs 2.02 ms)
+    const int sbw = det_stream_band(R.sigma_fused ? (int)L.deriv_sigma : 2);
+    const size_t stream_waves = (size_t)akz_div_up(L.w, sbw) * (size_t)akz_div_up(L.h, 32) * (size_t)n;
+    R.stream = c->stream_kernels && R.sigma_fused && L.w >= 8 && stream_waves >= c->stream_min_waves;
+    return R;
+}
+
+// lib.rs:199-201 — Lt[0] = gaussian_blur(image, base_scale_offset); Lsmooth[0] = Lt[0]
+template <typename InT> int32_t level0_front(akz_ctx* c, const InT* d_imgs, int n, const CallRoute& C, const GaussTaps& t0, const OffK& kk)
+{
+    AkzSet& S = c->S();
+    const int w = c->plan.w, h = c->plan.h;
+    const size_t P0 = (size_t)w * h;
+    hipStream_t s = c->stream;
     akz_timer_begin(c, AKZ_T_FRONT0, s);
-    if (fused0 && (w & 3) == 0 && c->front_pair) {
-#define AKZ_FRONT0(THV, NTV, TPBV)                                                                                  \
-    AKZ_LAUNCH((k_level_front2<4, 2, THV, NTV, InT, false, TPBV>),                                              \
-                       dim3(akz_div_up(w, kTW), akz_div_up(akz_div_up(h, THV), TPBV), (n + 1) / 2), dim3(NTV), 0, s,    \
-                       d_imgs, w, h, P0, n, t0, make_offk(2), S.Lt[0], (float*)nullptr, S.Lxy[0], (const float*)nullptr, 0)
+    if (C.fused0 && C.pair0) {
         // 32-row tiles (measured against 24 x 512 and against 5 row tiles per block with register prefetch: 10.18
         // vs 10.50 / 10.83 ms of scale space per 64 frames); 512 threads here, where the u8 input leaves registers
         // for eight waves per block (441 vs 490 us per 64 frames), 256 on the f32 levels (178 vs 184 us)
-        AKZ_FRONT0(32, 512, 1);
-#undef AKZ_FRONT0
+        AKZ_LAUNCH((k_level_front2<4, 2, 32, 512, InT, false, 1>), dim3(akz_div_up(w, kTW), akz_div_up(h, 32), (n + 1) / 2), dim3(512), 0, s,
+                   d_imgs, w, h, P0, n, t0, kk, S.Lt[0], (float*)nullptr, S.Lxy[0], (const float*)nullptr, 0);
         AKZ_LAUNCH_CHECK();
-    } else if (fused0) {
-        AKZ_LAUNCH((k_level_front<4, 2, InT, false>), dim3(akz_div_up(w, kTW), akz_div_up(h, kTH), n), dim3(256), 0,
-                           s, d_imgs, w, h, P0, t0, make_offk(2), S.Lt[0], (float*)nullptr, S.Lxy[0],
-                           (const float*)nullptr, 0);
+    } else if (C.fused0) {
+        AKZ_LAUNCH((k_level_front<4, 2, InT, false>), dim3(akz_div_up(w, kTW), akz_div_up(h, kTH), n), dim3(256), 0, s, d_imgs, w, h, P0,
+                   t0, kk, S.Lt[0], (float*)nullptr, S.Lxy[0], (const float*)nullptr, 0);
         AKZ_LAUNCH_CHECK();
-    } else if (tile0) {
+    } else if (C.tile0) {
         AKZ_TRY((launch_blur<4, 0, InT, EPI_BLUR>(c, d_imgs, w, h, P0, t0, S.Lt[0], nullptr, P0, 0, n)));
     } else {
         // generic radius: pixels -> f32 (scratch plane), horizontal pass -> Ldet[0] (free until the determinant
         // kernel of level 0 runs), vertical pass -> Lt[0], frame by frame
-        const int ks = 2 * r0 + 1;
+        const int ks = 2 * C.r0 + 1;
         if (ks > kAkzMaxTaps) return AKZ_E_INVALID;
         c->h_taps.assign((size_t)ks, 0.0f);
-        akz_host_gaussian_kernel(sigma0, ks, c->h_taps.data());
+        akz_host_gaussian_kernel(C.sigma0, ks, c->h_taps.data());
         AKZ_HIP(hipMemcpyAsync(c->d_taps, c->h_taps.data(), sizeof(float) * ks, hipMemcpyHostToDevice, s));
         AKZ_LAUNCH((k_to_f32<InT>), dim3((unsigned)((P0 * n + 255) / 256)), dim3(256), 0, s, d_imgs, S.tmp, P0 * n);
         AKZ_LAUNCH_CHECK();
         for (int f = 0; f < n; ++f) {
-            AKZ_LAUNCH(k_filter1d, grid_px(w, h, 1), dim3(256), 0, s, (const float*)(S.tmp + (size_t)f * P0),
-                               S.Ldet[0] + (size_t)f * P0, w, h, (const float*)c->d_taps, ks, 0);
-            AKZ_LAUNCH(k_filter1d, grid_px(w, h, 1), dim3(256), 0, s, (const float*)(S.Ldet[0] + (size_t)f * P0),
-                               S.Lt[0] + (size_t)f * P0, w, h, (const float*)c->d_taps, ks, 1);
+            AKZ_LAUNCH(k_filter1d, grid_px(w, h, 1), dim3(256), 0, s, (const float*)(S.tmp + (size_t)f * P0), S.Ldet[0] + (size_t)f * P0,
+                       w, h, (const float*)c->d_taps, ks, 0);
+            AKZ_LAUNCH(k_filter1d, grid_px(w, h, 1), dim3(256), 0, s, (const float*)(S.Ldet[0] + (size_t)f * P0), S.Lt[0] + (size_t)f * P0,
+                       w, h, (const float*)c->d_taps, ks, 1);
             AKZ_LAUNCH_CHECK();
         }
     }
     akz_timer_end(c, AKZ_T_FRONT0, s, 1, (uint64_t)P0 * n);
-    // lib.rs:206-211 — contrast factor on the ORIGINAL image
+    return AKZ_OK;
+}
+
+// lib.rs:206-211 — contrast factor on the ORIGINAL image
+template <typename InT> int32_t contrast_factor(akz_ctx* c, const InT* d_imgs, int n, const CallRoute& C, const GaussTaps& t1)
+{
+    const AkzPlan& P = c->plan;
+    AkzSet& S = c->S();
+    const int w = P.w, h = P.h, nbins = (int)c->cfg.contrast_factor_num_bins;
+    const size_t P0 = (size_t)w * h;
+    hipStream_t s = c->stream;
     // d_cmax, d_npoints, d_ncand, d_hist, d_fine: contiguous (carve_set)
     AKZ_HIP(hipMemsetAsync(S.d_cmax, 0, S.zero_bytes, s));
-    const bool pairc = (w & 3) == 0 && c->front_pair && nbins <= 510;
     akz_timer_begin(c, AKZ_T_CONTRAST, s);
-    const bool fine = pairc && c->contrast_fine;
-    if (pairc) {
-        // one wave per (frame pair, band, row segment): a batch is cut into kCWavesBatch waves, a few-frame call into
-        // kCSegFew-row segments so that one frame still fills the chip
-        const int nbands = akz_div_up(w, kCBand), npairs = (n + 1) / 2;
-        const int seg_rows = n <= kLatencyFrames ? kCSegFew
-                                                 : std::max(akz_div_up(h, akz_div_up(kCWavesBatch, npairs * nbands)), kCSegFew);
-        dim3 gridc(akz_div_up(nbands * akz_div_up(h, seg_rows), kCWaves), npairs);
+    if (C.pairc) {
+        dim3 gridc(akz_div_up(C.nbands * akz_div_up(h, C.seg_rows), kCWaves), C.npairs);
         AKZ_LAUNCH((k_contrast_pair<InT, EPI_CMAX>), gridc, dim3(64 * kCWaves), 0, s, d_imgs, w, h, P0, n, t1, S.d_cmax,
-                           (const double*)S.d_cthr, S.d_hist, S.d_npoints, nbins, fine ? S.d_fine : (uint32_t*)nullptr,
-                           (const uint32_t*)nullptr, nbands, seg_rows);
+                   (const double*)S.d_cthr, S.d_hist, S.d_npoints, nbins, C.fine ? S.d_fine : (uint32_t*)nullptr,
+                   (const uint32_t*)nullptr, C.nbands, C.seg_rows);
         AKZ_LAUNCH_CHECK();
         AKZ_LAUNCH(k_contrast_thresholds, dim3(n), dim3(512), 0, s, S.d_cmax, nbins, S.d_cthr);
         AKZ_LAUNCH_CHECK();
-        if (fine) {
-            AKZ_LAUNCH(k_contrast_resolve, dim3(n), dim3(256), 0, s, S.d_cmax, S.d_fine, S.d_npoints,
-                               (const double*)S.d_cthr, nbins, c->cfg.contrast_percentile, P.n_octaves, S.d_contrast,
-                               S.d_invk, S.d_cflag, c->contrast_force_odd ? 1 : 0);
+        if (C.fine) {
+            AKZ_LAUNCH(k_contrast_resolve, dim3(n), dim3(256), 0, s, S.d_cmax, S.d_fine, S.d_npoints, (const double*)S.d_cthr, nbins,
+                       c->cfg.contrast_percentile, P.n_octaves, S.d_contrast, S.d_invk, S.d_cflag, c->contrast_force_odd ? 1 : 0);
             AKZ_LAUNCH_CHECK();
         }
         AKZ_LAUNCH((k_contrast_pair<InT, EPI_CHIST>), gridc, dim3(64 * kCWaves), 0, s, d_imgs, w, h, P0, n, t1, S.d_cmax,
-                           (const double*)S.d_cthr, S.d_hist, S.d_npoints, nbins, (uint32_t*)nullptr,
-                           fine ? (const uint32_t*)S.d_cflag : (const uint32_t*)nullptr, nbands, seg_rows);
+                   (const double*)S.d_cthr, S.d_hist, S.d_npoints, nbins, (uint32_t*)nullptr,
+                   C.fine ? (const uint32_t*)S.d_cflag : (const uint32_t*)nullptr, C.nbands, C.seg_rows);
         AKZ_LAUNCH_CHECK();
     } else {
         AKZ_TRY((launch_blur<2, 1, InT, EPI_CMAX>(c, d_imgs, w, h, P0, t1, nullptr, nullptr, 0, 0, n)));
         AKZ_TRY((launch_blur<2, 1, InT, EPI_CHIST>(c, d_imgs, w, h, P0, t1, nullptr, nullptr, 0, 0, n)));
     }
-    AKZ_LAUNCH(k_contrast_finish, dim3(akz_div_up(n, 64)), dim3(64), 0, s, S.d_cmax, S.d_hist,
-                       S.d_npoints, nbins, c->cfg.contrast_percentile, n, P.n_octaves, S.d_contrast, S.d_invk,
-                       fine ? (const uint32_t*)S.d_cflag : (const uint32_t*)nullptr);
+    AKZ_LAUNCH(k_contrast_finish, dim3(akz_div_up(n, 64)), dim3(64), 0, s, S.d_cmax, S.d_hist, S.d_npoints, nbins,
+               c->cfg.contrast_percentile, n, P.n_octaves, S.d_contrast, S.d_invk, C.fine ? (const uint32_t*)S.d_cflag : (const uint32_t*)nullptr);
     AKZ_LAUNCH_CHECK();
     akz_timer_end(c, AKZ_T_CONTRAST, s, 2, (uint64_t)P0 * n);
+    return AKZ_OK;
+}
 
-    uint64_t fed_launches = 0, fed_units = 0;
-    // the side stream shortens the dependency chain of a few-frame call; a batch fills the chip either way (measured:
-    // 6342 vs 6310 frames/s) and its kernels are easier to read in a profile when they do not overlap each other
-    const bool det_side = c->det_side_stream && c->stream_det != nullptr && n <= kLatencyFrames;
-    int half_ready = -1;        // the level whose half-sized start image its predecessor's last FED launch has written
-    for (int i = 0; i < nlev; ++i) {
-        const AkzLevel& L = P.levels[i];
-        const size_t fs = L.pixels();
-        const float* smooth = S.Lt[0];
-        bool fused_front = false;
-        if (i > 0) {
-            const int nsteps = (int)L.tau.size();
-            // Ping-pong so the last FED step lands in Lt[i]; `init` is where the un-diffused Lt[i] lives.
-            float* bufA = S.Lt[i];
-            float* bufB = S.tmp;
-            const bool blocked = (L.w & 3) == 0 && c->fed_block > 1 && c->front_pair;   // k_fed_pair
-            // steps per launch: the first octave's levels have 3-4 steps; deeper octaves run more steps on smaller
-            // images, where fewer, longer launches win over the smaller useful tile
-            // (measured, 256 x 1080p: 4 / 5 / 6 / 8 steps per launch below the first octave -> 5186 / 5216 / 5259 /
-            // 5299 frames/s; a three-patch halo for up to 12 steps loses again)
-            int fed_block = L.octave == 0 ? (c->fed_block < 4 ? c->fed_block : 4) : c->fed_block;
-            // a call of a few frames is a chain of dependent launches (~5 us each before any work): below the first
-            // octave it runs up to 16 steps per launch (three- and four-patch halos, 40 x 40 / 32 x 32 useful tiles),
-            // which a batch would lose on (see above) and a single frame wins on
-            if (n <= kLatencyFrames && L.octave > 0 && c->fed_block == 8) fed_block = kFedMaxBlock;
-            const int nwrites = blocked ? (nsteps + fed_block - 1) / fed_block : nsteps;  // FED launches
-            // The level an octave ends with hands the next octave its half-sized start image straight from the registers of
-            // its last FED launch (fed_store_half) instead of being read back by k_half_size.  The image goes to the plane of
-            // the level AFTER the next one, which nobody touches until that level's own diffusion.
-            // k_level_resident: the whole level (front end + every FED step) in one launch, one workgroup per frame, when
-            // the level is small enough to live on one compute unit (octave 3 of a 1080p pyramid; octaves >= 2 of smaller frames)
-            int res_S = 0, res_nw = 0;
-            // One workgroup per frame: a call of few frames leaves most compute units idle under it, and the tile kernels'
-            // many small launches win (1080p, octave 3, serial phase times: 64 frames 5.85 vs 5.78 ms of scale space, 96 frames
-            // a tie, 128 frames 10.74 vs 10.84, 256 frames 20.30 vs 20.82)
-            const int res_min = c->resident_min_frames > 0 ? c->resident_min_frames : (3 * c->n_cu + 7) / 8;
-            const bool resident = c->resident_levels && n >= res_min && blocked && L.octave > 0 && L.deriv_sigma >= 2 && L.deriv_sigma <= 4 &&
-                                  !c->keep_all && nsteps >= 1 && nsteps <= kResMaxSteps &&
-                                  resident_geometry(L.w, L.h, kResR, kResWaves, &res_S, &res_nw);
-            float* half_next = nullptr;
-            size_t half_next_fs = 0;
-            if (!resident && blocked && nsteps > 0 && i + 2 < nlev && P.levels[i + 1].new_octave && P.levels[i + 1].w == (L.w >> 1) &&
-                P.levels[i + 1].h == (L.h >> 1) && !P.levels[i + 2].new_octave) {
-                half_next = S.Lt[i + 2];
-                half_next_fs = P.levels[i + 1].pixels();
-            }
-            const float* init;
-            if (L.new_octave && half_ready == i) {
-                init = S.Lt[i + 1];      // written by the previous level's last FED launch (fed_store_half)
-            } else if (L.new_octave) {
-                const AkzLevel& Lp = P.levels[i - 1];
-                // the first FED launch must not write where it reads: with an odd number of launches the
-                // first one writes Lt[i], so the half-sized image goes to the scratch plane, and vice versa
-                float* half_dst = (nwrites % 2 == 0) ? bufA : bufB;
-                if (nwrites == 0) half_dst = bufA;
-                if (resident) half_dst = bufB;   // (one launch that writes Lt[i]: the start image goes to the scratch plane)
-                AKZ_TRY(AKZ_SS(akz_dev_half_size)(s, S.Lt[i - 1], half_dst, Lp.w, Lp.h, n, Lp.pixels(), fs));
-                init = half_dst;
-            } else {
-                init = S.Lt[i - 1];  // lib.rs:230 clone(): read in place, never modified again
-            }
-            // lib.rs:232-248 — Lsmooth = blur(Lt, 1.0); Lx,Ly = simple Scharr; Lflow = pm_g2
-            fused_front = L.deriv_sigma >= 2 && L.deriv_sigma <= 4;
-            if (resident) {
-                FedTausN ft;
-                for (int q = 0; q < kResMaxSteps; ++q) ft.half_tau[q] = q < nsteps ? 0.5f * (float)L.tau[q] : 0.0f;
-                OffK kk = make_offk(L.deriv_sigma);
-                akz_timer_begin(c, AKZ_T_LEVEL_RESIDENT, s);
-#define AKZ_RES(SGV)                                                                                                 \
-    AKZ_LAUNCH((k_level_resident<SGV, kResR, kResWaves>), dim3(n), dim3(res_nw * 64), 0, s, init, L.w, L.h, res_S, fs, t1, kk, ft,   \
-               nsteps, S.Lt[i], S.Lxy[i], (const float*)S.d_invk, (int)L.octave)
-                switch (L.deriv_sigma) {
-                case 2: AKZ_RES(2); break;
-                case 3: AKZ_RES(3); break;
-                default: AKZ_RES(4); break;
-                }
-#undef AKZ_RES
-                AKZ_LAUNCH_CHECK();
-                akz_timer_end(c, AKZ_T_LEVEL_RESIDENT, s, 1, (uint64_t)fs * n);
-                fed_launches += nsteps;
-                fed_units += (uint64_t)nsteps * fs * n;
-            } else {
-            const int t_front = AKZ_T_FRONT_SG2 + (int)L.deriv_sigma - 2;
-            // the FED launches of the level: groups of up to fed_block steps, balanced sizes (5 -> 3 + 2)
-            std::vector<int> groups;
-            if (blocked)
-                for (int left = nsteps; left > 0;) {
-                    int ngr = (left + fed_block - 1) / fed_block;  // groups still to emit
-                    int g = (left + ngr - 1) / ngr;
-                    groups.push_back(g);
-                    left -= g;
-                }
-            // k_front_fed: front end + the first of those launches in one kernel (Lflow stays on chip unless a later
-            // launch of the level needs it: WRITE_FLOW).  The first octave's levels are one or two launches of at most 4
-            // steps (one halo patch, HP = 1); below it the first launch runs up to 8 steps behind a two-patch halo (HP = 2:
-            // rejected in rounds 2-3 at 9636 vs 9781 frames/s, adopted in round 5 at -4.9 % of the scale-space kernel time
-            // once the kernel had lost 17 % of its instructions).  A few-frame call's 9..16-step launches keep the split path.
-            const bool front_fed = c->fuse_front_fed && blocked && fused_front && !c->keep_all && !groups.empty() &&
-                                   groups[0] <= (L.octave == 0 ? 4 : 8);
-            if (front_fed) {
-                const int ng = (int)groups.size();
-                float* dst0 = ((ng - 1) % 2 == 0) ? bufA : bufB;
-                FedTaus ft;
-                for (int q = 0; q < kFedMaxBlock; ++q) ft.half_tau[q] = q < groups[0] ? 0.5f * (float)L.tau[q] : 0.0f;
-                OffK kk = make_offk(L.deriv_sigma);
-                const int t_ff = (L.octave == 0 ? AKZ_T_FRONT_FED_SG2 : AKZ_T_FRONT_FED_DEEP_SG2) + (int)L.deriv_sigma - 2;
-                akz_timer_begin(c, t_ff, s);
-#define AKZ_FF3(SGV, HPV, RGV, WFV)                                                                                  \
-    AKZ_LAUNCH((k_front_fed<SGV, HPV, RGV, WFV>),                                                             \
-                       dim3(akz_div_up(L.w, front_fed_tile(HPV)), akz_div_up(L.h, front_fed_tile(HPV)), (n + 1) / 2), \
-                       dim3(256), 0, s, init, L.w, L.h, fs, n, t1, kk, ft, groups[0], dst0, S.Lflow[i], S.Lxy[i],      \
-                       (const float*)S.d_invk, (int)L.octave, ng == 1 ? half_next : (float*)nullptr, half_next_fs)
-#define AKZ_FF2(SGV, HPV, RGV) if (ng > 1) { AKZ_FF3(SGV, HPV, RGV, true); } else { AKZ_FF3(SGV, HPV, RGV, false); }
-#define AKZ_FF(SGV)                                                                                                  \
-    if (groups[0] <= 3) { AKZ_FF2(SGV, 1, false) } else if (groups[0] == 4) { AKZ_FF2(SGV, 1, true) }               \
-    else if (groups[0] <= 7) { AKZ_FF2(SGV, 2, false) } else { AKZ_FF2(SGV, 2, true) }
-                switch (L.deriv_sigma) {
-                case 2: AKZ_FF(2) break;
-                case 3: AKZ_FF(3) break;
-                default: AKZ_FF(4) break;
-                }
-#undef AKZ_FF
-#undef AKZ_FF2
-#undef AKZ_FF3
-                AKZ_LAUNCH_CHECK();
-                akz_timer_end(c, t_ff, s, 1, (uint64_t)fs * n);
-            } else if (fused_front) {
-                akz_timer_begin(c, t_front, s);
-                float* lsm_out = c->keep_all ? S.Lsm[i] : nullptr;  // Lsmooth stays on chip unless the taps want it
-                dim3 gridf(akz_div_up(L.w, kTW), akz_div_up(L.h, kTH), n);
-                OffK kk = make_offk(L.deriv_sigma);
-#define AKZ_FRONT(SGV)                                                                                               \
-    AKZ_LAUNCH((k_level_front<2, SGV, float, true>), gridf, dim3(256), 0, s, init, L.w, L.h, fs, t1, kk,      \
-                       lsm_out, S.Lflow[i], S.Lxy[i], (const float*)S.d_invk, (int)L.octave)
-#define AKZ_FRONT2X(SGV, THV, NTV, TPBV)                                                                             \
-    AKZ_LAUNCH((k_level_front2<2, SGV, THV, NTV, float, true, TPBV>),                                            \
-                       dim3(akz_div_up(L.w, kTW), akz_div_up(akz_div_up(L.h, THV), TPBV), (n + 1) / 2), dim3(NTV), 0, s, \
-                       init, L.w, L.h, fs, n, t1, kk, lsm_out, S.Lflow[i], S.Lxy[i], (const float*)S.d_invk,            \
-                       (int)L.octave)
-#define AKZ_FRONT2(SGV)                                                                                              \
-    AKZ_FRONT2X(SGV, 32, 256, 1)
-                const bool pair = (L.w & 3) == 0 && c->front_pair;
-                switch (L.deriv_sigma) {
-                case 2: if (pair) { AKZ_FRONT2(2); } else AKZ_FRONT(2); break;
-                case 3: if (pair) { AKZ_FRONT2(3); } else AKZ_FRONT(3); break;
-                default: if (pair) { AKZ_FRONT2(4); } else AKZ_FRONT(4); break;
-                }
-#undef AKZ_FRONT
-#undef AKZ_FRONT2
-#undef AKZ_FRONT2X
-                AKZ_LAUNCH_CHECK();
-                akz_timer_end(c, t_front, s, 1, (uint64_t)fs * n);
-            } else {
-                AKZ_TRY((launch_blur<2, 1, float, EPI_FLOW>(c, init, L.w, L.h, fs, t1, S.Lsm[i], S.Lflow[i], fs,
-                                                           (int)L.octave, n)));
-            }
-            // lib.rs:251-256 — FED cycle
-            akz_timer_begin(c, AKZ_T_FED, s);
-            const float* src = init;
-            if (blocked) {
-                // temporally blocked: the ping-pong parity is chosen per GROUP so that the last group lands in Lt[i]
-                const int ng = (int)groups.size();  // == nwrites
-                int j = 0;
-                for (int gi = 0; gi < ng; ++gi) {
-                    float* dstb = ((ng - 1 - gi) % 2 == 0) ? bufA : bufB;
-                    if (gi == 0 && front_fed) {                    // k_front_fed did this launch
-                        j += groups[0];
-                        src = dstb;
-                        continue;
-                    }
-                    FedTaus ft;
-                    for (int q = 0; q < kFedMaxBlock; ++q) ft.half_tau[q] = q < groups[gi] ? 0.5f * (float)L.tau[j + q] : 0.0f;
-#define AKZ_FED_CASE(TT)                                                                                              \
-    case TT: {                                                                                                        \
-        dim3 gridp(akz_div_up(L.w, fed_tile_edge(TT)), akz_div_up(L.h, fed_tile_edge(TT)), (n + 1) / 2);              \
-        AKZ_LAUNCH((k_fed_pair<TT>), gridp, dim3(256), 0, s, src, S.Lflow[i], dstb, L.w, L.h, fs, n, ft,      \
-                   gi == ng - 1 ? half_next : (float*)nullptr, half_next_fs);                                        \
-    } break;
-                    const int t_fed = AKZ_T_FED_T1 + (groups[gi] <= 8 ? groups[gi] : 8) - 1;   // (9..16 steps: single-frame calls only)
+// Level i of an n-frame call: what its phases share, and the phases in the order scale_space_impl runs them.  Lives for one
+// pass of that loop: `R` and `t1` refer to its locals, and the second row of members is derived from the first (declaration order).
+struct LevelPass {
+    akz_ctx* c; int i, n; const LevelRoute& R; const GaussTaps& t1; OffK kk;   // (what scale_space_impl fills in)
+    AkzSet& S = c->S(); const AkzLevel& L = c->plan.levels[i]; size_t fs = L.pixels(); hipStream_t s = c->stream;
+    const float* init = nullptr;   // where the un-diffused Lt[i] lives (start_image)
+
+    int32_t start_image()
+    {
+        if (R.half_in) {
+            init = S.Lt[i + 1];      // written by the previous level's last FED launch (fed_store_half)
+        } else if (L.new_octave) {
+            const AkzLevel& Lp = c->plan.levels[i - 1];
+            // the first FED launch must not write where it reads: with an odd number of launches the
+            // first one writes Lt[i], so the half-sized image goes to the scratch plane, and vice versa
+            float* half_dst = fed_dst(S, i, -1, R.nwrites);
+            if (R.resident) half_dst = S.tmp;   // (one launch that writes Lt[i]: the start image goes to the scratch plane)
+            AKZ_TRY(AKZ_SS(akz_dev_half_size)(s, S.Lt[i - 1], half_dst, Lp.w, Lp.h, n, Lp.pixels(), fs));
+            init = half_dst;
+        } else {
+            init = S.Lt[i - 1];  // lib.rs:230 clone(): read in place, never modified again
+        }
+        return AKZ_OK;
+    }
+
+    int32_t run_resident()
+    {
+        const FedTausN ft = fed_taus<FedTausN>(L, 0, R.nsteps);
+        akz_timer_begin(c, AKZ_T_LEVEL_RESIDENT, s);
+        with_sigma(L.deriv_sigma, [&](auto sg) {
+            AKZ_LAUNCH((k_level_resident<decltype(sg)::value, kResR, kResWaves>), dim3(n), dim3(R.res_nw * 64), 0, s, init, L.w, L.h, R.res_S,
+                       fs, t1, kk, ft, R.nsteps, S.Lt[i], S.Lxy[i], (const float*)S.d_invk, (int)L.octave);
+        });
+        AKZ_LAUNCH_CHECK();
+        akz_timer_end(c, AKZ_T_LEVEL_RESIDENT, s, 1, (uint64_t)fs * n);
+        return AKZ_OK;
+    }
+
+    // the plane a FED launch leaves the next octave's start image in: the level's last launch, if the route hands one on
+    float* half_next(bool last) const { return last && R.half_out ? S.Lt[i + 2] : (float*)nullptr; }
+
+    int32_t run_front_fed()
+    {
+        const int ng = (int)R.groups.size(), g0 = R.groups[0];
+        const FedTaus ft = fed_taus<FedTaus>(L, 0, g0);
+        const int t_ff = (L.octave == 0 ? AKZ_T_FRONT_FED_SG2 : AKZ_T_FRONT_FED_DEEP_SG2) + (int)L.deriv_sigma - 2;
+        akz_timer_begin(c, t_ff, s);
+        auto launch = [&](auto sg, auto hp, auto ring, auto write_flow) {
+            constexpr int HP = decltype(hp)::value;
+            AKZ_LAUNCH((k_front_fed<decltype(sg)::value, HP, decltype(ring)::value, decltype(write_flow)::value>),
+                       dim3(akz_div_up(L.w, front_fed_tile(HP)), akz_div_up(L.h, front_fed_tile(HP)), (n + 1) / 2), dim3(256), 0, s, init,
+                       L.w, L.h, fs, n, t1, kk, ft, g0, fed_dst(S, i, 0, ng), S.Lflow[i], S.Lxy[i], (const float*)S.d_invk, (int)L.octave,
+                       half_next(ng == 1), R.half_out_fs);
+        };
+        with_sigma(L.deriv_sigma, [&](auto sg) {
+            with_bool(ng > 1, [&](auto write_flow) {
+                if (g0 <= 3) launch(sg, IntC<1>{}, std::false_type{}, write_flow);
+                else if (g0 == 4) launch(sg, IntC<1>{}, std::true_type{}, write_flow);
+                else if (g0 <= 7) launch(sg, IntC<2>{}, std::false_type{}, write_flow);
+                else launch(sg, IntC<2>{}, std::true_type{}, write_flow);
+            });
+        });
+        AKZ_LAUNCH_CHECK();
+        akz_timer_end(c, t_ff, s, 1, (uint64_t)fs * n);
+        return AKZ_OK;
+    }
+
+    // lib.rs:232-248 — Lsmooth = blur(Lt, 1.0); Lx,Ly = simple Scharr; Lflow = pm_g2
+    int32_t front_end()
+    {
+        if (R.front_fed) return run_front_fed();
+        if (!R.sigma_fused) return launch_blur<2, 1, float, EPI_FLOW>(c, init, L.w, L.h, fs, t1, S.Lsm[i], S.Lflow[i], fs, (int)L.octave, n);
+        const int t_front = AKZ_T_FRONT_SG2 + (int)L.deriv_sigma - 2;
+        akz_timer_begin(c, t_front, s);
+        float* lsm_out = c->keep_all ? S.Lsm[i] : nullptr;  // Lsmooth stays on chip unless the taps want it
+        with_sigma(L.deriv_sigma, [&](auto sg) {
+            constexpr int SG = decltype(sg)::value;
+            if (R.pair)
+                AKZ_LAUNCH((k_level_front2<2, SG, 32, 256, float, true, 1>), dim3(akz_div_up(L.w, kTW), akz_div_up(L.h, 32), (n + 1) / 2),
+                           dim3(256), 0, s, init, L.w, L.h, fs, n, t1, kk, lsm_out, S.Lflow[i], S.Lxy[i], (const float*)S.d_invk, (int)L.octave);
+            else
+                AKZ_LAUNCH((k_level_front<2, SG, float, true>), dim3(akz_div_up(L.w, kTW), akz_div_up(L.h, kTH), n), dim3(256), 0, s, init,
+                           L.w, L.h, fs, t1, kk, lsm_out, S.Lflow[i], S.Lxy[i], (const float*)S.d_invk, (int)L.octave);
+        });
+        AKZ_LAUNCH_CHECK();
+        akz_timer_end(c, t_front, s, 1, (uint64_t)fs * n);
+        return AKZ_OK;
+    }
+
+    // lib.rs:251-256 — FED cycle: the launches of the level that the front end did not run, each reading what the one before wrote
+    int32_t fed()
+    {
+        akz_timer_begin(c, AKZ_T_FED, s);
+        const float* src = init;
+        if (R.blocked) {
+            // temporally blocked: the ping-pong parity is chosen per GROUP so that the last group lands in Lt[i]
+            const int ng = (int)R.groups.size();  // == nwrites
+            for (int gi = 0, j = 0; gi < ng; j += R.groups[gi], ++gi) {
+                float* dstb = fed_dst(S, i, gi, ng);
+                if (!(gi == 0 && R.front_fed)) {                    // (k_front_fed did that launch)
+                    const FedTaus ft = fed_taus<FedTaus>(L, j, R.groups[gi]);
+                    const int t_fed = AKZ_T_FED_T1 + (R.groups[gi] <= 8 ? R.groups[gi] : 8) - 1;   // (9..16 steps: single-frame calls only)
                     akz_timer_begin(c, t_fed, s);
-                    switch (groups[gi]) {
-                        AKZ_FED_CASE(1) AKZ_FED_CASE(2) AKZ_FED_CASE(3) AKZ_FED_CASE(4)
-                        AKZ_FED_CASE(5) AKZ_FED_CASE(6) AKZ_FED_CASE(7) AKZ_FED_CASE(8)
-                        AKZ_FED_CASE(9) AKZ_FED_CASE(10) AKZ_FED_CASE(11) AKZ_FED_CASE(12)
-                        AKZ_FED_CASE(13) AKZ_FED_CASE(14) AKZ_FED_CASE(15) AKZ_FED_CASE(16)
-                    }
-#undef AKZ_FED_CASE
+                    with_steps(R.groups[gi], [&](auto steps) {
+                        constexpr int T = decltype(steps)::value;
+                        dim3 gridp(akz_div_up(L.w, fed_tile_edge(T)), akz_div_up(L.h, fed_tile_edge(T)), (n + 1) / 2);
+                        AKZ_LAUNCH((k_fed_pair<T>), gridp, dim3(256), 0, s, src, S.Lflow[i], dstb, L.w, L.h, fs, n, ft, half_next(gi == ng - 1),
+                                   R.half_out_fs);
+                    });
                     AKZ_LAUNCH_CHECK();
                     akz_timer_end(c, t_fed, s, 1, (uint64_t)fs * n);
-                    j += groups[gi];
-                    src = dstb;
                 }
-            } else
-            for (int j = 0; j < nsteps; ++j) {
-                float* dst = ((nsteps - 1 - j) % 2 == 0) ? bufA : bufB;
+                src = dstb;
+            }
+        } else {
+            for (int j = 0; j < R.nsteps; ++j) {
+                float* dst = fed_dst(S, i, j, R.nsteps);
                 float half_tau = 0.5f * (float)L.tau[j];
-                AKZ_LAUNCH(k_fed_step, grid_px(L.w, L.h, n), dim3(256), 0, s, src, S.Lflow[i], dst, L.w, L.h, fs,
-                                   half_tau);
+                AKZ_LAUNCH(k_fed_step, grid_px(L.w, L.h, n), dim3(256), 0, s, src, S.Lflow[i], dst, L.w, L.h, fs, half_tau);
                 AKZ_LAUNCH_CHECK();
                 src = dst;
             }
-            akz_timer_end(c, AKZ_T_FED, s, (uint64_t)nwrites, (uint64_t)nsteps * fs * n, (uint64_t)nwrites * fs * n);
-            if (half_next) half_ready = i + 1;
-            fed_launches += nsteps;
-            fed_units += (uint64_t)nsteps * fs * n;
-            if (nsteps == 0 && init != bufA)
-                AKZ_HIP(hipMemcpyAsync(bufA, init, sizeof(float) * fs * n, hipMemcpyDeviceToDevice, s));
-            }   // !resident
-            smooth = S.Lsm[i];
         }
-        // detector_response.rs:60-67 + :33-57
-        OffK k = make_offk(L.deriv_sigma);
-        if (!(i == 0 ? fused0 : fused_front)) {
-            AKZ_LAUNCH(k_deriv_first, grid_px(L.w, L.h, n), dim3(256), 0, s, smooth, S.Lxy[i], L.w, L.h, fs,
-                               (int)L.deriv_sigma, k);
+        akz_timer_end(c, AKZ_T_FED, s, (uint64_t)R.nwrites, (uint64_t)R.nsteps * fs * n, (uint64_t)R.nwrites * fs * n);
+        if (R.nsteps == 0 && init != S.Lt[i]) AKZ_HIP(hipMemcpyAsync(S.Lt[i], init, sizeof(float) * fs * n, hipMemcpyDeviceToDevice, s));
+        return AKZ_OK;
+    }
+
+    // detector_response.rs:60-67 + :33-57
+    int32_t determinant(bool det_side)
+    {
+        if (!R.derivs_done) {
+            const float* smooth = i == 0 ? S.Lt[0] : S.Lsm[i];
+            AKZ_LAUNCH(k_deriv_first, grid_px(L.w, L.h, n), dim3(256), 0, s, smooth, S.Lxy[i], L.w, L.h, fs, (int)L.deriv_sigma, kk);
             AKZ_LAUNCH_CHECK();
         }
-        {
-            // {Lx, Ly} of this level are complete on `s_main`: the determinant / candidate kernel is a side branch
-            hipStream_t s_main = s;
-            if (det_side) {
-                AKZ_HIP(hipEventRecord(c->ev_level[i], s_main));
-                AKZ_HIP(hipStreamWaitEvent(c->stream_det, c->ev_level[i], 0));
-            }
-            hipStream_t s = det_side ? c->stream_det : s_main;
-            CandParams cp;
-            cp.thr = (float)c->cfg.detector_threshold;
-            cp.border = L.cand_border;
-            cp.level = (uint32_t)i;
-            cp.cap = c->max_cand;
-            cp.x_lo = L.cand_x_lo; cp.x_hi = L.cand_x_hi; cp.y_lo = L.cand_y_lo; cp.y_hi = L.cand_y_hi;
-            dim3 grid2(akz_div_up(L.w, 64), akz_div_up(L.h, 32), n);
-            float* ldet_out = c->keep_all ? S.Ldet[i] : nullptr;   // refinement reads the candidates' own 3x3 values
-#define AKZ_D2(SGV)                                                                                                  \
-    AKZ_LAUNCH((k_deriv_second_cand<SGV>), grid2, dim3(256), 0, s, S.Lxy[i], ldet_out, L.w, L.h, fs,          \
-                       (int)L.deriv_sigma, k, L.sigma_quat, cp, (CandU*)S.d_cand_u, S.d_ncand, c->d_err)
-#define AKZ_D2P(SGV)                                                                                                 \
-    AKZ_LAUNCH((k_deriv_second_cand2<SGV, kDTH, 256>),                                                       \
-                       dim3(akz_div_up(L.w, 64), akz_div_up(L.h, kDTH), (n + 1) / 2), dim3(256), 0, s, S.Lxy[i],     \
-                       ldet_out, L.w, L.h, fs, n, k, L.sigma_quat, cp, (CandU*)S.d_cand_u, S.d_ncand, c->d_err)
-            const bool pair2 = (L.w & 3) == 0 && c->front_pair;
-            const bool t_det_on = L.deriv_sigma >= 2 && L.deriv_sigma <= 4;
-            if (t_det_on) akz_timer_begin(c, AKZ_T_DET_SG2 + (int)L.deriv_sigma - 2, s);
-            // streaming kernel: a wave per (band of columns, segment of rows, frame); segments sized so that the
-            // launch holds a few waves per SIMD of the chip, never shorter than 32 rows (each segment re-reads
-            // 2 sigma + 2 rows of warm-up)
-#define AKZ_DS(SGV)                                                                                                  \
-    {                                                                                                                \
-        const int nb = akz_div_up(L.w, det_stream_band(SGV));                                                        \
-        int nseg = akz_div_up(c->det_stream_waves, nb * n);                                                          \
-        const int max_seg = akz_div_up(L.h, 32);                                                                     \
-        nseg = nseg < 1 ? 1 : (nseg > max_seg ? max_seg : nseg);                                                     \
-        const int seg_rows = akz_div_up(L.h, nseg);                                                                  \
-        nseg = akz_div_up(L.h, seg_rows);                                                                            \
-        if (ldet_out)                                                                                                \
-            AKZ_LAUNCH((k_det_stream<SGV, true>), dim3(akz_div_up(nb * nseg, 4), n), dim3(256), 0, s, S.Lxy[i],  \
-                               ldet_out, L.w, L.h, fs, k, L.sigma_quat, cp, (CandU*)S.d_cand_u, S.d_ncand, c->d_err, nb, \
-                               seg_rows);                                                                            \
-        else                                                                                                         \
-            AKZ_LAUNCH((k_det_stream<SGV, false>), dim3(akz_div_up(nb * nseg, 4), n), dim3(256), 0, s, S.Lxy[i], \
-                               ldet_out, L.w, L.h, fs, k, L.sigma_quat, cp, (CandU*)S.d_cand_u, S.d_ncand, c->d_err, nb, \
-                               seg_rows);                                                                            \
-    }
-            // the streaming kernel wants a few thousand waves (band x 32-row segment x frame); a single frame or the
-            // smallest levels of a small batch keep the tile kernel (single 1080p frame: 1.85 vs 2.02 ms)
-            const int sbw = det_stream_band(L.deriv_sigma >= 2 && L.deriv_sigma <= 4 ? (int)L.deriv_sigma : 2);
-            const size_t stream_waves = (size_t)akz_div_up(L.w, sbw) * (size_t)akz_div_up(L.h, 32) * (size_t)n;
-            const bool stream = c->stream_kernels && t_det_on && L.w >= 8 && stream_waves >= c->stream_min_waves;
-            switch (L.deriv_sigma) {
-            case 2: if (stream) { AKZ_DS(2); } else if (pair2) { AKZ_D2P(2); } else AKZ_D2(2); break;
-            case 3: if (stream) { AKZ_DS(3); } else if (pair2) { AKZ_D2P(3); } else AKZ_D2(3); break;
-            case 4: if (stream) { AKZ_DS(4); } else if (pair2) { AKZ_D2P(4); } else AKZ_D2(4); break;
-            default: AKZ_D2(0); break;
-            }
-#undef AKZ_DS
-#undef AKZ_D2
-#undef AKZ_D2P
-            AKZ_LAUNCH_CHECK();
-            if (t_det_on) akz_timer_end(c, AKZ_T_DET_SG2 + (int)L.deriv_sigma - 2, s, 1, (uint64_t)fs * n);
+        // {Lx, Ly} of this level are complete on `s`: the determinant / candidate kernel is a side branch
+        if (det_side) {
+            AKZ_HIP(hipEventRecord(c->ev_level[i], s));
+            AKZ_HIP(hipStreamWaitEvent(c->stream_det, c->ev_level[i], 0));
         }
+        hipStream_t s_det = det_side ? c->stream_det : s;
+        CandParams cp;
+        cp.thr = (float)c->cfg.detector_threshold;
+        cp.border = L.cand_border;
+        cp.level = (uint32_t)i;
+        cp.cap = c->max_cand;
+        cp.x_lo = L.cand_x_lo; cp.x_hi = L.cand_x_hi; cp.y_lo = L.cand_y_lo; cp.y_hi = L.cand_y_hi;
+        float* ldet_out = c->keep_all ? S.Ldet[i] : nullptr;   // refinement reads the candidates' own 3x3 values
+        CandU* cand = (CandU*)S.d_cand_u;
+        if (R.sigma_fused) akz_timer_begin(c, AKZ_T_DET_SG2 + (int)L.deriv_sigma - 2, s_det);
+        if (!R.sigma_fused) {   // any other derivative sigma: the generic tile kernel
+            AKZ_LAUNCH((k_deriv_second_cand<0>), dim3(akz_div_up(L.w, 64), akz_div_up(L.h, 32), n), dim3(256), 0, s_det, S.Lxy[i], ldet_out,
+                       L.w, L.h, fs, (int)L.deriv_sigma, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err);
+        } else {
+            with_sigma(L.deriv_sigma, [&](auto sg) {
+                constexpr int SG = decltype(sg)::value;
+                if (R.stream) {
+                    // streaming kernel: a wave per (band of columns, segment of rows, frame); segments sized so that the
+                    // launch holds a few waves per SIMD of the chip, never shorter than 32 rows (each segment re-reads
+                    // 2 sigma + 2 rows of warm-up)
+                    const int nb = akz_div_up(L.w, det_stream_band(SG));
+                    int nseg = akz_div_up(c->det_stream_waves, nb * n);
+                    const int max_seg = akz_div_up(L.h, 32);
+                    nseg = nseg < 1 ? 1 : (nseg > max_seg ? max_seg : nseg);
+                    const int seg_rows = akz_div_up(L.h, nseg);
+                    nseg = akz_div_up(L.h, seg_rows);
+                    with_bool(ldet_out != nullptr, [&](auto write_det) {
+                        AKZ_LAUNCH((k_det_stream<SG, decltype(write_det)::value>), dim3(akz_div_up(nb * nseg, 4), n), dim3(256), 0, s_det,
+                                   S.Lxy[i], ldet_out, L.w, L.h, fs, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err, nb, seg_rows);
+                    });
+                } else if (R.pair) {
+                    AKZ_LAUNCH((k_deriv_second_cand2<SG, kDTH, 256>), dim3(akz_div_up(L.w, 64), akz_div_up(L.h, kDTH), (n + 1) / 2), dim3(256),
+                               0, s_det, S.Lxy[i], ldet_out, L.w, L.h, fs, n, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err);
+                } else {
+                    AKZ_LAUNCH((k_deriv_second_cand<SG>), dim3(akz_div_up(L.w, 64), akz_div_up(L.h, 32), n), dim3(256), 0, s_det, S.Lxy[i],
+                               ldet_out, L.w, L.h, fs, (int)L.deriv_sigma, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err);
+                }
+            });
+        }
+        AKZ_LAUNCH_CHECK();
+        if (R.sigma_fused) akz_timer_end(c, AKZ_T_DET_SG2 + (int)L.deriv_sigma - 2, s_det, 1, (uint64_t)fs * n);
+        return AKZ_OK;
     }
-    if (det_side) {
+};
+
+int32_t sort_candidates(akz_ctx* c, int n)
+{
+    AkzSet& S = c->S();
+    const AkzPlan& P = c->plan;
+    const int nlev = (int)P.levels.size();
+    uint32_t np2 = 1;
+    while (np2 < c->max_cand) np2 <<= 1;
+    const uint32_t lds_keys = np2 < kAkzLdsSortKeys ? np2 : kAkzLdsSortKeys;
+    CandLevelRows cand_rows;
+    for (int i = 0; i < kAkzMaxLevels; ++i) cand_rows.h[i] = i < nlev ? (uint32_t)P.levels[i].h : 0u;
+    if (n <= kLatencyFrames)
+        AKZ_LAUNCH(k_cand_rank, dim3(akz_div_up((int)c->max_cand, 32), nlev, n), dim3(256), 0, c->stream, (const CandU*)S.d_cand_u,
+                   S.d_ncand, c->max_cand, S.d_cand, S.d_cand_nb);
+    else
+        AKZ_LAUNCH(k_cand_sort, dim3(nlev, n), dim3(1024), std::max<size_t>(sizeof(unsigned long long) * lds_keys, kCandRadixLdsBytes), c->stream,
+                   (const CandU*)S.d_cand_u, S.d_ncand, c->max_cand, S.d_cand, S.d_cand_nb, S.d_keys_cand, np2, lds_keys, cand_rows);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+}  // namespace
+
+template <typename InT>
+static int32_t scale_space_impl(akz_ctx* c, const InT* d_imgs, int n)
+{
+    const AkzPlan& P = c->plan;
+    const int nlev = (int)P.levels.size();
+    if (nlev == 0) return AKZ_OK;
+    hipStream_t s = c->stream;
+    const CallRoute C = route_call(c, n);
+    GaussTaps t0 = make_taps(C.tile0 ? C.sigma0 : 1.6f);
+    GaussTaps t1 = make_taps(1.0f);
+    if (t1.n != 5 || (C.tile0 && t0.n != 9)) return AKZ_E_INTERNAL;
+
+    akz_timer_begin(c, AKZ_T_SCALE_SPACE, s);
+    const OffK kk0 = make_offk(P.levels[0].deriv_sigma);
+    AKZ_TRY(level0_front(c, d_imgs, n, C, t0, kk0));
+    AKZ_TRY(contrast_factor(c, d_imgs, n, C, t1));
+    bool half_handed = false;   // the level before wrote this level's half-sized start image with its last FED launch
+    for (int i = 0; i < nlev; ++i) {
+        const LevelRoute R = route_level(c, i, n, C.fused0, half_handed);
+        LevelPass lv{c, i, n, R, t1, i == 0 ? kk0 : make_offk(P.levels[i].deriv_sigma)};
+        if (i > 0) {
+            AKZ_TRY(lv.start_image());
+            if (R.resident) {
+                AKZ_TRY(lv.run_resident());
+            } else {
+                AKZ_TRY(lv.front_end());
+                AKZ_TRY(lv.fed());
+            }
+        }
+        AKZ_TRY(lv.determinant(C.det_side));
+        half_handed = R.half_out;
+    }
+    if (C.det_side) {
         AKZ_HIP(hipEventRecord(c->ev_det_done, c->stream_det));
         AKZ_HIP(hipStreamWaitEvent(s, c->ev_det_done, 0));
     }
-    {
-        uint32_t np2 = 1;
-        while (np2 < c->max_cand) np2 <<= 1;
-        const uint32_t lds_keys = np2 < kAkzLdsSortKeys ? np2 : kAkzLdsSortKeys;
-        CandLevelRows cand_rows;
-        for (int i = 0; i < kAkzMaxLevels; ++i) cand_rows.h[i] = i < nlev ? (uint32_t)P.levels[i].h : 0u;
-        if (n <= kLatencyFrames)
-            AKZ_LAUNCH(k_cand_rank, dim3(akz_div_up((int)c->max_cand, 32), nlev, n), dim3(256), 0, s, (const CandU*)S.d_cand_u,
-                               S.d_ncand, c->max_cand, S.d_cand, S.d_cand_nb);
-        else
-            AKZ_LAUNCH(k_cand_sort, dim3(nlev, n), dim3(1024),
-                               std::max<size_t>(sizeof(unsigned long long) * lds_keys, kCandRadixLdsBytes), s, (const CandU*)S.d_cand_u,
-                               S.d_ncand, c->max_cand, S.d_cand, S.d_cand_nb, S.d_keys_cand, np2, lds_keys, cand_rows);
-        AKZ_LAUNCH_CHECK();
-    }
+    AKZ_TRY(sort_candidates(c, n));
     akz_timer_end(c, AKZ_T_SCALE_SPACE, s, 0, (uint64_t)n);
-    (void)fed_launches;
-    (void)fed_units;
     return AKZ_OK;
 }
 

@@ -1796,6 +1796,25 @@ def test_every_option_gives_the_same_bits(gpu, oracle, name, kw):
         ctx.close()
 
 
+def test_streaming_determinant_kernel_writes_the_ldet_tap(gpu, oracle):
+    """k_det_stream<sigma, WRITE_DET = true>: a keep_all context streams its determinant launches only in a batch of many
+    large frames, so the option set "streaming kernels everywhere" is given to a keep_all context here.  Ldet of every level
+    of both frames of a pair, keypoints and descriptor bytes equal the oracle's at 640x400 and at a ragged 333x251."""
+    akaze, _ = gpu
+    for (w, h) in ((640, 400), (333, 251)):
+        frames = [synth_frame(w, h, seed=3000 + i, n_rect=40, n_disc=40) for i in range(2)]
+        ctx = akaze.Context(akaze.Akaze.default(), w, h, 2, _opts(keep_all=True, stream_min_waves=1, stream_waves=64))
+        got = ctx.extract_batch(frames)
+        orc = oracle.Akaze(w, h, oracle.default_config())
+        for i in reversed(range(2)):        # (the oracle's buffers are those of the frame it extracted last)
+            okp, od = orc.extract(frames[i])
+            _kp_eq(got[i][0], okp, f"{w}x{h} frame {i}")
+            _eq(got[i][1], od, f"{w}x{h} frame {i} desc")
+            for lvl in range(orc.num_levels):
+                _eq(ctx.level_buffer(i, lvl, "Ldet", w, h), orc.buffer(lvl, "Ldet"), f"{w}x{h} frame {i} Ldet[{lvl}]")
+        ctx.close()
+
+
 @pytest.mark.parametrize("w,h,nfr", [(960, 540, 1), (960, 540, 5), (1024, 512, 2), (1024, 576, 1), (640, 360, 3), (320, 180, 1),
                                      (512, 96, 2), (168, 1100, 1)])
 def test_levels_resident_on_one_compute_unit(gpu, oracle, w, h, nfr):
