@@ -1138,6 +1138,48 @@ __device__ __forceinline__ uint2 xcd_block2(uint32_t bx, uint32_t by, uint32_t g
     return make_uint2(t - y * gx, y);
 }
 
+// do_subpixel_refinement, scale_space_extrema.rs:301-347.  Moves the keypoint to the vertex of the quadratic through the nine
+// determinant values around it and doubles its size; false (the keypoint untouched but for the angle) when the vertex lies
+// more than a pixel away.
+// Ldet around (x, y): the keypoint sits on the pixel of the candidate that occupies its cache slot, and the candidate list
+// carries those nine values (k_deriv_second_cand*, k_cand_sort), so the Ldet planes are never read here.  kp->angle holds
+// the candidate's index inside its level (k_sup_resolve / k_suppress) until it is overwritten below.
+__device__ __forceinline__ bool subpixel_fit(const LevelTable& T, const float* __restrict__ cand_nb, uint32_t max_cand, int frame,
+                                             DevKp* kp)
+{
+    const LevelDesc* Lp = &T.L[kp->class_id];
+    const float ratio = ldexpf(1.0f, (int)kp->octave);
+    int x = (int)sat_u32(roundf(kp->x / ratio));
+    int y = (int)sat_u32(roundf(kp->y / ratio));
+    const uint32_t cidx = __float_as_uint(kp->angle);
+    const float4* nbp = reinterpret_cast<const float4*>(cand_nb + (((size_t)frame * kAkzMaxLevels + kp->class_id) * max_cand + cidx) * 8);
+    const float4 n0 = nbp[0], n1 = nbp[1];
+    kp->angle = 0.0f;
+    float x_i = kp->response;   // Ldet at the pixel (> threshold > 0, so |v| = v)
+    float x_m_y_m = n0.x, y_m = n0.y, x_p_y_m = n0.z, x_m = n0.w, x_p = n1.x, x_m_y_p = n1.y, y_p = n1.z, x_p_y_p = n1.w;
+    float d_x = 0.5f * (x_p - x_m);
+    float d_y = 0.5f * (y_p - y_m);
+    float d_xx = x_p + x_m - 2.0f * x_i;
+    float d_yy = y_p + y_m - 2.0f * x_i;
+    float d_xy = 0.25f * (x_p_y_p + x_m_y_m) - 0.25f * (x_p_y_m + x_m_y_p);
+    float inv_det_a = 1.0f / (d_xx * d_yy - d_xy * d_xy);
+    float inv_a0 = inv_det_a * d_yy;
+    float inv_a1 = inv_det_a * -d_xy;
+    float inv_a2 = inv_det_a * -d_xy;
+    float inv_a3 = inv_det_a * d_xx;
+    float dst0 = -d_x * inv_a0 + -d_y * inv_a1;
+    float dst1 = -d_x * inv_a2 + -d_y * inv_a3;
+    const bool keep = fabsf(dst0) <= 1.0f && fabsf(dst1) <= 1.0f;
+    if (keep) {
+        float nx = (float)x + dst0, ny = (float)y + dst1;
+        float power = ldexpf(1.0f, (int)Lp->octave);
+        kp->x = nx * power + 0.5f * (power - 1.0f);
+        kp->y = ny * power + 0.5f * (power - 1.0f);
+        kp->size = kp->size * 2.0f;
+    }
+    return keep;
+}
+
 __global__ __launch_bounds__(256) void k_refine(LevelTable T, const OriTables* __restrict__ ori_p,
                                                 const DevKp* __restrict__ in,
                                                 const uint32_t* __restrict__ n_in, uint32_t stride,
@@ -1165,43 +1207,10 @@ __global__ __launch_bounds__(256) void k_refine(LevelTable T, const OriTables* _
     DevKp kp;
     bool keep = false;
     const LevelDesc* Lp = &T.L[0];
-    float ratio = 1.0f;
     if (active) {
         kp = in[(size_t)frame * stride + ki];
         Lp = &T.L[kp.class_id];
-        // do_subpixel_refinement, :301-347 (every lane computes the same scalars)
-        ratio = ldexpf(1.0f, (int)kp.octave);
-        int x = (int)sat_u32(roundf(kp.x / ratio));
-        int y = (int)sat_u32(roundf(kp.y / ratio));
-        // Ldet around (x, y): the keypoint sits on the pixel of the candidate that occupies its cache slot, and the
-        // candidate list carries those nine values (k_deriv_second_cand*, k_cand_sort), so the Ldet planes are
-        // never read here.  kp.angle holds the candidate's index inside its level until it is overwritten below.
-        const uint32_t cidx = __float_as_uint(kp.angle);
-        const float4* nbp = reinterpret_cast<const float4*>(cand_nb + (((size_t)frame * kAkzMaxLevels + kp.class_id) * max_cand + cidx) * 8);
-        const float4 n0 = nbp[0], n1 = nbp[1];
-        kp.angle = 0.0f;
-        float x_i = kp.response;   // Ldet at the pixel (> threshold > 0, so |v| = v)
-        float x_m_y_m = n0.x, y_m = n0.y, x_p_y_m = n0.z, x_m = n0.w, x_p = n1.x, x_m_y_p = n1.y, y_p = n1.z, x_p_y_p = n1.w;
-        float d_x = 0.5f * (x_p - x_m);
-        float d_y = 0.5f * (y_p - y_m);
-        float d_xx = x_p + x_m - 2.0f * x_i;
-        float d_yy = y_p + y_m - 2.0f * x_i;
-        float d_xy = 0.25f * (x_p_y_p + x_m_y_m) - 0.25f * (x_p_y_m + x_m_y_p);
-        float inv_det_a = 1.0f / (d_xx * d_yy - d_xy * d_xy);
-        float inv_a0 = inv_det_a * d_yy;
-        float inv_a1 = inv_det_a * -d_xy;
-        float inv_a2 = inv_det_a * -d_xy;
-        float inv_a3 = inv_det_a * d_xx;
-        float dst0 = -d_x * inv_a0 + -d_y * inv_a1;
-        float dst1 = -d_x * inv_a2 + -d_y * inv_a3;
-        keep = fabsf(dst0) <= 1.0f && fabsf(dst1) <= 1.0f;
-        if (keep) {
-            float nx = (float)x + dst0, ny = (float)y + dst1;
-            float power = ldexpf(1.0f, (int)Lp->octave);
-            kp.x = nx * power + 0.5f * (power - 1.0f);
-            kp.y = ny * power + 0.5f * (power - 1.0f);
-            kp.size = kp.size * 2.0f;
-        }
+        keep = subpixel_fit(T, cand_nb, max_cand, frame, &kp);   // every lane computes the same scalars
     }
     // compute_main_orientation, :229-288
     if (active && keep) {
@@ -1784,37 +1793,7 @@ __global__ __launch_bounds__(256) void k_refine_pos(LevelTable T, const DevKp* _
     const uint32_t ki = blockIdx.x * 256 + threadIdx.x;
     if (ki >= n) return;
     DevKp kp = in[(size_t)frame * stride + ki];
-    const LevelDesc* Lp = &T.L[kp.class_id];
-    // do_subpixel_refinement, :301-347
-    const float ratio = ldexpf(1.0f, (int)kp.octave);
-    int x = (int)sat_u32(roundf(kp.x / ratio));
-    int y = (int)sat_u32(roundf(kp.y / ratio));
-    const uint32_t cidx = __float_as_uint(kp.angle);   // the candidate's index inside its level (k_sup_resolve / k_suppress)
-    const float4* nbp = reinterpret_cast<const float4*>(cand_nb + (((size_t)frame * kAkzMaxLevels + kp.class_id) * max_cand + cidx) * 8);
-    const float4 n0 = nbp[0], n1 = nbp[1];
-    kp.angle = 0.0f;
-    float x_i = kp.response;   // Ldet at the pixel (> threshold > 0, so |v| = v)
-    float x_m_y_m = n0.x, y_m = n0.y, x_p_y_m = n0.z, x_m = n0.w, x_p = n1.x, x_m_y_p = n1.y, y_p = n1.z, x_p_y_p = n1.w;
-    float d_x = 0.5f * (x_p - x_m);
-    float d_y = 0.5f * (y_p - y_m);
-    float d_xx = x_p + x_m - 2.0f * x_i;
-    float d_yy = y_p + y_m - 2.0f * x_i;
-    float d_xy = 0.25f * (x_p_y_p + x_m_y_m) - 0.25f * (x_p_y_m + x_m_y_p);
-    float inv_det_a = 1.0f / (d_xx * d_yy - d_xy * d_xy);
-    float inv_a0 = inv_det_a * d_yy;
-    float inv_a1 = inv_det_a * -d_xy;
-    float inv_a2 = inv_det_a * -d_xy;
-    float inv_a3 = inv_det_a * d_xx;
-    float dst0 = -d_x * inv_a0 + -d_y * inv_a1;
-    float dst1 = -d_x * inv_a2 + -d_y * inv_a3;
-    const bool keep = fabsf(dst0) <= 1.0f && fabsf(dst1) <= 1.0f;
-    if (keep) {
-        float nx = (float)x + dst0, ny = (float)y + dst1;
-        float power = ldexpf(1.0f, (int)Lp->octave);
-        kp.x = nx * power + 0.5f * (power - 1.0f);
-        kp.y = ny * power + 0.5f * (power - 1.0f);
-        kp.size = kp.size * 2.0f;
-    }
+    const bool keep = subpixel_fit(T, cand_nb, max_cand, frame, &kp);
     out[(size_t)frame * stride + ki] = kp;
     flag[(size_t)frame * stride + ki] = keep ? 1u : 0u;
 }
@@ -2317,100 +2296,72 @@ int32_t akz_upload_tables(akz_ctx* c)
     return AKZ_OK;
 }
 
-int32_t akz_run_keypoints(akz_ctx* c, int n, DevKp* d_kps, akz_descriptor* d_descs, uint32_t cap_per_img,
-                          uint32_t* d_n_out, uint32_t* h_err_copy)
+// ---- the keypoint stage's host code: route, then launch ---------------------------------------------------------------
+// The templated kernels, named once in the order the code object has carried them since they were written: implicit
+// instantiations are emitted in the order of their first mention (rs_ransac.hip's kKernelOrder), so the host code below can
+// be edited without reordering the device code.
+[[maybe_unused]] static const void* const kKernelOrder[] = {
+    (const void*)k_sup_resolve<true>,        (const void*)k_sup_resolve<false>,      (const void*)k_compact<false>,
+    (const void*)k_rank_sort<RANK_RESPONSE>, (const void*)k_rank_sort<RANK_SPATIAL>, (const void*)k_compact<true>};
+
+// Every decision of one call.  route_keypoints makes them and enqueues nothing; the phase functions below launch what the
+// route says and decide nothing.
+enum VisitOrder {
+    VISIT_STORED,    // non-default pattern: k_describe walks the list as stored
+    VISIT_RASTER,    // the pre-sort order, written by the response sort
+    VISIT_RANK,      // k_rank_sort<RANK_SPATIAL>
+    VISIT_TILE,      // k_tile_order
+    VISIT_BITONIC,   // k_spatial_order
+};
+struct KeypointRoute {
+    // A12b, first pass
+    bool sup_parallel;       // k_cand_rows, k_sup_adj, k_sup_resolve first; k_suppress then takes only the frames they flag
+    bool resolve_chunked;    // k_sup_resolve<true>: the chunks of a frame on workgroups of their own
+    dim3 grid_adj, grid_resolve;
+    bool big_pass;           // k_suppress_big after k_suppress
+    bool clear_big_flag;     // d_big_flag is cleared on its own (the parallel path clears it together with its flags)
+    // A12b, second pass
+    uint32_t kb, yr_stride;  // blocks of 256 cache entries, 64-entry chunks per frame
+    // A13 + A14
+    uint32_t kw;             // blocks of four waves, one keypoint per wave
+    bool fast_desc;          // the default pattern: k_describe_fast / k_orient_describe and a visiting order
+    bool orient_in_desc;     // k_refine_pos here, the orientation in k_orient_describe
+    // A15
+    uint32_t maxf;
+    bool rank_sorts;         // k_rank_sort, not one block per frame
+    bool raster_visit;
+    dim3 grid_rank;
+    uint32_t np2, lds_keys;  // padded list length of the largest frame; keys the bitonic orders hold in LDS
+    size_t sort_lds;
+    // A16 + A17
+    VisitOrder order;
+    uint32_t nbuckets;       // (level, tile) buckets of a frame: VISIT_TILE and VISIT_BITONIC
+    size_t order_lds;
+};
+
+static KeypointRoute route_keypoints(const akz_ctx* c, int n, const LevelTable& T)
 {
-    AkzTimerScope timer_scope(c);
-    const AkzPlan& P = c->plan;
-    AkzSet& S = c->S();
-    hipStream_t s = c->stream;  // candidate detection streams Ldet: it stays on the scale-space stream
-    LevelTable T;
-    if ((int)P.levels.size() > kMaxLevels) return AKZ_E_INVALID;
-    build_level_table(c, &T);
-    if (T.n == 0) {
-        AKZ_HIP(hipMemsetAsync(d_n_out, 0, sizeof(uint32_t) * n, s));
-        AKZ_HIP(hipEventRecord(c->ev_ss_done[c->cur], c->stream));
-        AKZ_HIP(hipStreamWaitEvent(c->stream_kp, c->ev_ss_done[c->cur], 0));
-        AKZ_HIP(hipEventRecord(c->ev_kp_done[c->cur], c->stream_kp));
-        c->kp_pending[c->cur] = true;
-        return AKZ_OK;
-    }
-    // ---- hand over to the keypoint stream: everything below is latency-bound per-frame work that overlaps
-    // the next micro-batch's scale space ----
-    AKZ_HIP(hipEventRecord(c->ev_ss_done[c->cur], c->stream));
-    s = c->stream_kp;
-    AKZ_HIP(hipStreamWaitEvent(s, c->ev_ss_done[c->cur], 0));
-    // A12b
-    if (c->sup_parallel) {
-        // the fallback flags sit directly before the scratch, whose first words are the chunk flags, the reverse-list
-        // counters and the replaced marks
-        AKZ_HIP(hipMemsetAsync(S.d_sup_flag, 0, (size_t)((char*)S.d_sup - (char*)S.d_sup_flag) +
-                                                    sizeof(uint32_t) * sup_zero_words(c->sup_cap, (uint32_t)n), s));
-        hipLaunchKernelGGL(k_cand_rows, dim3(T.n, n), dim3(1024), 0, s, T, S.d_ncand, S.d_cand, c->max_cand, S.d_cand_rows);
-        AKZ_LAUNCH_CHECK();
-        const uint32_t adj_blocks = (uint32_t)akz_div_up((int)c->sup_cap, 256);
-        hipLaunchKernelGGL(k_sup_adj, dim3(n > 16 && adj_blocks > 48u ? 48u : adj_blocks, n), dim3(256), 0, s, T, S.d_ncand, S.d_cand,
-                           c->max_cand, S.d_sup, c->sup_cap, S.d_sup_flag, (const uint32_t*)S.d_cand_rows);
-        AKZ_LAUNCH_CHECK();
-        if (n <= 16)
-            hipLaunchKernelGGL((k_sup_resolve<true>), dim3(akz_div_up((int)c->sup_cap, 1024), n), dim3(1024), 0, s, T, S.d_ncand,
-                               S.d_cand, c->max_cand, S.d_sup, c->sup_cap, S.d_sup_flag, S.d_cache, c->max_kp, S.d_ncache,
-                               c->d_err, S.d_lvl_slot);
-        else
-            hipLaunchKernelGGL((k_sup_resolve<false>), dim3(1, n), dim3(1024), 0, s, T, S.d_ncand, S.d_cand, c->max_cand,
-                               S.d_sup, c->sup_cap, S.d_sup_flag, S.d_cache, c->max_kp, S.d_ncache, c->d_err, S.d_lvl_slot);
-        AKZ_LAUNCH_CHECK();
-    }
+    KeypointRoute R = {};
+    R.sup_parallel = c->sup_parallel;
+    R.resolve_chunked = n <= 16;
+    const uint32_t adj_blocks = (uint32_t)akz_div_up((int)c->sup_cap, 256);
+    R.grid_adj = dim3(n > 16 && adj_blocks > 48u ? 48u : adj_blocks, n);
+    R.grid_resolve = R.resolve_chunked ? dim3(akz_div_up((int)c->sup_cap, 1024), n) : dim3(1, n);
     // contexts created for more than kActCap keypoints per frame: a frame whose active list outgrows the LDS starts over in
     // k_suppress_big (its list: d_big_act, max_kp entries per frame)
-    const bool big_pass = c->max_kp > (uint32_t)kActCap;
-    if (big_pass && !c->sup_parallel) AKZ_HIP(hipMemsetAsync(S.d_big_flag, 0, sizeof(uint32_t) * (size_t)n, s));   // (else: cleared with the flags above)
-    hipLaunchKernelGGL(k_suppress, dim3(n), dim3(64), sizeof(ActEntry) * kActCap, s, T, S.d_ncand,
-                       S.d_cand, c->max_cand, S.d_cache, c->max_kp, S.d_ncache, c->d_err,
-                       c->sup_parallel ? (const uint32_t*)S.d_sup_flag : (const uint32_t*)nullptr, S.d_lvl_slot,
-                       big_pass ? S.d_big_flag : (uint32_t*)nullptr);
-    AKZ_LAUNCH_CHECK();
-    if (big_pass) {
-        hipLaunchKernelGGL(k_suppress_big, dim3(n), dim3(64), 0, s, T, S.d_ncand, S.d_cand, c->max_cand, S.d_cache, c->max_kp,
-                           S.d_ncache, c->d_err, (const uint32_t*)S.d_big_flag, S.d_lvl_slot,
-                           reinterpret_cast<ActEntry*>(S.d_big_act), c->max_kp);
-        AKZ_LAUNCH_CHECK();
-    }
-    const uint32_t kb = (uint32_t)akz_div_up((int)c->max_kp, 256);
-    float2* const yr_tab = reinterpret_cast<float2*>(S.d_chunk_yr);
-    const uint32_t yr_stride = (uint32_t)akz_div_up((int)c->max_kp, 64);
-    hipLaunchKernelGGL(k_chunk_yrange, dim3((uint32_t)akz_div_up((int)yr_stride, 4), n), dim3(256), 0, s, S.d_cache, c->max_kp,
-                       S.d_ncache, yr_tab, yr_stride);
-    AKZ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_filter_upper, dim3(kb, n), dim3(256), sizeof(float2) * (size_t)yr_stride, s, S.d_cache, c->max_kp, S.d_ncache,
-                       (const uint32_t*)S.d_lvl_slot, T.n, (const float2*)yr_tab, yr_stride, S.d_flag_b);
-    AKZ_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_compact<false>), dim3(n), dim3(1024), 0, s, S.d_cache, (const akz_descriptor*)nullptr,
-                       S.d_flag_b, S.d_ncache, c->max_kp, S.d_kp_a, (akz_descriptor*)nullptr, c->max_kp, S.d_n_a,
-                       c->d_err, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    AKZ_LAUNCH_CHECK();
-    // A13 + A14
-    const uint32_t kw = (uint32_t)akz_div_up((int)c->max_kp, 4);
-    akz_timer_begin(c, AKZ_T_REFINE, s);
-    // default pattern: the orientation is computed by the descriptor kernel (k_orient_describe); here only the fit
-    // (not with the parity taps on: akz_debug_get_keypoints stage 1 is the list after refinement AND orientation)
-    const bool fast_desc = c->cfg.descriptor_pattern_size == 10 && c->cfg.descriptor_channels == 3;
-    const bool orient_in_desc = fast_desc && !c->keep_all;
-    if (orient_in_desc)
-        hipLaunchKernelGGL(k_refine_pos, dim3((uint32_t)akz_div_up((int)c->max_kp, 256), n), dim3(256), 0, s, T, S.d_kp_a, S.d_n_a,
-                           c->max_kp, S.d_kp_b, S.d_flag_b, (const float*)S.d_cand_nb, c->max_cand);
-    else
-        hipLaunchKernelGGL(k_refine, dim3(kw, n), dim3(256), 0, s, T, (const OriTables*)c->d_ori, S.d_kp_a, S.d_n_a, c->max_kp, S.d_kp_b,
-                           S.d_flag_b, c->d_err, (const float*)S.d_cand_nb, c->max_cand);
-    AKZ_LAUNCH_CHECK();
-    akz_timer_end(c, AKZ_T_REFINE, s, 1, (uint64_t)n);
-    hipLaunchKernelGGL((k_compact<false>), dim3(n), dim3(1024), 0, s, S.d_kp_b, (const akz_descriptor*)nullptr,
-                       S.d_flag_b, S.d_n_a, c->max_kp, S.d_kp_c, (akz_descriptor*)nullptr, c->max_kp, S.d_n_c,
-                       c->d_err, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    AKZ_LAUNCH_CHECK();
-    // A15
-    uint32_t maxf = c->cfg.maximum_features > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c->cfg.maximum_features;
-    const bool rank_sorts = n <= 8;            // few frames: the chip-wide rank sort; many: one bitonic block per frame
+    R.big_pass = c->max_kp > (uint32_t)kActCap;
+    R.clear_big_flag = R.big_pass && !R.sup_parallel;
+    R.kb = (uint32_t)akz_div_up((int)c->max_kp, 256);
+    R.yr_stride = (uint32_t)akz_div_up((int)c->max_kp, 64);
+    R.kw = (uint32_t)akz_div_up((int)c->max_kp, 4);
+    // default pattern: the orientation is computed by the descriptor kernel (k_orient_describe); the refinement does only the
+    // fit (not with the parity taps on: akz_debug_get_keypoints stage 1 is the list after refinement AND orientation)
+    R.fast_desc = c->cfg.descriptor_pattern_size == 10 && c->cfg.descriptor_channels == 3;
+    R.orient_in_desc = R.fast_desc && !c->keep_all;
+    R.maxf = c->cfg.maximum_features > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c->cfg.maximum_features;
+    // few frames: the chip-wide rank sort; many: one block per frame, where the networks cost less than the n^2 comparisons
+    // (74 vs 190 us per 64 frames of ~5 000 keypoints; a single 1080p frame: 154 -> ~20 us per sort the other way)
+    R.rank_sorts = n <= 8;
     // Visiting order of the descriptor stage.  The response-sorted list is spatially random; the list BEFORE the sort is
     // in cache order (level-major, close to raster), and the sort knows where it sent every element — so when nothing is
     // truncated the descriptor kernel can walk the pre-sort order for free.  The (level, 32-px tile) order of
@@ -2418,61 +2369,213 @@ int32_t akz_run_keypoints(akz_ctx* c, int n, DevKp* d_kps, akz_descriptor* d_des
     // and costs a second sort (153 us).  A few-frame call, where every launch is on the critical path, takes the free
     // order; a batch takes the tile order (in the pipeline its sort hides and the lower traffic shows: 7 353-7 372 vs
     // 7 301-7 321 frames/s).
-    const bool raster_visit = rank_sorts && maxf >= c->max_kp;
-    const dim3 grid_rank((uint32_t)akz_div_up((int)c->max_kp, kRankI), n);
-    uint32_t np2 = 1;
-    while (np2 < c->max_kp) np2 <<= 1;
-    const uint32_t lds_keys = np2 < kAkzLdsSortKeys ? np2 : kAkzLdsSortKeys;   // longer lists: global key scratch
-    if (rank_sorts)
-        hipLaunchKernelGGL((k_rank_sort<RANK_RESPONSE>), grid_rank, dim3(256), 0, s, S.d_kp_c, S.d_n_c, c->max_kp, maxf, 0,
-                           S.d_kp_d, S.d_n_d, raster_visit ? S.d_perm : (uint32_t*)nullptr);
-    else
-        hipLaunchKernelGGL(k_sort, dim3(n), dim3(1024),
-                           std::max<size_t>(sizeof(unsigned long long) * lds_keys, kRadixSortLdsBytes), s, S.d_kp_c, S.d_n_c,
-                           c->max_kp, maxf, S.d_kp_d, S.d_n_d, S.d_keys_kp, np2, lds_keys,
-                           raster_visit ? S.d_perm : (uint32_t*)nullptr);
-    AKZ_LAUNCH_CHECK();
-    // A16 + A17
-    akz_timer_begin(c, AKZ_T_DESCRIBE, s);
-    if (c->cfg.descriptor_pattern_size == 10 && c->cfg.descriptor_channels == 3) {
-        if (!raster_visit) {
-            if (rank_sorts)
-                hipLaunchKernelGGL((k_rank_sort<RANK_SPATIAL>), grid_rank, dim3(256), 0, s, S.d_kp_d, S.d_n_d, c->max_kp, 0u,
-                                   c->desc_tile_shift, (DevKp*)nullptr, (uint32_t*)nullptr, S.d_perm);
-            else {
-                uint32_t nbuckets = 0;
-                for (int e = 0; e < T.n; ++e)
-                    nbuckets += (((uint32_t)(T.L[e].w - 1) >> c->desc_tile_shift) + 1u) * (((uint32_t)(T.L[e].h - 1) >> c->desc_tile_shift) + 1u);
-                if (nbuckets <= kTileOrderMaxBuckets)
-                    hipLaunchKernelGGL(k_tile_order, dim3(n), dim3(1024), sizeof(uint32_t) * nbuckets, s, T, S.d_kp_d, S.d_n_d,
-                                       c->max_kp, S.d_perm, c->desc_tile_shift);
-                else
-                    hipLaunchKernelGGL(k_spatial_order, dim3(n), dim3(1024), sizeof(unsigned long long) * lds_keys, s, T, S.d_kp_d,
-                                       S.d_n_d, c->max_kp, S.d_perm, c->desc_tile_shift, S.d_keys_kp, np2, lds_keys);
-            }
-        }
-        AKZ_LAUNCH_CHECK();
-        if (orient_in_desc) {
-            akz_timer_begin(c, AKZ_T_ORIENT_DESCRIBE_K, s);
-            AKZ_LAUNCH(k_orient_describe, dim3(((uint32_t)akz_div_up((int)c->max_kp, kODWaves) + 7u) & ~7u, n), dim3(64 * kODWaves), 0, s, T,
-                       (const OriTables*)c->d_ori, (const DescTables*)c->d_desc, S.d_kp_d, S.d_n_d, c->max_kp,
-                       S.d_perm, S.d_desc_tmp, S.d_flag_d, c->d_err);
-            akz_timer_end(c, AKZ_T_ORIENT_DESCRIBE_K, s, 1, (uint64_t)n);
-        } else
-            hipLaunchKernelGGL(k_describe_fast, dim3((uint32_t)akz_div_up((int)c->max_kp, kDescWaves), n), dim3(64 * kDescWaves), 0, s, T,
-                               (const DescTables*)c->d_desc, S.d_kp_d, S.d_n_d, c->max_kp, S.d_perm, S.d_desc_tmp, S.d_flag_d);
-    } else {
-        hipLaunchKernelGGL(k_describe, dim3(kw, n), dim3(256), 0, s, T, (const DescTables*)c->d_desc, S.d_kp_d,
-                           S.d_n_d, c->max_kp, S.d_desc_tmp, S.d_flag_d);
+    R.raster_visit = R.rank_sorts && R.maxf >= c->max_kp;
+    R.grid_rank = dim3((uint32_t)akz_div_up((int)c->max_kp, kRankI), n);
+    R.np2 = 1;
+    while (R.np2 < c->max_kp) R.np2 <<= 1;
+    R.lds_keys = R.np2 < kAkzLdsSortKeys ? R.np2 : kAkzLdsSortKeys;   // longer lists: global key scratch
+    R.sort_lds = R.rank_sorts ? 0 : std::max<size_t>(sizeof(unsigned long long) * R.lds_keys, kRadixSortLdsBytes);
+    R.order = !R.fast_desc ? VISIT_STORED : R.raster_visit ? VISIT_RASTER : R.rank_sorts ? VISIT_RANK : VISIT_TILE;
+    if (R.order == VISIT_TILE) {
+        for (int e = 0; e < T.n; ++e)
+            R.nbuckets += (((uint32_t)(T.L[e].w - 1) >> c->desc_tile_shift) + 1u) * (((uint32_t)(T.L[e].h - 1) >> c->desc_tile_shift) + 1u);
+        // the counting sort while its buckets fit the LDS, the bitonic network over (level, tile, index) keys beyond
+        if (R.nbuckets > kTileOrderMaxBuckets) R.order = VISIT_BITONIC;
+        R.order_lds = R.order == VISIT_TILE ? sizeof(uint32_t) * R.nbuckets : sizeof(unsigned long long) * R.lds_keys;
     }
-    AKZ_LAUNCH_CHECK();
-    akz_timer_end(c, AKZ_T_DESCRIBE, s, 1, (uint64_t)n);
-    hipLaunchKernelGGL((k_compact<true>), dim3(n), dim3(1024), 0, s, S.d_kp_d, S.d_desc_tmp, S.d_flag_d, S.d_n_d,
-                       c->max_kp, d_kps, d_descs, cap_per_img, d_n_out, (uint32_t*)nullptr, (const uint32_t*)c->d_err, h_err_copy);
-    AKZ_LAUNCH_CHECK();
+    return R;
+}
+
+// Hand over to the keypoint stream: everything after this is latency-bound per-frame work that overlaps the next
+// micro-batch's scale space.
+static int32_t kp_hand_over(akz_ctx* c)
+{
+    AKZ_HIP(hipEventRecord(c->ev_ss_done[c->cur], c->stream));
+    AKZ_HIP(hipStreamWaitEvent(c->stream_kp, c->ev_ss_done[c->cur], 0));
+    return AKZ_OK;
+}
+
+static int32_t kp_close(akz_ctx* c)
+{
     AKZ_HIP(hipEventRecord(c->ev_kp_done[c->cur], c->stream_kp));
     c->kp_pending[c->cur] = true;
     return AKZ_OK;
+}
+
+// A12b, first pass
+static int32_t kp_suppress(akz_ctx* c, int n, const LevelTable& T, const KeypointRoute& R)
+{
+    AkzSet& S = c->S();
+    hipStream_t s = c->stream_kp;
+    if (R.sup_parallel) {
+        // the fallback flags sit directly before the scratch, whose first words are the chunk flags, the reverse-list
+        // counters and the replaced marks
+        AKZ_HIP(hipMemsetAsync(S.d_sup_flag, 0, (size_t)((char*)S.d_sup - (char*)S.d_sup_flag) +
+                                                    sizeof(uint32_t) * sup_zero_words(c->sup_cap, (uint32_t)n), s));
+        hipLaunchKernelGGL(k_cand_rows, dim3(T.n, n), dim3(1024), 0, s, T, S.d_ncand, S.d_cand, c->max_cand, S.d_cand_rows);
+        AKZ_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_sup_adj, R.grid_adj, dim3(256), 0, s, T, S.d_ncand, S.d_cand, c->max_cand, S.d_sup, c->sup_cap,
+                           S.d_sup_flag, (const uint32_t*)S.d_cand_rows);
+        AKZ_LAUNCH_CHECK();
+        if (R.resolve_chunked)
+            hipLaunchKernelGGL((k_sup_resolve<true>), R.grid_resolve, dim3(1024), 0, s, T, S.d_ncand, S.d_cand, c->max_cand, S.d_sup,
+                               c->sup_cap, S.d_sup_flag, S.d_cache, c->max_kp, S.d_ncache, c->d_err, S.d_lvl_slot);
+        else
+            hipLaunchKernelGGL((k_sup_resolve<false>), R.grid_resolve, dim3(1024), 0, s, T, S.d_ncand, S.d_cand, c->max_cand, S.d_sup,
+                               c->sup_cap, S.d_sup_flag, S.d_cache, c->max_kp, S.d_ncache, c->d_err, S.d_lvl_slot);
+        AKZ_LAUNCH_CHECK();
+    }
+    if (R.clear_big_flag) AKZ_HIP(hipMemsetAsync(S.d_big_flag, 0, sizeof(uint32_t) * (size_t)n, s));
+    hipLaunchKernelGGL(k_suppress, dim3(n), dim3(64), sizeof(ActEntry) * kActCap, s, T, S.d_ncand, S.d_cand, c->max_cand, S.d_cache,
+                       c->max_kp, S.d_ncache, c->d_err, R.sup_parallel ? (const uint32_t*)S.d_sup_flag : (const uint32_t*)nullptr,
+                       S.d_lvl_slot, R.big_pass ? S.d_big_flag : (uint32_t*)nullptr);
+    AKZ_LAUNCH_CHECK();
+    if (R.big_pass) {
+        hipLaunchKernelGGL(k_suppress_big, dim3(n), dim3(64), 0, s, T, S.d_ncand, S.d_cand, c->max_cand, S.d_cache, c->max_kp,
+                           S.d_ncache, c->d_err, (const uint32_t*)S.d_big_flag, S.d_lvl_slot,
+                           reinterpret_cast<ActEntry*>(S.d_big_act), c->max_kp);
+        AKZ_LAUNCH_CHECK();
+    }
+    return AKZ_OK;
+}
+
+// A12b, second pass: cache -> d_kp_a
+static int32_t kp_filter_upper(akz_ctx* c, int n, const LevelTable& T, const KeypointRoute& R)
+{
+    AkzSet& S = c->S();
+    hipStream_t s = c->stream_kp;
+    float2* const yr_tab = reinterpret_cast<float2*>(S.d_chunk_yr);
+    hipLaunchKernelGGL(k_chunk_yrange, dim3((uint32_t)akz_div_up((int)R.yr_stride, 4), n), dim3(256), 0, s, S.d_cache, c->max_kp,
+                       S.d_ncache, yr_tab, R.yr_stride);
+    AKZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_filter_upper, dim3(R.kb, n), dim3(256), sizeof(float2) * (size_t)R.yr_stride, s, S.d_cache, c->max_kp,
+                       S.d_ncache, (const uint32_t*)S.d_lvl_slot, T.n, (const float2*)yr_tab, R.yr_stride, S.d_flag_b);
+    AKZ_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_compact<false>), dim3(n), dim3(1024), 0, s, S.d_cache, (const akz_descriptor*)nullptr,
+                       S.d_flag_b, S.d_ncache, c->max_kp, S.d_kp_a, (akz_descriptor*)nullptr, c->max_kp, S.d_n_a,
+                       c->d_err, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+// A13 + A14: d_kp_a -> d_kp_c
+static int32_t kp_refine(akz_ctx* c, int n, const LevelTable& T, const KeypointRoute& R)
+{
+    AkzSet& S = c->S();
+    hipStream_t s = c->stream_kp;
+    akz_timer_begin(c, AKZ_T_REFINE, s);
+    if (R.orient_in_desc)
+        hipLaunchKernelGGL(k_refine_pos, dim3(R.kb, n), dim3(256), 0, s, T, S.d_kp_a, S.d_n_a, c->max_kp, S.d_kp_b, S.d_flag_b,
+                           (const float*)S.d_cand_nb, c->max_cand);
+    else
+        hipLaunchKernelGGL(k_refine, dim3(R.kw, n), dim3(256), 0, s, T, (const OriTables*)c->d_ori, S.d_kp_a, S.d_n_a, c->max_kp,
+                           S.d_kp_b, S.d_flag_b, c->d_err, (const float*)S.d_cand_nb, c->max_cand);
+    AKZ_LAUNCH_CHECK();
+    akz_timer_end(c, AKZ_T_REFINE, s, 1, (uint64_t)n);
+    hipLaunchKernelGGL((k_compact<false>), dim3(n), dim3(1024), 0, s, S.d_kp_b, (const akz_descriptor*)nullptr,
+                       S.d_flag_b, S.d_n_a, c->max_kp, S.d_kp_c, (akz_descriptor*)nullptr, c->max_kp, S.d_n_c,
+                       c->d_err, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+// A15: d_kp_c -> d_kp_d
+static int32_t kp_response_sort(akz_ctx* c, int n, const KeypointRoute& R)
+{
+    AkzSet& S = c->S();
+    hipStream_t s = c->stream_kp;
+    uint32_t* const perm = R.raster_visit ? S.d_perm : (uint32_t*)nullptr;
+    if (R.rank_sorts)
+        hipLaunchKernelGGL((k_rank_sort<RANK_RESPONSE>), R.grid_rank, dim3(256), 0, s, S.d_kp_c, S.d_n_c, c->max_kp, R.maxf, 0,
+                           S.d_kp_d, S.d_n_d, perm);
+    else
+        hipLaunchKernelGGL(k_sort, dim3(n), dim3(1024), R.sort_lds, s, S.d_kp_c, S.d_n_c, c->max_kp, R.maxf, S.d_kp_d, S.d_n_d,
+                           S.d_keys_kp, R.np2, R.lds_keys, perm);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+// the order in which the descriptor kernel visits d_kp_d: d_perm
+static int32_t kp_visit_order(akz_ctx* c, int n, const LevelTable& T, const KeypointRoute& R)
+{
+    AkzSet& S = c->S();
+    hipStream_t s = c->stream_kp;
+    switch (R.order) {
+    case VISIT_STORED:
+    case VISIT_RASTER: return AKZ_OK;
+    case VISIT_RANK:
+        hipLaunchKernelGGL((k_rank_sort<RANK_SPATIAL>), R.grid_rank, dim3(256), 0, s, S.d_kp_d, S.d_n_d, c->max_kp, 0u,
+                           c->desc_tile_shift, (DevKp*)nullptr, (uint32_t*)nullptr, S.d_perm);
+        break;
+    case VISIT_TILE:
+        hipLaunchKernelGGL(k_tile_order, dim3(n), dim3(1024), R.order_lds, s, T, S.d_kp_d, S.d_n_d, c->max_kp, S.d_perm,
+                           c->desc_tile_shift);
+        break;
+    case VISIT_BITONIC:
+        hipLaunchKernelGGL(k_spatial_order, dim3(n), dim3(1024), R.order_lds, s, T, S.d_kp_d, S.d_n_d, c->max_kp, S.d_perm,
+                           c->desc_tile_shift, S.d_keys_kp, R.np2, R.lds_keys);
+        break;
+    }
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+// A16 + A17: descriptors of d_kp_d -> d_desc_tmp
+static int32_t kp_describe(akz_ctx* c, int n, const LevelTable& T, const KeypointRoute& R)
+{
+    AkzSet& S = c->S();
+    hipStream_t s = c->stream_kp;
+    if (R.orient_in_desc) {
+        akz_timer_begin(c, AKZ_T_ORIENT_DESCRIBE_K, s);
+        AKZ_LAUNCH(k_orient_describe, dim3(((uint32_t)akz_div_up((int)c->max_kp, kODWaves) + 7u) & ~7u, n), dim3(64 * kODWaves), 0, s, T,
+                   (const OriTables*)c->d_ori, (const DescTables*)c->d_desc, S.d_kp_d, S.d_n_d, c->max_kp,
+                   S.d_perm, S.d_desc_tmp, S.d_flag_d, c->d_err);
+        akz_timer_end(c, AKZ_T_ORIENT_DESCRIBE_K, s, 1, (uint64_t)n);
+    } else if (R.fast_desc)
+        hipLaunchKernelGGL(k_describe_fast, dim3((uint32_t)akz_div_up((int)c->max_kp, kDescWaves), n), dim3(64 * kDescWaves), 0, s, T,
+                           (const DescTables*)c->d_desc, S.d_kp_d, S.d_n_d, c->max_kp, S.d_perm, S.d_desc_tmp, S.d_flag_d);
+    else
+        hipLaunchKernelGGL(k_describe, dim3(R.kw, n), dim3(256), 0, s, T, (const DescTables*)c->d_desc, S.d_kp_d, S.d_n_d, c->max_kp,
+                           S.d_desc_tmp, S.d_flag_d);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+// final compaction into the caller's arrays, and the event the next user of this buffer set waits for
+static int32_t kp_finish(akz_ctx* c, int n, DevKp* d_kps, akz_descriptor* d_descs, uint32_t cap_per_img, uint32_t* d_n_out,
+                         uint32_t* h_err_copy)
+{
+    AkzSet& S = c->S();
+    hipLaunchKernelGGL((k_compact<true>), dim3(n), dim3(1024), 0, c->stream_kp, S.d_kp_d, S.d_desc_tmp, S.d_flag_d, S.d_n_d,
+                       c->max_kp, d_kps, d_descs, cap_per_img, d_n_out, (uint32_t*)nullptr, (const uint32_t*)c->d_err, h_err_copy);
+    AKZ_LAUNCH_CHECK();
+    return kp_close(c);
+}
+
+int32_t akz_run_keypoints(akz_ctx* c, int n, DevKp* d_kps, akz_descriptor* d_descs, uint32_t cap_per_img,
+                          uint32_t* d_n_out, uint32_t* h_err_copy)
+{
+    AkzTimerScope timer_scope(c);
+    LevelTable T;
+    if ((int)c->plan.levels.size() > kMaxLevels) return AKZ_E_INVALID;
+    build_level_table(c, &T);
+    if (T.n == 0) {
+        // (candidate detection streams Ldet on the scale-space stream; with no level there is nothing for the other one to do)
+        AKZ_HIP(hipMemsetAsync(d_n_out, 0, sizeof(uint32_t) * n, c->stream));
+        AKZ_TRY(kp_hand_over(c));
+        return kp_close(c);
+    }
+    const KeypointRoute R = route_keypoints(c, n, T);
+    AKZ_TRY(kp_hand_over(c));
+    AKZ_TRY(kp_suppress(c, n, T, R));
+    AKZ_TRY(kp_filter_upper(c, n, T, R));
+    AKZ_TRY(kp_refine(c, n, T, R));
+    AKZ_TRY(kp_response_sort(c, n, R));
+    akz_timer_begin(c, AKZ_T_DESCRIBE, c->stream_kp);
+    AKZ_TRY(kp_visit_order(c, n, T, R));
+    AKZ_TRY(kp_describe(c, n, T, R));
+    akz_timer_end(c, AKZ_T_DESCRIBE, c->stream_kp, 1, (uint64_t)n);
+    return kp_finish(c, n, d_kps, d_descs, cap_per_img, d_n_out, h_err_copy);
 }
 
 // ---- parity tap: the transcendentals of the orientation / descriptor kernels as the DEVICE evaluates them ----

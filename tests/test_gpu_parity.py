@@ -1862,6 +1862,71 @@ def test_call_size_selects_kernels_not_results(gpu, oracle, nfr):
     ctx.close()
 
 
+def test_batch_visiting_order_beyond_the_tile_buckets(gpu, oracle):
+    """k_spatial_order: a batch of more than eight frames orders the descriptor stage's visits by (level, tile) with a
+    counting sort while the tiles of all levels fit its 15 360 LDS buckets, and with the bitonic network over
+    (level, tile row, tile column, index) keys beyond.  4-pixel tiles (desc_tile_shift=2) at 320x240 make 4 x 80 x 60 +
+    4 x 40 x 30 = 24 000 buckets.  The order decides only which keypoint a wave visits when: keypoints and descriptors of
+    all nine frames equal the oracle's byte for byte."""
+    akaze, _ = gpu
+    w, h, nfr = 320, 240, 9
+    frames = [synth_frame(w, h, seed=8800 + (i % 3), n_rect=40, n_disc=40) for i in range(nfr)]
+    orc = oracle.Akaze(w, h, oracle.default_config())
+    want = [orc.extract(frames[i]) for i in range(3)]
+    assert min(len(kp) for kp, _ in want) > 100
+    ctx = akaze.Context(akaze.Akaze.default(), w, h, nfr, _opts(desc_tile_shift=2))
+    got = ctx.extract_batch(frames)
+    for i in range(nfr):
+        okp, od = want[i % 3]
+        _kp_eq(got[i][0], okp, f"4-pixel tiles, frame {i}")
+        _eq(got[i][1], od, f"4-pixel tiles, frame {i} desc")
+    ctx.close()
+
+
+def test_frames_without_a_level(gpu, oracle):
+    """A frame whose shorter side is below 40 pixels has no evolution level (evolution.rs:89-90): the keypoint stage
+    launches nothing, zeroes the counts and still hands its buffer set on, so a second call on the same context works.
+    Both calls return what the oracle returns: no keypoint, no descriptor."""
+    akaze, _ = gpu
+    w, h = 64, 32
+    frames = [synth_frame(w, h, seed=3000 + i, n_rect=40, n_disc=40) for i in range(2)]
+    orc = oracle.Akaze(w, h, oracle.default_config())
+    ctx = akaze.Context(akaze.Akaze.default(), w, h, 2)
+    for call in range(2):
+        got = ctx.extract_batch(frames)
+        for i, f in enumerate(frames):
+            okp, od = orc.extract(f)
+            assert len(okp) == 0
+            _kp_eq(got[i][0], okp, f"no level, call {call}, frame {i}")
+            _eq(got[i][1], od, f"no level, call {call}, frame {i} desc")
+    ctx.close()
+
+
+def test_batch_response_sort_by_the_network_in_lds(gpu, oracle):
+    """The bitonic half of k_sort with its keys in LDS: a batch of more than eight frames sorts a frame of up to 8 192
+    keypoints by radix, one of 8 193 .. 16 384 by the bitonic network over 64-bit keys in LDS, a longer one through the
+    global key scratch (test_large_keypoint_lists_and_overflow_report).  640x480 noise at Akaze::dense() ends with 10 200
+    keypoints (the list the sort sees is at most a few border cases longer) beside eight copies of a quiet frame that
+    takes the radix sort in the same launch: both equal the oracle byte for byte."""
+    akaze, _ = gpu
+    w, h = 640, 480
+    noise = np.random.default_rng(11).integers(0, 256, (h, w), dtype=np.uint8)
+    quiet = synth_frame(w, h, 5)
+    orc = oracle.Akaze(w, h, oracle.default_config(threshold=0.0001))
+    okp, od = orc.extract(noise)
+    qkp, qd = orc.extract(quiet)
+    assert 8192 < len(okp) <= 15000 and len(qkp) <= 8192, (len(okp), len(qkp))
+    ak = akaze.Akaze.dense()
+    ak.max_keypoints = 16384
+    ctx = akaze.Context(ak, w, h, 9)
+    got = ctx.extract_batch([quiet] * 4 + [noise] + [quiet] * 4)
+    for i in range(9):
+        wkp, wd = (okp, od) if i == 4 else (qkp, qd)
+        _kp_eq(got[i][0], wkp, f"LDS bitonic sort, frame {i}")
+        _eq(got[i][1], wd, f"LDS bitonic sort, frame {i} desc")
+    ctx.close()
+
+
 def test_host_calls_with_and_without_pinned_staging(gpu, oracle):
     """akz_extract_batch stages inputs and outputs through pinned blocks while they stay below 96 MB and falls back to
     plain copies above (72 frames x 16 384 keypoint slots x 92 B = 108 MB): both give the oracle's bytes, and a second
