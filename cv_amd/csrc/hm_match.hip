@@ -1054,10 +1054,14 @@ static int32_t launch_knn2(hm_ctx* c, const HmProb* h_probs, uint32_t n_probs, u
     std::vector<HmProbX> px(n_probs);
     size_t words = 0;
     const size_t ew = c->use_fp4 ? 64 : 128;   // words of recoded descriptor
-    std::unordered_map<const void*, size_t> seen;   // block -> its job (a window call has thousands of problems over few blocks)
+    // block -> its jobs (a window call has thousands of problems over few blocks).  A job recodes rows [0, min(*count, cap)) of
+    // its block, so one address met with another count or another capacity is another job: a buffer passed both as the
+    // queries and as the targets of a call, each side with its own counts, must not share the shorter side's recoding.
+    std::unordered_multimap<const void*, size_t> seen;
     auto expanded = [&](const uint4* src, const uint32_t* cnt, uint32_t cap) -> size_t {
-        auto it = seen.find((const void*)src);
-        if (it != seen.end()) return job_off[it->second];
+        const auto same = seen.equal_range((const void*)src);
+        for (auto it = same.first; it != same.second; ++it)
+            if (jobs[it->second].count == cnt && jobs[it->second].cap == cap) return job_off[it->second];
         seen.emplace((const void*)src, jobs.size());
         jobs.push_back(HmExpandJob{(const uint32_t*)src, cnt, cap, nullptr});
         job_off.push_back(words);
@@ -1317,7 +1321,8 @@ extern "C" int32_t hm_knn_batch_device(hm_ctx* c, const void* d_q, const void* d
 //                                                              still checks are_landmarks_sharing_view, :1528)
 //   else                                                 -> 0
 // The reference collects the landmarks in a HashMap, so its order among equal distances is unspecified; here ties
-// go to the lower landmark key (parity unpinned for ties).  One thread per feature: n_views * k <= 96 entries.
+// go to the lower landmark key (parity unpinned for ties).  One thread per feature: n_views * k <= 64 * 3 = 192 entries,
+// read once each; only the best three are kept.
 __global__ __launch_bounds__(256) void k_best_of_views(const akz_neighbor* __restrict__ knn, const uint32_t* __restrict__ nq,
                                                        uint32_t cap, uint32_t n_views, uint32_t k,
                                                        const uint32_t* __restrict__ landmarks, const uint32_t* __restrict__ view_idx,
@@ -1756,7 +1761,8 @@ extern "C" int32_t hm_match_batch_device(hm_ctx* c, const void* d_a, const void*
 // Frame-level place recognition.  Replaces
 //   hasher.hash_bag(features)                      cv-sfm/src/lib.rs:672   (HammingHasher<64, 512>, :205,216)
 //   lsh_to_frame.knn_values(&lsh, search_num)      cv-sfm/src/lib.rs:622-624
-// hash_bag is the matcher's own workload with the codebook as the target set: k_knn_mfma<1> gives every feature
+// hash_bag is the matcher's own workload with the codebook as the target set: launch_knn2 with k = 1 — the MFMA kernel the
+// context's creation flags select (FP4 wide, FP4 register-staged or int8; the VALU kernel exists for k = 2 only) — gives every feature
 // its nearest codeword (lowest index among equals), k_bag_bits ORs the word bits into the frame's hash.  The
 // hashing crate (hamming-lsh 0.3.2) is not vendored in the reference: parity unpinned, see oracle/lsh_oracle.c.
 

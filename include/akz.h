@@ -300,7 +300,9 @@ int32_t hm_knn2(hm_ctx* ctx, const akz_descriptor* q, uint32_t nq, const akz_des
                 uint32_t nt, akz_neighbor* out);
 /* LinearKnn{metric: Hamming, iter: t}.knn(q, k) for k = 1, 2 or 3 — the registration path asks for 3
  * (cv-sfm/src/lib.rs:1474).  out[nq][k], ascending (distance, index); the reference returns min(k, nt)
- * neighbours, here the slots past nt hold {index 2^22 - 1, distance 1023}. */
+ * neighbours, here the slots past nt hold {index 2^22 - 1, distance 1023}.  The distance is over all 512 bits of both rows:
+ * an extracted descriptor has bits 486..511 clear, but a row that sets them (a codeword, a hash, any caller's BitArray<64>) has
+ * them counted like every other bit, in every kernel, so distances reach 512. */
 int32_t hm_knn(hm_ctx* ctx, const akz_descriptor* q, uint32_t nq, const akz_descriptor* t, uint32_t nt,
                uint32_t k, akz_neighbor* out);
 /* LinearKnn keeps its targets (`iter`) and is asked once per query (akaze/tests/estimate_pose.rs:82-88).  hm_set_targets
@@ -323,7 +325,8 @@ int32_t hm_knn_views_device(hm_ctx* ctx, const void* d_q, const void* d_nq, cons
                             uint32_t n_views, uint32_t k, void* d_out, void* stream_to_wait);
 /* The batched form: problem p = every feature of query block iq[p] (of d_q, count d_nq[iq[p]]) against target block it[p]
  * (of d_t), k neighbours each — the window of recent views of every frame of a micro-batch (n_frames x K problems) in one
- * call; every distinct block is recoded once.  iq / it host index arrays, n_probs <= 65535; d_out [n_probs][cap][k], slots past
+ * call; every distinct block is recoded once per count it is read with (d_q and d_t may be one buffer, with different counts
+ * per side).  iq / it host index arrays, n_probs <= 65535; d_out [n_probs][cap][k], slots past
  * a target block's count as in hm_knn. */
 int32_t hm_knn_batch_device(hm_ctx* ctx, const void* d_q, const void* d_nq, const void* d_t, const void* d_nt,
                             uint32_t cap_per_img, const uint32_t* iq, const uint32_t* it, uint32_t n_probs, uint32_t k,
@@ -369,7 +372,8 @@ int32_t hm_landmark_matches_batch_device(hm_ctx* ctx, const void* d_best, const 
  * sorted by Reverse(sum over the match's landmarks of landmark(..).observations.len()) before model_inliers (:1619-1622) sees
  * it — matches on well-observed landmarks first, equal sums in feature order — and a consensus that samples by position
  * (ARRSAC does) depends on it.  d_obs_counts [n_world] u32: observations of every landmark key (the caller's graph knows them;
- * a key >= n_world counts 0); both landmarks of a merged match count.  The sort runs on the device, in the kernel that
+ * a key >= n_world counts 0); both landmarks of a merged match count, their sum saturating at 2^32 - 1 (sums that reach it are
+ * equal and keep their feature order).  The sort runs on the device, in the kernel that
  * builds the list (a stable LSD radix sort in LDS); with d_obs_counts == NULL this is hm_landmark_matches_batch_device.
  * Pass the lists to rs_p3p_arrsac_batch_device WITHOUT RS_BATCH_SHUFFLE to keep the order. */
 int32_t hm_landmark_matches_ordered_batch_device(hm_ctx* ctx, const void* d_best, const void* d_decision, const void* d_merge_ok,

@@ -233,7 +233,9 @@ uint32_t orc_landmark_matches(const uint32_t* best, const uint32_t* decision, co
  * order (:1489-1542 walks the features in order), `retain` of the matches whose landmarks were all counted once (:1555-1559),
  * then `sort_by_key(Reverse(sum of landmark(..).observations.len()))` (:1561-1574) — a STABLE sort: equal sums keep the
  * feature order —, then the filter_map that drops matches without a robust triangulation (:1583-1604).  obs[l] = number of
- * observations of landmark key l (l < n_world; a key beyond the table counts 0). */
+ * observations of landmark key l (l < n_world; a key beyond the table counts 0).  The reference sums usize; the ABI takes
+ * 32-bit counts and states that the sum of a merged match saturates at 2^32 - 1, so two such sums are equal and keep their
+ * feature order. */
 uint32_t orc_landmark_matches_ordered(const uint32_t* best, const uint32_t* decision, const uint8_t* merge_ok, const uint32_t* obs,
                                       uint32_t nq, const double* world, uint32_t n_world, uint32_t merged_base, uint32_t* pairs)
 {
@@ -248,6 +250,7 @@ uint32_t orc_landmark_matches_ordered(const uint32_t* best, const uint32_t* deci
         if (k == 2 && orc_lm_claims(best, decision, merge_ok, nq, l1) != 1) continue;
         uint64_t sum = l0 < n_world ? obs[l0] : 0;
         if (k == 2) sum += l1 < n_world ? obs[l1] : 0;
+        if (sum > 0xFFFFFFFFull) sum = 0xFFFFFFFFull;             /* the ABI's sort key is 32 bits wide: it saturates (akz.h) */
         feat[m] = i;
         key[m] = sum;
         m++;
