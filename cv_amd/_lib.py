@@ -192,6 +192,10 @@ RS_SV_OK, RS_SV_NO_MODEL, RS_SV_FEW_LANDMARKS, RS_SV_LOST_HALF, RS_SV_FEW_ROBUST
 RS_SV_MAX_MATCHES, RS_SV_MAX_RUNS, RS_SV_MAX_ITERATIONS, RS_SV_STATS = 2048, 9, 1 << 20, 24
 RS_SV_S_INLIERS, RS_SV_S_RUN_MATCHES, RS_SV_S_RUN_STOP, RS_SV_S_ROBUST, RS_SV_S_NO_OTHER, RS_SV_S_STAGE = 0, 1, 10, 19, 20, 21
 
+RS_AV_OK, RS_AV_NOT_ACCEPTED, RS_AV_BAD_INDEX, RS_AV_BAD_TABLE = range(4)
+RS_AV_S_OBSERVATIONS, RS_AV_S_MERGED, RS_AV_S_DEMOTED, RS_AV_S_NEW_LANDMARKS = range(4)
+RS_AV_STATS, RS_AV_COUNTS, RS_LT_TILE = 4, 4, 1024
+
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
 
@@ -236,6 +240,7 @@ ABI_SYMBOLS = [
     "rs_observation_filter_params_default", "rs_filter_observations_device", "rs_optimize_reconstruction_batch_device",
     "rs_single_view_params_default", "rs_refine_poses_batch_device",
     "rs_covisibility_params_default", "rs_covisibility_candidates_device", "rs_covisibility_record_device", "rs_pose_graph_rows_device",
+    "rs_landmarks_sharing_view_device", "rs_add_views_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -388,6 +393,8 @@ def lib():
     L.rs_covisibility_candidates_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, u32, cvp] + [vp] * 7
     L.rs_covisibility_record_device.argtypes = [vp, vp, vp, u32, vp, u32, cvp, vp, vp, vp, vp]
     L.rs_pose_graph_rows_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+    L.rs_landmarks_sharing_view_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, vp, vp]
+    L.rs_add_views_device.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, u32, u32, u32, vp, u32] + [vp] * 8 + [u32, u32] + [vp] * 10
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

@@ -191,6 +191,13 @@ struct RsCovisibilityState {
     size_t bytes = 0;
 };
 RsCovisibilityState* rs_internal_covisibility(rs_ctx* c);
+// What rs_landmark_table.hip keeps in an rs_ctx, grown on demand and freed by rs_destroy: the words of one rs_add_views_device
+// call (five per landmark, one per block, per scan tile and per feature of a slot, the slots' own).
+struct RsLandmarkTableState {
+    void* d_scratch = nullptr;
+    size_t bytes = 0;
+};
+RsLandmarkTableState* rs_internal_landmark_table(rs_ctx* c);
 
 // A context's scratch, grown on demand: *d holds at least `need` bytes afterwards (what it held before is not kept).
 inline int32_t akz_grow_scratch(hipStream_t stream, void** d, size_t* have, size_t need)

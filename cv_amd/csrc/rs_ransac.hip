@@ -1489,6 +1489,7 @@ struct rs_ctx : RsArena {
     RsObsFilterState obs_filter;                                       // rs_observation_filter.hip's (akz_common.h)
     RsSingleViewState single_view;                                     // rs_single_view.hip's (akz_common.h)
     RsCovisibilityState covisibility;                                  // rs_covisibility.hip's (akz_common.h)
+    RsLandmarkTableState landmark_table;                               // rs_landmark_table.hip's (akz_common.h)
 };
 
 // (akz_common.h) what rs_triangulate.hip enqueues with
@@ -1497,6 +1498,7 @@ RsPoseGraphState* rs_internal_pose_graph(rs_ctx* c) { return &c->pose_graph; }
 RsObsFilterState* rs_internal_obs_filter(rs_ctx* c) { return &c->obs_filter; }
 RsSingleViewState* rs_internal_single_view(rs_ctx* c) { return &c->single_view; }
 RsCovisibilityState* rs_internal_covisibility(rs_ctx* c) { return &c->covisibility; }
+RsLandmarkTableState* rs_internal_landmark_table(rs_ctx* c) { return &c->landmark_table; }
 
 // Every device array of an arena, once: where its pointer lives and its bytes per scene (n matches, H hypothesis slots).
 struct RsSlot {
@@ -1624,6 +1626,7 @@ extern "C" int32_t rs_destroy(rs_ctx* c)
         hipFree(c->obs_filter.d_chain);
         hipFree(c->single_view.d_scratch);
         hipFree(c->covisibility.d_scratch);
+        hipFree(c->landmark_table.d_scratch);
         if (c->ev) hipEventDestroy(c->ev);
         if (c->stream) hipStreamDestroy(c->stream);
         delete c;

@@ -14,8 +14,13 @@ hm_hash_bag_device -> hm_knn_batch_device (k = 3, frames x views problems) -> hm
 hm_landmark_matches_batch_device -> rs_p3p_arrsac_batch_device (and, with refine(), hm_landmark_original_matches_batch_device ->
 rs_refine_poses_batch_device: the single-view optimiser and consistency filter of cv-sfm/src/lib.rs:1625-1775) on the blocks where akz_extract_batch_device left them; nothing
 returns to the host in between.  What stays with the caller is the reference's control plane: which views a frame is matched
-against, which landmark each stored feature observes (and so which features observe each landmark: a LandmarkTable), and
-for the merge candidates (decision 2) the graph test are_landmarks_sharing_view — handed in as a mask.  The table of
+against.  Which landmark each stored feature observes, which features observe each landmark (a LandmarkTable) and the row
+lengths come from the device too: add_views() behind refine() is VSlamData::add_view for the accepted frames of the
+micro-batch (cv-sfm/src/lib.rs:432-483, merge_landmarks :699-721) and leaves the next generation of the table, the landmark
+map match_views() reads and the counts consensus() sorts by where the next call takes them; sharing_view() behind
+match_views() is the graph test are_landmarks_sharing_view (:1435-1449) for the merge candidates (decision 2), whose mask
+triangulate_merged() and consensus() take (cv_amd/landmark_table.py; add_views_and_regenerate there chains refine ->
+add_views -> triangulate -> regenerate with one wait).  A caller may still hand in a mask of its own.  The table of
 triangulated landmarks is made on the device from the poses and the observation lists: triangulate() for the rows indexed
 by landmark key, triangulate_merged() between match_views() and consensus() for the rows of the merge candidates
 (cv-sfm/src/lib.rs:1590-1593, 2958-3000); a caller may still bring a table of its own.  There is no CPU fallback.
@@ -27,6 +32,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .knn import Matcher
+from .landmark_table import LandmarkUpdate
 from .ransac import EssentialConsensus
 from .single_view import RefineOutputs, SingleViewRefiner
 from . import triangulation
@@ -73,12 +79,13 @@ class Registration:
         self._sets = [dict(best=z((F, cap, 3, 2), torch.int32), decision=z((F, cap), torch.int32), pairs=z((F, cap, 2), torch.int32),
                            npairs=z((F,), torch.int32), pose=z((F, 12), torch.float64), best_id=z((F,), torch.int32),
                            inliers=z((F, cap), torch.int32), n_inliers=z((F,), torch.int32), stats=z((F, 32), torch.uint8),
-                           originals=z((F, cap, 2), torch.int32), noriginals=z((F,), torch.int32),
+                           originals=z((F, cap, 2), torch.int32), noriginals=z((F,), torch.int32), merge_ok=z((F, cap), torch.uint8),
                            refined=RefineOutputs(z((F, 12), torch.float64), z((F,), torch.int32), z((F, cap), torch.uint8),
                                                  z((F,), torch.int32), z((F, _lib.RS_SV_STATS), torch.int32)),
                            done=torch.cuda.Event(), used=False) for _ in range(2)]
         self.refiner = SingleViewRefiner(self.cons)
         self.sv_prm = self.refiner.params()              # the reference's single-view defaults
+        self.landmarks = LandmarkUpdate(self.cons)
         self._calls = 0
         self._hm_s = torch.cuda.ExternalStream(self.hm_stream(), device=self.dev)
         self._rs_s = torch.cuda.ExternalStream(self.rs_stream(), device=self.dev)
@@ -224,6 +231,37 @@ class Registration:
                                     stream_to_wait=self.hm_stream())
         cur["done"].record(self._rs_s)
         return self.refined
+
+    def sharing_view(self, table):
+        """are_landmarks_sharing_view (cv-sfm/src/lib.rs:1435-1449) for the merge candidates of the last match_views() over
+        `table` (a triangulation.LandmarkTable): self.merge_ok [F][cap] uint8, non-zero where decision 2 names two landmarks of
+        the table that share no view.  Reads self.best / decision where match_views() left them: enqueued on rs_stream() behind
+        the matcher's stream, no host step.  Returns the mask: hand it to triangulate_merged() and, with rs_stream() as
+        stream_to_wait, to consensus()."""
+        F = len(self._fb)
+        self.landmarks.sharing_view_device(table.d_start.data_ptr(), table.d_obs.data_ptr(), table.n_obs, table.n_landmarks,
+                                           self.best.data_ptr(), self.decision.data_ptr(), self.cap, F, self.merge_ok.data_ptr(),
+                                           self.hm_stream())
+        return self.merge_ok
+
+    def add_views(self, table, d_poses, d_split=None, d_split_count=None, skip=None, obs_room=None, lm_room=None):
+        """VSlamData::add_view (cv-sfm/src/lib.rs:432-483) for the frames of the last refine() whose verdict is RS_SV_OK, over
+        `table` — the LandmarkTable that refine() read — out of place.  d_poses [blocks][12] float64: the views' poses; the rows
+        of the accepted frames are written from the refined poses.  d_split [room][2] / d_split_count [1] (optional): the split
+        list of the observation filter that wrote `table`, whose rows become landmarks of one observation.  skip [F] (optional,
+        a numpy array or device tensor): non-zero leaves a slot out — the reference's remove_view after a refused
+        record_view_constraints is this call again, from `table`, with that slot skipped.  Enqueued on rs_stream() behind the
+        refinement; no wait -> landmark_table.AddViewsTensors: table(torch) for the next triangulate() / refine(), landmarks_out
+        for the next match_views(), obs_counts_out for the next consensus()."""
+        d_kps, d_counts, d_world, n_world, d_merge_ok, d_obs_counts = self._consensus_args
+        split_room = None if d_split is None else int(np.prod(d_split.shape)) // 2
+        o = self.landmarks.add_views_tensors(self.torch, table, d_poses, self.cap, [int(b) for b in self._fb], d_counts, self.originals,
+                                             self.noriginals, self.refined.final, self.refined.verdict, self.refined.pose,
+                                             best=None if d_merge_ok is None else self.best, skip=skip, split=d_split,
+                                             split_count=d_split_count, split_room=split_room, n_world=n_world, obs_room=obs_room,
+                                             lm_room=lm_room)
+        self._cur["done"].record(self._rs_s)             # this set's lists have been read when the call has run
+        return o
 
     def sync(self):
         check(_lib.lib().hm_sync(self.matcher.handle), "hm_sync")

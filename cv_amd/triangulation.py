@@ -113,18 +113,23 @@ class LandmarkTable:
         self.dev = dev
 
     @classmethod
-    def from_device(cls, torch, d_start, d_obs, n_landmarks, n_obs):
+    def from_device(cls, torch, d_start, d_obs, n_landmarks, n_obs, d_obs_counts=None):
         """A table over arrays that are on the device already (reconstruction.ObservationFilter's filtered table): d_start
         [n_landmarks + 1] and d_obs [n_obs][2], 4-byte integer tensors that are kept, not copied.  n_obs is the room of d_obs; how
         many rows the table fills is d_start[n_landmarks], known on the device.  Nothing is brought to the host, so nothing is
-        validated here: the kernels refuse a list that leaves [0, n_obs]."""
+        validated here: the kernels refuse a list that leaves [0, n_obs].  d_obs_counts [n_landmarks] (optional): the row lengths
+        where the producer wrote them (landmark_table.AddViewsTensors); computed from d_start on the current torch stream
+        otherwise."""
         if not (d_start.is_cuda and d_obs.is_cuda and d_start.is_contiguous() and d_obs.is_contiguous() and d_start.element_size() == 4 and
                 d_obs.element_size() == 4 and d_start.numel() >= n_landmarks + 1 and d_obs.numel() >= 2 * n_obs):
             raise ValueError("contiguous 4-byte device tensors of [n_landmarks + 1] and [n_obs][2]")
         t = cls.__new__(cls)
         t.torch, t.n_landmarks, t.n_obs, t.dev = torch, int(n_landmarks), int(n_obs), d_start.device
         t.d_start, t.d_obs = d_start, d_obs
-        t.d_obs_counts = (d_start.view(torch.int32)[1:n_landmarks + 1] - d_start.view(torch.int32)[:n_landmarks]).contiguous()
+        if d_obs_counts is not None:
+            t.d_obs_counts = d_obs_counts
+        else:
+            t.d_obs_counts = (d_start.view(torch.int32)[1:n_landmarks + 1] - d_start.view(torch.int32)[:n_landmarks]).contiguous()
         return t
 
     def new_world(self, extra_rows=0):

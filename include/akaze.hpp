@@ -928,6 +928,57 @@ private:
     rs_single_view_params p_;
     rs_ctx* ctx_ = nullptr;
 };
+
+// cv-sfm's landmark bookkeeping around the registration of a micro-batch over rs_landmarks_sharing_view_device and
+// rs_add_views_device: the graph test behind a merge candidate (VSlam::are_landmarks_sharing_view, cv-sfm/src/lib.rs:1435-1449)
+// and VSlamData::add_view with merge_landmarks (lib.rs:432-483, 699-721) for the accepted frames, out of place.  It works on the
+// context of the consensus that registered the frames (`ctx`, not owned: the calls queue behind the refinement on that
+// context's stream, no host step) or, built from a device number, on a small context of its own.  Every argument named d_* is
+// device memory the caller owns (the layouts are include/akz.h's); the calls enqueue and return.
+class LandmarkBook {
+public:
+    enum Verdict : uint32_t { Ok = RS_AV_OK, NotAccepted = RS_AV_NOT_ACCEPTED, BadIndex = RS_AV_BAD_INDEX, BadTable = RS_AV_BAD_TABLE };
+    explicit LandmarkBook(rs_ctx* ctx) : ctx_(ctx) { akaze::require_abi(); }
+    explicit LandmarkBook(int device = 0) : owned_(true)
+    {
+        akaze::require_abi();
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+    }
+    ~LandmarkBook() { if (owned_ && ctx_) rs_destroy(ctx_); }
+    LandmarkBook(const LandmarkBook&) = delete;
+    LandmarkBook& operator=(const LandmarkBook&) = delete;
+    void sharing_view(const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks, const void* d_best, const void* d_decision,
+                      uint32_t cap_per_img, uint32_t n_frames, void* d_merge_ok, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_landmarks_sharing_view_device(ctx_, d_obs_start, d_obs, n_obs, n_landmarks, d_best, d_decision, cap_per_img, n_frames,
+                                                      d_merge_ok, stream_to_wait),
+                     "rs_landmarks_sharing_view_device");
+    }
+    void add_views(const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks, uint32_t n_world, const void* d_split,
+                   const void* d_split_count, uint32_t split_room, uint32_t cap_per_img, uint32_t n_blocks, const std::vector<uint32_t>& ik,
+                   const void* d_counts, const void* d_matches, const void* d_nmatches, const void* d_final, const void* d_verdict,
+                   const void* d_pose_out, const void* d_best, const void* d_skip, uint32_t obs_room, uint32_t lm_room, void* d_poses,
+                   void* d_obs_start_out, void* d_obs_out, void* d_counts_out, void* d_landmarks_out, void* d_obs_counts_out,
+                   void* d_frame_verdict, void* d_stats, void* d_call_verdict, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_add_views_device(ctx_, d_obs_start, d_obs, n_obs, n_landmarks, n_world, d_split, d_split_count, split_room, cap_per_img,
+                                         n_blocks, ik.data(), (uint32_t)ik.size(), d_counts, d_matches, d_nmatches, d_final, d_verdict, d_pose_out,
+                                         d_best, d_skip, obs_room, lm_room, d_poses, d_obs_start_out, d_obs_out, d_counts_out, d_landmarks_out,
+                                         d_obs_counts_out, d_frame_verdict, d_stats, d_call_verdict, stream_to_wait),
+                     "rs_add_views_device");
+    }
+    // the least rooms add_views accepts
+    static uint64_t room(uint32_t n, uint32_t split_room, uint32_t n_frames, uint32_t cap_per_img)
+    {
+        return (uint64_t)n + split_room + (uint64_t)n_frames * cap_per_img;
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_ctx* ctx_ = nullptr;
+    bool owned_ = false;
+};
 }  // namespace cv_sfm
 
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over

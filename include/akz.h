@@ -1173,6 +1173,74 @@ int32_t rs_refine_poses_batch_device(rs_ctx* ctx, const void* d_kps, uint32_t ca
                                      const void* d_best_id, const void* d_inliers, const void* d_n_inliers, uint32_t n_scenes,
                                      const rs_single_view_params* params, void* d_pose_out, void* d_verdict, void* d_final,
                                      void* d_n_final, void* d_stats, void* stream_to_wait);
+/* ---- the landmark table of a reconstruction on the device: the graph test behind a merge, add_view for a micro-batch ----
+ * What cv-sfm keeps on the host between the registration of a frame and the next generation of its landmarks
+ * (VSlam::are_landmarks_sharing_view, cv-sfm/src/lib.rs:1435-1449; VSlamData::add_view, add_landmark and merge_landmarks,
+ * lib.rs:432-500, 699-721).  Integer data movement over the table rs_triangulate_landmarks_device reads; the decisions are
+ * include/akz_landmark_table_math.h (compiled for the device and, by the tests, for the host: equal byte for byte), whose head
+ * lists the departures from the reference — the rule for two frames of one call that name one landmark among them. */
+enum {
+    RS_AV_OK = 0,
+    RS_AV_NOT_ACCEPTED = 1,    /* the slot's refinement verdict is not RS_SV_OK, d_skip names it, or the call was refused */
+    RS_AV_BAD_INDEX = 2,       /* a count above cap_per_img, a final match that names nothing, or a feature in two final matches:
+                                * the slot is refused alone and contributes nothing */
+    RS_AV_BAD_TABLE = 3,       /* d_call_verdict only: the starts of the input table do not ascend inside [0, n_obs] */
+    /* d_stats words (u32) of a slot: */
+    RS_AV_S_OBSERVATIONS = 0,  /* observations added to rows of the input table (its final matches) */
+    RS_AV_S_MERGED = 1,        /* merges applied */
+    RS_AV_S_DEMOTED = 2,       /* merges demoted: the observation went to the first landmark alone */
+    RS_AV_S_NEW_LANDMARKS = 3, /* rows added behind the table (its features in no final match) */
+    RS_AV_STATS = 4,
+    RS_AV_COUNTS = 4,          /* d_counts_out: {rows filled, observations filled, merges applied, merges demoted} */
+    RS_LT_TILE = 1024          /* rows of the input table one workgroup scans (the tests walk its boundaries) */
+};
+/* are_landmarks_sharing_view for every merge candidate of a micro-batch.  The landmark table as
+ * rs_triangulate_landmarks_device takes it (d_obs_start [n_landmarks + 1], d_obs [n_obs][2] {block, feature}; the table fills
+ * the first min(d_obs_start[n_landmarks], n_obs) observations); d_best [n_frames][cap_per_img][3]{landmark, distance} and
+ * d_decision [n_frames][cap_per_img] as hm_best_of_views_batch_device leaves them.  d_merge_ok [n_frames][cap_per_img] u8, every
+ * byte written: 1 iff the decision is 2, best[0] and best[1] are below n_landmarks, both lists lie inside the table and share no
+ * block; 0 otherwise (an absent landmark, 0xFFFFFFFF, included).  Nothing is read out of bounds.  The mask is what
+ * rs_triangulate_merged_device and hm_landmark_matches_*_batch_device take.  n_frames <= 65535.  One launch on rs_stream() after
+ * stream_to_wait (may be NULL); returns after enqueueing. */
+int32_t rs_landmarks_sharing_view_device(rs_ctx* ctx, const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks,
+                                         const void* d_best, const void* d_decision, uint32_t cap_per_img, uint32_t n_frames,
+                                         void* d_merge_ok, void* stream_to_wait);
+/* add_view for the accepted frames of a micro-batch and the rows of the observation filter's split list: the next generation of
+ * the table, out of place (an output array that overlaps d_obs_start or d_obs: AKZ_E_INVALID).
+ * Inputs: the table (d_obs_start, d_obs, n_obs, n_landmarks); n_world, the row numbering of d_matches (as in
+ * rs_refine_poses_batch_device; a row below n_world but not below n_landmarks names nothing); the optional split list d_split
+ * [split_room][2] with its length d_split_count [1] u32 on the device (rs_filter_observations_device's d_split_out and
+ * d_counts[1]; both NULL and split_room 0 for none).  Slot f < n_frames is the frame in keypoint block ik[f] (a host list of
+ * distinct blocks below n_blocks, else AKZ_E_INVALID) with what the refinement left on the device: d_counts [n_blocks] u32 the
+ * feature counts, d_matches [n_frames][cap_per_img][2] {feature, world row} with d_nmatches [n_frames], d_final
+ * [n_frames][cap_per_img] u8, d_verdict [n_frames] (RS_SV_*), d_pose_out [n_frames][12] f64, d_best (optional, needed where a
+ * merged row occurs), d_skip [n_frames] u32 (optional, non-zero: leave the slot out).  obs_room >= n_obs + split_room + n_frames *
+ * cap_per_img and lm_room >= n_landmarks + split_room + n_frames * cap_per_img, else AKZ_E_INVALID: no kernel can overflow.
+ * A slot is accepted iff its verdict is RS_SV_OK, it is not skipped and it is valid: count and d_nmatches[f] <= cap_per_img and
+ * every final match (d_final != 0) names a feature below the count, once, and a row below min(n_world, n_landmarks) or the merged
+ * row n_world + f * cap_per_img + feature of its own slot with best[0] != best[1] both below n_landmarks.  A merged match
+ * (a, b) is applied iff no other final match of an accepted slot of the call names a or b; else it is demoted to a match of a.
+ * Outputs: d_obs_start_out [lm_room + 1], d_obs_out [obs_room][2].  Keys are stable.  Row l < n_landmarks: empty if l is the b of
+ * an applied merge; else its old list, the old list of the b merged into it, the new observations {ik[f], feature} in ascending
+ * slot order.  Row n_landmarks + k, k < min(*d_split_count, split_room): the k-th split observation.  Then, for the accepted
+ * slots in slot order, one row {ik[f], j} for every feature j below the count that is in no final match, ascending (add_landmark).
+ * Every start from there to lm_room equals the total: the rows beyond are empty.  d_obs_out behind the total is not written.
+ * d_counts_out [RS_AV_COUNTS] u32.  d_landmarks_out [n_blocks][cap_per_img] u32, every word written: the key of the row whose
+ * list holds {block, feature} (the lowest, where a broken table lists a feature twice), 0xFFFFFFFF for none — what
+ * hm_best_of_views_batch_device reads.  d_obs_counts_out [lm_room] u32: the row lengths
+ * (hm_landmark_matches_ordered_batch_device's d_obs_counts).  d_poses [n_blocks][12] f64, in place: row ik[f] = d_pose_out[f] for
+ * the accepted slots.  d_frame_verdict [n_frames] u32 (RS_AV_*), d_stats [n_frames][RS_AV_STATS] u32, d_call_verdict [1] u32:
+ * RS_AV_OK, or RS_AV_BAD_TABLE for a table whose starts do not ascend inside [0, n_obs] — no slot is accepted then and the
+ * outputs describe an empty table.  A stage behind may take (lm_room, obs_room) as its (n_landmarks, n_obs) without waiting for
+ * d_counts_out: the empty rows are RS_TRI_TOO_FEW / RS_OF_SINGLE there.  Enqueues on rs_stream() after stream_to_wait (may be
+ * NULL) and returns; allocates nothing beyond growing the context's scratch. */
+int32_t rs_add_views_device(rs_ctx* ctx, const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks, uint32_t n_world,
+                            const void* d_split, const void* d_split_count, uint32_t split_room, uint32_t cap_per_img, uint32_t n_blocks,
+                            const uint32_t* ik, uint32_t n_frames, const void* d_counts, const void* d_matches, const void* d_nmatches,
+                            const void* d_final, const void* d_verdict, const void* d_pose_out, const void* d_best, const void* d_skip,
+                            uint32_t obs_room, uint32_t lm_room, void* d_poses, void* d_obs_start_out, void* d_obs_out, void* d_counts_out,
+                            void* d_landmarks_out, void* d_obs_counts_out, void* d_frame_verdict, void* d_stats, void* d_call_verdict,
+                            void* stream_to_wait);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched

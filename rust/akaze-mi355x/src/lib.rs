@@ -168,6 +168,17 @@ extern "C" {
                                     d_n_inliers: *const c_void, n_scenes: u32, params: *const RsSingleViewParams, d_pose_out: *mut c_void,
                                     d_verdict: *mut c_void, d_final: *mut c_void, d_n_final: *mut c_void, d_stats: *mut c_void,
                                     stream_to_wait: *mut c_void) -> i32;
+    fn rs_landmarks_sharing_view_device(ctx: *mut c_void, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32,
+                                        d_best: *const c_void, d_decision: *const c_void, cap_per_img: u32, n_frames: u32,
+                                        d_merge_ok: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_add_views_device(ctx: *mut c_void, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32, n_world: u32,
+                           d_split: *const c_void, d_split_count: *const c_void, split_room: u32, cap_per_img: u32, n_blocks: u32,
+                           ik: *const u32, n_frames: u32, d_counts: *const c_void, d_matches: *const c_void, d_nmatches: *const c_void,
+                           d_final: *const c_void, d_verdict: *const c_void, d_pose_out: *const c_void, d_best: *const c_void,
+                           d_skip: *const c_void, obs_room: u32, lm_room: u32, d_poses: *mut c_void, d_obs_start_out: *mut c_void,
+                           d_obs_out: *mut c_void, d_counts_out: *mut c_void, d_landmarks_out: *mut c_void, d_obs_counts_out: *mut c_void,
+                           d_frame_verdict: *mut c_void, d_stats: *mut c_void, d_call_verdict: *mut c_void,
+                           stream_to_wait: *mut c_void) -> i32;
     fn hm_landmark_original_matches_batch_device(ctx: *mut c_void, d_best: *const c_void, d_decision: *const c_void, d_merge_ok: *const c_void,
                                                  d_obs_counts: *const c_void, d_nq: *const c_void, iq: *const u32, cap_per_img: u32,
                                                  n_frames: u32, n_world: u32, d_pairs: *mut c_void, d_npairs: *mut c_void,
@@ -1468,6 +1479,69 @@ impl SingleViewRefiner {
         let st = rs_refine_poses_batch_device(self.ctx, d_kps, cap_per_img, n_blocks, d_poses, cam, d_obs_start, d_obs, n_obs, n_landmarks, d_world,
                                               n_world, ik.as_ptr(), d_matches, d_nmatches, d_best, d_pose, d_best_id, d_inliers, d_n_inliers,
                                               ik.len() as u32, &self.params, d_pose_out, d_verdict, d_final, d_n_final, d_stats, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+}
+
+/// The verdict on a slot of `LandmarkBook::add_views` (`d_frame_verdict`) and on the call (`d_call_verdict`).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum AddViewVerdict {
+    Ok = 0,
+    NotAccepted = 1,
+    BadIndex = 2,
+    BadTable = 3,
+}
+
+/// The words of a slot's `d_stats` row and of `d_counts_out`, and the rows of the input table one workgroup scans.
+pub const RS_AV_STATS: usize = 4;
+pub const RS_AV_S_OBSERVATIONS: usize = 0;
+pub const RS_AV_S_MERGED: usize = 1;
+pub const RS_AV_S_DEMOTED: usize = 2;
+pub const RS_AV_S_NEW_LANDMARKS: usize = 3;
+pub const RS_AV_COUNTS: usize = 4;
+pub const RS_LT_TILE: u32 = 1024;
+
+/// cv-sfm's landmark bookkeeping around the registration of a micro-batch: `are_landmarks_sharing_view` for the merge
+/// candidates (cv-sfm/src/lib.rs:1435-1449, `rs_landmarks_sharing_view_device`) and `add_view` with `merge_landmarks` for the
+/// accepted frames (lib.rs:432-483, 699-721, `rs_add_views_device`), on the context of the consensus that registered them (not
+/// owned).  Every `d_*` argument is device memory the caller owns, laid out as include/akz.h documents; the calls enqueue and
+/// return.
+pub struct LandmarkBook {
+    ctx: *mut c_void,
+}
+impl LandmarkBook {
+    /// # Safety
+    /// `ctx` is a live `rs_ctx` that outlives this object.
+    pub unsafe fn new(ctx: *mut c_void) -> Self {
+        require_abi();
+        Self { ctx }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn sharing_view(&self, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32, d_best: *const c_void,
+                               d_decision: *const c_void, cap_per_img: u32, n_frames: u32, d_merge_ok: *mut c_void,
+                               stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_landmarks_sharing_view_device(self.ctx, d_obs_start, d_obs, n_obs, n_landmarks, d_best, d_decision, cap_per_img, n_frames,
+                                                  d_merge_ok, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn add_views(&self, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32, n_world: u32,
+                            d_split: *const c_void, d_split_count: *const c_void, split_room: u32, cap_per_img: u32, n_blocks: u32, ik: &[u32],
+                            d_counts: *const c_void, d_matches: *const c_void, d_nmatches: *const c_void, d_final: *const c_void,
+                            d_verdict: *const c_void, d_pose_out: *const c_void, d_best: *const c_void, d_skip: *const c_void, obs_room: u32,
+                            lm_room: u32, d_poses: *mut c_void, d_obs_start_out: *mut c_void, d_obs_out: *mut c_void,
+                            d_counts_out: *mut c_void, d_landmarks_out: *mut c_void, d_obs_counts_out: *mut c_void,
+                            d_frame_verdict: *mut c_void, d_stats: *mut c_void, d_call_verdict: *mut c_void,
+                            stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_add_views_device(self.ctx, d_obs_start, d_obs, n_obs, n_landmarks, n_world, d_split, d_split_count, split_room, cap_per_img,
+                                     n_blocks, ik.as_ptr(), ik.len() as u32, d_counts, d_matches, d_nmatches, d_final, d_verdict, d_pose_out,
+                                     d_best, d_skip, obs_room, lm_room, d_poses, d_obs_start_out, d_obs_out, d_counts_out, d_landmarks_out,
+                                     d_obs_counts_out, d_frame_verdict, d_stats, d_call_verdict, stream_to_wait);
         if st == 0 { Ok(()) } else { Err(st) }
     }
 }
