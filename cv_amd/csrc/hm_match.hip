@@ -20,9 +20,8 @@
 
 #include <hip/hip_ext.h>
 
-#include <unordered_map>
-
 #include "akz_common.h"
+#include "hm_plan.h"
 
 namespace {
 
@@ -861,6 +860,47 @@ __global__ __launch_bounds__(1024) void k_pairs(const HmPairProb* __restrict__ p
 
 }  // namespace
 
+// The per-launch event pool behind hm_timing_enable / hm_timing_get (bench.py's MFMA roofline): optional timing of the k-NN
+// launches, HIP events on the matcher stream.
+struct HmKnnTimer {
+    bool on = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // launches whose duration has not been read yet
+    std::vector<hipEvent_t> pool;
+    double ms = 0.0;
+    uint64_t launches = 0;
+    // the start / stop events of the next k-NN launch, which is counted; two nulls (an untimed launch) when timing is off or
+    // no event is to be had
+    std::pair<hipEvent_t, hipEvent_t> take()
+    {
+        hipEvent_t e[2] = {nullptr, nullptr};
+        if (!on) return {nullptr, nullptr};
+        for (hipEvent_t& x : e) {
+            if (!pool.empty()) { x = pool.back(); pool.pop_back(); }
+            else if (hipEventCreate(&x) != hipSuccess) x = nullptr;
+        }
+        if (!e[0] || !e[1]) {
+            for (hipEvent_t x : e)
+                if (x) pool.push_back(x);
+            return {nullptr, nullptr};
+        }
+        pending.emplace_back(e[0], e[1]);
+        launches += 1;
+        return pending.back();
+    }
+    // waits for the pending launches, adds their durations to `ms` and hands their events back to the pool
+    void drain()
+    {
+        for (auto& pr : pending) {
+            float t = 0.0f;
+            hipEventSynchronize(pr.second);
+            if (hipEventElapsedTime(&t, pr.first, pr.second) == hipSuccess) ms += (double)t;
+            pool.push_back(pr.first);
+            pool.push_back(pr.second);
+        }
+        pending.clear();
+    }
+};
+
 struct hm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -869,6 +909,7 @@ struct hm_ctx {
     uint4* d_a = nullptr;
     uint4* d_b = nullptr;
     uint32_t* d_na = nullptr;  // [2]: na, nb
+    uint32_t h_na[2] = {0, 0}; // what the current host-buffer call copies there (every such call ends with a stream sync)
     uint32_t resident_nt = 0;  // hm_set_targets: d_b holds this many target descriptors (0: nothing resident)
     bool resident = false;
     uint64_t generation = 0;   // of the resident set: hm_set_targets hands out a new one per upload (hm_targets_generation)
@@ -882,7 +923,7 @@ struct hm_ctx {
     // for the previous call's copies, i.e. for the previous micro-batch's whole extraction)
     struct StageSlot {
         void* d = nullptr;
-        void* h = nullptr;
+        void* h = nullptr;         // pinned staging twin
         size_t bytes = 0;
         hipEvent_t ev = nullptr;
         bool pending = false;
@@ -891,24 +932,17 @@ struct hm_ctx {
     StageSlot ring[kStageRing];
     uint64_t ring_pos = 0;
     StageSlot* slot = nullptr;     // the current call's slot
-    void* d_probs = nullptr;       // = slot->d
-    void* h_probs = nullptr;       // = slot->h, pinned staging twin
-    // scratch knn results for batched device calls
     // MFMA path: +-1 recoded descriptor blocks
-    uint32_t* d_exp = nullptr;
-    size_t exp_words = 0;
+    void* d_exp = nullptr;
+    size_t exp_bytes = 0;
     bool use_mfma = true;
     bool use_fp4 = true;           // E2M1 recoding + v_mfma_scale_f32_32x32x64_f8f6f4 (AKZ_MATCH_FP4=0: int8 MFMA)
     bool use_glds = true;          // the wide FP4 kernel, tiles by LDS-DMA (HM_OPT_NO_LDS_DMA: k_knn_mfma4, register-staged)
-    // optional timing of the k-NN launches (HIP events on the matcher stream), for bench.py's MFMA roofline
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> t_pending;
-    std::vector<hipEvent_t> t_pool;
-    double t_ms = 0.0;
-    uint64_t t_launches = 0, t_macs = 0;
-    akz_neighbor* d_bfwd = nullptr;
-    akz_neighbor* d_brev = nullptr;
-    size_t bscratch_elems = 0;
+    HmKnnTimer timer;
+    // scratch knn results: hm_knn / hm_knn_targets / hm_knn2 (forward) and the batched device calls (both directions)
+    void* d_bfwd = nullptr;
+    void* d_brev = nullptr;
+    size_t bfwd_bytes = 0, brev_bytes = 0;
     hipEvent_t ev = nullptr;
     // scratch of the host-buffer place-recognition calls (hm_hash_bag, hm_hash_knn)
     void* d_lsh = nullptr;
@@ -916,8 +950,8 @@ struct hm_ctx {
 };
 
 // Problem descriptors are built in pinned host memory and copied stream-ordered; the staging
-// buffer is reused only after the previous copy has completed.
-static int32_t hm_ensure_probs(hm_ctx* c, size_t bytes)
+// buffer is reused only after the previous copy has completed.  A call takes the ring's next slot, at least `bytes` large ...
+static int32_t hm_stage_take(hm_ctx* c, size_t bytes)
 {
     hm_ctx::StageSlot& S = c->ring[c->ring_pos++ % hm_ctx::kStageRing];
     c->slot = &S;
@@ -937,17 +971,23 @@ static int32_t hm_ensure_probs(hm_ctx* c, size_t bytes)
         AKZ_HIP(hipHostMalloc(&S.h, nb, hipHostMallocDefault));
         S.bytes = nb;
     }
-    c->d_probs = S.d;
-    c->h_probs = S.h;
     return AKZ_OK;
 }
-static int32_t hm_push_probs(hm_ctx* c, size_t off, const void* src, size_t bytes)
+// ... and pushes what its kernels read to byte offset `off` of it
+static int32_t hm_stage_push(hm_ctx* c, size_t off, const void* src, size_t bytes)
 {
-    memcpy((char*)c->h_probs + off, src, bytes);
-    AKZ_HIP(hipMemcpyAsync((char*)c->d_probs + off, (char*)c->h_probs + off, bytes, hipMemcpyHostToDevice, c->stream));
-    AKZ_HIP(hipEventRecord(c->slot->ev, c->stream));
-    c->slot->pending = true;
+    hm_ctx::StageSlot& S = *c->slot;
+    memcpy((char*)S.h + off, src, bytes);
+    AKZ_HIP(hipMemcpyAsync((char*)S.d + off, (char*)S.h + off, bytes, hipMemcpyHostToDevice, c->stream));
+    AKZ_HIP(hipEventRecord(S.ev, c->stream));
+    S.pending = true;
     return AKZ_OK;
+}
+// the device address of what was pushed there
+template <typename T>
+static const T* hm_staged(const hm_ctx* c, size_t off)
+{
+    return reinterpret_cast<const T*>((const char*)c->slot->d + off);
 }
 
 extern "C" int32_t hm_create_ex(int32_t device, uint32_t max_queries, uint32_t max_targets, uint32_t flags, hm_ctx** out)
@@ -963,8 +1003,6 @@ extern "C" int32_t hm_create_ex(int32_t device, uint32_t max_queries, uint32_t m
         AKZ_HIP(hipSetDevice(device));
         hm_ctx* c = new hm_ctx();
         c->device = device;
-        c->max_q = max_queries;
-        c->max_t = max_targets;
         uint32_t m = max_queries > max_targets ? max_queries : max_targets;
         c->max_q = c->max_t = m;  // symmetric matching swaps the roles
         {
@@ -1013,8 +1051,8 @@ extern "C" int32_t hm_destroy(hm_ctx* c)
             if (S.h) hipHostFree(S.h);
             if (S.ev) hipEventDestroy(S.ev);
         }
-        for (auto& pr : c->t_pending) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-        for (auto e : c->t_pool) hipEventDestroy(e);
+        c->timer.drain();
+        for (auto e : c->timer.pool) hipEventDestroy(e);
         hipFree(c->d_exp);
         hipFree(c->d_bfwd);
         hipFree(c->d_brev);
@@ -1036,117 +1074,126 @@ extern "C" int32_t hm_sync(hm_ctx* c)
     });
 }
 
-static int32_t launch_knn2(hm_ctx* c, const HmProb* h_probs, uint32_t n_probs, uint32_t max_nq, size_t probs_off,
-                           int knn = 2)
+// ---- one k-NN search over n_probs problems: launch_knn and its steps -------------------------------------------------
+// The call's descriptors sit at the start of its staging slot: [HmProbX x n_probs][HmExpandJob x jobs] (the VALU kernel:
+// [HmProb x n_probs]); bytes of staging the knn stage of a call needs
+static size_t knn_stage_bytes(uint32_t n_probs)
 {
-    if (n_probs == 0) return AKZ_OK;
-    if (!c->use_mfma && knn == 2) {   // the VALU kernel exists for k = 2 only
-        HmProb* dp = reinterpret_cast<HmProb*>((char*)c->d_probs + probs_off);
-        AKZ_TRY(hm_push_probs(c, probs_off, h_probs, sizeof(HmProb) * n_probs));
-        dim3 grid((max_nq + kQPB - 1) / kQPB, n_probs);
-        hipLaunchKernelGGL(k_knn2, grid, dim3(kBlock), 0, c->stream, dp);
-        AKZ_LAUNCH_CHECK();
-        return AKZ_OK;
-    }
-    // unique descriptor blocks referenced by the problems -> one +-1 recoding each
-    std::vector<HmExpandJob> jobs;
-    std::vector<size_t> job_off;   // word offset of each job's output inside d_exp
-    std::vector<HmProbX> px(n_probs);
-    size_t words = 0;
-    const size_t ew = c->use_fp4 ? 64 : 128;   // words of recoded descriptor
-    // block -> its jobs (a window call has thousands of problems over few blocks).  A job recodes rows [0, min(*count, cap)) of
-    // its block, so one address met with another count or another capacity is another job: a buffer passed both as the
-    // queries and as the targets of a call, each side with its own counts, must not share the shorter side's recoding.
-    std::unordered_multimap<const void*, size_t> seen;
-    auto expanded = [&](const uint4* src, const uint32_t* cnt, uint32_t cap) -> size_t {
-        const auto same = seen.equal_range((const void*)src);
-        for (auto it = same.first; it != same.second; ++it)
-            if (jobs[it->second].count == cnt && jobs[it->second].cap == cap) return job_off[it->second];
-        seen.emplace((const void*)src, jobs.size());
-        jobs.push_back(HmExpandJob{(const uint32_t*)src, cnt, cap, nullptr});
-        job_off.push_back(words);
-        words += (size_t)cap * ew;
-        return job_off.back();
-    };
-    std::vector<size_t> qoff(n_probs), toff(n_probs);
-    uint32_t max_cap = 0;
-    for (uint32_t i = 0; i < n_probs; ++i) {
-        qoff[i] = expanded(h_probs[i].q, h_probs[i].nq, h_probs[i].q_cap);
-        toff[i] = expanded(h_probs[i].t, h_probs[i].nt, h_probs[i].t_cap);
-        max_cap = std::max(max_cap, std::max(h_probs[i].q_cap, h_probs[i].t_cap));
-    }
-    if (words > c->exp_words) {
-        AKZ_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_exp) AKZ_HIP(hipFree(c->d_exp));
-        c->d_exp = nullptr;
-        AKZ_HIP(hipMalloc(&c->d_exp, sizeof(uint32_t) * words));
-        c->exp_words = words;
-    }
-    for (size_t i = 0; i < jobs.size(); ++i) jobs[i].dst = c->d_exp + job_off[i];
-    for (uint32_t i = 0; i < n_probs; ++i)
-        px[i] = HmProbX{c->d_exp + qoff[i], h_probs[i].nq, h_probs[i].q_cap, c->d_exp + toff[i], h_probs[i].nt,
-                        h_probs[i].t_cap, h_probs[i].out};
-    // descriptors for this call: [HmProbX x n_probs][HmExpandJob x jobs] inside the knn region of the staging buffer
-    const size_t jobs_off = probs_off + akz_align_up(sizeof(HmProbX) * n_probs, 64);
-    AKZ_TRY(hm_push_probs(c, probs_off, px.data(), sizeof(HmProbX) * n_probs));
-    AKZ_TRY(hm_push_probs(c, jobs_off, jobs.data(), sizeof(HmExpandJob) * jobs.size()));
-    if (c->use_fp4)
-        hipLaunchKernelGGL(k_expand4, dim3((max_cap * 16 + 255) / 256, (uint32_t)jobs.size()), dim3(256), 0, c->stream,
-                           reinterpret_cast<const HmExpandJob*>((char*)c->d_probs + jobs_off));
-    else
-        hipLaunchKernelGGL(k_expand, dim3((max_cap * 16 + 255) / 256, (uint32_t)jobs.size()), dim3(256), 0, c->stream,
-                           reinterpret_cast<const HmExpandJob*>((char*)c->d_probs + jobs_off));
-    AKZ_LAUNCH_CHECK();
-    // timing: the launch carries its own start / stop events (hipExtLaunchKernel: the dispatch's begin and end timestamps,
-    // i.e. the duration rocprofv3's kernel trace reports) — an event bracket on the stream would also count the time the
-    // launch waits for the other streams' kernels
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (c->timing) {
-        auto take = [&]() {
-            hipEvent_t e = nullptr;
-            if (!c->t_pool.empty()) { e = c->t_pool.back(); c->t_pool.pop_back(); }
-            else if (hipEventCreate(&e) != hipSuccess) e = nullptr;
-            return e;
-        };
-        ev0 = take();
-        ev1 = take();
-        if (!ev0 || !ev1) ev0 = ev1 = nullptr;
-    }
-    {
-        dim3 grid((max_nq + 255) / 256, n_probs);
-        const HmProbX* dp = reinterpret_cast<const HmProbX*>((char*)c->d_probs + probs_off);
-        if (c->use_fp4 && c->use_glds) {
-            switch (knn) {
-            case 1: hipExtLaunchKernelGGL(k_knn_mfma4w<1>, grid, dim3(kWideBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            case 3: hipExtLaunchKernelGGL(k_knn_mfma4w<3>, grid, dim3(kWideBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            default: hipExtLaunchKernelGGL(k_knn_mfma4w<2>, grid, dim3(kWideBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            }
-        } else if (c->use_fp4) {
-            switch (knn) {
-            case 1: hipExtLaunchKernelGGL(k_knn_mfma4<1>, grid, dim3(kMfmaBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            case 3: hipExtLaunchKernelGGL(k_knn_mfma4<3>, grid, dim3(kMfmaBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            default: hipExtLaunchKernelGGL(k_knn_mfma4<2>, grid, dim3(kMfmaBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            }
-        } else {
-            switch (knn) {
-            case 1: hipExtLaunchKernelGGL(k_knn_mfma<1>, grid, dim3(kMfmaBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            case 3: hipExtLaunchKernelGGL(k_knn_mfma<3>, grid, dim3(kMfmaBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            default: hipExtLaunchKernelGGL(k_knn_mfma<2>, grid, dim3(kMfmaBlock), 0, c->stream, ev0, ev1, 0, dp); break;
-            }
-        }
-    }
-    if (ev0 && ev1) {
-        c->t_pending.emplace_back(ev0, ev1);
-        c->t_launches += 1;
-    }
+    return akz_align_up(sizeof(HmProbX) * n_probs, 64) + akz_align_up(sizeof(HmExpandJob) * 2 * n_probs, 64) + 256;
+}
+static size_t knn_jobs_off(uint32_t n_probs) { return akz_align_up(sizeof(HmProbX) * n_probs, 64); }
+
+// The MFMA kernels, each instantiation named once: [family][k - 1] with its workgroup size.  The family is the context's
+// kernel switch.
+struct HmKnnKernel {
+    void (*fn)(const HmProbX*);
+    int block;
+};
+static const HmKnnKernel kKnnKernels[3][3] = {
+    {{k_knn_mfma4w<1>, kWideBlock}, {k_knn_mfma4w<2>, kWideBlock}, {k_knn_mfma4w<3>, kWideBlock}},   // FP4, tiles by LDS-DMA
+    {{k_knn_mfma4<1>, kMfmaBlock}, {k_knn_mfma4<2>, kMfmaBlock}, {k_knn_mfma4<3>, kMfmaBlock}},      // FP4, register-staged
+    {{k_knn_mfma<1>, kMfmaBlock}, {k_knn_mfma<2>, kMfmaBlock}, {k_knn_mfma<3>, kMfmaBlock}},         // int8
+};
+static int knn_family(const hm_ctx* c) { return !c->use_fp4 ? 2 : c->use_glds ? 0 : 1; }
+
+static int32_t launch_knn_valu(hm_ctx* c, const HmProb* h_probs, uint32_t n_probs, uint32_t max_nq)
+{
+    AKZ_TRY(hm_stage_push(c, 0, h_probs, sizeof(HmProb) * n_probs));
+    dim3 grid((max_nq + kQPB - 1) / kQPB, n_probs);
+    hipLaunchKernelGGL(k_knn2, grid, dim3(kBlock), 0, c->stream, hm_staged<HmProb>(c, 0));
     AKZ_LAUNCH_CHECK();
     return AKZ_OK;
 }
 
-// bytes of staging the knn stage of a call needs
-static size_t knn_stage_bytes(uint32_t n_probs)
+// the problems on the recoded blocks, and the expand jobs that write those
+static int32_t push_recoded(hm_ctx* c, const HmProb* h_probs, uint32_t n_probs, const HmPlan& plan)
 {
-    return akz_align_up(sizeof(HmProbX) * n_probs, 64) + akz_align_up(sizeof(HmExpandJob) * 2 * n_probs, 64) + 256;
+    uint32_t* const exp = static_cast<uint32_t*>(c->d_exp);
+    std::vector<HmProbX> px(n_probs);
+    for (uint32_t i = 0; i < n_probs; ++i)
+        px[i] = HmProbX{exp + plan.q_off[i], h_probs[i].nq, h_probs[i].q_cap, exp + plan.t_off[i], h_probs[i].nt,
+                        h_probs[i].t_cap, h_probs[i].out};
+    std::vector<HmExpandJob> jobs(plan.jobs.size());
+    for (size_t i = 0; i < jobs.size(); ++i)
+        jobs[i] = HmExpandJob{(const uint32_t*)plan.jobs[i].src, (const uint32_t*)plan.jobs[i].count, plan.jobs[i].cap,
+                              exp + plan.jobs[i].off};
+    AKZ_TRY(hm_stage_push(c, 0, px.data(), sizeof(HmProbX) * n_probs));
+    return hm_stage_push(c, knn_jobs_off(n_probs), jobs.data(), sizeof(HmExpandJob) * jobs.size());
+}
+
+static int32_t launch_expand(hm_ctx* c, uint32_t n_probs, const HmPlan& plan)
+{
+    const dim3 grid((plan.max_cap * 16 + 255) / 256, (uint32_t)plan.jobs.size());
+    hipLaunchKernelGGL(c->use_fp4 ? k_expand4 : k_expand, grid, dim3(256), 0, c->stream,
+                       hm_staged<HmExpandJob>(c, knn_jobs_off(n_probs)));
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+static int32_t launch_knn_mfma(hm_ctx* c, uint32_t n_probs, uint32_t max_nq, int k)
+{
+    // timing: the launch carries its own start / stop events (hipExtLaunchKernel: the dispatch's begin and end timestamps,
+    // i.e. the duration rocprofv3's kernel trace reports) — an event bracket on the stream would also count the time the
+    // launch waits for the other streams' kernels
+    const std::pair<hipEvent_t, hipEvent_t> ev = c->timer.take();
+    const HmKnnKernel& kn = kKnnKernels[knn_family(c)][k - 1];
+    hipExtLaunchKernelGGL(kn.fn, dim3((max_nq + 255) / 256, n_probs), dim3(kn.block), 0, c->stream, ev.first, ev.second, 0,
+                          hm_staged<HmProbX>(c, 0));
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
+// k neighbours (1, 2 or 3) of every query of every problem, in the staging slot the caller took (knn_stage_bytes(n_probs))
+static int32_t launch_knn(hm_ctx* c, const HmProb* h_probs, uint32_t n_probs, uint32_t max_nq, int k)
+{
+    if (n_probs == 0) return AKZ_OK;
+    if (!c->use_mfma && k == 2) return launch_knn_valu(c, h_probs, n_probs, max_nq);   // the VALU kernel exists for k = 2 only
+    // unique descriptor blocks referenced by the problems -> one +-1 recoding each
+    const HmPlan plan = hm_plan_recoding(h_probs, n_probs, c->use_fp4 ? 64 : 128);
+    AKZ_TRY(akz_grow_scratch(c->stream, &c->d_exp, &c->exp_bytes, sizeof(uint32_t) * plan.words));
+    AKZ_TRY(push_recoded(c, h_probs, n_probs, plan));
+    AKZ_TRY(launch_expand(c, n_probs, plan));
+    return launch_knn_mfma(c, n_probs, max_nq, k);
+}
+
+// ---- the host-buffer calls --------------------------------------------------------------------------------------------
+// Their descriptors are staged in d_a / d_b with the two counts in d_na.  Targets given (t != null) overwrite d_b and end
+// the residency of a set hm_set_targets put there; without them d_b is left alone.
+static int32_t hm_upload(hm_ctx* c, const akz_descriptor* q, uint32_t nq, const akz_descriptor* t, uint32_t nt)
+{
+    c->h_na[0] = nq;
+    c->h_na[1] = nt;
+    AKZ_HIP(hipMemcpyAsync(c->d_na, c->h_na, sizeof(c->h_na), hipMemcpyHostToDevice, c->stream));
+    if (nq) AKZ_HIP(hipMemcpyAsync(c->d_a, q, (size_t)nq * 64, hipMemcpyHostToDevice, c->stream));
+    if (!t) return AKZ_OK;
+    c->resident = false;   // (the staging buffer of the targets is overwritten)
+    if (nt) AKZ_HIP(hipMemcpyAsync(c->d_b, t, (size_t)nt * 64, hipMemcpyHostToDevice, c->stream));
+    return AKZ_OK;
+}
+
+// d_bfwd / d_brev hold at least `elems` neighbours each afterwards
+static int32_t hm_grow_lists(hm_ctx* c, size_t elems)
+{
+    AKZ_TRY(akz_grow_scratch(c->stream, &c->d_bfwd, &c->bfwd_bytes, sizeof(akz_neighbor) * elems));
+    return akz_grow_scratch(c->stream, &c->d_brev, &c->brev_bytes, sizeof(akz_neighbor) * elems);
+}
+
+// Search and copy back k neighbours per query, after the entry point's own checks: against t (hm_knn, hm_knn2) or, t null,
+// against the nt resident targets (hm_knn_targets).
+static int32_t hm_knn_host(hm_ctx* c, const akz_descriptor* q, uint32_t nq, const akz_descriptor* t, uint32_t nt, uint32_t k,
+                           akz_neighbor* out)
+{
+    if (nq == 0) return AKZ_OK;
+    AKZ_HIP(hipSetDevice(c->device));
+    AKZ_TRY(hm_stage_take(c, knn_stage_bytes(1)));
+    AKZ_TRY(hm_grow_lists(c, (size_t)nq * 3));
+    AKZ_TRY(hm_upload(c, q, nq, t, nt));
+    akz_neighbor* lists = static_cast<akz_neighbor*>(c->d_bfwd);
+    HmProb p = {c->d_a, c->d_na, nq, c->d_b, c->d_na + 1, nt ? nt : 1u, lists};
+    AKZ_TRY(launch_knn(c, &p, 1, nq, (int)k));
+    AKZ_HIP(hipMemcpyAsync(out, lists, sizeof(akz_neighbor) * k * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    AKZ_HIP(hipStreamSynchronize(c->stream));
+    return AKZ_OK;
 }
 
 extern "C" int32_t hm_knn2(hm_ctx* c, const akz_descriptor* q, uint32_t nq, const akz_descriptor* t, uint32_t nt,
@@ -1156,19 +1203,7 @@ extern "C" int32_t hm_knn2(hm_ctx* c, const akz_descriptor* q, uint32_t nq, cons
         if (!c || !q || !t || !out) return AKZ_E_INVALID;
         if (nt < 2) return AKZ_E_INVALID;  // the reference asserts two neighbours (estimate_pose.rs:89)
         if (nq > c->max_q || nt > c->max_t) return AKZ_E_TOO_LARGE;
-        if (nq == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        AKZ_TRY(hm_ensure_probs(c, knn_stage_bytes(1)));
-        uint32_t cnt[2] = {nq, nt};
-        AKZ_HIP(hipMemcpyAsync(c->d_na, cnt, sizeof(cnt), hipMemcpyHostToDevice, c->stream));
-        AKZ_HIP(hipMemcpyAsync(c->d_a, q, (size_t)nq * 64, hipMemcpyHostToDevice, c->stream));
-        c->resident = false;   // (the staging buffer of the targets is overwritten)
-        AKZ_HIP(hipMemcpyAsync(c->d_b, t, (size_t)nt * 64, hipMemcpyHostToDevice, c->stream));
-        HmProb p = {c->d_a, c->d_na, nq, c->d_b, c->d_na + 1, nt, c->d_fwd};
-        AKZ_TRY(launch_knn2(c, &p, 1, nq, 0));
-        AKZ_HIP(hipMemcpyAsync(out, c->d_fwd, sizeof(akz_neighbor) * 2 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-        AKZ_HIP(hipStreamSynchronize(c->stream));
-        return AKZ_OK;
+        return hm_knn_host(c, q, nq, t, nt, 2, out);
     });
 }
 
@@ -1179,29 +1214,7 @@ extern "C" int32_t hm_knn(hm_ctx* c, const akz_descriptor* q, uint32_t nq, const
     return akz_guard([&]() -> int32_t {
         if (!c || !q || !t || !out || k < 1 || k > 3) return AKZ_E_INVALID;
         if (nq > c->max_q || nt > c->max_t) return AKZ_E_TOO_LARGE;
-        if (nq == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        AKZ_TRY(hm_ensure_probs(c, knn_stage_bytes(1)));
-        size_t need = (size_t)nq * 3;
-        if (need > c->bscratch_elems) {
-            AKZ_HIP(hipStreamSynchronize(c->stream));
-            if (c->d_bfwd) AKZ_HIP(hipFree(c->d_bfwd));
-            if (c->d_brev) AKZ_HIP(hipFree(c->d_brev));
-            c->d_bfwd = c->d_brev = nullptr;
-            AKZ_HIP(hipMalloc(&c->d_bfwd, sizeof(akz_neighbor) * need));
-            AKZ_HIP(hipMalloc(&c->d_brev, sizeof(akz_neighbor) * need));
-            c->bscratch_elems = need;
-        }
-        uint32_t cnt[2] = {nq, nt};
-        AKZ_HIP(hipMemcpyAsync(c->d_na, cnt, sizeof(cnt), hipMemcpyHostToDevice, c->stream));
-        AKZ_HIP(hipMemcpyAsync(c->d_a, q, (size_t)nq * 64, hipMemcpyHostToDevice, c->stream));
-        c->resident = false;   // (the staging buffer of the targets is overwritten)
-        if (nt) AKZ_HIP(hipMemcpyAsync(c->d_b, t, (size_t)nt * 64, hipMemcpyHostToDevice, c->stream));
-        HmProb p = {c->d_a, c->d_na, nq, c->d_b, c->d_na + 1, nt ? nt : 1u, c->d_bfwd};
-        AKZ_TRY(launch_knn2(c, &p, 1, nq, 0, (int)k));
-        AKZ_HIP(hipMemcpyAsync(out, c->d_bfwd, sizeof(akz_neighbor) * k * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-        AKZ_HIP(hipStreamSynchronize(c->stream));
-        return AKZ_OK;
+        return hm_knn_host(c, q, nq, t, nt, k, out);
     });
 }
 
@@ -1241,29 +1254,25 @@ extern "C" int32_t hm_knn_targets(hm_ctx* c, const akz_descriptor* q, uint32_t n
     return akz_guard([&]() -> int32_t {
         if (!c || !q || !out || k < 1 || k > 3 || !c->resident) return AKZ_E_INVALID;
         if (nq > c->max_q) return AKZ_E_TOO_LARGE;
-        if (nq == 0) return AKZ_OK;
-        AKZ_HIP(hipSetDevice(c->device));
-        AKZ_TRY(hm_ensure_probs(c, knn_stage_bytes(1)));
-        const size_t need = (size_t)nq * 3;
-        if (need > c->bscratch_elems) {
-            AKZ_HIP(hipStreamSynchronize(c->stream));
-            if (c->d_bfwd) AKZ_HIP(hipFree(c->d_bfwd));
-            if (c->d_brev) AKZ_HIP(hipFree(c->d_brev));
-            c->d_bfwd = c->d_brev = nullptr;
-            AKZ_HIP(hipMalloc(&c->d_bfwd, sizeof(akz_neighbor) * need));
-            AKZ_HIP(hipMalloc(&c->d_brev, sizeof(akz_neighbor) * need));
-            c->bscratch_elems = need;
-        }
-        const uint32_t nt = c->resident_nt;
-        uint32_t cnt[2] = {nq, nt};
-        AKZ_HIP(hipMemcpyAsync(c->d_na, cnt, sizeof(cnt), hipMemcpyHostToDevice, c->stream));
-        AKZ_HIP(hipMemcpyAsync(c->d_a, q, (size_t)nq * 64, hipMemcpyHostToDevice, c->stream));
-        HmProb p = {c->d_a, c->d_na, nq, c->d_b, c->d_na + 1, nt ? nt : 1u, c->d_bfwd};
-        AKZ_TRY(launch_knn2(c, &p, 1, nq, 0, (int)k));
-        AKZ_HIP(hipMemcpyAsync(out, c->d_bfwd, sizeof(akz_neighbor) * k * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-        AKZ_HIP(hipStreamSynchronize(c->stream));
-        return AKZ_OK;
+        return hm_knn_host(c, q, nq, nullptr, c->resident_nt, k, out);
     });
+}
+
+// ---- the device-buffer calls ------------------------------------------------------------------------------------------
+// Problem p of a call over blocks of cap descriptors: every feature of query block iq[p] of d_q (iq null: block 0) against
+// target block it[p] of d_t, its lists at d_out [n_probs][cap][k].
+static int32_t knn_blocks_enqueue(hm_ctx* c, const void* d_q, const void* d_nq, const void* d_t, const void* d_nt, uint32_t cap,
+                                  const uint32_t* iq, const uint32_t* it, uint32_t n_probs, uint32_t k, void* d_out)
+{
+    AKZ_TRY(hm_stage_take(c, knn_stage_bytes(n_probs)));
+    std::vector<HmProb> hp(n_probs);
+    for (uint32_t p = 0; p < n_probs; ++p) {
+        const uint32_t a = iq ? iq[p] : 0u, b = it[p];
+        hp[p] = HmProb{(const uint4*)d_q + (size_t)a * cap * 4, (const uint32_t*)d_nq + a, cap,
+                       (const uint4*)d_t + (size_t)b * cap * 4, (const uint32_t*)d_nt + b, cap,
+                       (akz_neighbor*)d_out + (size_t)p * cap * k};
+    }
+    return launch_knn(c, hp.data(), n_probs, cap, (int)k);
 }
 
 // One query frame against n_views stored views (cv-sfm/src/lib.rs:1468-1486: every feature of the new frame is
@@ -1279,14 +1288,7 @@ extern "C" int32_t hm_knn_views_device(hm_ctx* c, const void* d_q, const void* d
         if (cap_per_img == 0 || cap_per_img >= (1u << (kIdxBits - 1))) return AKZ_E_INVALID;
         if (n_views == 0) return AKZ_OK;
         AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
-        AKZ_TRY(hm_ensure_probs(c, knn_stage_bytes(n_views)));
-        std::vector<HmProb> hp(n_views);
-        for (uint32_t v = 0; v < n_views; ++v)
-            hp[v] = HmProb{(const uint4*)d_q, (const uint32_t*)d_nq, cap_per_img,
-                           (const uint4*)d_views + (size_t)view_idx[v] * cap_per_img * 4,
-                           (const uint32_t*)d_nviews + view_idx[v], cap_per_img,
-                           (akz_neighbor*)d_out + (size_t)v * cap_per_img * k};
-        return launch_knn2(c, hp.data(), n_views, cap_per_img, 0, (int)k);
+        return knn_blocks_enqueue(c, d_q, d_nq, d_views, d_nviews, cap_per_img, nullptr, view_idx, n_views, k, d_out);
     });
 }
 
@@ -1302,13 +1304,7 @@ extern "C" int32_t hm_knn_batch_device(hm_ctx* c, const void* d_q, const void* d
         if (cap_per_img == 0 || cap_per_img >= (1u << (kIdxBits - 1)) || n_probs > 65535u) return AKZ_E_INVALID;
         if (n_probs == 0) return AKZ_OK;
         AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
-        AKZ_TRY(hm_ensure_probs(c, knn_stage_bytes(n_probs)));
-        std::vector<HmProb> hp(n_probs);
-        for (uint32_t p = 0; p < n_probs; ++p)
-            hp[p] = HmProb{(const uint4*)d_q + (size_t)iq[p] * cap_per_img * 4, (const uint32_t*)d_nq + iq[p], cap_per_img,
-                           (const uint4*)d_t + (size_t)it[p] * cap_per_img * 4, (const uint32_t*)d_nt + it[p], cap_per_img,
-                           (akz_neighbor*)d_out + (size_t)p * cap_per_img * k};
-        return launch_knn2(c, hp.data(), n_probs, cap_per_img, 0, (int)k);
+        return knn_blocks_enqueue(c, d_q, d_nq, d_t, d_nt, cap_per_img, iq, it, n_probs, k, d_out);
     });
 }
 
@@ -1373,6 +1369,24 @@ __global__ __launch_bounds__(256) void k_best_of_views(const akz_neighbor* __res
     decision[i] = dec;
 }
 
+// n_frames frames in one launch; iq null: the one frame of hm_best_of_views_device, its count d_nq[0]
+static int32_t best_of_views_enqueue(hm_ctx* c, const void* d_knn, const void* d_nq, const uint32_t* iq, uint32_t cap_per_img,
+                                     const uint32_t* view_idx, uint32_t n_frames, uint32_t n_views, uint32_t k, const void* d_landmarks,
+                                     const void* d_nviews, uint32_t better_by, void* d_best, void* d_decision, void* stream_to_wait)
+{
+    AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
+    const size_t vi_bytes = akz_align_up(sizeof(uint32_t) * (size_t)n_frames * n_views, 64);
+    AKZ_TRY(hm_stage_take(c, vi_bytes + sizeof(uint32_t) * n_frames + 64));
+    AKZ_TRY(hm_stage_push(c, 0, view_idx, sizeof(uint32_t) * (size_t)n_frames * n_views));
+    if (iq) AKZ_TRY(hm_stage_push(c, vi_bytes, iq, sizeof(uint32_t) * n_frames));
+    hipLaunchKernelGGL(k_best_of_views, dim3((cap_per_img + 255) / 256, n_frames), dim3(256), 0, c->stream,
+                       (const akz_neighbor*)d_knn, (const uint32_t*)d_nq, cap_per_img, n_views, k, (const uint32_t*)d_landmarks,
+                       hm_staged<uint32_t>(c, 0), (const uint32_t*)d_nviews, better_by, (uint2*)d_best, (uint32_t*)d_decision,
+                       iq ? hm_staged<uint32_t>(c, vi_bytes) : (const uint32_t*)nullptr);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
 extern "C" int32_t hm_best_of_views_device(hm_ctx* c, const void* d_knn, const void* d_nq, uint32_t cap_per_img,
                                            const uint32_t* view_idx, uint32_t n_views, uint32_t k, const void* d_landmarks,
                                            const void* d_nviews, uint32_t better_by, void* d_best, void* d_decision,
@@ -1381,15 +1395,8 @@ extern "C" int32_t hm_best_of_views_device(hm_ctx* c, const void* d_knn, const v
     return akz_guard([&]() -> int32_t {
         if (!c || !d_knn || !d_nq || !view_idx || !d_landmarks || !d_nviews || !d_best || !d_decision) return AKZ_E_INVALID;
         if (k < 1 || k > 3 || n_views == 0 || n_views > 64 || cap_per_img == 0) return AKZ_E_INVALID;
-        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
-        AKZ_TRY(hm_ensure_probs(c, 256));
-        AKZ_TRY(hm_push_probs(c, 0, view_idx, sizeof(uint32_t) * n_views));
-        hipLaunchKernelGGL(k_best_of_views, dim3((cap_per_img + 255) / 256), dim3(256), 0, c->stream, (const akz_neighbor*)d_knn,
-                           (const uint32_t*)d_nq, cap_per_img, n_views, k, (const uint32_t*)d_landmarks,
-                           (const uint32_t*)c->d_probs, (const uint32_t*)d_nviews, better_by, (uint2*)d_best,
-                           (uint32_t*)d_decision, (const uint32_t*)nullptr);
-        AKZ_LAUNCH_CHECK();
-        return AKZ_OK;
+        return best_of_views_enqueue(c, d_knn, d_nq, nullptr, cap_per_img, view_idx, 1, n_views, k, d_landmarks, d_nviews, better_by,
+                                     d_best, d_decision, stream_to_wait);
     });
 }
 
@@ -1405,17 +1412,8 @@ extern "C" int32_t hm_best_of_views_batch_device(hm_ctx* c, const void* d_knn, c
         if (!c || !d_knn || !d_nq || !iq || !view_idx || !d_landmarks || !d_nviews || !d_best || !d_decision) return AKZ_E_INVALID;
         if (k < 1 || k > 3 || n_views == 0 || n_views > 64 || cap_per_img == 0 || n_frames > 65535u) return AKZ_E_INVALID;
         if (n_frames == 0) return AKZ_OK;
-        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
-        const size_t vi_bytes = akz_align_up(sizeof(uint32_t) * (size_t)n_frames * n_views, 64);
-        AKZ_TRY(hm_ensure_probs(c, vi_bytes + sizeof(uint32_t) * n_frames + 64));
-        AKZ_TRY(hm_push_probs(c, 0, view_idx, sizeof(uint32_t) * (size_t)n_frames * n_views));
-        AKZ_TRY(hm_push_probs(c, vi_bytes, iq, sizeof(uint32_t) * n_frames));
-        hipLaunchKernelGGL(k_best_of_views, dim3((cap_per_img + 255) / 256, n_frames), dim3(256), 0, c->stream,
-                           (const akz_neighbor*)d_knn, (const uint32_t*)d_nq, cap_per_img, n_views, k, (const uint32_t*)d_landmarks,
-                           (const uint32_t*)c->d_probs, (const uint32_t*)d_nviews, better_by, (uint2*)d_best, (uint32_t*)d_decision,
-                           (const uint32_t*)((const char*)c->d_probs + vi_bytes));
-        AKZ_LAUNCH_CHECK();
-        return AKZ_OK;
+        return best_of_views_enqueue(c, d_knn, d_nq, iq, cap_per_img, view_idx, n_frames, n_views, k, d_landmarks, d_nviews, better_by,
+                                     d_best, d_decision, stream_to_wait);
     });
 }
 
@@ -1581,11 +1579,11 @@ static int32_t lm_matches_enqueue(hm_ctx* c, const void* d_best, const void* d_d
         if (d_merge_ok && (uint64_t)n_world + (uint64_t)n_frames * cap_per_img > 0xFFFFFFFFull) return AKZ_E_TOO_LARGE;
         if (n_frames == 0) return AKZ_OK;
         AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
-        AKZ_TRY(hm_ensure_probs(c, sizeof(uint32_t) * n_frames + 64));
-        AKZ_TRY(hm_push_probs(c, 0, iq, sizeof(uint32_t) * n_frames));
+        AKZ_TRY(hm_stage_take(c, sizeof(uint32_t) * n_frames + 64));
+        AKZ_TRY(hm_stage_push(c, 0, iq, sizeof(uint32_t) * n_frames));
         AKZ_HIP(hipFuncSetAttribute((const void*)k_landmark_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLmLdsBytes));
         hipLaunchKernelGGL(k_landmark_pairs, dim3(n_frames), dim3(1024), kLmLdsBytes, c->stream, (const uint2*)d_best,
-                           (const uint32_t*)d_decision, (const uint8_t*)d_merge_ok, (const uint32_t*)d_nq, (const uint32_t*)c->d_probs,
+                           (const uint32_t*)d_decision, (const uint8_t*)d_merge_ok, (const uint32_t*)d_nq, hm_staged<uint32_t>(c, 0),
                            cap_per_img, (const double*)d_world, n_world, (uint2*)d_pairs, (uint32_t*)d_npairs,
                            (const uint32_t*)d_obs_counts);
         AKZ_LAUNCH_CHECK();
@@ -1639,7 +1637,7 @@ extern "C" int32_t hm_timing_enable(hm_ctx* c, int32_t on)
 {
     return akz_guard([&]() -> int32_t {
         if (!c) return AKZ_E_INVALID;
-        c->timing = on != 0;
+        c->timer.on = on != 0;
         return AKZ_OK;
     });
 }
@@ -1647,19 +1645,12 @@ extern "C" int32_t hm_timing_get(hm_ctx* c, double* ms, uint64_t* launches, int3
 {
     return akz_guard([&]() -> int32_t {
         if (!c) return AKZ_E_INVALID;
-        for (auto& pr : c->t_pending) {
-            float t = 0.0f;
-            hipEventSynchronize(pr.second);
-            if (hipEventElapsedTime(&t, pr.first, pr.second) == hipSuccess) c->t_ms += (double)t;
-            c->t_pool.push_back(pr.first);
-            c->t_pool.push_back(pr.second);
-        }
-        c->t_pending.clear();
-        if (ms) *ms = c->t_ms;
-        if (launches) *launches = c->t_launches;
+        c->timer.drain();
+        if (ms) *ms = c->timer.ms;
+        if (launches) *launches = c->timer.launches;
         if (reset) {
-            c->t_ms = 0.0;
-            c->t_launches = 0;
+            c->timer.ms = 0.0;
+            c->timer.launches = 0;
         }
         return AKZ_OK;
     });
@@ -1681,20 +1672,16 @@ extern "C" int32_t hm_match(hm_ctx* c, const akz_descriptor* a, uint32_t na, con
         }
         AKZ_HIP(hipSetDevice(c->device));
         const size_t pair_off = akz_align_up(knn_stage_bytes(2), 256);
-        AKZ_TRY(hm_ensure_probs(c, pair_off + sizeof(HmPairProb) + 256));
-        uint32_t cnt[2] = {na, nb};
-        AKZ_HIP(hipMemcpyAsync(c->d_na, cnt, sizeof(cnt), hipMemcpyHostToDevice, c->stream));
-        AKZ_HIP(hipMemcpyAsync(c->d_a, a, (size_t)na * 64, hipMemcpyHostToDevice, c->stream));
-        c->resident = false;   // (the staging buffer of the targets is overwritten)
-        AKZ_HIP(hipMemcpyAsync(c->d_b, b, (size_t)nb * 64, hipMemcpyHostToDevice, c->stream));
+        AKZ_TRY(hm_stage_take(c, pair_off + sizeof(HmPairProb) + 256));
+        AKZ_TRY(hm_upload(c, a, na, b, nb));
         HmProb p[2] = {{c->d_a, c->d_na, na, c->d_b, c->d_na + 1, nb, c->d_fwd},
                        {c->d_b, c->d_na + 1, nb, c->d_a, c->d_na, na, c->d_rev}};
-        AKZ_TRY(launch_knn2(c, p, symmetric ? 2 : 1, na > nb ? na : nb, 0));
+        AKZ_TRY(launch_knn(c, p, symmetric ? 2 : 1, na > nb ? na : nb, 2));
         uint32_t kcap = cap < na ? cap : na;
         HmPairProb pp = {c->d_fwd, c->d_rev, c->d_na, c->d_na + 1, na, nb, c->d_pairs, kcap, c->d_npairs};
-        HmPairProb* dpp = reinterpret_cast<HmPairProb*>((char*)c->d_probs + pair_off);
-        AKZ_TRY(hm_push_probs(c, pair_off, &pp, sizeof(pp)));
-        hipLaunchKernelGGL(k_pairs, dim3(1), dim3(1024), 0, c->stream, dpp, (int)rule, param_u, param_f, (int)symmetric);
+        AKZ_TRY(hm_stage_push(c, pair_off, &pp, sizeof(pp)));
+        hipLaunchKernelGGL(k_pairs, dim3(1), dim3(1024), 0, c->stream, hm_staged<HmPairProb>(c, pair_off), (int)rule, param_u, param_f,
+                           (int)symmetric);
         AKZ_LAUNCH_CHECK();
         uint32_t n = 0;
         AKZ_HIP(hipMemcpyAsync(&n, c->d_npairs, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1718,18 +1705,9 @@ extern "C" int32_t hm_match_batch_device(hm_ctx* c, const void* d_a, const void*
         if (n_pairs == 0) return AKZ_OK;
         AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         const uint32_t ndir = symmetric ? 2u : 1u;
-        size_t need = (size_t)n_pairs * cap_per_img * 2;
-        if (need > c->bscratch_elems) {
-            AKZ_HIP(hipStreamSynchronize(c->stream));
-            if (c->d_bfwd) AKZ_HIP(hipFree(c->d_bfwd));
-            if (c->d_brev) AKZ_HIP(hipFree(c->d_brev));
-            c->d_bfwd = c->d_brev = nullptr;
-            AKZ_HIP(hipMalloc(&c->d_bfwd, sizeof(akz_neighbor) * need));
-            AKZ_HIP(hipMalloc(&c->d_brev, sizeof(akz_neighbor) * need));
-            c->bscratch_elems = need;
-        }
+        AKZ_TRY(hm_grow_lists(c, (size_t)n_pairs * cap_per_img * 2));
         size_t knn_bytes = akz_align_up(knn_stage_bytes(n_pairs * ndir), 256);
-        AKZ_TRY(hm_ensure_probs(c, knn_bytes + sizeof(HmPairProb) * n_pairs));
+        AKZ_TRY(hm_stage_take(c, knn_bytes + sizeof(HmPairProb) * n_pairs));
         std::vector<HmProb> hp(n_pairs * ndir);
         std::vector<HmPairProb> hpp(n_pairs);
         const uint4* A = (const uint4*)d_a;
@@ -1739,19 +1717,18 @@ extern "C" int32_t hm_match_batch_device(hm_ctx* c, const void* d_a, const void*
         for (uint32_t p = 0; p < n_pairs; ++p) {
             const uint4* qa = A + (size_t)ia[p] * cap_per_img * 4;
             const uint4* tb = B + (size_t)ib[p] * cap_per_img * 4;
-            akz_neighbor* fwd = c->d_bfwd + (size_t)p * cap_per_img * 2;
-            akz_neighbor* rev = c->d_brev + (size_t)p * cap_per_img * 2;
+            akz_neighbor* fwd = static_cast<akz_neighbor*>(c->d_bfwd) + (size_t)p * cap_per_img * 2;
+            akz_neighbor* rev = static_cast<akz_neighbor*>(c->d_brev) + (size_t)p * cap_per_img * 2;
             hp[p] = HmProb{qa, NA + ia[p], cap_per_img, tb, NB + ib[p], cap_per_img, fwd};
             if (symmetric) hp[n_pairs + p] = HmProb{tb, NB + ib[p], cap_per_img, qa, NA + ia[p], cap_per_img, rev};
             hpp[p] = HmPairProb{fwd, rev, NA + ia[p], NB + ib[p], cap_per_img, cap_per_img,
                                 (uint32_t*)d_pairs + (size_t)p * cap_per_img * 2, cap_per_img,
                                 (uint32_t*)d_n_out + p};
         }
-        AKZ_TRY(launch_knn2(c, hp.data(), n_pairs * ndir, cap_per_img, 0));
-        HmPairProb* dpp = reinterpret_cast<HmPairProb*>((char*)c->d_probs + knn_bytes);
-        AKZ_TRY(hm_push_probs(c, knn_bytes, hpp.data(), sizeof(HmPairProb) * n_pairs));
-        hipLaunchKernelGGL(k_pairs, dim3(n_pairs), dim3(1024), 0, c->stream, dpp, (int)rule, param_u, param_f,
-                           (int)symmetric);
+        AKZ_TRY(launch_knn(c, hp.data(), n_pairs * ndir, cap_per_img, 2));
+        AKZ_TRY(hm_stage_push(c, knn_bytes, hpp.data(), sizeof(HmPairProb) * n_pairs));
+        hipLaunchKernelGGL(k_pairs, dim3(n_pairs), dim3(1024), 0, c->stream, hm_staged<HmPairProb>(c, knn_bytes), (int)rule, param_u,
+                           param_f, (int)symmetric);
         AKZ_LAUNCH_CHECK();
         return AKZ_OK;
     });
@@ -1761,7 +1738,7 @@ extern "C" int32_t hm_match_batch_device(hm_ctx* c, const void* d_a, const void*
 // Frame-level place recognition.  Replaces
 //   hasher.hash_bag(features)                      cv-sfm/src/lib.rs:672   (HammingHasher<64, 512>, :205,216)
 //   lsh_to_frame.knn_values(&lsh, search_num)      cv-sfm/src/lib.rs:622-624
-// hash_bag is the matcher's own workload with the codebook as the target set: launch_knn2 with k = 1 — the MFMA kernel the
+// hash_bag is the matcher's own workload with the codebook as the target set: launch_knn with k = 1 — the MFMA kernel the
 // context's creation flags select (FP4 wide, FP4 register-staged or int8; the VALU kernel exists for k = 2 only) — gives every feature
 // its nearest codeword (lowest index among equals), k_bag_bits ORs the word bits into the frame's hash.  The
 // hashing crate (hamming-lsh 0.3.2) is not vendored in the reference: parity unpinned, see oracle/lsh_oracle.c.
@@ -1783,14 +1760,14 @@ static int32_t hash_bag_launch(hm_ctx* c, const uint4* d_descs, const uint32_t* 
 {
     // the codeword count has to be readable on the device like every other count: it rides in the staging slot
     const size_t cnt_off = akz_align_up(knn_stage_bytes(n_frames), 256);
-    AKZ_TRY(hm_ensure_probs(c, cnt_off + 64));
-    AKZ_TRY(hm_push_probs(c, cnt_off, &n_codewords, sizeof(uint32_t)));
-    const uint32_t* d_ncw = reinterpret_cast<const uint32_t*>((char*)c->d_probs + cnt_off);
+    AKZ_TRY(hm_stage_take(c, cnt_off + 64));
+    AKZ_TRY(hm_stage_push(c, cnt_off, &n_codewords, sizeof(uint32_t)));
+    const uint32_t* d_ncw = hm_staged<uint32_t>(c, cnt_off);
     std::vector<HmProb> hp(n_frames);
     for (uint32_t f = 0; f < n_frames; ++f)
         hp[f] = HmProb{d_descs + (size_t)f * cap * 4, d_counts + f, cap, d_codewords, d_ncw, n_codewords,
                        d_words + (size_t)f * cap};
-    AKZ_TRY(launch_knn2(c, hp.data(), n_frames, cap, 0, 1));
+    AKZ_TRY(launch_knn(c, hp.data(), n_frames, cap, 1));
     const uint32_t hash_words = n_codewords / 32u;
     AKZ_HIP(hipMemsetAsync(d_hash, 0, sizeof(uint32_t) * (size_t)n_frames * hash_words, c->stream));
     hipLaunchKernelGGL(k_bag_bits, dim3((cap + 255u) / 256u, n_frames), dim3(256), 0, c->stream, d_words, d_counts, cap,
@@ -1814,19 +1791,6 @@ extern "C" int32_t hm_hash_bag_device(hm_ctx* c, const void* d_descs, const void
     });
 }
 
-// grow-only device scratch of the host-buffer place-recognition calls
-static int32_t hm_lsh_scratch(hm_ctx* c, size_t bytes)
-{
-    if (bytes <= c->lsh_bytes) return AKZ_OK;
-    AKZ_HIP(hipStreamSynchronize(c->stream));
-    if (c->d_lsh) AKZ_HIP(hipFree(c->d_lsh));
-    c->d_lsh = nullptr;
-    c->lsh_bytes = 0;
-    AKZ_HIP(hipMalloc(&c->d_lsh, bytes));
-    c->lsh_bytes = bytes;
-    return AKZ_OK;
-}
-
 extern "C" int32_t hm_hash_bag(hm_ctx* c, const akz_descriptor* feats, uint32_t n, const akz_descriptor* codewords,
                                uint32_t n_codewords, uint8_t* hash, akz_neighbor* words)
 {
@@ -1837,13 +1801,10 @@ extern "C" int32_t hm_hash_bag(hm_ctx* c, const akz_descriptor* feats, uint32_t 
         AKZ_HIP(hipSetDevice(c->device));
         const uint32_t cap = n ? n : 1u;
         const size_t hash_off = akz_align_up(sizeof(akz_neighbor) * (size_t)cap, 256);
-        AKZ_TRY(hm_lsh_scratch(c, hash_off + n_codewords / 8));
+        AKZ_TRY(akz_grow_scratch(c->stream, &c->d_lsh, &c->lsh_bytes, hash_off + n_codewords / 8));
         akz_neighbor* d_words = reinterpret_cast<akz_neighbor*>(c->d_lsh);
         uint32_t* d_hash = reinterpret_cast<uint32_t*>((char*)c->d_lsh + hash_off);
-        AKZ_HIP(hipMemcpyAsync(c->d_na, &n, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        if (n) AKZ_HIP(hipMemcpyAsync(c->d_a, feats, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
-        c->resident = false;   // (the staging buffer of the targets is overwritten)
-        AKZ_HIP(hipMemcpyAsync(c->d_b, codewords, (size_t)n_codewords * 64, hipMemcpyHostToDevice, c->stream));
+        AKZ_TRY(hm_upload(c, feats, n, codewords, n_codewords));
         AKZ_TRY(hash_bag_launch(c, c->d_a, c->d_na, cap, 1, c->d_b, n_codewords, d_hash, d_words));
         AKZ_HIP(hipMemcpyAsync(hash, d_hash, n_codewords / 8, hipMemcpyDeviceToHost, c->stream));
         if (words && n)
@@ -1881,7 +1842,7 @@ extern "C" int32_t hm_hash_knn(hm_ctx* c, const uint8_t* query, const uint8_t* h
         AKZ_HIP(hipSetDevice(c->device));
         const uint32_t words = hash_bytes / 4u;
         const size_t q_off = akz_align_up((size_t)n * hash_bytes, 256), d_off = q_off + akz_align_up(hash_bytes, 256);
-        AKZ_TRY(hm_lsh_scratch(c, d_off + sizeof(uint32_t) * (size_t)n));
+        AKZ_TRY(akz_grow_scratch(c->stream, &c->d_lsh, &c->lsh_bytes, d_off + sizeof(uint32_t) * (size_t)n));
         uint32_t* d_h = reinterpret_cast<uint32_t*>(c->d_lsh);
         uint32_t* d_q = reinterpret_cast<uint32_t*>((char*)c->d_lsh + q_off);
         uint32_t* d_d = reinterpret_cast<uint32_t*>((char*)c->d_lsh + d_off);

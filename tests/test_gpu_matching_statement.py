@@ -367,3 +367,163 @@ def test_hash_knn_catalogue(gpu, hash_bytes):
                         assert idx.tolist() == list(range(min(k, n)))                  # insertion order
     finally:
         m.close()
+
+
+# ---- the host half: the timing pool, scratch that grows and is reused, the staging ring past one turn ----------------------
+# Descriptor blocks hold 65 queries x 193 targets unless stated: 65 = two column blocks of the wide kernel plus one query,
+# 193 = one tile past the three-stage ring — the smallest sizes that cross every boundary of all four kernels.
+
+def _near_copies(rng, a, nb):
+    """nb random rows with row 3 * i a near copy of a[i] (2 bits away) wherever it fits: pairs that every rule accepts."""
+    b = S.random_rows(rng, nb)
+    for i in range(min(len(a), nb // 3)):
+        b[3 * i] = S.flip(a[i], [i % 512, (i + 200) % 512])
+    return b
+
+
+def _timing(L, m, reset=0):
+    from cv_amd import _lib
+    ms, n = C.c_double(-1.0), C.c_uint64(77)
+    _lib.check(L.hm_timing_get(m.handle, C.byref(ms), C.byref(n), reset), "hm_timing_get")
+    return ms.value, n.value
+
+
+@pytest.mark.parametrize("kernel", ["fp4", "fp4_regs", "int8", "valu"])
+def test_timing_counts_the_knn_launches(gpu, kernel):
+    """hm_timing_enable / hm_timing_get (bench.py's MFMA roofline rests on them): three hm_knn calls (k = 1, 2, 3) and one
+    symmetric hm_match are four k-NN launches (the two directions of a match are two problems of ONE launch), a finite time
+    above zero, and answers equal to the statement.  A read with reset leaves 0 launches and 0.0 ms; with timing off nothing is
+    counted.  The VALU switch: its kernel exists for k = 2 only and its branch of launch_knn returns before the events are
+    taken, so the k = 2 search and the match go uncounted; k = 1 and k = 3 run (and are counted) on the FP4 kernel: 2."""
+    _, knn = gpu
+    from cv_amd import _lib
+    L = _lib.lib()
+    rng = S._rng(69, 1)
+    q, t = S.random_rows(rng, 65), S.random_rows(rng, 193)
+    b = _near_copies(rng, q, 193)
+    want_pairs = S.match(q, b, S.RULE_STRICT, 24, 0.5, True)
+    assert len(want_pairs) >= 60
+    m = knn.Matcher(193, kernel=kernel)
+    try:
+        assert _timing(L, m) == (0.0, 0)
+        _lib.check(L.hm_timing_enable(m.handle, 1), "hm_timing_enable")
+        for k in (1, 2, 3):
+            _check_case(m.knn(q, t, k), q, t, k, None, f"{kernel}, timed: k {k}")
+        assert np.array_equal(m.match(q, b, S.RULE_STRICT, 24, 0.5, True), want_pairs)
+        ms, n = _timing(L, m)
+        assert n == (2 if kernel == "valu" else 4), (kernel, n)
+        assert np.isfinite(ms) and ms > 0.0, (kernel, ms)
+        assert _timing(L, m, reset=1) == (ms, n)                                   # nothing new: the same sums, then cleared
+        assert _timing(L, m) == (0.0, 0)
+        _lib.check(L.hm_timing_enable(m.handle, 0), "hm_timing_enable")
+        _check_case(m.knn(q, t, 3), q, t, 3, None, f"{kernel}, untimed")
+        assert _timing(L, m) == (0.0, 0)
+    finally:
+        m.close()
+
+
+def test_scratch_grows_and_is_reused(gpu):
+    """Every grow-only scratch of the context through small, large, small on one fresh Matcher: the k-NN lists and the recoded
+    blocks (hm_knn, then hm_set_targets + hm_knn_targets — once more on a second fresh context, where the resident path does the
+    growing), the place-recognition scratch (hm_hash_knn), the batched lists (hm_match_batch_device — on that Matcher, whose
+    lists are large by then, and on a third fresh context of capacity 64, where the batched path does the growing)."""
+    _, knn = gpu
+    from cv_amd import _lib
+    L = _lib.lib()
+    rng = S._rng(69, 2)
+    t = S.random_rows(rng, 193)
+    qs = {n: S.random_rows(rng, n) for n in (40, 1500)}
+    for n in qs:
+        qs[n][::7] = t[(np.arange(len(qs[n][::7])) * 5) % 193]                      # exact copies: distance 0, and ties among queries
+    want = {n: S.knn(qs[n], t, 3) for n in qs}
+    m, m2, m3 = knn.Matcher(2048), knn.Matcher(2048), knn.Matcher(64)
+    try:
+        for n in (40, 1500, 40):
+            S.check_neighbors(m.knn(qs[n], t, 3), *want[n], S.ABI_ABSENT, f"hm_knn, {n} queries")
+        for mm in (m, m2):
+            mm.set_targets(t)
+            for n in (40, 1500, 40):
+                S.check_neighbors(mm.knn_targets(qs[n], 3), *want[n], S.ABI_ABSENT, f"hm_knn_targets, {n} queries")
+        hashes = rng.integers(0, 256, (300, 64), dtype=np.uint8)
+        hashes[299] = hashes[2]; hashes[7] = hashes[2]                              # ties, inside the short store as well
+        query = S.flip(hashes[2], [0, 77, 511])
+        for n in (8, 300, 8):
+            idx, dist = S.hash_knn(query, hashes[:n], 5)
+            out = np.full(5, 0xFFFFFFFF, np.uint64).view(S.NB); n_out = C.c_uint32(77)
+            stored = np.ascontiguousarray(hashes[:n])
+            _lib.check(L.hm_hash_knn(m.handle, query.ctypes.data, stored.ctypes.data, n, 64, 5, out.ctypes.data, C.byref(n_out)), "hm_hash_knn")
+            assert n_out.value == 5 and np.array_equal(out["index"], idx) and np.array_equal(out["distance"], dist), n
+            assert idx[0] == 2 and idx[1] == 7 and dist[0] == dist[1] == 3
+        cap, nblk = 64, 5
+        counts = np.array([64, 33, 2, 50, 1], np.int32)                             # (the last: fewer than two on a side, no pairs)
+        a = np.full((nblk, cap, 64), 0x5A, np.uint8); bb = np.full((nblk, cap, 64), 0xA5, np.uint8)
+        for blk in range(nblk):
+            a[blk, :counts[blk]] = S.random_rows(rng, counts[blk])
+            bb[blk, :counts[4 - blk]] = _near_copies(rng, a[blk, :counts[blk]], counts[4 - blk])
+        d_a, d_b, d_na, d_nb = _up(a), _up(bb), _up(counts), _up(counts[::-1].copy())
+        total = 0
+        for mm in (m, m3):
+            for ia, ib in (([1], [1]), ([0, 1, 2, 3, 4], [0, 1, 2, 3, 4]), ([3], [3])):
+                n = len(ia)
+                d_pairs, d_n = _filled(n * cap * 8), _filled(n * 4)
+                _lib.check(L.hm_match_batch_device(mm.handle, d_a.data_ptr(), d_na.data_ptr(), d_b.data_ptr(), d_nb.data_ptr(), cap, _u32p(ia), _u32p(ib),
+                                                   n, S.RULE_STRICT, 24, 0.5, 1, d_pairs.data_ptr(), d_n.data_ptr(), _wait()), "match_batch")
+                _lib.check(L.hm_sync(mm.handle), "hm_sync")
+                gp, gn = _down(d_pairs, np.uint32, (n, cap, 2)), _down(d_n, np.uint32, (n,))
+                for p, (x, y) in enumerate(zip(ia, ib)):
+                    wp = S.match(a[x, :counts[x]], bb[y, :counts[4 - y]], S.RULE_STRICT, 24, 0.5, True)
+                    assert gn[p] == len(wp) and np.array_equal(gp[p, :gn[p]], wp) and (gp[p, gn[p]:] == 0xFFFFFFFF).all(), (n, p, gn[p], len(wp))
+                    total += len(wp)
+        assert total >= 80                                                         # the pairs are there to be found
+    finally:
+        m.close()
+        m2.close()
+        m3.close()
+
+
+@pytest.mark.parametrize("times", [1, 8])
+def test_staging_ring_past_one_turn_with_a_slot_regrown(gpu, times):
+    """Six hm_knn_batch_device calls on a fresh context with no host wait in between, each into its own output slab: the ring
+    of four staging slots goes round once and a half.  The calls hold 1, 1, 1, 1, n, 1 problems, n the first count whose
+    descriptors (knn_stage_bytes: a 56-byte HmProbX and two 32-byte HmExpandJobs per problem, each table padded to 64, plus
+    256) no longer fit what the slot got at its first use (twice the bytes of one problem, rounded up to 4 096): the fifth call
+    regrows the slot of the first, whose kernels may still be running.  The two sizes and the slot's growth rule are restated
+    here — a test cannot read them from the library —, so n = 33 is the boundary only while hm_match.hip keeps them; the
+    second case takes eight times that count (264 problems, 31 936 bytes), which regrows the slot under any layout near it."""
+    _, knn = gpu
+    from cv_amd import _lib
+    L = _lib.lib()
+    up64 = lambda x: (x + 63) // 64 * 64
+    stage = lambda n: up64(56 * n) + up64(32 * 2 * n) + 256
+    first = (2 * stage(1) + 4095) // 4096 * 4096
+    n_big = next(n for n in range(1, 1000) if stage(n) > first)
+    assert (first, n_big) == (4096, 33) and stage(n_big - 1) <= first < stage(n_big)
+    cap, nblk, k = 64, 4, 3
+    rng = S._rng(69, 3)
+    counts = np.array([64, 33, 1, 50], np.int32)
+    blocks = np.full((nblk, cap, 64), 0x5A, np.uint8)
+    for blk in range(nblk):
+        blocks[blk, :counts[blk]] = S.random_rows(rng, counts[blk])
+    blocks[1, :20] = blocks[0, 40:60]                                               # distance 0 across blocks, ties inside
+    blocks[3, 10:14] = blocks[0, 7]
+    answer = {(x, y): S.knn(blocks[x, :counts[x]], blocks[y, :counts[y]], k) for x in range(nblk) for y in range(nblk)}
+    calls = []
+    for c, n in enumerate((1, 1, 1, 1, n_big * times, 1)):
+        iq = np.array([(c + p) % nblk for p in range(n)], np.uint32)
+        it = np.array([(c + p // nblk + 1) % nblk for p in range(n)], np.uint32)
+        calls.append((iq, it, _filled(n * cap * k * 8)))
+    d_blocks, d_counts = _up(blocks), _up(counts)
+    m = knn.Matcher(cap)
+    try:
+        wait = _wait()
+        for iq, it, d_out in calls:
+            _lib.check(L.hm_knn_batch_device(m.handle, d_blocks.data_ptr(), d_counts.data_ptr(), d_blocks.data_ptr(), d_counts.data_ptr(), cap,
+                                             _u32p(iq), _u32p(it), len(iq), k, d_out.data_ptr(), wait), "knn_batch")
+        _lib.check(L.hm_sync(m.handle), "hm_sync")
+        for c, (iq, it, d_out) in enumerate(calls):
+            got = _down(d_out, S.NB, (len(iq), cap, k))
+            for p, (x, y) in enumerate(zip(iq, it)):
+                S.check_neighbors(got[p, :counts[x]], *answer[x, y], S.ABI_ABSENT, f"call {c}, problem {p}: block {x} -> block {y}")
+                assert (got[p, counts[x]:]["index"] == 0xFFFFFFFF).all(), (c, p)
+    finally:
+        m.close()
