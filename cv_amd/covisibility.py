@@ -10,13 +10,12 @@ arrays ThreeViewConstraints.run_tensors reads (views, lm_start, lm), so the chai
 record -> PoseGraph.edges / rows_device -> ReconstructionOptimizer keeps every array on the device: reconstruction.regenerate
 does that.  The reference walks HashMaps here; the one admissible order the device fixes is in DESIGN.md §7.
 """
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._lib import check
+from . import _device, _lib
+from ._device import call
 
 VERDICTS = ("ok", "few_constraints", "bad_index", "no_graph")
 
@@ -59,49 +58,44 @@ class Covisibility:
 
     def candidates_device(self, d_obs_start, d_obs, n_obs, n_landmarks, cap, n_blocks, d_reason, d_targets, n_targets, params, d_views,
                           d_lm_start, d_lm, d_slot_count, d_target_verdict, d_stats, stream_to_wait=None):
-        """rs_covisibility_candidates_device: arguments named d_* are device pointers (ints).  Enqueues and returns."""
-        check(_lib.lib().rs_covisibility_candidates_device(
-            self._cons._h, d_obs_start, d_obs, n_obs, n_landmarks, cap, n_blocks, d_reason, d_targets, n_targets, C.byref(params), d_views,
-            d_lm_start, d_lm, d_slot_count, d_target_verdict, d_stats, stream_to_wait), "rs_covisibility_candidates_device")
+        """rs_covisibility_candidates_device: d_* and stream_to_wait as _device.arg / wait take them.  Enqueues and returns."""
+        call("rs_covisibility_candidates_device", self._cons._h, d_obs_start, d_obs, n_obs, n_landmarks, cap, n_blocks, d_reason,
+             d_targets, n_targets, params, d_views, d_lm_start, d_lm, d_slot_count, d_target_verdict, d_stats,
+             _device.wait(stream_to_wait))
 
     def record_device(self, d_constraint_verdict, d_targets, n_targets, d_graph_start, n_graphs, params, d_recorded, d_target_verdict,
                       d_stats, stream_to_wait=None):
-        """rs_covisibility_record_device: arguments named d_* are device pointers (ints).  Enqueues and returns."""
-        check(_lib.lib().rs_covisibility_record_device(
-            self._cons._h, d_constraint_verdict, d_targets, n_targets, d_graph_start, n_graphs, C.byref(params), d_recorded,
-            d_target_verdict, d_stats, stream_to_wait), "rs_covisibility_record_device")
+        """rs_covisibility_record_device: d_* and stream_to_wait as _device.arg / wait take them.  Enqueues and returns."""
+        call("rs_covisibility_record_device", self._cons._h, d_constraint_verdict, d_targets, n_targets, d_graph_start, n_graphs,
+             params, d_recorded, d_target_verdict, d_stats, _device.wait(stream_to_wait))
 
     def run_tensors(self, torch, table, cap, n_blocks, reason, targets, params=None):
         """The candidates of `targets` (a numpy array or a 4-byte device tensor) over `table` (a triangulation.LandmarkTable)
         with `reason` [n_landmarks] uint8 as rs_triangulate_landmarks_device wrote it.  Enqueued behind the current torch
         stream; no wait -> CovisibilityTensors."""
-        from .pose_graph import PoseGraph
         dev = table.dev
         params = params or self.params()
         limit = self.limit(params)
-        d_targets = PoseGraph._tensor(torch, targets, np.uint32, dev)
+        d_targets = _device.tensor(torch, targets, np.uint32, dev)
         n_targets = int(np.prod(targets.shape))
         n_slots = n_targets * limit
         z32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
         o = CovisibilityTensors(z32(max(n_slots, 1), 3), z32(n_slots + 1), z32(max(n_slots * int(params.optimization_maximum_landmarks), 1), 3),
                                 z32(max(n_slots, 1)), z32(max(n_targets, 1)), z32(max(n_targets, 1), _lib.RS_CV_STATS), d_targets, limit,
                                 n_targets)
-        self.candidates_device(table.d_start.data_ptr(), table.d_obs.data_ptr(), table.n_obs, table.n_landmarks, cap, n_blocks,
-                               reason.data_ptr(), d_targets.data_ptr(), n_targets, params, o.views.data_ptr(), o.lm_start.data_ptr(),
-                               o.lm.data_ptr(), o.slot_count.data_ptr(), o.target_verdict.data_ptr(), o.stats.data_ptr(),
-                               _lib.wait_handle(torch.cuda.current_stream(dev)))
+        self.candidates_device(table.d_start, table.d_obs, table.n_obs, table.n_landmarks, cap, n_blocks, reason, d_targets, n_targets,
+                               params, o.views, o.lm_start, o.lm, o.slot_count, o.target_verdict, o.stats, torch.cuda.current_stream(dev))
         return o
 
     def record_tensors(self, torch, candidates, constraint_verdict, graph_start, params=None):
         """The record behind the constraint stage's verdicts [n_slots] of `candidates` (a CovisibilityTensors, whose
         target_verdict and stats are updated in place).  No wait -> d_recorded [n_slots] int32, what PoseGraph.edges and the
         relaxation take as the constraints' verdicts."""
-        from .pose_graph import PoseGraph
         dev = candidates.views.device
-        d_gs = PoseGraph._tensor(torch, graph_start, np.uint32, dev)
+        d_gs = _device.tensor(torch, graph_start, np.uint32, dev)
         d_recorded = torch.zeros((max(candidates.n_slots, 1),), dtype=torch.int32, device=dev)
-        self.record_device(constraint_verdict.data_ptr(), candidates.targets.data_ptr(), candidates.n_targets, d_gs.data_ptr(),
-                           int(np.prod(graph_start.shape)) - 1, params or self.params(), d_recorded.data_ptr(),
-                           candidates.target_verdict.data_ptr(), candidates.stats.data_ptr(), _lib.wait_handle(torch.cuda.current_stream(dev)))
-        candidates.graph_start = d_gs             # alive until the stream has run
+        self.record_device(constraint_verdict, candidates.targets, candidates.n_targets, d_gs, int(np.prod(graph_start.shape)) - 1,
+                           params or self.params(), d_recorded, candidates.target_verdict, candidates.stats,
+                           torch.cuda.current_stream(dev))
+        candidates.graph_start = d_gs             # a field of what the caller holds: _device.keep_alive's rule
         return d_recorded

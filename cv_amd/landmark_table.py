@@ -12,14 +12,12 @@ poses of the new views — stays on the device, so that a micro-batch goes from 
 step: add_views_and_regenerate below chains the stages with one wait.  The one rule that is not the reference's (two frames
 of a call that name one landmark) is in DESIGN.md §7.
 """
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._lib import check
-from .pose_graph import PoseGraph
+from . import _device, _lib
+from ._device import call, host_u32 as u32
 from .triangulation import LandmarkTable
 
 VERDICTS = ("ok", "not_accepted", "bad_index", "bad_table")
@@ -71,21 +69,20 @@ class LandmarkUpdate:
         self._cons = consensus
 
     def sharing_view_device(self, d_obs_start, d_obs, n_obs, n_landmarks, d_best, d_decision, cap, n_frames, d_merge_ok, stream_to_wait=None):
-        """rs_landmarks_sharing_view_device: arguments named d_* are device pointers (ints).  Enqueues and returns."""
-        check(_lib.lib().rs_landmarks_sharing_view_device(self._cons._h, d_obs_start, d_obs, n_obs, n_landmarks, d_best, d_decision, cap,
-                                                          n_frames, d_merge_ok, stream_to_wait), "rs_landmarks_sharing_view_device")
+        """rs_landmarks_sharing_view_device: d_* and stream_to_wait as _device.arg / wait take them.  Enqueues and returns."""
+        call("rs_landmarks_sharing_view_device", self._cons._h, d_obs_start, d_obs, n_obs, n_landmarks, d_best, d_decision, cap, n_frames,
+             d_merge_ok, _device.wait(stream_to_wait))
 
     def add_views_device(self, d_obs_start, d_obs, n_obs, n_landmarks, n_world, d_split, d_split_count, split_room, cap, n_blocks, ik, d_counts,
                          d_matches, d_nmatches, d_final, d_verdict, d_pose_out, d_best, d_skip, obs_room, lm_room, d_poses, d_obs_start_out,
                          d_obs_out, d_counts_out, d_landmarks_out, d_obs_counts_out, d_frame_verdict, d_stats, d_call_verdict,
                          stream_to_wait=None):
-        """rs_add_views_device: arguments named d_* are device pointers (ints), ik a sequence of blocks.  Enqueues and returns."""
-        fb = np.ascontiguousarray(ik, np.uint32).reshape(-1)
-        check(_lib.lib().rs_add_views_device(self._cons._h, d_obs_start, d_obs, n_obs, n_landmarks, n_world, d_split, d_split_count, split_room,
-                                             cap, n_blocks, fb.ctypes.data_as(C.c_void_p), len(fb), d_counts, d_matches, d_nmatches, d_final,
-                                             d_verdict, d_pose_out, d_best, d_skip, obs_room, lm_room, d_poses, d_obs_start_out, d_obs_out,
-                                             d_counts_out, d_landmarks_out, d_obs_counts_out, d_frame_verdict, d_stats, d_call_verdict,
-                                             stream_to_wait), "rs_add_views_device")
+        """rs_add_views_device: d_* and stream_to_wait as _device.arg / wait take them, ik a sequence of blocks.  Enqueues and returns."""
+        blocks, n = _device.index_list(ik)
+        call("rs_add_views_device", self._cons._h, d_obs_start, d_obs, n_obs, n_landmarks, n_world, d_split, d_split_count, split_room,
+             cap, n_blocks, blocks, n, d_counts, d_matches, d_nmatches, d_final, d_verdict, d_pose_out, d_best, d_skip, obs_room, lm_room,
+             d_poses, d_obs_start_out, d_obs_out, d_counts_out, d_landmarks_out, d_obs_counts_out, d_frame_verdict, d_stats,
+             d_call_verdict, _device.wait(stream_to_wait))
 
     def sharing_view_tensors(self, torch, table, best, decision, out=None, stream_to_wait=None):
         """The mask of the merge candidates over `table` (a LandmarkTable): best [F][cap][3][2] and decision [F][cap] as
@@ -93,13 +90,13 @@ class LandmarkUpdate:
         stream (or stream_to_wait); no wait -> d_merge_ok [F][cap] uint8 on the device."""
         dev = table.dev
         F, cap = int(decision.shape[0]), int(decision.shape[1])
-        d_best, d_decision = PoseGraph._tensor(torch, best, np.uint32, dev), PoseGraph._tensor(torch, decision, np.uint32, dev)
+        d_best, d_decision = _device.tensor(torch, best, np.uint32, dev), _device.tensor(torch, decision, np.uint32, dev)
         if out is None:
             out = torch.zeros((max(F, 1), cap), dtype=torch.uint8, device=dev)
-        self.sharing_view_device(table.d_start.data_ptr(), table.d_obs.data_ptr(), table.n_obs, table.n_landmarks, d_best.data_ptr(),
-                                 d_decision.data_ptr(), cap, F, out.data_ptr(),
-                                 stream_to_wait or _lib.wait_handle(torch.cuda.current_stream(dev)))
-        out._inputs = (d_best, d_decision)               # alive until the stream has run
+        self.sharing_view_device(table.d_start, table.d_obs, table.n_obs, table.n_landmarks, d_best, d_decision, cap, F, out,
+                                 _device.wait_or_current(torch, stream_to_wait, dev))
+        # the caller gets a bare tensor back: the consensus holds what was uploaded for this call
+        _device.keep_alive(self._cons, *(d for d, a in ((d_best, best), (d_decision, decision)) if d is not a))
         return out
 
     def add_views_tensors(self, torch, table, d_poses, cap, frame_blocks, counts, matches, nmatches, final, verdict, pose_out, best=None,
@@ -114,8 +111,7 @@ class LandmarkUpdate:
         dev = table.dev
         F = len(frame_blocks)
         n_blocks = int(d_poses.shape[0])
-        t = lambda a, dt: None if a is None else PoseGraph._tensor(torch, a, dt, dev)
-        p = lambda a: None if a is None else a.data_ptr()
+        t = lambda a, dt: None if a is None else _device.tensor(torch, a, dt, dev)
         ins = [t(counts, np.uint32), t(matches, np.uint32), t(nmatches, np.uint32), t(final, np.uint8), t(verdict, np.uint32),
                t(pose_out, np.float64), t(best, np.uint32), t(skip, np.uint32), t(split, np.uint32), t(split_count, np.uint32)]
         if split is None:
@@ -128,14 +124,11 @@ class LandmarkUpdate:
         z32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
         o = AddViewsTensors(z32(lm_room + 1), z32(max(obs_room, 1), 2), z32(_lib.RS_AV_COUNTS), z32(n_blocks, cap), z32(max(lm_room, 1)),
                             z32(max(F, 1)), z32(max(F, 1), _lib.RS_AV_STATS), z32(1), d_poses, lm_room, obs_room, F)
-        self.add_views_device(table.d_start.data_ptr(), table.d_obs.data_ptr(), table.n_obs, table.n_landmarks,
-                              table.n_landmarks if n_world is None else n_world, p(ins[8]), p(ins[9]), split_room, cap, n_blocks, frame_blocks,
-                              p(ins[0]), p(ins[1]), p(ins[2]), p(ins[3]), p(ins[4]), p(ins[5]), p(ins[6]), p(ins[7]), obs_room, lm_room,
-                              d_poses.data_ptr(), o.obs_start_out.data_ptr(), o.obs_out.data_ptr(), o.counts_out.data_ptr(),
-                              o.landmarks_out.data_ptr(), o.obs_counts_out.data_ptr(), o.frame_verdict.data_ptr(), o.stats.data_ptr(),
-                              o.call_verdict.data_ptr(), stream_to_wait or _lib.wait_handle(torch.cuda.current_stream(dev)))
-        o._inputs = (ins, table)                         # alive until the stream has run
-        return o
+        self.add_views_device(table.d_start, table.d_obs, table.n_obs, table.n_landmarks, table.n_landmarks if n_world is None else n_world,
+                              ins[8], ins[9], split_room, cap, n_blocks, frame_blocks, *ins[:8], obs_room, lm_room, d_poses, o.obs_start_out,
+                              o.obs_out, o.counts_out, o.landmarks_out, o.obs_counts_out, o.frame_verdict, o.stats, o.call_verdict,
+                              _device.wait_or_current(torch, stream_to_wait, dev))
+        return _device.keep_alive(o, ins, table)
 
     def run_sharing_view(self, torch, table, best, decision):
         """sharing_view_tensors, then WAITS and copies to the host -> mask [F][cap] uint8."""
@@ -152,7 +145,6 @@ class LandmarkUpdate:
 
 def to_host(o):
     """An AddViewsTensors whose stream has been waited for -> AddViewsResult."""
-    u32 = lambda t: t.cpu().numpy().view(np.uint32)
     counts = u32(o.counts_out)
     rows, n = int(counts[0]), int(counts[1])
     return AddViewsResult(u32(o.obs_start_out)[:rows + 1], u32(o.obs_out)[:n], counts, u32(o.landmarks_out), u32(o.obs_counts_out)[:rows],

@@ -12,13 +12,12 @@ the device (relax waits and brings the verdicts to the host; relax_batch_device 
 flatten_constraints walks a HashMap in the reference, which defines no order of a view's edges: `flatten` builds one
 admissible order on the host.
 """
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._lib import check
+from . import _device, _lib
+from ._device import call
 
 VERDICTS = ("ok", "few_views", "nonfinite", "bad_index")
 VIEW_STATES = ("updated", "no_constraint", "nonfinite")
@@ -73,27 +72,27 @@ class PoseGraph:
     def resident_views(self, views=_lib.RS_PG_DEFAULT_RESIDENT_VIEWS):
         """parity tap: graphs of more than `views` views (at most RS_PG_RESIDENT_VIEWS) take the swept form from now on (0:
         every graph; a limit of at most 8 holds for the call's views in all); without an argument: the default again"""
-        check(_lib.lib().rs_pose_graph_debug_resident_views(self._cons._h, views), "rs_pose_graph_debug_resident_views")
+        call("rs_pose_graph_debug_resident_views", self._cons._h, views)
 
     def edges_device(self, d_views, d_constraint_poses, d_constraint_verdict, n_constraints, d_edges, stream_to_wait=None):
-        """rs_pose_graph_edges_device: arguments named d_* are device pointers (ints).  Enqueues and returns."""
-        check(_lib.lib().rs_pose_graph_edges_device(self._cons._h, d_views, d_constraint_poses, d_constraint_verdict, n_constraints,
-                                                    d_edges, stream_to_wait), "rs_pose_graph_edges_device")
+        """rs_pose_graph_edges_device: d_* and stream_to_wait as _device.arg / wait take them.  Enqueues and returns."""
+        call("rs_pose_graph_edges_device", self._cons._h, d_views, d_constraint_poses, d_constraint_verdict, n_constraints, d_edges,
+             _device.wait(stream_to_wait))
 
     def relax_batch_device(self, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views,
                            d_constraint_verdict, d_edges, n_constraints, params, d_graph_verdict, d_view_state, d_stats,
                            stream_to_wait=None):
-        """rs_pose_graph_relax_batch_device: arguments named d_* are device pointers (ints).  Enqueues on the consensus'
+        """rs_pose_graph_relax_batch_device: d_* and stream_to_wait as _device.arg / wait take them.  Enqueues on the consensus'
         stream and returns; its sync() waits."""
-        check(_lib.lib().rs_pose_graph_relax_batch_device(
-            self._cons._h, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views, d_constraint_verdict,
-            d_edges, n_constraints, C.byref(params), d_graph_verdict, d_view_state, d_stats, stream_to_wait), "rs_pose_graph_relax_batch_device")
+        call("rs_pose_graph_relax_batch_device", self._cons._h, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges,
+             n_rows, d_views, d_constraint_verdict, d_edges, n_constraints, params, d_graph_verdict, d_view_state, d_stats,
+             _device.wait(stream_to_wait))
 
     def rows_device(self, d_views, n_constraints, n_views, d_row_start, d_row_edges, d_flags, stream_to_wait=None):
-        """rs_pose_graph_rows_device: `flatten` with order=None on the device; arguments named d_* are device pointers (ints).
+        """rs_pose_graph_rows_device: `flatten` with order=None on the device; d_* and stream_to_wait as _device.arg / wait take them.
         Enqueues and returns."""
-        check(_lib.lib().rs_pose_graph_rows_device(self._cons._h, d_views, n_constraints, n_views, d_row_start, d_row_edges, d_flags,
-                                                   stream_to_wait), "rs_pose_graph_rows_device")
+        call("rs_pose_graph_rows_device", self._cons._h, d_views, n_constraints, n_views, d_row_start, d_row_edges, d_flags,
+             _device.wait(stream_to_wait))
 
     def rows(self, torch, views, n_views):
         """rows_device on a device tensor views [n][3] (4-byte integers).  Enqueued behind the current torch stream; no wait ->
@@ -104,18 +103,8 @@ class PoseGraph:
         d_row_start = torch.zeros((n_views + 1,), dtype=torch.int32, device=dev)
         d_row_edges = torch.zeros((max(6 * n, 1),), dtype=torch.int32, device=dev)
         d_flags = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.rows_device(views.data_ptr(), n, n_views, d_row_start.data_ptr(), d_row_edges.data_ptr(), d_flags.data_ptr(),
-                         _lib.wait_handle(torch.cuda.current_stream(dev)))
+        self.rows_device(views, n, n_views, d_row_start, d_row_edges, d_flags, torch.cuda.current_stream(dev))
         return d_row_start, d_row_edges[:6 * n], d_flags
-
-    @staticmethod
-    def _tensor(torch, a, dtype, dev):
-        """a device tensor as it is (contiguous, of the right width), a host array uploaded"""
-        if isinstance(a, torch.Tensor):
-            if not (a.is_cuda and a.is_contiguous() and a.element_size() == np.dtype(dtype).itemsize):
-                raise ValueError("contiguous device tensors of the documented element type only")
-            return a
-        return _lib.device_bytes(torch, np.ascontiguousarray(a, dtype), dev)
 
     def edges(self, torch, views, constraints, device=0):
         """The edge table [n][6][12] float64 on the device of the constraints (views [n][3], and `constraints`: a
@@ -124,11 +113,13 @@ class PoseGraph:
         takes as `edges`."""
         poses, verdicts = (constraints.poses, constraints.verdicts) if hasattr(constraints, "verdicts") else constraints
         dev = views.device if isinstance(views, torch.Tensor) else torch.device("cuda", device)
-        d_views, d_poses, d_verdicts = self._tensor(torch, views, np.uint32, dev), self._tensor(torch, poses, np.float64, dev), self._tensor(torch, verdicts, np.uint32, dev)
+        d_views, d_poses, d_verdicts = (_device.tensor(torch, a, dt, dev)
+                                        for a, dt in ((views, np.uint32), (poses, np.float64), (verdicts, np.uint32)))
         n = int(np.prod(views.shape)) // 3
         d_edges = torch.zeros((max(n, 1), 6, 12), dtype=torch.float64, device=dev)
-        self.edges_device(d_views.data_ptr(), d_poses.data_ptr(), d_verdicts.data_ptr(), n, d_edges.data_ptr(),
-                          _lib.wait_handle(torch.cuda.current_stream(dev)))
+        self.edges_device(d_views, d_poses, d_verdicts, n, d_edges, torch.cuda.current_stream(dev))
+        if d_poses is not poses:                         # an upload nobody else holds; the tuple holds the other two for relax()
+            _device.keep_alive(self._cons, d_poses)
         return d_edges, (d_views, d_verdicts, n)
 
     def relax(self, torch, poses, graph_start, row_start, row_edges, edges, params=None, device=0):
@@ -140,19 +131,18 @@ class PoseGraph:
         d_edges, (d_views, d_verdicts, n_constraints) = edges
         dev = d_edges.device
         in_place = isinstance(poses, torch.Tensor)
-        d_poses = self._tensor(torch, poses, np.float64, dev)
+        d_poses = _device.tensor(torch, poses, np.float64, dev)
         n_views = int(np.prod(poses.shape)) // 12
         n_graphs, n_rows = int(np.prod(graph_start.shape)) - 1, int(np.prod(row_edges.shape))
         if int(np.prod(row_start.shape)) != n_views + 1 or n_graphs < 0:
             raise ValueError("row_start is [n_views + 1], graph_start [n_graphs + 1]")
-        d_gs, d_rs, d_re = (self._tensor(torch, a, np.uint32, dev) for a in (graph_start, row_start, row_edges))
+        d_gs, d_rs, d_re = (_device.tensor(torch, a, np.uint32, dev) for a in (graph_start, row_start, row_edges))
         d_out = torch.full((max(n_graphs, 1) * (1 + _lib.RS_PG_STATS) + max(n_views, 1),), -1, dtype=torch.int32, device=dev)
         d_verdict, d_stats, d_state = d_out[:max(n_graphs, 1)], d_out[max(n_graphs, 1):max(n_graphs, 1) * (1 + _lib.RS_PG_STATS)], d_out[max(n_graphs, 1) * (1 + _lib.RS_PG_STATS):]
-        self.relax_batch_device(d_poses.data_ptr(), n_views, d_gs.data_ptr(), n_graphs, d_rs.data_ptr(), d_re.data_ptr(), n_rows,
-                                d_views.data_ptr(), d_verdicts.data_ptr(), d_edges.data_ptr(), n_constraints, params or self.params(),
-                                d_verdict.data_ptr(), d_state.data_ptr(), d_stats.data_ptr(), _lib.wait_handle(torch.cuda.current_stream(dev)))
+        self.relax_batch_device(d_poses, n_views, d_gs, n_graphs, d_rs, d_re, n_rows, d_views, d_verdicts, d_edges, n_constraints,
+                                params or self.params(), d_verdict, d_state, d_stats, torch.cuda.current_stream(dev))
         self._cons.sync()
-        out = d_out.cpu().numpy().view(np.uint32)
+        out = _device.host_u32(d_out)
         ng = max(n_graphs, 1)
         return PoseGraphResult(out[:n_graphs].copy(), out[ng * (1 + _lib.RS_PG_STATS):][:n_views].copy(),
                                out[ng:ng * (1 + _lib.RS_PG_STATS)].reshape(ng, _lib.RS_PG_STATS)[:n_graphs].copy(),

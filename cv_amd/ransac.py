@@ -10,8 +10,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._lib import KP_DTYPE, check
+from . import _device, _lib
+from ._device import call
+from ._lib import KP_DTYPE
 
 
 @dataclass
@@ -28,8 +29,8 @@ class CameraIntrinsics:
         intr = np.array([self.focals[0], self.focals[1], self.principal_point[0], self.principal_point[1], self.skew],
                         np.float64)
         out = np.empty((len(kps), 3), np.float64)
-        check(_lib.lib().rs_calibrate(intr.ctypes.data, int(self.k1 is not None), float(self.k1 or 0.0),
-                                      kps.ctypes.data, len(kps), out.ctypes.data), "rs_calibrate")
+        call("rs_calibrate", intr.ctypes.data, int(self.k1 is not None), float(self.k1 or 0.0), kps.ctypes.data, len(kps),
+             out.ctypes.data)
         return out
 
 
@@ -46,7 +47,7 @@ class EssentialConsensus:
     def __init__(self, max_matches=8192, max_hypotheses=16384, device=0):
         self._h = C.c_void_p()
         self.max_hyp = max_hypotheses
-        check(_lib.lib().rs_create(device, max_matches, max_hypotheses, C.byref(self._h)), "rs_create")
+        call("rs_create", device, max_matches, max_hypotheses, C.byref(self._h))
 
     def close(self):
         if self._h:
@@ -66,8 +67,8 @@ class EssentialConsensus:
         n = len(a)
         pose = np.empty((3, 4), np.float64); best = C.c_uint32(); ninl = C.c_uint32()
         inl = np.empty(max(n, 1), np.uint32)
-        check(getattr(_lib.lib(), fn)(self._h, a.ctypes.data, b.ctypes.data, n, si.ctypes.data, len(si), float(threshold),
-                                      pose.ctypes.data, C.byref(best), inl.ctypes.data, n, C.byref(ninl)), fn)
+        call(fn, self._h, a.ctypes.data, b.ctypes.data, n, si.ctypes.data, len(si), float(threshold), pose.ctypes.data,
+             C.byref(best), inl.ctypes.data, n, C.byref(ninl))
         if best.value == 0xFFFFFFFF:
             return None
         return pose, inl[:ninl.value].copy(), best.value
@@ -86,7 +87,7 @@ class EssentialConsensus:
         """(E [n_samples, 10, 3, 3] with b^T E a = 0, unused slots zero; n_solutions [n_samples]) of the last single-scene
         five-point call (rs_debug_essentials)."""
         E = np.zeros((n_samples, 10, 3, 3), np.float64); n = np.zeros(n_samples, np.uint32)
-        check(_lib.lib().rs_debug_essentials(self._h, E.ctypes.data, n.ctypes.data, n_samples), "rs_debug_essentials")
+        call("rs_debug_essentials", self._h, E.ctypes.data, n.ctypes.data, n_samples)
         return E, n
 
     def arrsac_model_inliers(self, bearings_a, bearings_b, threshold, n_hypotheses=8192, seed=0, sample_idx=None,
@@ -115,10 +116,8 @@ class EssentialConsensus:
         pose = np.empty((3, 4), np.float64); best = C.c_uint32(); ninl = C.c_uint32()
         inl = np.empty(max(n, 1), np.uint32)
         st = _lib.ArrsacStats()
-        fn = _lib.lib().rs_p3p_arrsac if p3p else _lib.lib().rs_essential_arrsac
-        check(fn(self._h, a.ctypes.data, b.ctypes.data, n, si.ctypes.data if si is not None else None,
-                 C.byref(prm), pose.ctypes.data, C.byref(best), inl.ctypes.data, n, C.byref(ninl), C.byref(st)),
-              "rs_p3p_arrsac" if p3p else "rs_essential_arrsac")
+        call("rs_p3p_arrsac" if p3p else "rs_essential_arrsac", self._h, a.ctypes.data, b.ctypes.data, n,
+             si.ctypes.data if si is not None else None, prm, pose.ctypes.data, C.byref(best), inl.ctypes.data, n, C.byref(ninl), st)
         if best.value == 0xFFFFFFFF:
             return None
         stats = {"poses": st.poses, "survivors": st.survivors, "blocks": st.blocks,
@@ -130,7 +129,7 @@ class EssentialConsensus:
         """The minimal samples rs_essential_arrsac (8; 5 with the five-point estimator) / rs_p3p_arrsac (3) draw on the
         device for (seed, n)."""
         out = np.empty((n_hypotheses, sample_size), np.uint32)
-        check(_lib.lib().rs_arrsac_samples(seed, n, n_hypotheses, sample_size, out.ctypes.data), "rs_arrsac_samples")
+        call("rs_arrsac_samples", seed, n, n_hypotheses, sample_size, out.ctypes.data)
         return out
 
     def p3p_model_inliers(self, bearings, world, sample_idx, threshold):
@@ -141,12 +140,12 @@ class EssentialConsensus:
     def poses(self, n_hyp):
         """(poses [n_hyp,4,3,4], ok [n_hyp,4]) of the last single-scene call (rs_debug_poses)."""
         P = np.zeros((n_hyp, 4, 3, 4), np.float64); ok = np.zeros((n_hyp, 4), np.uint32)
-        check(_lib.lib().rs_debug_poses(self._h, P.ctypes.data, ok.ctypes.data, n_hyp), "rs_debug_poses")
+        call("rs_debug_poses", self._h, P.ctypes.data, ok.ctypes.data, n_hyp)
         return P, ok
 
     # ---- micro-batch entry: every frame pair of the matcher's output in one chain of launches ----
     def reserve(self, max_scenes):
-        check(_lib.lib().rs_batch_reserve(self._h, max_scenes), "rs_batch_reserve")
+        call("rs_batch_reserve", self._h, max_scenes)
 
     @staticmethod
     def make_params(threshold, n_hypotheses=8192, seed=0, block_size=64, init_blocks=4, max_candidates=1024, bound=True,
@@ -172,25 +171,21 @@ class EssentialConsensus:
 
     def model_inliers_batch_device(self, d_kps_a, d_kps_b, cap_per_img, ia, ib, d_pairs, d_npairs, cam_a, cam_b, params,
                                    d_pose, d_best_id, d_inliers, d_n_inliers, d_stats=None, shuffle=True, stream_to_wait=None):
-        """rs_essential_arrsac_batch_device: all arguments named d_* are device pointers (ints); ia / ib host index lists.
+        """rs_essential_arrsac_batch_device: d_* and stream_to_wait as _device.arg / wait take them; ia / ib host index lists.
         Enqueues and returns; sync() waits."""
-        n = len(ia)
-        a = (C.c_uint32 * n)(*ia); b = (C.c_uint32 * n)(*ib)
-        check(_lib.lib().rs_essential_arrsac_batch_device(
-            self._h, d_kps_a, d_kps_b, cap_per_img, a, b, d_pairs, d_npairs, n, C.byref(cam_a), C.byref(cam_b), C.byref(params),
-            _lib.RS_BATCH_SHUFFLE if shuffle else 0, d_pose, d_best_id, d_inliers, d_n_inliers, d_stats, stream_to_wait),
-            "rs_essential_arrsac_batch_device")
+        (a, n), (b, _) = _device.index_list(ia), _device.index_list(ib)
+        call("rs_essential_arrsac_batch_device", self._h, d_kps_a, d_kps_b, cap_per_img, a, b, d_pairs, d_npairs, n, cam_a, cam_b,
+             params, _lib.RS_BATCH_SHUFFLE if shuffle else 0, d_pose, d_best_id, d_inliers, d_n_inliers, d_stats,
+             _device.wait(stream_to_wait))
 
     def p3p_model_inliers_batch_device(self, d_kps, cap_per_img, ik, d_pairs, d_npairs, d_world, n_world, cam, params, d_pose,
                                        d_best_id, d_inliers, d_n_inliers, d_stats=None, shuffle=True, stream_to_wait=None):
         """rs_p3p_arrsac_batch_device: scene s = (feature of keypoint block ik[s], world point index) pairs; d_world
         [n_world][4] f64 (a scene naming a point >= n_world is refused: no model).  Enqueues and returns; sync() waits."""
-        n = len(ik)
-        k = (C.c_uint32 * n)(*ik)
-        check(_lib.lib().rs_p3p_arrsac_batch_device(
-            self._h, d_kps, cap_per_img, k, d_pairs, d_npairs, n, d_world, n_world, C.byref(cam), C.byref(params),
-            _lib.RS_BATCH_SHUFFLE if shuffle else 0, d_pose, d_best_id, d_inliers, d_n_inliers, d_stats, stream_to_wait),
-            "rs_p3p_arrsac_batch_device")
+        k, n = _device.index_list(ik)
+        call("rs_p3p_arrsac_batch_device", self._h, d_kps, cap_per_img, k, d_pairs, d_npairs, n, d_world, n_world, cam, params,
+             _lib.RS_BATCH_SHUFFLE if shuffle else 0, d_pose, d_best_id, d_inliers, d_n_inliers, d_stats,
+             _device.wait(stream_to_wait))
 
     def triangulate_inliers(self, d_kps_a, d_kps_b, cap_per_img, ia, ib, d_pairs, d_npairs, cam_a, cam_b, d_pose, d_best_id,
                             d_inliers, d_n_inliers, d_points, d_reason=None, params=None, stream_to_wait=None):
@@ -198,15 +193,13 @@ class EssentialConsensus:
         CameraPoint of every inlier (cv-sfm/src/lib.rs:1023-1029, 1332) -> d_points [scenes][cap_per_img][4] f64, d_reason
         (optional) [scenes][cap_per_img] u8; scenes without a model write nothing.  Enqueues and returns."""
         from .triangulation import make_params
-        n = len(ia)
-        a = (C.c_uint32 * n)(*ia); b = (C.c_uint32 * n)(*ib)
-        prm = params or make_params()
-        check(_lib.lib().rs_triangulate_pairs_batch_device(
-            self._h, d_kps_a, d_kps_b, cap_per_img, a, b, d_pairs, d_npairs, n, C.byref(cam_a), C.byref(cam_b), d_pose, d_best_id,
-            d_inliers, d_n_inliers, C.byref(prm), d_points, d_reason, stream_to_wait), "rs_triangulate_pairs_batch_device")
+        (a, n), (b, _) = _device.index_list(ia), _device.index_list(ib)
+        call("rs_triangulate_pairs_batch_device", self._h, d_kps_a, d_kps_b, cap_per_img, a, b, d_pairs, d_npairs, n, cam_a, cam_b,
+             d_pose, d_best_id, d_inliers, d_n_inliers, params or make_params(), d_points, d_reason, _device.wait(stream_to_wait))
 
     def sync(self):
-        check(_lib.lib().rs_sync(self._h), "rs_sync")
+        call("rs_sync", self._h)
+        vars(self).pop("_inputs", None)                  # _device.keep_alive: the stream has been waited for
 
     def stream(self):
         return _lib.lib().rs_stream(self._h)
@@ -215,16 +208,14 @@ class EssentialConsensus:
         """(bearings_a, bearings_b, order) of scene `scene` of the last batched call (rs_debug_scene)."""
         n = C.c_uint32()
         a = np.zeros((cap, 3), np.float64); b = np.zeros((cap, 3), np.float64); o = np.zeros(cap, np.uint32)
-        check(_lib.lib().rs_debug_scene(self._h, scene, C.byref(n), a.ctypes.data, b.ctypes.data, o.ctypes.data, cap),
-              "rs_debug_scene")
+        call("rs_debug_scene", self._h, scene, C.byref(n), a.ctypes.data, b.ctypes.data, o.ctypes.data, cap)
         return a[:n.value], b[:n.value], o[:n.value]
 
     def scene_world(self, scene, cap):
         """(bearings, world points [n][4], order) of scene `scene` of the last rs_p3p_arrsac_batch_device call."""
         n = C.c_uint32()
         a = np.zeros((cap, 3), np.float64); b = np.zeros((cap, 4), np.float64); o = np.zeros(cap, np.uint32)
-        check(_lib.lib().rs_debug_scene_world(self._h, scene, C.byref(n), a.ctypes.data, b.ctypes.data, o.ctypes.data, cap),
-              "rs_debug_scene_world")
+        call("rs_debug_scene_world", self._h, scene, C.byref(n), a.ctypes.data, b.ctypes.data, o.ctypes.data, cap)
         return a[:n.value], b[:n.value], o[:n.value]
 
     def far(self, poses, bearings_a, bearings_b, thresh):
@@ -232,8 +223,7 @@ class EssentialConsensus:
         P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
         a = np.ascontiguousarray(bearings_a, np.float64).reshape(-1, 3); b = np.ascontiguousarray(bearings_b, np.float64).reshape(-1, 3)
         out = np.zeros((len(P), len(a)), np.uint8)
-        check(_lib.lib().rs_debug_far(self._h, P.ctypes.data, len(P), a.ctypes.data, b.ctypes.data, len(a), float(thresh),
-                                      out.ctypes.data), "rs_debug_far")
+        call("rs_debug_far", self._h, P.ctypes.data, len(P), a.ctypes.data, b.ctypes.data, len(a), float(thresh), out.ctypes.data)
         return out.astype(bool)
 
     def residuals(self, poses, bearings_a, bearings_b, paired=False):
@@ -242,11 +232,10 @@ class EssentialConsensus:
         P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
         a = np.ascontiguousarray(bearings_a, np.float64); b = np.ascontiguousarray(bearings_b, np.float64)
         out = np.zeros((len(P), 2, len(a)) if paired else (len(P), len(a)), np.float64)
-        check(_lib.lib().rs_debug_residuals(self._h, P.ctypes.data, len(P), a.ctypes.data, b.ctypes.data, len(a), int(paired),
-                                            out.ctypes.data), "rs_debug_residuals")
+        call("rs_debug_residuals", self._h, P.ctypes.data, len(P), a.ctypes.data, b.ctypes.data, len(a), int(paired), out.ctypes.data)
         return out
 
     def counts(self, n_hyp):
         out = np.zeros((n_hyp, 4), np.uint32)
-        check(_lib.lib().rs_debug_counts(self._h, out.ctypes.data, out.size), "rs_debug_counts")
+        call("rs_debug_counts", self._h, out.ctypes.data, out.size)
         return out

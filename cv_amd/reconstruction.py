@@ -11,15 +11,16 @@ chains reconstruction_optimization_iterations rounds of PoseGraph's relaxation a
 of the filtered lists.  The run_tensors methods enqueue and return device tensors — a chain that must not stop at the host
 goes on from them (the filtered table as a triangulation.LandmarkTable) —, the run methods wait and copy to the host.
 """
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._lib import check
-from .pose_graph import PoseGraph
-from .triangulation import LandmarkTable
+from . import _device, _lib
+from ._device import call, host_u32 as u32
+from .covisibility import Covisibility
+from .pose_graph import PoseGraph, PoseGraphResult
+from .three_view import ThreeViewConstraints
+from .triangulation import LandmarkTable, triangulate_landmarks_device
 
 LANDMARK_STATES = ("kept", "single", "pair_split", "no_point", "kicked", "bad_index", "skipped")
 VERDICTS = ("ok", "few_landmarks", "bad_range", "skipped")
@@ -69,10 +70,6 @@ class ObservationFilterResult:
     tensors: object           # the ObservationFilterTensors it was read from
 
 
-def _tensor(torch, a, dtype, dev):
-    return PoseGraph._tensor(torch, a, dtype, dev)
-
-
 class ObservationFilter:
     """The filter on the context (and stream) of an EssentialConsensus, so that it queues behind that object's other calls."""
 
@@ -88,11 +85,10 @@ class ObservationFilter:
     def filter_device(self, d_kps, cap, n_blocks, d_poses, cam, d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start, d_view_start, n_recons,
                       d_skip, params, d_keep, d_lm_state, d_tri_reason, d_robust, d_obs_start_out, d_obs_out, d_split_out, d_counts,
                       d_recon_verdict, d_stats, stream_to_wait=None):
-        """rs_filter_observations_device: arguments named d_* are device pointers (ints).  Enqueues and returns."""
-        check(_lib.lib().rs_filter_observations_device(
-            self._cons._h, d_kps, cap, n_blocks, d_poses, C.byref(cam), d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start, d_view_start,
-            n_recons, d_skip, C.byref(params), d_keep, d_lm_state, d_tri_reason, d_robust, d_obs_start_out, d_obs_out, d_split_out, d_counts,
-            d_recon_verdict, d_stats, stream_to_wait), "rs_filter_observations_device")
+        """rs_filter_observations_device: d_* and stream_to_wait as _device.arg / wait take them.  Enqueues and returns."""
+        call("rs_filter_observations_device", self._cons._h, d_kps, cap, n_blocks, d_poses, cam, d_obs_start, d_obs, n_obs, n_landmarks,
+             d_recon_start, d_view_start, n_recons, d_skip, params, d_keep, d_lm_state, d_tri_reason, d_robust, d_obs_start_out,
+             d_obs_out, d_split_out, d_counts, d_recon_verdict, d_stats, _device.wait(stream_to_wait))
 
     @staticmethod
     def _outputs(torch, dev, n_obs, n_landmarks, n_recons, rounds=1):
@@ -110,17 +106,13 @@ class ObservationFilter:
         n_recons = int(np.prod(recon_start.shape)) - 1
         if n_recons < 0 or int(np.prod(view_start.shape)) != n_recons + 1:
             raise ValueError("recon_start and view_start are [n_recons + 1]")
-        d_rs, d_vs = _tensor(torch, recon_start, np.uint32, dev), _tensor(torch, view_start, np.uint32, dev)
-        d_skip = None if skip is None else _tensor(torch, skip, np.uint32, dev)
+        d_rs, d_vs = _device.tensor(torch, recon_start, np.uint32, dev), _device.tensor(torch, view_start, np.uint32, dev)
+        d_skip = None if skip is None else _device.tensor(torch, skip, np.uint32, dev)
         o = self._outputs(torch, dev, table.n_obs, table.n_landmarks, n_recons)
-        self.filter_device(d_kps.data_ptr(), cap, n_blocks, d_poses.data_ptr(), cam, table.d_start.data_ptr(), table.d_obs.data_ptr(),
-                           table.n_obs, table.n_landmarks, d_rs.data_ptr(), d_vs.data_ptr(), n_recons,
-                           None if d_skip is None else d_skip.data_ptr(), params or self.params(), o.keep.data_ptr(), o.lm_state.data_ptr(),
-                           o.tri_reason.data_ptr(), o.robust.data_ptr(), o.obs_start_out.data_ptr(), o.obs_out.data_ptr(),
-                           o.split_out.data_ptr(), o.counts.data_ptr(), o.recon_verdict.data_ptr(), o.stats.data_ptr(),
-                           _lib.wait_handle(torch.cuda.current_stream(dev)))
-        o._inputs = (d_rs, d_vs, d_skip)          # alive until the stream has run
-        return o
+        self.filter_device(d_kps, cap, n_blocks, d_poses, cam, table.d_start, table.d_obs, table.n_obs, table.n_landmarks, d_rs, d_vs,
+                           n_recons, d_skip, params or self.params(), o.keep, o.lm_state, o.tri_reason, o.robust, o.obs_start_out,
+                           o.obs_out, o.split_out, o.counts, o.recon_verdict, o.stats, torch.cuda.current_stream(dev))
+        return _device.keep_alive(o, d_rs, d_vs, d_skip)
 
     def run(self, torch, table, d_kps, cap, n_blocks, d_poses, cam, recon_start, view_start, skip=None, params=None):
         """run_tensors, then WAITS and copies to the host -> ObservationFilterResult."""
@@ -130,7 +122,6 @@ class ObservationFilter:
 
 
 def _to_host(o, n_recons, rnd=0):
-    u32 = lambda t: t.cpu().numpy().view(np.uint32)
     counts = u32(o.counts).reshape(-1, 2)[rnd]
     room = max(o.n_obs, 1)
     return ObservationFilterResult(
@@ -163,13 +154,12 @@ class ReconstructionOptimizer:
                         d_edges, n_constraints, pg_params, d_kps, cap, cam, d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start, params,
                         d_verdict, d_graph_verdict, d_view_state, d_pg_stats, d_keep, d_lm_state, d_tri_reason, d_robust, d_obs_start_out,
                         d_obs_out, d_split_out, d_counts, d_recon_verdict, d_of_stats, d_world=None, d_world_reason=None, stream_to_wait=None):
-        """rs_optimize_reconstruction_batch_device: arguments named d_* are device pointers (ints).  Enqueues and returns."""
-        check(_lib.lib().rs_optimize_reconstruction_batch_device(
-            self._cons._h, d_poses, n_views, d_graph_start, n_graphs, d_row_start, d_row_edges, n_rows, d_views, d_constraint_verdict, d_edges,
-            n_constraints, C.byref(pg_params), d_kps, cap, C.byref(cam), d_obs_start, d_obs, n_obs, n_landmarks, d_recon_start,
-            C.byref(params), d_verdict, d_graph_verdict, d_view_state, d_pg_stats, d_keep, d_lm_state, d_tri_reason, d_robust,
-            d_obs_start_out, d_obs_out, d_split_out, d_counts, d_recon_verdict, d_of_stats, d_world, d_world_reason, stream_to_wait),
-            "rs_optimize_reconstruction_batch_device")
+        """rs_optimize_reconstruction_batch_device: d_* and stream_to_wait as _device.arg / wait take them.  Enqueues and returns."""
+        call("rs_optimize_reconstruction_batch_device", self._cons._h, d_poses, n_views, d_graph_start, n_graphs, d_row_start,
+             d_row_edges, n_rows, d_views, d_constraint_verdict, d_edges, n_constraints, pg_params, d_kps, cap, cam, d_obs_start, d_obs,
+             n_obs, n_landmarks, d_recon_start, params, d_verdict, d_graph_verdict, d_view_state, d_pg_stats, d_keep, d_lm_state,
+             d_tri_reason, d_robust, d_obs_start_out, d_obs_out, d_split_out, d_counts, d_recon_verdict, d_of_stats, d_world,
+             d_world_reason, _device.wait(stream_to_wait))
 
     def run_tensors(self, torch, poses, graph_start, row_start, row_edges, edges, table, d_kps, cap, cam, recon_start, pg_params=None,
                     params=None, world=True):
@@ -183,34 +173,27 @@ class ReconstructionOptimizer:
         rounds = max(int(params.reconstruction_optimization_iterations), 1)
         n_views = int(np.prod(poses.shape)) // 12
         n_graphs, n_rows = int(np.prod(graph_start.shape)) - 1, int(np.prod(row_edges.shape))
-        d_gs, d_rs, d_re, d_recon = (_tensor(torch, a, np.uint32, dev) for a in (graph_start, row_start, row_edges, recon_start))
+        d_gs, d_rs, d_re, d_recon = (_device.tensor(torch, a, np.uint32, dev) for a in (graph_start, row_start, row_edges, recon_start))
         i32 = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device=dev)
         d_verdict, d_gv, d_state, d_pg_stats = i32(max(n_graphs, 1)), i32(max(n_graphs, 1)), i32(max(n_views, 1)), i32(max(n_graphs, 1), _lib.RS_PG_STATS)
         o = ObservationFilter._outputs(torch, dev, table.n_obs, table.n_landmarks, n_graphs, rounds)
         d_world = table.new_world() if world else None
         d_reason = torch.zeros((max(table.n_landmarks, 1),), dtype=torch.uint8, device=dev) if world else None
-        self.optimize_device(poses.data_ptr(), n_views, d_gs.data_ptr(), n_graphs, d_rs.data_ptr(), d_re.data_ptr(), n_rows, d_views.data_ptr(),
-                             d_verdicts.data_ptr(), d_edges.data_ptr(), n_constraints, pg_params, d_kps.data_ptr(), cap, cam,
-                             table.d_start.data_ptr(), table.d_obs.data_ptr(), table.n_obs, table.n_landmarks, d_recon.data_ptr(), params,
-                             d_verdict.data_ptr(), d_gv.data_ptr(), d_state.data_ptr(), d_pg_stats.data_ptr(), o.keep.data_ptr(),
-                             o.lm_state.data_ptr(), o.tri_reason.data_ptr(), o.robust.data_ptr(), o.obs_start_out.data_ptr(),
-                             o.obs_out.data_ptr(), o.split_out.data_ptr(), o.counts.data_ptr(), o.recon_verdict.data_ptr(), o.stats.data_ptr(),
-                             None if d_world is None else d_world.data_ptr(), None if d_reason is None else d_reason.data_ptr(),
-                             _lib.wait_handle(torch.cuda.current_stream(dev)))
-        o._inputs = (d_gs, d_rs, d_re, d_recon)
-        return d_verdict, (d_gv, d_state, d_pg_stats), o, d_world, d_reason
+        self.optimize_device(poses, n_views, d_gs, n_graphs, d_rs, d_re, n_rows, d_views, d_verdicts, d_edges, n_constraints, pg_params,
+                             d_kps, cap, cam, table.d_start, table.d_obs, table.n_obs, table.n_landmarks, d_recon, params, d_verdict,
+                             d_gv, d_state, d_pg_stats, o.keep, o.lm_state, o.tri_reason, o.robust, o.obs_start_out, o.obs_out,
+                             o.split_out, o.counts, o.recon_verdict, o.stats, d_world, d_reason, torch.cuda.current_stream(dev))
+        return d_verdict, (d_gv, d_state, d_pg_stats), _device.keep_alive(o, d_gs, d_rs, d_re, d_recon), d_world, d_reason
 
     def run(self, torch, poses, graph_start, row_start, row_edges, edges, table, d_kps, cap, cam, recon_start, pg_params=None, params=None,
             world=True):
         """run_tensors, then WAITS and copies verdicts, states and stats to the host -> ReconstructionResult (the world table
         stays on the device, where the registration chain reads it)."""
-        from .pose_graph import PoseGraphResult
         params = params or self.params()
         d_verdict, (d_gv, d_state, d_pg_stats), o, d_world, d_reason = self.run_tensors(
             torch, poses, graph_start, row_start, row_edges, edges, table, d_kps, cap, cam, recon_start, pg_params, params, world)
         self._cons.sync()
         n_graphs, n_views = int(np.prod(graph_start.shape)) - 1, int(np.prod(poses.shape)) // 12
-        u32 = lambda t: t.cpu().numpy().view(np.uint32)
         last = max(int(params.reconstruction_optimization_iterations), 1) - 1
         return ReconstructionResult(u32(d_verdict)[:n_graphs], PoseGraphResult(u32(d_gv)[:n_graphs], u32(d_state)[:n_views], u32(d_pg_stats)[:n_graphs], poses),
                                     _to_host(o, n_graphs, last), d_world, d_reason, o)
@@ -237,20 +220,17 @@ def regenerate(torch, consensus, table, d_kps, cap, cam, poses, graph_start, rec
     before.  poses [n_views][12] float64 is relaxed in place.  `reason` [n_landmarks] uint8: the robust triangulation's reason
     bytes; computed here under `poses` and params.triangulate when not given.  WAITS once, at the end -> RegenerateResult of
     device tensors."""
-    from .covisibility import Covisibility
-    from .three_view import ThreeViewConstraints
-    from .triangulation import triangulate_landmarks_device
     n_views = int(np.prod(poses.shape)) // 12
     dev = table.dev
-    first_world = None
     pg = PoseGraph(consensus)
     opt = ReconstructionOptimizer(pg)
     params = params or opt.params()
-    wait = lambda: _lib.wait_handle(torch.cuda.current_stream(dev))
     if reason is None:
         reason = torch.zeros((max(table.n_landmarks, 1),), dtype=torch.uint8, device=dev)
-        first_world = table.new_world()          # the call only enqueues: the table it writes stays referenced until the wait below
-        triangulate_landmarks_device(consensus._h, table, d_kps, cap, n_views, poses, cam, params.triangulate, first_world, reason, wait())
+        first_world = table.new_world()          # the call only enqueues: the table it writes is held until the wait below
+        triangulate_landmarks_device(consensus._h, table, d_kps, cap, n_views, poses, cam, params.triangulate, first_world, reason,
+                                     torch.cuda.current_stream(dev))
+        _device.keep_alive(consensus, first_world)
     targets = np.arange(n_views, dtype=np.uint32) if targets is None else targets
     cov = Covisibility(consensus)
     cv_params = cv_params or cov.params()
@@ -263,5 +243,4 @@ def regenerate(torch, consensus, table, d_kps, cap, cam, poses, graph_start, rec
     d_verdict, pose_graph, o, d_world, d_world_reason = opt.run_tensors(torch, poses, graph_start, rows[0], rows[1], edges, table, d_kps, cap,
                                                                         cam, recon_start, pg_params, params)
     consensus.sync()
-    del first_world
     return RegenerateResult(cand, constraints, recorded, rows, d_verdict, pose_graph, o, d_world, d_world_reason)

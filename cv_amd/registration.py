@@ -25,22 +25,15 @@ triangulated landmarks is made on the device from the poses and the observation 
 by landmark key, triangulate_merged() between match_views() and consensus() for the rows of the merge candidates
 (cv-sfm/src/lib.rs:1590-1593, 2958-3000); a caller may still bring a table of its own.  There is no CPU fallback.
 """
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from ._lib import check
+from . import _device, _lib
+from ._device import call
 from .knn import Matcher
 from .landmark_table import LandmarkUpdate
 from .ransac import EssentialConsensus
 from .single_view import RefineOutputs, SingleViewRefiner
 from . import triangulation
-
-
-def _u32(vals):
-    a = np.ascontiguousarray(vals, np.uint32).reshape(-1)
-    return a, a.ctypes.data_as(C.c_void_p)
 
 
 class Registration:
@@ -116,7 +109,6 @@ class Registration:
         hash_bag, the k = 3 searches and the best-of-views decision on the matcher's stream and returns.  Outputs:
         self.hash, self.best / decision (slot = position in frame_blocks) — of THIS call until the next match_views() (two
         output sets alternate)."""
-        L = _lib.lib()
         cur = self._sets[self._calls & 1]
         self._select(self._calls & 1)
         self._calls += 1
@@ -126,24 +118,21 @@ class Registration:
         F = len(frame_blocks)
         V = len(view_blocks[0])
         assert F <= self.F and V <= self.V and all(len(v) == V for v in view_blocks)
-        fb, fb_p = _u32(frame_blocks)
-        iq, iq_p = _u32(np.repeat(fb, V))
-        it, it_p = _u32(view_blocks)
-        self._fb = fb
+        fb_p, _ = _device.index_list(frame_blocks)
+        fb = self._fb = fb_p[:F]
+        iq_p, _ = _device.index_list(np.repeat(fb, V))
+        it_p, _ = _device.index_list(view_blocks)
         h = self.matcher.handle
         # hash_bag runs over the frames' blocks where they lie: block b of d_descs -> row b of the hash table of THIS call
         # (the new frames are contiguous in every caller so far: hash the span)
-        b0, b1 = int(fb.min()), int(fb.max()) + 1
+        b0, b1 = min(fb), max(fb) + 1
         assert b1 - b0 <= self.F
-        check(L.hm_hash_bag_device(h, d_descs[b0:b1].data_ptr(), d_counts[b0:b1].data_ptr(), self.cap, b1 - b0,
-                                   self.d_codewords.data_ptr(), self.n_codewords, self.hash.data_ptr(), self.words.data_ptr(),
-                                   stream_to_wait), "hm_hash_bag_device")
+        call("hm_hash_bag_device", h, d_descs[b0:b1], d_counts[b0:b1], self.cap, b1 - b0, self.d_codewords, self.n_codewords, self.hash,
+             self.words, _device.wait(stream_to_wait))
         self.hash_block0 = b0
-        check(L.hm_knn_batch_device(h, d_descs.data_ptr(), d_counts.data_ptr(), d_descs.data_ptr(), d_counts.data_ptr(), self.cap,
-                                    iq_p, it_p, F * V, self.k, self.knn.data_ptr(), None), "hm_knn_batch_device")
-        check(L.hm_best_of_views_batch_device(h, self.knn.data_ptr(), d_counts.data_ptr(), fb_p, self.cap, it_p, F, V, self.k,
-                                              d_landmarks.data_ptr(), d_counts.data_ptr(), self.better_by, self.best.data_ptr(),
-                                              self.decision.data_ptr(), None), "hm_best_of_views_batch_device")
+        call("hm_knn_batch_device", h, d_descs, d_counts, d_descs, d_counts, self.cap, iq_p, it_p, F * V, self.k, self.knn, None)
+        call("hm_best_of_views_batch_device", h, self.knn, d_counts, fb_p, self.cap, it_p, F, V, self.k, d_landmarks, d_counts,
+             self.better_by, self.best, self.decision, None)
 
     def triangulate(self, table, d_kps, d_poses, d_world=None, d_reason=None, params=None, stream_to_wait=None):
         """The world table on the device: row l of d_world = triangulate_landmark_robust(landmark l) (cv-sfm/src/lib.rs:
@@ -185,21 +174,14 @@ class Registration:
         (shuffle defaults to True).  Outputs: self.pairs / npairs, self.pose / best_id / inliers / n_inliers / stats."""
         if shuffle is None:
             shuffle = d_obs_counts is None
-        L = _lib.lib()
         cur, fb = self._cur, self._fb
-        F = len(fb)
-        _, fb_p = _u32(fb)
+        fb_p, F = _device.index_list(fb)
         rows = n_world if d_merge_ok is None else n_world + F * self.cap
         assert d_world.shape[0] >= rows
-        check(L.hm_landmark_matches_ordered_batch_device(self.matcher.handle, self.best.data_ptr(), self.decision.data_ptr(),
-                                                         None if d_merge_ok is None else d_merge_ok.data_ptr(),
-                                                         None if d_obs_counts is None else d_obs_counts.data_ptr(), d_counts.data_ptr(),
-                                                         fb_p, self.cap, F, d_world.data_ptr(), n_world, self.pairs.data_ptr(),
-                                                         self.npairs.data_ptr(), stream_to_wait), "hm_landmark_matches_ordered_batch_device")
-        self.cons.p3p_model_inliers_batch_device(d_kps.data_ptr(), self.cap, [int(b) for b in fb], self.pairs.data_ptr(),
-                                                 self.npairs.data_ptr(), d_world.data_ptr(), rows, self.cam, self.prm,
-                                                 self.pose.data_ptr(), self.best_id.data_ptr(), self.inliers.data_ptr(),
-                                                 self.n_inliers.data_ptr(), self.stats.data_ptr(), shuffle=shuffle,
+        call("hm_landmark_matches_ordered_batch_device", self.matcher.handle, self.best, self.decision, d_merge_ok, d_obs_counts,
+             d_counts, fb_p, self.cap, F, d_world, n_world, self.pairs, self.npairs, _device.wait(stream_to_wait))
+        self.cons.p3p_model_inliers_batch_device(d_kps, self.cap, fb, self.pairs, self.npairs, d_world, rows, self.cam, self.prm,
+                                                 self.pose, self.best_id, self.inliers, self.n_inliers, self.stats, shuffle=shuffle,
                                                  stream_to_wait=self.hm_stream())
         cur["done"].record(self._rs_s)
         cur["used"] = True
@@ -214,19 +196,13 @@ class Registration:
         the torch stream the table was written on (default: nothing to wait for).  Outputs: self.originals / noriginals and
         self.refined (a single_view.RefineOutputs: pose, verdict, final, n_final, stats) — the pose for the pose graph and the
         final_matches map over self.originals."""
-        L = _lib.lib()
         cur, fb = self._cur, self._fb
         d_kps, d_counts, d_world, n_world, d_merge_ok, d_obs_counts = self._consensus_args
-        F = len(fb)
-        _, fb_p = _u32(fb)
-        check(L.hm_landmark_original_matches_batch_device(self.matcher.handle, self.best.data_ptr(), self.decision.data_ptr(),
-                                                          None if d_merge_ok is None else d_merge_ok.data_ptr(),
-                                                          None if d_obs_counts is None else d_obs_counts.data_ptr(), d_counts.data_ptr(),
-                                                          fb_p, self.cap, F, n_world, self.originals.data_ptr(), self.noriginals.data_ptr(),
-                                                          None if stream is None else _lib.wait_handle(stream)),
-              "hm_landmark_original_matches_batch_device")
+        fb_p, F = _device.index_list(fb)
+        call("hm_landmark_original_matches_batch_device", self.matcher.handle, self.best, self.decision, d_merge_ok, d_obs_counts,
+             d_counts, fb_p, self.cap, F, n_world, self.originals, self.noriginals, _device.wait(stream))
         self.refiner.refine_tensors(self.torch, d_kps, d_poses, self.cam, d_obs_start, d_obs, n_landmarks, d_world, n_world,
-                                    [int(b) for b in fb], self.originals, self.noriginals, None if d_merge_ok is None else self.best,
+                                    fb, self.originals, self.noriginals, None if d_merge_ok is None else self.best,
                                     self.pose, self.best_id, self.inliers, self.n_inliers, params or self.sv_prm, out=self.refined,
                                     stream_to_wait=self.hm_stream())
         cur["done"].record(self._rs_s)
@@ -239,9 +215,8 @@ class Registration:
         the matcher's stream, no host step.  Returns the mask: hand it to triangulate_merged() and, with rs_stream() as
         stream_to_wait, to consensus()."""
         F = len(self._fb)
-        self.landmarks.sharing_view_device(table.d_start.data_ptr(), table.d_obs.data_ptr(), table.n_obs, table.n_landmarks,
-                                           self.best.data_ptr(), self.decision.data_ptr(), self.cap, F, self.merge_ok.data_ptr(),
-                                           self.hm_stream())
+        self.landmarks.sharing_view_device(table.d_start, table.d_obs, table.n_obs, table.n_landmarks, self.best, self.decision,
+                                           self.cap, F, self.merge_ok, self.hm_stream())
         return self.merge_ok
 
     def add_views(self, table, d_poses, d_split=None, d_split_count=None, skip=None, obs_room=None, lm_room=None):
@@ -255,7 +230,7 @@ class Registration:
         for the next match_views(), obs_counts_out for the next consensus()."""
         d_kps, d_counts, d_world, n_world, d_merge_ok, d_obs_counts = self._consensus_args
         split_room = None if d_split is None else int(np.prod(d_split.shape)) // 2
-        o = self.landmarks.add_views_tensors(self.torch, table, d_poses, self.cap, [int(b) for b in self._fb], d_counts, self.originals,
+        o = self.landmarks.add_views_tensors(self.torch, table, d_poses, self.cap, self._fb, d_counts, self.originals,
                                              self.noriginals, self.refined.final, self.refined.verdict, self.refined.pose,
                                              best=None if d_merge_ok is None else self.best, skip=skip, split=d_split,
                                              split_count=d_split_count, split_room=split_room, n_world=n_world, obs_room=obs_room,
@@ -264,7 +239,7 @@ class Registration:
         return o
 
     def sync(self):
-        check(_lib.lib().hm_sync(self.matcher.handle), "hm_sync")
+        call("hm_sync", self.matcher.handle)
         self.cons.sync()
 
     def close(self):

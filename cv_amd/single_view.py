@@ -10,13 +10,10 @@ Every new frame of a micro-batch is worked by one persistent workgroup on the de
 is no CPU fallback.  The pose that enters the pose graph and the observations that enter the landmark table are the outputs of
 this stage, not the consensus'.
 """
-import ctypes as C
 from dataclasses import dataclass
 
-import numpy as np
-
-from . import _lib
-from ._lib import check
+from . import _device, _lib
+from ._device import call, host_u32
 
 VERDICTS = ("ok", "no_model", "few_landmarks", "lost_half", "few_robust", "bad_index")
 
@@ -35,8 +32,8 @@ class RefineOutputs:
     def host(self):
         """-> (pose [S][3][4], verdict [S] u32, final [S][cap] bool, n_final [S] u32, stats [S][RS_SV_STATS] u32); the caller
         has waited for the stream."""
-        return (self.pose.cpu().numpy().reshape(-1, 3, 4), self.verdict.cpu().numpy().view(np.uint32), self.final.cpu().numpy().astype(bool),
-                self.n_final.cpu().numpy().view(np.uint32), self.stats.cpu().numpy().view(np.uint32))
+        return (self.pose.cpu().numpy().reshape(-1, 3, 4), host_u32(self.verdict), self.final.cpu().numpy().astype(bool),
+                host_u32(self.n_final), host_u32(self.stats))
 
 
 class SingleViewRefiner:
@@ -55,14 +52,12 @@ class SingleViewRefiner:
     def refine_batch_device(self, d_kps, cap_per_img, n_blocks, d_poses, cam, d_obs_start, d_obs, n_obs, n_landmarks, d_world, n_world, ik,
                             d_matches, d_nmatches, d_best, d_pose, d_best_id, d_inliers, d_n_inliers, params, d_pose_out, d_verdict, d_final,
                             d_n_final, d_stats, stream_to_wait=None):
-        """rs_refine_poses_batch_device: arguments named d_* are device pointers (ints; d_best may be None), ik a host list of the
-        new frames' keypoint blocks, one per scene.  Enqueues on the consensus' stream and returns; its sync() waits."""
-        n = len(ik)
-        blocks = (C.c_uint32 * max(1, n))(*ik)
-        check(_lib.lib().rs_refine_poses_batch_device(
-            self._cons._h, d_kps, cap_per_img, n_blocks, d_poses, C.byref(cam), d_obs_start, d_obs, n_obs, n_landmarks, d_world, n_world,
-            blocks, d_matches, d_nmatches, d_best, d_pose, d_best_id, d_inliers, d_n_inliers, n, C.byref(params), d_pose_out, d_verdict,
-            d_final, d_n_final, d_stats, stream_to_wait), "rs_refine_poses_batch_device")
+        """rs_refine_poses_batch_device: d_* and stream_to_wait as _device.arg / wait take them (d_best may be None), ik a host
+        list of the new frames' keypoint blocks, one per scene.  Enqueues on the consensus' stream and returns; its sync() waits."""
+        blocks, n = _device.index_list(ik)
+        call("rs_refine_poses_batch_device", self._cons._h, d_kps, cap_per_img, n_blocks, d_poses, cam, d_obs_start, d_obs, n_obs,
+             n_landmarks, d_world, n_world, blocks, d_matches, d_nmatches, d_best, d_pose, d_best_id, d_inliers, d_n_inliers, n, params,
+             d_pose_out, d_verdict, d_final, d_n_final, d_stats, _device.wait(stream_to_wait))
 
     def refine_tensors(self, torch, d_kps, d_poses, cam, d_obs_start, d_obs, n_landmarks, d_world, n_world, ik, d_matches, d_nmatches, d_best,
                        d_pose, d_best_id, d_inliers, d_n_inliers, params=None, out=None, stream_to_wait=None):
@@ -75,9 +70,7 @@ class SingleViewRefiner:
         n_blocks = int(d_kps.shape[0])
         cap = d_kps.numel() * d_kps.element_size() // (28 * n_blocks)
         dev = d_kps.device
-        for t in (d_kps, d_poses, d_obs_start, d_obs, d_world, d_matches, d_nmatches, d_pose, d_best_id, d_inliers, d_n_inliers):
-            if not (t.is_cuda and t.is_contiguous()):
-                raise ValueError("contiguous device tensors only")
+        _device.require_device(d_kps, d_poses, d_obs_start, d_obs, d_world, d_matches, d_nmatches, d_pose, d_best_id, d_inliers, d_n_inliers)
         if d_poses.dtype != torch.float64 or d_poses.numel() != 12 * n_blocks or d_obs_start.numel() != n_landmarks + 1:
             raise ValueError("d_poses is [n_blocks][12] float64, d_obs_start [n_landmarks + 1]")
         if d_matches.numel() < 2 * S * cap or d_inliers.numel() < S * cap:
@@ -92,10 +85,7 @@ class SingleViewRefiner:
                                 torch.zeros(max(S, 1), dtype=torch.int32, device=dev),
                                 torch.zeros((max(S, 1), _lib.RS_SV_STATS), dtype=torch.int32, device=dev))
         n_obs = int(d_obs.numel() // 2)
-        self.refine_batch_device(d_kps.data_ptr(), cap, n_blocks, d_poses.data_ptr(), cam, d_obs_start.data_ptr(),
-                                 d_obs.data_ptr() if n_obs else None, n_obs, n_landmarks, d_world.data_ptr(), n_world, [int(b) for b in ik],
-                                 d_matches.data_ptr(), d_nmatches.data_ptr(), None if d_best is None else d_best.data_ptr(),
-                                 d_pose.data_ptr(), d_best_id.data_ptr(), d_inliers.data_ptr(), d_n_inliers.data_ptr(),
-                                 params or self.params(), out.pose.data_ptr(), out.verdict.data_ptr(), out.final.data_ptr(),
-                                 out.n_final.data_ptr(), out.stats.data_ptr(), stream_to_wait)
+        self.refine_batch_device(d_kps, cap, n_blocks, d_poses, cam, d_obs_start, d_obs if n_obs else None, n_obs, n_landmarks, d_world,
+                                 n_world, ik, d_matches, d_nmatches, d_best, d_pose, d_best_id, d_inliers, d_n_inliers,
+                                 params or self.params(), out.pose, out.verdict, out.final, out.n_final, out.stats, stream_to_wait)
         return out

@@ -17,13 +17,12 @@ One wavefront per constraint (cv_amd/csrc/rs_three_view_constraint.hip).  The sh
 count use the caller's RNG and Rust's tie order in the reference and stay on the host: `order_landmarks` builds one
 admissible order.
 """
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._lib import check
+from . import _device, _lib
+from ._device import call
 
 VERDICTS = ("ok", "few_scales", "few_bearing_pairs", "few_matches", "lost_half", "few_robust", "bad_index")
 
@@ -82,16 +81,14 @@ class ThreeViewInit:
     def init_batch_device(self, d_kps, cap_per_img, n_blocks, ic, i_first, i_second, cam, d_pose_first, d_pose_second, d_triples,
                           d_ntriples, d_first_only, d_nfirst, d_second_only, d_nsecond, params, d_pose_out, d_verdict, d_combined,
                           d_first_ok, d_second_ok, d_stats, stream_to_wait=None):
-        """rs_three_view_init_batch_device: arguments named d_* are device pointers (ints), ic / i_first / i_second host lists of
+        """rs_three_view_init_batch_device: d_* and stream_to_wait as _device.arg / wait take them, ic / i_first / i_second host lists of
         keypoint-block indices, one per scene.  Enqueues on the consensus' stream and returns; its sync() waits."""
-        n = len(ic)
-        if len(i_first) != n or len(i_second) != n:
+        (a, n), (b, nb), (c, nc) = (_device.index_list(x) for x in (ic, i_first, i_second))
+        if nb != n or nc != n:
             raise ValueError("one centre, first and second block per scene")
-        a, b, c = ((C.c_uint32 * n)(*x) for x in (ic, i_first, i_second))
-        check(_lib.lib().rs_three_view_init_batch_device(
-            self._cons._h, d_kps, cap_per_img, n_blocks, a, b, c, C.byref(cam), d_pose_first, d_pose_second, d_triples, d_ntriples,
-            d_first_only, d_nfirst, d_second_only, d_nsecond, n, C.byref(params), d_pose_out, d_verdict, d_combined, d_first_ok,
-            d_second_ok, d_stats, stream_to_wait), "rs_three_view_init_batch_device")
+        call("rs_three_view_init_batch_device", self._cons._h, d_kps, cap_per_img, n_blocks, a, b, c, cam, d_pose_first,
+             d_pose_second, d_triples, d_ntriples, d_first_only, d_nfirst, d_second_only, d_nsecond, n, params, d_pose_out,
+             d_verdict, d_combined, d_first_ok, d_second_ok, d_stats, _device.wait(stream_to_wait))
 
     def init(self, torch, keypoints, cam, pose_first, pose_second, first_pairs, second_pairs, params=None, permutation=None, device=0):
         """One triple from host arrays: keypoints = (centre, first, second) KP_DTYPE arrays, the two CameraToCamera poses
@@ -115,12 +112,11 @@ class ThreeViewInit:
         d_pose = torch.zeros(24, dtype=torch.float64, device=dev)
         d_masks = torch.zeros((3, cap), dtype=torch.uint8, device=dev)
         d_out = torch.zeros(1 + _lib.RS_TV_STATS, dtype=torch.int32, device=dev)
-        self.init_batch_device(d_kps.data_ptr(), cap, 3, [0], [1], [2], cam, d_pf.data_ptr(), d_ps.data_ptr(), d_t.data_ptr(),
-                               d_n.data_ptr(), d_f.data_ptr(), d_n.data_ptr() + 4, d_s.data_ptr(), d_n.data_ptr() + 8,
-                               params or self.params(), d_pose.data_ptr(), d_out.data_ptr(), d_masks[0].data_ptr(), d_masks[1].data_ptr(),
-                               d_masks[2].data_ptr(), d_out.data_ptr() + 4, _lib.wait_handle(torch.cuda.current_stream(dev)))
+        self.init_batch_device(d_kps, cap, 3, [0], [1], [2], cam, d_pf, d_ps, d_t, d_n, d_f, d_n.data_ptr() + 4, d_s,
+                               d_n.data_ptr() + 8, params or self.params(), d_pose, d_out, d_masks[0], d_masks[1], d_masks[2],
+                               d_out.data_ptr() + 4, torch.cuda.current_stream(dev))
         self._cons.sync()
-        out = d_out.cpu().numpy().view(np.uint32)
+        out = _device.host_u32(d_out)
         ok = int(out[0]) == _lib.RS_TV_OK
         masks = d_masks.cpu().numpy().astype(bool)
         return ThreeViewResult(int(out[0]), d_pose.cpu().numpy().reshape(2, 3, 4) if ok else None,
@@ -167,11 +163,10 @@ class ThreeViewConstraints:
 
     def batch_device(self, d_kps, cap_per_img, n_blocks, d_poses, cam, d_views, d_lm_start, d_lm, n_lm, n_constraints, params,
                      d_pose_out, d_verdict, d_stats, stream_to_wait=None):
-        """rs_three_view_constraint_batch_device: arguments named d_* are device pointers (ints).  Enqueues on the consensus'
-        stream and returns; its sync() waits."""
-        check(_lib.lib().rs_three_view_constraint_batch_device(
-            self._cons._h, d_kps, cap_per_img, n_blocks, d_poses, C.byref(cam), d_views, d_lm_start, d_lm, n_lm, n_constraints,
-            C.byref(params), d_pose_out, d_verdict, d_stats, stream_to_wait), "rs_three_view_constraint_batch_device")
+        """rs_three_view_constraint_batch_device: d_* and stream_to_wait as _device.arg / wait take them.  Enqueues on the
+        consensus' stream and returns; its sync() waits."""
+        call("rs_three_view_constraint_batch_device", self._cons._h, d_kps, cap_per_img, n_blocks, d_poses, cam, d_views, d_lm_start,
+             d_lm, n_lm, n_constraints, params, d_pose_out, d_verdict, d_stats, _device.wait(stream_to_wait))
 
     def run_tensors(self, torch, kps, poses, cam, views, lm_start, lm, params=None):
         """One batch from torch tensors on the device: kps [n_blocks][cap] keypoints (uint8 [n_blocks][cap][28] as
@@ -182,22 +177,19 @@ class ThreeViewConstraints:
         n, n_blocks, n_lm = int(views.shape[0]), int(kps.shape[0]), int(lm.shape[0])
         if lm_start.numel() != n + 1 or poses.numel() != 12 * n_blocks or poses.dtype != torch.float64:
             raise ValueError("lm_start is [n + 1], poses [n_blocks][12] float64")
-        for t in (kps, poses, views, lm_start, lm):
-            if not (t.is_cuda and t.is_contiguous()):
-                raise ValueError("contiguous device tensors only")
+        _device.require_device(kps, poses, views, lm_start, lm)
         cap = kps.numel() * kps.element_size() // (28 * n_blocks)
         dev = kps.device
         d_pose = torch.zeros((max(n, 1), 24), dtype=torch.float64, device=dev)
         d_out = torch.zeros((max(n, 1), 1 + _lib.RS_TVC_STATS), dtype=torch.int32, device=dev)
         d_verdict, d_stats = d_out[:, 0].contiguous(), d_out[:, 1:].contiguous()
-        self.batch_device(kps.data_ptr(), cap, n_blocks, poses.data_ptr(), cam, views.data_ptr(), lm_start.data_ptr(),
-                          lm.data_ptr() if n_lm else None, n_lm, n, params or self.params(), d_pose.data_ptr(), d_verdict.data_ptr(),
-                          d_stats.data_ptr(), _lib.wait_handle(torch.cuda.current_stream(dev)))
+        self.batch_device(kps, cap, n_blocks, poses, cam, views, lm_start, lm if n_lm else None, n_lm, n, params or self.params(),
+                          d_pose, d_verdict, d_stats, torch.cuda.current_stream(dev))
         return d_verdict[:n], d_pose[:n], d_stats[:n]
 
     def run(self, torch, kps, poses, cam, views, lm_start, lm, params=None):
         """run_tensors, waits.  -> ThreeViewConstraintResult (host arrays)."""
         d_verdict, d_pose, d_stats = self.run_tensors(torch, kps, poses, cam, views, lm_start, lm, params)
         self._cons.sync()
-        return ThreeViewConstraintResult(d_verdict.cpu().numpy().view(np.uint32), d_pose.cpu().numpy().reshape(-1, 2, 3, 4),
-                                         d_stats.cpu().numpy().view(np.uint32))
+        return ThreeViewConstraintResult(_device.host_u32(d_verdict), d_pose.cpu().numpy().reshape(-1, 2, 3, 4),
+                                         _device.host_u32(d_stats))

@@ -16,8 +16,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import check
+from . import _device, _lib
+from ._device import call
 
 
 def make_params(epsilon=1e-12, max_iterations=1000, robust_minimum_observations=3, n_views=0xFFFFFFFF,
@@ -70,9 +70,8 @@ class LinearEigenTriangulator:
         point = np.empty(4, np.float64)
         reason = C.c_uint8()
         prm = self.params()
-        check(_lib.lib().rs_triangulate_observations(self._handle(), poses.ctypes.data if len(pairs) else None,
-                                                     bearings.ctypes.data if len(pairs) else None, len(pairs), C.byref(prm),
-                                                     point.ctypes.data, C.byref(reason)), "rs_triangulate_observations")
+        call("rs_triangulate_observations", self._handle(), poses.ctypes.data if len(pairs) else None,
+             bearings.ctypes.data if len(pairs) else None, len(pairs), prm, point.ctypes.data, C.byref(reason))
         return (point if reason.value == 0 else None), reason.value
 
     def triangulate_observations(self, pairs):
@@ -120,9 +119,9 @@ class LandmarkTable:
         validated here: the kernels refuse a list that leaves [0, n_obs].  d_obs_counts [n_landmarks] (optional): the row lengths
         where the producer wrote them (landmark_table.AddViewsTensors); computed from d_start on the current torch stream
         otherwise."""
-        if not (d_start.is_cuda and d_obs.is_cuda and d_start.is_contiguous() and d_obs.is_contiguous() and d_start.element_size() == 4 and
-                d_obs.element_size() == 4 and d_start.numel() >= n_landmarks + 1 and d_obs.numel() >= 2 * n_obs):
-            raise ValueError("contiguous 4-byte device tensors of [n_landmarks + 1] and [n_obs][2]")
+        _device.require_device(d_start, d_obs, itemsize=4)
+        if d_start.numel() < n_landmarks + 1 or d_obs.numel() < 2 * n_obs:
+            raise ValueError("d_start is [n_landmarks + 1], d_obs [n_obs][2]")
         t = cls.__new__(cls)
         t.torch, t.n_landmarks, t.n_obs, t.dev = torch, int(n_landmarks), int(n_obs), d_start.device
         t.d_start, t.d_obs = d_start, d_obs
@@ -141,17 +140,14 @@ class LandmarkTable:
 
 def triangulate_landmarks_device(handle, table, d_kps, cap, n_blocks, d_poses, cam, params, d_world, d_reason=None,
                                  stream_to_wait=None):
-    """rs_triangulate_landmarks_device: rows [0, table.n_landmarks) of d_world; enqueues on the context's stream and returns."""
-    check(_lib.lib().rs_triangulate_landmarks_device(
-        handle, d_kps.data_ptr(), cap, n_blocks, d_poses.data_ptr(), C.byref(cam), table.d_start.data_ptr(), table.d_obs.data_ptr(),
-        table.n_obs, table.n_landmarks, C.byref(params), d_world.data_ptr(), None if d_reason is None else d_reason.data_ptr(),
-        stream_to_wait), "rs_triangulate_landmarks_device")
+    """rs_triangulate_landmarks_device: rows [0, table.n_landmarks) of d_world; d_* and stream_to_wait as _device.arg / wait take them.
+    Enqueues on the context's stream and returns."""
+    call("rs_triangulate_landmarks_device", handle, d_kps, cap, n_blocks, d_poses, cam, table.d_start, table.d_obs, table.n_obs,
+         table.n_landmarks, params, d_world, d_reason, _device.wait(stream_to_wait))
 
 
 def triangulate_merged_device(handle, table, d_kps, cap, n_blocks, d_poses, cam, params, d_best, d_decision, d_merge_ok, n_frames,
                               n_world, d_world, d_reason=None, stream_to_wait=None):
     """rs_triangulate_merged_device: rows n_world + f * cap + j of d_world for the admitted merge candidates."""
-    check(_lib.lib().rs_triangulate_merged_device(
-        handle, d_kps.data_ptr(), cap, n_blocks, d_poses.data_ptr(), C.byref(cam), table.d_start.data_ptr(), table.d_obs.data_ptr(),
-        table.n_obs, table.n_landmarks, C.byref(params), d_best.data_ptr(), d_decision.data_ptr(), d_merge_ok.data_ptr(), n_frames,
-        n_world, d_world.data_ptr(), None if d_reason is None else d_reason.data_ptr(), stream_to_wait), "rs_triangulate_merged_device")
+    call("rs_triangulate_merged_device", handle, d_kps, cap, n_blocks, d_poses, cam, table.d_start, table.d_obs, table.n_obs,
+         table.n_landmarks, params, d_best, d_decision, d_merge_ok, n_frames, n_world, d_world, d_reason, _device.wait(stream_to_wait))

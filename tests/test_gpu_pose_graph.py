@@ -297,6 +297,38 @@ def test_the_chain_stays_on_the_device(gpu, cons):
     assert res2.poses.tobytes() == hr["poses"].tobytes() and res2.verdicts.tolist() == [P.OK, P.OK]
 
 
+def test_a_torch_stream_object_is_waited_for(gpu, cons):
+    """The case cv_amd/_device.py exists for: the producer runs on the current torch stream — the legacy default stream, whose
+    handle is 0, which the ABI reads as "nothing to wait for" — and rows_device gets the tensors themselves and the stream
+    OBJECT.  A few milliseconds of matmuls keep the stream busy in front of an asynchronous copy of views [64][3] from pinned
+    memory; nothing waits on the host.  A call that did not wait would read the zeros the tensor held before, which are valid
+    view indices: a wrong answer, never a fault."""
+    from cv_amd import _device, _lib
+    from cv_amd.pose_graph import PoseGraph, flatten
+    torch = gpu
+    dev = torch.device("cuda", 0)
+    n, n_views = 64, 16
+    views = np.random.default_rng(0x57A3).integers(0, n_views, (n, 3)).astype(np.int32)
+    pinned = torch.from_numpy(views).pin_memory()
+    a = torch.ones((2048, 2048), dtype=torch.float32, device=dev)
+    d_views = torch.zeros((n, 3), dtype=torch.int32, device=dev)
+    d_row_start = torch.zeros((n_views + 1,), dtype=torch.int32, device=dev)
+    d_row_edges = torch.zeros((6 * n,), dtype=torch.int32, device=dev)
+    d_flags = torch.zeros((1,), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)                        # the zeros are there: from here on nothing waits on the host
+    cur = torch.cuda.current_stream(dev)
+    assert _device.wait(cur) == _lib.STREAM_LEGACY or cur.cuda_stream != 0
+    for _ in range(8):
+        a = (a @ a) * (1.0 / 2048)
+    d_views.copy_(pinned, non_blocking=True)
+    PoseGraph(cons).rows_device(d_views, n, n_views, d_row_start, d_row_edges, d_flags, stream_to_wait=cur)
+    cons.sync()
+    row_start, row_edges = flatten(views, n_views)
+    assert np.array_equal(d_row_start.cpu().numpy().view(np.uint32), row_start)
+    assert np.array_equal(d_row_edges.cpu().numpy().view(np.uint32), row_edges)
+    assert int(d_flags.cpu()[0]) == 0
+
+
 def test_cpp_host_mirror_pose_graph(gpu, cons, tmp_path):
     """cv_sfm::PoseGraph of include/akaze.hpp from a native process (tests/cpp/pose_graph.cpp): its flatten and its printed
     verdicts, states, stats and poses equal the ctypes path's."""

@@ -96,9 +96,10 @@ def test_registration_chain_of_a_micro_batch(gpu, oracle):
     reg = Registration(torch, CAP, F, V, codewords, cam, threshold=thr, n_hypotheses=n_hyp, seed=11, **kw)
     frame_blocks = [V + f for f in range(F)]
     view_blocks = [[V + f - 1 - v for v in range(V)] for f in range(F)]
-    for rep in range(2):        # twice: the second call runs over the first one's leftovers
-        reg.enqueue(d_kps, d_descs, d_counts, frame_blocks, view_blocks, d_lm, d_world, n_world,
-                    stream_to_wait=_lib.wait_handle(torch.cuda.current_stream()))
+    cur = torch.cuda.current_stream()
+    # twice: the second call runs over the first one's leftovers, and names the stream to wait for by the torch object, not the raw handle
+    for wait in (_lib.wait_handle(cur), cur):
+        reg.enqueue(d_kps, d_descs, d_counts, frame_blocks, view_blocks, d_lm, d_world, n_world, stream_to_wait=wait)
     reg.sync()
     g_hash = reg.hash.cpu().numpy(); g_knn = reg.knn.cpu().numpy(); g_best = reg.best.cpu().numpy().view(np.uint32)
     g_dec = reg.decision.cpu().numpy().view(np.uint32); g_pairs = reg.pairs.cpu().numpy().view(np.uint32)
