@@ -195,6 +195,9 @@ RS_SV_S_INLIERS, RS_SV_S_RUN_MATCHES, RS_SV_S_RUN_STOP, RS_SV_S_ROBUST, RS_SV_S_
 RS_AV_OK, RS_AV_NOT_ACCEPTED, RS_AV_BAD_INDEX, RS_AV_BAD_TABLE = range(4)
 RS_AV_S_OBSERVATIONS, RS_AV_S_MERGED, RS_AV_S_DEMOTED, RS_AV_S_NEW_LANDMARKS = range(4)
 RS_AV_STATS, RS_AV_COUNTS, RS_LT_TILE = 4, 4, 1024
+RS_IR_OK, RS_IR_BAD_TABLE, RS_IR_BAD_INDEX, RS_IR_SHARED_BLOCK = range(4)
+RS_IR_C_ROWS, RS_IR_C_OBSERVATIONS, RS_IR_C_APPLIED, RS_IR_C_DEMOTED, RS_IR_C_NEW_ROWS, RS_IR_C_DROPPED, RS_IR_COUNTS = range(7)
+RS_NR_OK, RS_NR_NOT_NORMAL, RS_NR_BAD_INDEX = range(3)
 
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
@@ -241,6 +244,7 @@ ABI_SYMBOLS = [
     "rs_single_view_params_default", "rs_refine_poses_batch_device",
     "rs_covisibility_params_default", "rs_covisibility_candidates_device", "rs_covisibility_record_device", "rs_pose_graph_rows_device",
     "rs_landmarks_sharing_view_device", "rs_add_views_device",
+    "rs_merge_map_device", "rs_incorporate_reconstruction_device", "rs_normalize_reconstruction_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -395,6 +399,10 @@ def lib():
     L.rs_pose_graph_rows_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
     L.rs_landmarks_sharing_view_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, vp, vp]
     L.rs_add_views_device.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, u32, u32, u32, vp, u32] + [vp] * 8 + [u32, u32] + [vp] * 10
+    L.rs_merge_map_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, u32, u32, vp, vp, vp]
+    L.rs_incorporate_reconstruction_device.argtypes = ([vp, vp, vp, u32, u32, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, u32, u32] +
+                                                       [vp] * 9)
+    L.rs_normalize_reconstruction_device.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, u32, vp, vp, u32, vp, vp, vp]
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

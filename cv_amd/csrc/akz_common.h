@@ -192,7 +192,8 @@ struct RsCovisibilityState {
 };
 RsCovisibilityState* rs_internal_covisibility(rs_ctx* c);
 // What rs_landmark_table.hip keeps in an rs_ctx, grown on demand and freed by rs_destroy: the words of one rs_add_views_device
-// call (five per landmark, one per block, per scan tile and per feature of a slot, the slots' own).
+// call (five per landmark, one per block, per scan tile and per feature of a slot, the slots' own).  The calls of
+// rs_reconstruction_merge.hip use the same scratch: they run on the same stream, one call after another.
 struct RsLandmarkTableState {
     void* d_scratch = nullptr;
     size_t bytes = 0;

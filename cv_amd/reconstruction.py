@@ -244,3 +244,43 @@ def regenerate(torch, consensus, table, d_kps, cap, cam, poses, graph_start, rec
                                                                         cam, recon_start, pg_params, params)
     consensus.sync()
     return RegenerateResult(cand, constraints, recorded, rows, d_verdict, pose_graph, o, d_world, d_world_reason)
+
+
+def merge_reconstructions(torch, consensus, dst_table, src_table, d_kps, cap, cam, d_poses, dst_views, src_views, bridge_block, src_pose, slot,
+                          matches, nmatches, final, counts, src_landmarks, best=None, n_world=None, skip=None, **kw):
+    """What VSlam::try_merge_reconstructions does behind the bridging frame's add_view (cv-sfm/src/lib.rs:2153-2188:
+    the landmark map, incorporate_reconstruction), then regenerate_reconstruction, with ONE wait at the end: merge_map ->
+    incorporate -> the robust triangulation of the merged table with (lm_room, obs_room) as its sizes, so that nothing is read
+    back -> regenerate with the carried-over views as its targets.  dst_table: the destination after the bridging frame's
+    add_views; src_table: the source; dst_views, src_views: (first, end) block ranges of the two reconstructions' views in the
+    block pool — they must be adjacent, so that the merged graph is one range of graph_start (ValueError otherwise; renumbering
+    blocks is not done here); the bridging frame's block lies in one of them.  src_pose [12]: the bridging frame's pose in the
+    source, copied before add_views overwrote its row of d_poses.  slot, matches, nmatches, final, best, n_world: the
+    refinement call over the destination that registered the bridging frame and its slot; counts [n_blocks]; src_landmarks
+    [n_blocks][cap] the source's per-feature landmark map; skip [n_src_views] (optional) over the source's views in block order
+    without the bridging frame's.  A refused record does not loop in here: the caller runs again from the old tables with
+    `skip`, as with add_views.  kw: regenerate's parameter arguments.  -> (MergeMapTensors, IncorporateTensors, (world [lm_room][4], reason [lm_room]) of the
+    merged table under the incorporated poses, RegenerateResult)."""
+    from .reconstruction_merge import ReconstructionMerge
+    (d0, d1), (s0, s1) = (int(v) for v in dst_views), (int(v) for v in src_views)
+    if not (d0 <= d1 and s0 <= s1 and (d1 == s0 or s1 == d0)):
+        raise ValueError("the destination's and the source's view ranges must be adjacent in the block pool")
+    lo, hi = min(d0, s0), max(d1, s1)
+    if not lo <= bridge_block < hi:
+        raise ValueError("the bridging frame's block lies in neither range")
+    src_blocks = [b for b in range(s0, s1) if b != bridge_block]
+    rm = ReconstructionMerge(consensus)
+    merge_map = rm.merge_map_tensors(torch, matches, nmatches, final, cap, slot, counts, src_landmarks, bridge_block, dst_table.n_landmarks,
+                                     best=best, n_world=n_world)
+    merged = rm.incorporate_tensors(torch, dst_table, src_table, merge_map, d_poses, cap, src_blocks, bridge_block, src_pose, skip=skip)
+    table = merged.table(torch)
+    params = kw.pop("params", None) or ReconstructionOptimizer.params()
+    world = table.new_world()
+    reason = torch.zeros((max(table.n_landmarks, 1),), dtype=torch.uint8, device=table.dev)
+    rs_stream = torch.cuda.ExternalStream(consensus.stream(), device=table.dev)
+    with torch.cuda.stream(rs_stream):                   # the calls below order themselves behind the current torch stream
+        triangulate_landmarks_device(consensus._h, table, d_kps, cap, int(d_poses.shape[0]), d_poses, cam, params.triangulate, world, reason,
+                                     torch.cuda.current_stream(table.dev))
+        result = regenerate(torch, consensus, table, d_kps, cap, cam, d_poses, np.array([lo, hi], np.uint32),
+                            np.array([0, merged.lm_room], np.uint32), targets=np.array(src_blocks, np.uint32), reason=reason, params=params, **kw)
+    return merge_map, merged, (world, reason), result

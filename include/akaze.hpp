@@ -979,6 +979,64 @@ private:
     rs_ctx* ctx_ = nullptr;
     bool owned_ = false;
 };
+
+// cv-sfm's loop closure between two reconstructions and its normalisation over rs_merge_map_device,
+// rs_incorporate_reconstruction_device and rs_normalize_reconstruction_device: the landmark map of the bridging frame
+// (VSlam::try_merge_reconstructions, cv-sfm/src/lib.rs:2159-2170), incorporate_reconstruction (lib.rs:1817-1887), out of place,
+// and normalize_reconstruction (lib.rs:2241-2283).  It works on the context of the consensus that registered the bridging frame
+// (`ctx`, not owned) or, built from a device number, on a small context of its own.  Every argument named d_* is device memory
+// the caller owns (the layouts are include/akz.h's); the calls enqueue and return.
+class ReconstructionMerge {
+public:
+    enum Verdict : uint32_t { Ok = RS_IR_OK, BadTable = RS_IR_BAD_TABLE, BadIndex = RS_IR_BAD_INDEX, SharedBlock = RS_IR_SHARED_BLOCK };
+    enum NormalizeVerdict : uint32_t { Normalized = RS_NR_OK, NotNormal = RS_NR_NOT_NORMAL, NormalizeBadIndex = RS_NR_BAD_INDEX };
+    explicit ReconstructionMerge(rs_ctx* ctx) : ctx_(ctx) { akaze::require_abi(); }
+    explicit ReconstructionMerge(int device = 0) : owned_(true)
+    {
+        akaze::require_abi();
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+    }
+    ~ReconstructionMerge() { if (owned_ && ctx_) rs_destroy(ctx_); }
+    ReconstructionMerge(const ReconstructionMerge&) = delete;
+    ReconstructionMerge& operator=(const ReconstructionMerge&) = delete;
+    void merge_map(const void* d_matches, const void* d_nmatches, const void* d_final, const void* d_best, uint32_t n_world,
+                   uint32_t n_dst_landmarks, uint32_t cap_per_img, uint32_t slot, const void* d_counts, const void* d_src_landmarks,
+                   uint32_t n_blocks, uint32_t bridge_block, void* d_map, void* d_map_count, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_merge_map_device(ctx_, d_matches, d_nmatches, d_final, d_best, n_world, n_dst_landmarks, cap_per_img, slot, d_counts,
+                                         d_src_landmarks, n_blocks, bridge_block, d_map, d_map_count, stream_to_wait),
+                     "rs_merge_map_device");
+    }
+    void incorporate(const void* d_dst_start, const void* d_dst_obs, uint32_t n_dst_obs, uint32_t n_dst_landmarks, const void* d_src_start,
+                     const void* d_src_obs, uint32_t n_src_obs, uint32_t n_src_landmarks, const void* d_map, const void* d_map_count,
+                     uint32_t map_room, uint32_t cap_per_img, uint32_t n_blocks, const std::vector<uint32_t>& src_blocks, uint32_t bridge_block,
+                     const void* d_src_pose, const void* d_skip, uint32_t obs_room, uint32_t lm_room, void* d_poses, void* d_obs_start_out,
+                     void* d_obs_out, void* d_counts_out, void* d_landmarks_out, void* d_obs_counts_out, void* d_src_key_out,
+                     void* d_call_verdict, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_incorporate_reconstruction_device(ctx_, d_dst_start, d_dst_obs, n_dst_obs, n_dst_landmarks, d_src_start, d_src_obs,
+                                                          n_src_obs, n_src_landmarks, d_map, d_map_count, map_room, cap_per_img, n_blocks,
+                                                          src_blocks.data(), (uint32_t)src_blocks.size(), bridge_block, d_src_pose, d_skip,
+                                                          obs_room, lm_room, d_poses, d_obs_start_out, d_obs_out, d_counts_out, d_landmarks_out,
+                                                          d_obs_counts_out, d_src_key_out, d_call_verdict, stream_to_wait),
+                     "rs_incorporate_reconstruction_device");
+    }
+    void normalize(const std::vector<uint32_t>& view_blocks, const void* d_counts, const void* d_landmarks, uint32_t cap_per_img,
+                   uint32_t n_blocks, const void* d_world, uint32_t n_world, void* d_poses, void* d_constraint_poses, uint32_t n_constraints,
+                   void* d_stats, void* d_verdict, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_normalize_reconstruction_device(ctx_, view_blocks.data(), (uint32_t)view_blocks.size(), d_counts, d_landmarks,
+                                                        cap_per_img, n_blocks, d_world, n_world, d_poses, d_constraint_poses, n_constraints,
+                                                        d_stats, d_verdict, stream_to_wait),
+                     "rs_normalize_reconstruction_device");
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_ctx* ctx_ = nullptr;
+    bool owned_ = false;
+};
 }  // namespace cv_sfm
 
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over

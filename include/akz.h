@@ -1241,6 +1241,81 @@ int32_t rs_add_views_device(rs_ctx* ctx, const void* d_obs_start, const void* d_
                             uint32_t obs_room, uint32_t lm_room, void* d_poses, void* d_obs_start_out, void* d_obs_out, void* d_counts_out,
                             void* d_landmarks_out, void* d_obs_counts_out, void* d_frame_verdict, void* d_stats, void* d_call_verdict,
                             void* stream_to_wait);
+/* ---- two reconstructions become one on the device: the landmark map of a bridging frame, incorporate, normalise ----
+ * cv-sfm's loop closure between reconstructions (VSlam::try_merge_reconstructions, cv-sfm/src/lib.rs:2116-2193;
+ * incorporate_reconstruction, lib.rs:1817-1887) and normalize_reconstruction (lib.rs:2241-2283) over the tables
+ * rs_add_views_device writes.  The decisions and the pose arithmetic are include/akz_reconstruction_merge_math.h (compiled for
+ * the device and, by the tests, for the host: equal byte for byte), whose head lists the departures from the reference. */
+enum {
+    RS_IR_OK = 0,
+    RS_IR_BAD_TABLE = 1,       /* either table's starts do not ascend inside its n_obs */
+    RS_IR_BAD_INDEX = 2,       /* a kept source observation names a feature >= cap_per_img */
+    RS_IR_SHARED_BLOCK = 3,    /* a kept source observation names a block the destination table names too */
+    /* d_counts_out words (u32): */
+    RS_IR_C_ROWS = 0,          /* rows filled */
+    RS_IR_C_OBSERVATIONS = 1,  /* observations filled */
+    RS_IR_C_APPLIED = 2,       /* map entries applied */
+    RS_IR_C_DEMOTED = 3,       /* map entries demoted */
+    RS_IR_C_NEW_ROWS = 4,      /* rows added behind the destination's */
+    RS_IR_C_DROPPED = 5,       /* source observations dropped (the bridging frame's, the skipped views') */
+    RS_IR_COUNTS = 6,
+    RS_NR_OK = 0,
+    RS_NR_NOT_NORMAL = 1,      /* the mean distance is zero, subnormal, infinite or NaN (no robust point at all): nothing is written */
+    RS_NR_BAD_INDEX = 2        /* a view block >= n_blocks or the first view's count above cap_per_img: nothing is written */
+};
+/* The map of lib.rs:2159-2170 for the bridging frame, slot `slot` of a refinement call over the DESTINATION table: d_matches
+ * [..][cap_per_img][2], d_nmatches, d_final [..][cap_per_img] u8 and the optional d_best with n_world, as rs_add_views_device
+ * takes them; d_counts [n_blocks] u32; d_src_landmarks [n_blocks][cap_per_img] u32 the SOURCE reconstruction's per-feature
+ * landmark map (an earlier d_landmarks_out); bridge_block < n_blocks (else AKZ_E_INVALID) the frame's keypoint block.
+ * d_map [cap_per_img][2] u32 {source landmark, destination landmark}, d_map_count [1] u32: one entry per final match of the slot
+ * that names something under rs_add_views_device's rules (the destination of a merged match is best[0], the reference's
+ * dest_landmarks[0]) and whose feature has a source landmark (not 0xFFFFFFFF), in ascending feature order; a feature in two
+ * final matches takes the first.  A slot whose count or d_nmatches is above cap_per_img gives an empty map.  Entries behind the
+ * count are not written.  One launch of one workgroup on rs_stream() after stream_to_wait (may be NULL); returns after
+ * enqueueing; allocates nothing beyond growing the context's scratch. */
+int32_t rs_merge_map_device(rs_ctx* ctx, const void* d_matches, const void* d_nmatches, const void* d_final, const void* d_best, uint32_t n_world,
+                            uint32_t n_dst_landmarks, uint32_t cap_per_img, uint32_t slot, const void* d_counts, const void* d_src_landmarks,
+                            uint32_t n_blocks, uint32_t bridge_block, void* d_map, void* d_map_count, void* stream_to_wait);
+/* incorporate_reconstruction, out of place.  The destination table (d_dst_start [n_dst_landmarks + 1], d_dst_obs [n_dst_obs][2])
+ * is the table after the bridging frame's add_views; the source table is given the same way; d_map [map_room][2] with its length
+ * d_map_count [1] on the device (the first min(*d_map_count, map_room) entries count).  src_blocks [n_src_views] is a host list
+ * of distinct blocks below n_blocks that does not hold bridge_block (else AKZ_E_INVALID): the source's other views.  d_src_pose
+ * [12] f64 is the bridging frame's pose in the source, copied before add_views overwrote that row of d_poses.  d_skip
+ * [n_src_views] u32 (optional, non-zero: the view is left out).  obs_room >= n_dst_obs + n_src_obs and lm_room >=
+ * n_dst_landmarks + n_src_landmarks, and no output may overlap an input table or the map: else AKZ_E_INVALID.
+ * A source observation is kept iff its block is in src_blocks and not skipped (the bridging frame's are dropped: the reference
+ * removes that view from the source first).  A map entry is applied iff it names a row of each table and no other entry names
+ * its source landmark and none its destination landmark; else it is demoted and its source landmark is unmapped.  Outputs, in
+ * rs_add_views_device's shapes: row l < n_dst_landmarks is its old list, then the kept observations of the source landmark
+ * mapped to it in source order; the unmapped source landmarks with a kept observation become rows n_dst_landmarks + k in
+ * ascending source key; every start from there to lm_room equals the total.  d_counts_out [RS_IR_COUNTS], d_landmarks_out
+ * [n_blocks][cap_per_img] every word written, d_obs_counts_out [lm_room], d_src_key_out [n_src_landmarks] the destination key of
+ * every source landmark or 0xFFFFFFFF, d_call_verdict [1] (RS_IR_*).  d_poses [n_blocks][12] f64 in place: with T =
+ * inverse(d_src_pose) * d_poses[bridge_block], d_poses[b] = d_poses[b] * T for every kept source view b.  On a verdict other
+ * than RS_IR_OK the outputs describe the destination table unchanged (a destination whose own starts are broken: as many
+ * empty rows), every source key is 0xFFFFFFFF and the poses are untouched.  Enqueues on rs_stream() after stream_to_wait (may be
+ * NULL) and returns; allocates nothing beyond growing the context's scratch. */
+int32_t rs_incorporate_reconstruction_device(rs_ctx* ctx, const void* d_dst_start, const void* d_dst_obs, uint32_t n_dst_obs,
+                                             uint32_t n_dst_landmarks, const void* d_src_start, const void* d_src_obs, uint32_t n_src_obs,
+                                             uint32_t n_src_landmarks, const void* d_map, const void* d_map_count, uint32_t map_room,
+                                             uint32_t cap_per_img, uint32_t n_blocks, const uint32_t* src_blocks, uint32_t n_src_views,
+                                             uint32_t bridge_block, const void* d_src_pose, const void* d_skip, uint32_t obs_room,
+                                             uint32_t lm_room, void* d_poses, void* d_obs_start_out, void* d_obs_out, void* d_counts_out,
+                                             void* d_landmarks_out, void* d_obs_counts_out, void* d_src_key_out, void* d_call_verdict,
+                                             void* stream_to_wait);
+/* normalize_reconstruction for one reconstruction: view_blocks [n_views] a host list of distinct blocks (n_views >= 1, else
+ * AKZ_E_INVALID), the first the reference's first view; d_counts [n_blocks], d_landmarks [n_blocks][cap_per_img] (a
+ * d_landmarks_out), d_world [n_world][4] f64.  The mean runs over the first view's features j < count whose landmark is below
+ * n_world and whose world row has a Euclidean point (w > 0): |(pose * point).xyz / w|, summed in include/akz_sum_order.h's
+ * order for 256 threads and divided by the count.  If it is a normal number every listed view's pose becomes pose *
+ * inverse(first) with its translation times 1 / mean, and the translations of d_constraint_poses [n_constraints][2][12] f64
+ * (optional) are multiplied by the same factor, both in place; else nothing but d_stats and d_verdict is written.  d_stats [2]
+ * f64 {mean, count}, d_verdict [1] u32 (RS_NR_*).  One launch of one workgroup of 256 on rs_stream() after stream_to_wait (may
+ * be NULL); returns after enqueueing; allocates nothing beyond growing the context's scratch. */
+int32_t rs_normalize_reconstruction_device(rs_ctx* ctx, const uint32_t* view_blocks, uint32_t n_views, const void* d_counts,
+                                           const void* d_landmarks, uint32_t cap_per_img, uint32_t n_blocks, const void* d_world,
+                                           uint32_t n_world, void* d_poses, void* d_constraint_poses, uint32_t n_constraints, void* d_stats,
+                                           void* d_verdict, void* stream_to_wait);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched

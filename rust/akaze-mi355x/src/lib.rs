@@ -179,6 +179,22 @@ extern "C" {
                            d_obs_out: *mut c_void, d_counts_out: *mut c_void, d_landmarks_out: *mut c_void, d_obs_counts_out: *mut c_void,
                            d_frame_verdict: *mut c_void, d_stats: *mut c_void, d_call_verdict: *mut c_void,
                            stream_to_wait: *mut c_void) -> i32;
+    fn rs_merge_map_device(ctx: *mut c_void, d_matches: *const c_void, d_nmatches: *const c_void, d_final: *const c_void, d_best: *const c_void,
+                           n_world: u32, n_dst_landmarks: u32, cap_per_img: u32, slot: u32, d_counts: *const c_void,
+                           d_src_landmarks: *const c_void, n_blocks: u32, bridge_block: u32, d_map: *mut c_void, d_map_count: *mut c_void,
+                           stream_to_wait: *mut c_void) -> i32;
+    fn rs_incorporate_reconstruction_device(ctx: *mut c_void, d_dst_start: *const c_void, d_dst_obs: *const c_void, n_dst_obs: u32,
+                                            n_dst_landmarks: u32, d_src_start: *const c_void, d_src_obs: *const c_void, n_src_obs: u32,
+                                            n_src_landmarks: u32, d_map: *const c_void, d_map_count: *const c_void, map_room: u32,
+                                            cap_per_img: u32, n_blocks: u32, src_blocks: *const u32, n_src_views: u32, bridge_block: u32,
+                                            d_src_pose: *const c_void, d_skip: *const c_void, obs_room: u32, lm_room: u32,
+                                            d_poses: *mut c_void, d_obs_start_out: *mut c_void, d_obs_out: *mut c_void,
+                                            d_counts_out: *mut c_void, d_landmarks_out: *mut c_void, d_obs_counts_out: *mut c_void,
+                                            d_src_key_out: *mut c_void, d_call_verdict: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_normalize_reconstruction_device(ctx: *mut c_void, view_blocks: *const u32, n_views: u32, d_counts: *const c_void,
+                                          d_landmarks: *const c_void, cap_per_img: u32, n_blocks: u32, d_world: *const c_void, n_world: u32,
+                                          d_poses: *mut c_void, d_constraint_poses: *mut c_void, n_constraints: u32, d_stats: *mut c_void,
+                                          d_verdict: *mut c_void, stream_to_wait: *mut c_void) -> i32;
     fn hm_landmark_original_matches_batch_device(ctx: *mut c_void, d_best: *const c_void, d_decision: *const c_void, d_merge_ok: *const c_void,
                                                  d_obs_counts: *const c_void, d_nq: *const c_void, iq: *const u32, cap_per_img: u32,
                                                  n_frames: u32, n_world: u32, d_pairs: *mut c_void, d_npairs: *mut c_void,
@@ -1542,6 +1558,91 @@ impl LandmarkBook {
                                      n_blocks, ik.as_ptr(), ik.len() as u32, d_counts, d_matches, d_nmatches, d_final, d_verdict, d_pose_out,
                                      d_best, d_skip, obs_room, lm_room, d_poses, d_obs_start_out, d_obs_out, d_counts_out, d_landmarks_out,
                                      d_obs_counts_out, d_frame_verdict, d_stats, d_call_verdict, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+}
+
+/// The verdict on `ReconstructionMerge::incorporate` (`d_call_verdict`).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum IncorporateVerdict {
+    Ok = 0,
+    BadTable = 1,
+    BadIndex = 2,
+    SharedBlock = 3,
+}
+
+/// The verdict on `ReconstructionMerge::normalize` (`d_verdict`).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum NormalizeVerdict {
+    Ok = 0,
+    NotNormal = 1,
+    BadIndex = 2,
+}
+
+/// The words of `d_counts_out` of `ReconstructionMerge::incorporate`.
+pub const RS_IR_C_ROWS: usize = 0;
+pub const RS_IR_C_OBSERVATIONS: usize = 1;
+pub const RS_IR_C_APPLIED: usize = 2;
+pub const RS_IR_C_DEMOTED: usize = 3;
+pub const RS_IR_C_NEW_ROWS: usize = 4;
+pub const RS_IR_C_DROPPED: usize = 5;
+pub const RS_IR_COUNTS: usize = 6;
+
+/// cv-sfm's loop closure between two reconstructions and its normalisation: the landmark map of the bridging frame
+/// (cv-sfm/src/lib.rs:2159-2170, `rs_merge_map_device`), `incorporate_reconstruction` (lib.rs:1817-1887,
+/// `rs_incorporate_reconstruction_device`) and `normalize_reconstruction` (lib.rs:2241-2283,
+/// `rs_normalize_reconstruction_device`), on the context of the consensus that registered the bridging frame (not owned).
+/// Every `d_*` argument is device memory the caller owns, laid out as include/akz.h documents; the calls enqueue and return.
+/// Like the other declarations of this file these are source only: they are not compiled here (no toolchain).
+pub struct ReconstructionMerge {
+    ctx: *mut c_void,
+}
+impl ReconstructionMerge {
+    /// # Safety
+    /// `ctx` is a live `rs_ctx` that outlives this object.
+    pub unsafe fn new(ctx: *mut c_void) -> Self {
+        require_abi();
+        Self { ctx }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn merge_map(&self, d_matches: *const c_void, d_nmatches: *const c_void, d_final: *const c_void, d_best: *const c_void,
+                            n_world: u32, n_dst_landmarks: u32, cap_per_img: u32, slot: u32, d_counts: *const c_void,
+                            d_src_landmarks: *const c_void, n_blocks: u32, bridge_block: u32, d_map: *mut c_void, d_map_count: *mut c_void,
+                            stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_merge_map_device(self.ctx, d_matches, d_nmatches, d_final, d_best, n_world, n_dst_landmarks, cap_per_img, slot, d_counts,
+                                     d_src_landmarks, n_blocks, bridge_block, d_map, d_map_count, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn incorporate(&self, d_dst_start: *const c_void, d_dst_obs: *const c_void, n_dst_obs: u32, n_dst_landmarks: u32,
+                              d_src_start: *const c_void, d_src_obs: *const c_void, n_src_obs: u32, n_src_landmarks: u32,
+                              d_map: *const c_void, d_map_count: *const c_void, map_room: u32, cap_per_img: u32, n_blocks: u32,
+                              src_blocks: &[u32], bridge_block: u32, d_src_pose: *const c_void, d_skip: *const c_void, obs_room: u32,
+                              lm_room: u32, d_poses: *mut c_void, d_obs_start_out: *mut c_void, d_obs_out: *mut c_void,
+                              d_counts_out: *mut c_void, d_landmarks_out: *mut c_void, d_obs_counts_out: *mut c_void,
+                              d_src_key_out: *mut c_void, d_call_verdict: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_incorporate_reconstruction_device(self.ctx, d_dst_start, d_dst_obs, n_dst_obs, n_dst_landmarks, d_src_start, d_src_obs,
+                                                      n_src_obs, n_src_landmarks, d_map, d_map_count, map_room, cap_per_img, n_blocks,
+                                                      src_blocks.as_ptr(), src_blocks.len() as u32, bridge_block, d_src_pose, d_skip,
+                                                      obs_room, lm_room, d_poses, d_obs_start_out, d_obs_out, d_counts_out,
+                                                      d_landmarks_out, d_obs_counts_out, d_src_key_out, d_call_verdict, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn normalize(&self, view_blocks: &[u32], d_counts: *const c_void, d_landmarks: *const c_void, cap_per_img: u32, n_blocks: u32,
+                            d_world: *const c_void, n_world: u32, d_poses: *mut c_void, d_constraint_poses: *mut c_void,
+                            n_constraints: u32, d_stats: *mut c_void, d_verdict: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_normalize_reconstruction_device(self.ctx, view_blocks.as_ptr(), view_blocks.len() as u32, d_counts, d_landmarks,
+                                                    cap_per_img, n_blocks, d_world, n_world, d_poses, d_constraint_poses, n_constraints,
+                                                    d_stats, d_verdict, stream_to_wait);
         if st == 0 { Ok(()) } else { Err(st) }
     }
 }
