@@ -491,8 +491,46 @@ int32_t rs_five_point_batch(rs_ctx* ctx, const double* bearings_a, const double*
  *   RS_PRUNE_HALVE  the candidate cap halves with every block after init_blocks (ARRSAC's preemption function
  *                   f(i) = floor(M 2^-floor(i/B))), down to one survivor; with estimations_per_block == 0 the block
  *                   loop ends when the cap reaches 1 (a single survivor cannot be overtaken; stats count what ran).
+ * The rules in full (tests/consensus_statement.py states them in Python and holds oracle and device to that statement):
+ *   blocks      With none of the rules asked for (no RS_PRUNE_BOUND, no RS_PRUNE_SPRT, max_candidates == 0,
+ *               estimations_per_block == 0) all matches are one block.  Otherwise the decisions below are taken after every
+ *               block but the last: nothing is retired and nothing re-sampled once every match has been scored.  `best` is
+ *               the largest count among the live poses, `seen` the matches scored so far, `left` = n - seen.
+ *   bound       count + left < best retires a pose.  It is applied wherever blocks are decided, also without RS_PRUNE_BOUND
+ *               (it cannot change the result); the flag alone asks for block-wise scoring.
+ *   SPRT        only while 0 < best < seen.  With natural logarithms from the host's libm the test is
+ *               c l_in + (seen - c) l_out > ln(sprt_ratio), evaluated in this form in f64:
+ *               l_in = ln(delta) - (ln(best) - ln(seen)),  l_out = ln(1 - delta) - (ln(seen - best) - ln(seen)).  Its left side is -seen KL(eps || delta)
+ *               <= 0 at c == best, and it grows with c where eps <= delta: a pose at the best count is never rejected, and
+ *               while eps <= delta no pose is (the implementations say both outright; neither changes a decision).
+ *   cap         applies when more poses are live than the cap allows.  The ranking (distance to best, then id) is taken over
+ *               the live poses as they entered this block's decisions.  Poses nearer than the cap-th of that ranking stay
+ *               if bound and SPRT let them; the places the nearer ones leave go, in ascending id, to the poses as far as
+ *               the cap-th one that bound and SPRT have not retired: a retired pose takes no place.
+ *   halving     after block b >= init_blocks the cap is max(1, max_candidates >> (b - init_blocks)) (shifts of 31 and more
+ *               give 1): with init_blocks == 0 the first decision, after block 1, already halves once.
+ *   re-sampling after every block b >= init_blocks but the last: the best pose is the live one with the largest count, lowest
+ *               id; its inliers among the matches seen are listed in scoring order; sample number h (numbers go on from
+ *               n_hypotheses, estimations_per_block a round) draws K distinct positions of that list from stream h of
+ *               seed ^ 0xA5A5A5A55A5A5A5A.  A round whose list is shorter than K, or that finds no live pose, draws
+ *               nothing and still takes its numbers.  New poses are scored on the matches seen and join after the
+ *               block's retirements.
+ *   result      the live pose with the largest count over the matches scored, lowest id; inlier_idx lists its inliers among
+ *               ALL matches in ascending index, also when the halving ended the loop early.
+ *   stats       poses = 4 x the hypothesis slots numbered (rounds that drew nothing included); survivors = live poses at the
+ *               end; blocks = blocks scored; residuals_evaluated = every (live pose, match) of every block, + seen for the
+ *               list of a re-sampling round that found a live pose, + seen for every valid pose it added (the final inlier
+ *               list is not counted); residuals_exhaustive = poses x n.  A scene of a batched call with fewer matches than
+ *               a minimal sample has all of them zero.
+ * n smaller than a minimal sample: AKZ_E_INVALID from the single-scene entries ("no model" for such a scene of a batched
+ * call).  "No model" otherwise means that no sample gave a pose.  The eight-point solver gives four poses for ANY eight
+ * matches, also for one match repeated eight times (it takes a vector of the then eight-dimensional null space): such a
+ * call returns a pose without support, best_id 0 and an empty inlier list, not "no model".  Lambda Twist on three equal
+ * points gives none.
  * sample_idx == NULL draws the n_hypotheses minimal samples on the device from xoshiro256++ streams seeded with
- * `seed` (rs_arrsac_samples reproduces them on the host).  The arrsac crate is not vendored in the reference: the
+ * `seed` (rs_arrsac_samples reproduces them on the host): stream h is xoshiro256++ whose four state words are the first four
+ * outputs of splitmix64 started at seed + 0xD1B54A32D192ED03 (h + 1); an index is (next() >> 32) * n >> 32, a repeated
+ * index is drawn again.  The arrsac crate is not vendored in the reference: the
  * sampler, the retirement rules and their order are this library's, specified by oracle/arrsac_oracle.c and held to
  * it bit for bit (parity with the crate unpinned beyond the count pin of akaze/tests/estimate_pose.rs:75).
  * best_id / best_pose / inlier_idx as for rs_essential_batch.
@@ -589,7 +627,9 @@ int32_t rs_batch_reserve(rs_ctx* ctx, uint32_t max_scenes);
 enum { RS_BATCH_SHUFFLE = 1u << 0 };   /* score the matches in a seeded shuffled order (the reference shuffles them with
                                         * the caller's rng, cv-sfm/src/lib.rs:1385): position j of scene s holds the
                                         * match with the j-th smallest 32-bit key splitmix64((seed_s ^ 0x5851F42D4C957F2D)
-                                        * + 0xD1342543DE82EF95 j) >> 32, ties in index order; needs cap_per_img <= 8192 */
+                                        * + 0xD1342543DE82EF95 j) >> 32 (splitmix64(x): the first output of the generator
+                                        * started at x, i.e. the mix of x + 0x9E3779B97F4A7C15), ties in index order; needs
+                                        * cap_per_img <= 8192 */
 /* Scene s (0 <= s < n_scenes): pair list s of d_pairs ([cap_per_img][2] u32, count d_npairs[s] — hm_match_batch_device's
  * outputs), whose [a, b] index the keypoints of block ia[s] of d_kps_a and block ib[s] of d_kps_b ([..][cap_per_img]
  * akz_keypoint — akz_extract_batch_device's output).  Each scene runs rs_essential_arrsac's procedure on its calibrated
