@@ -198,6 +198,9 @@ RS_AV_STATS, RS_AV_COUNTS, RS_LT_TILE = 4, 4, 1024
 RS_IR_OK, RS_IR_BAD_TABLE, RS_IR_BAD_INDEX, RS_IR_SHARED_BLOCK = range(4)
 RS_IR_C_ROWS, RS_IR_C_OBSERVATIONS, RS_IR_C_APPLIED, RS_IR_C_DEMOTED, RS_IR_C_NEW_ROWS, RS_IR_C_DROPPED, RS_IR_COUNTS = range(7)
 RS_NR_OK, RS_NR_NOT_NORMAL, RS_NR_BAD_INDEX = range(3)
+RS_EX_OK, RS_EX_OVERFLOW, RS_EX_BAD_TABLE = range(3)
+RS_EX_C_POINTS, RS_EX_C_NO_POINT, RS_EX_C_INFINITE, RS_EX_C_BAD_ROWS, RS_EX_COUNTS = range(5)
+RS_EX_CAMERA_WORDS, RS_EX_CAMERA_VERTICES = 10, 5
 
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
@@ -245,6 +248,7 @@ ABI_SYMBOLS = [
     "rs_covisibility_params_default", "rs_covisibility_candidates_device", "rs_covisibility_record_device", "rs_pose_graph_rows_device",
     "rs_landmarks_sharing_view_device", "rs_add_views_device",
     "rs_merge_map_device", "rs_incorporate_reconstruction_device", "rs_normalize_reconstruction_device",
+    "rs_export_reconstruction_device", "rs_write_ply", "akz_sample_colors_batch_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -314,6 +318,7 @@ def lib():
     L.akz_vertical_filter.argtypes = [vp, vp, i32, i32, vp, u32, vp]
     L.akz_half_size.argtypes = [vp, vp, i32, i32, vp]
     L.akz_sample_colors_rgb8.argtypes = [vp, vp, i32, i32, i32, vp, u32, vp]
+    L.akz_sample_colors_batch_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, u32, vp, vp]
     L.hm_create.argtypes = [i32, u32, u32, C.POINTER(vp)]
     L.hm_create_ex.argtypes = [i32, u32, u32, u32, C.POINTER(vp)]
     L.hm_destroy.argtypes = [vp]
@@ -403,6 +408,8 @@ def lib():
     L.rs_incorporate_reconstruction_device.argtypes = ([vp, vp, vp, u32, u32, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, u32, u32] +
                                                        [vp] * 9)
     L.rs_normalize_reconstruction_device.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, u32, vp, vp, u32, vp, vp, vp]
+    L.rs_export_reconstruction_device.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.rs_write_ply.argtypes = [C.c_char_p, vp, vp, u32, u32, i32]
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

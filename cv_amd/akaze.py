@@ -15,7 +15,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 from ._lib import KP_DTYPE, AkzError, Config, LevelInfo, Options, check, make_options  # noqa: F401
 
 USIZE_MAX = 2 ** 64 - 1
@@ -117,6 +117,10 @@ class Akaze:
         ctx = self.__dict__.pop("_ctx", None)
         if ctx is not None:
             ctx.close()
+
+    def sample_colors_device(self, d_rgb, n, w, h, stride, d_kps, d_counts, cap, d_colors, stream_to_wait=None):
+        """Context.sample_colors_device on this instance's context for `n` frames of w x h."""
+        self.context(w, h, n).sample_colors_device(d_rgb, n, w, h, stride, d_kps, d_counts, cap, d_colors, stream_to_wait)
 
     # ---- the reference API ---------------------------------------------------------------
     def extract(self, image):
@@ -301,6 +305,13 @@ class Context:
                                                 rgb.strides[0], kps.ctypes.data, len(kps), out.ctypes.data),
               "akz_sample_colors_rgb8")
         return out
+
+    def sample_colors_device(self, d_rgb, n, w, h, stride, d_kps, d_counts, cap, d_colors, stream_to_wait=None):
+        """akz_sample_colors_batch_device: sample_colors for a micro-batch where it lies on the device.  d_rgb [n] RGB8 images of
+        h rows of `stride` bytes, d_kps [n][cap] and d_counts [n] as akz_extract_batch_device leaves them, d_colors [n][cap][3]
+        uint8 (rows at or behind a frame's count are not written): d_* and stream_to_wait as _device.arg / wait take them.
+        Enqueues on akz_stream() and returns."""
+        _device.call("akz_sample_colors_batch_device", self._h, d_rgb, n, w, h, stride, d_kps, d_counts, cap, d_colors, _device.wait(stream_to_wait))
 
     def timing_enable(self, on=True):
         check(_lib.lib().akz_timing_enable(self._h, int(on)))

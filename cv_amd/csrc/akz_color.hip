@@ -26,32 +26,54 @@ __device__ __forceinline__ uint8_t blend_cubic(float p0, float p1, float p2, flo
     return clamp_u8(pval);
 }
 
-__global__ __launch_bounds__(256) void k_bicubic_rgb8(const uint8_t* __restrict__ rgb, int w, int h,
-                                                      const akz_keypoint* __restrict__ kps, uint32_t n,
-                                                      uint8_t* __restrict__ colors)
+// interpolate_bicubic at (x, y) on an RGB8 image of h rows of `stride` bytes -> out [3]
+__device__ __forceinline__ void bicubic_rgb8(const uint8_t* __restrict__ rgb, int w, int h, size_t stride, float x, float y, uint8_t* out)
 {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float x = kps[i].x, y = kps[i].y;
     // bicubic.rs:39-46
     const float left = floorf(x) - 1.0f, right = left + 4.0f;
     const float top = floorf(y) - 1.0f, bottom = top + 4.0f;
     const float xw = x - (left + 1.0f), yw = y - (top + 1.0f);
-    uint8_t out[3] = {0, 0, 0};
+    out[0] = out[1] = out[2] = 0;
     if (!(left < 0.0f || right >= (float)w || top < 0.0f || bottom >= (float)h)) {
         const uint32_t l = (uint32_t)left, t = (uint32_t)top;
         uint8_t col[4][3];
         for (int r = 0; r < 4; ++r) {
-            const uint8_t* p = rgb + ((size_t)(t + r) * w + l) * 3;
+            const uint8_t* p = rgb + (size_t)(t + r) * stride + (size_t)l * 3;
             for (int ch = 0; ch < 3; ++ch)
                 col[r][ch] = blend_cubic((float)p[ch], (float)p[3 + ch], (float)p[6 + ch], (float)p[9 + ch], xw);
         }
         for (int ch = 0; ch < 3; ++ch)
             out[ch] = blend_cubic((float)col[0][ch], (float)col[1][ch], (float)col[2][ch], (float)col[3][ch], yw);
     }
+}
+
+__global__ __launch_bounds__(256) void k_bicubic_rgb8(const uint8_t* __restrict__ rgb, int w, int h,
+                                                      const akz_keypoint* __restrict__ kps, uint32_t n,
+                                                      uint8_t* __restrict__ colors)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint8_t out[3];
+    bicubic_rgb8(rgb, w, h, (size_t)w * 3, kps[i].x, kps[i].y, out);
     colors[(size_t)i * 3 + 0] = out[0];
     colors[(size_t)i * 3 + 1] = out[1];
     colors[(size_t)i * 3 + 2] = out[2];
+}
+
+// frame blockIdx.y of a micro-batch: feature j below min(count, cap) of the frame; the rows behind are not written
+__global__ __launch_bounds__(256) void k_bicubic_rgb8_batch(const uint8_t* __restrict__ rgb, int w, int h, size_t stride,
+                                                            const akz_keypoint* __restrict__ kps, const uint32_t* __restrict__ counts,
+                                                            uint32_t cap, uint8_t* __restrict__ colors)
+{
+    const uint32_t f = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t count = counts[f] < cap ? counts[f] : cap;
+    if (j >= count) return;
+    const size_t at = (size_t)f * cap + j;
+    uint8_t out[3];
+    bicubic_rgb8(rgb + (size_t)f * h * stride, w, h, stride, kps[at].x, kps[at].y, out);
+    colors[at * 3 + 0] = out[0];
+    colors[at * 3 + 1] = out[1];
+    colors[at * 3 + 2] = out[2];
 }
 
 }  // namespace
@@ -83,6 +105,31 @@ extern "C" int32_t akz_sample_colors_rgb8(akz_ctx* c, const uint8_t* rgb, int32_
         AKZ_LAUNCH_CHECK();
         AKZ_HIP(hipMemcpyAsync(colors, d_col, col_bytes, hipMemcpyDeviceToHost, s));
         AKZ_HIP(hipStreamSynchronize(s));
+        return AKZ_OK;
+    });
+}
+
+// The same lookup for a whole micro-batch, where the data lies on the device: d_rgb [n] RGB8 images of h rows of `stride`
+// bytes, d_kps [n][cap_per_img] and d_counts [n] as akz_extract_batch_device leaves them -> d_colors [n][cap_per_img][3].  One
+// launch on the stream the extraction's outputs complete on (akz_stream()), behind stream_to_wait.
+extern "C" int32_t akz_sample_colors_batch_device(akz_ctx* c, const void* d_rgb, int32_t n, int32_t w, int32_t h, int32_t stride,
+                                                  const void* d_kps, const void* d_counts, uint32_t cap_per_img, void* d_colors,
+                                                  void* stream_to_wait)
+{
+    return akz_guard([&]() -> int32_t {
+        if (!d_rgb || !d_kps || !d_counts || !d_colors || n < 1 || n > 65535 || w <= 0 || h <= 0 || stride < 3 * w || cap_per_img == 0)
+            return AKZ_E_INVALID;
+        if (cap_per_img > 0xFFFFFFFFu - 256u) return AKZ_E_TOO_LARGE;
+        if (!c) return AKZ_E_INVALID;
+        AKZ_HIP(hipSetDevice(c->device));
+        hipStream_t s = c->stream_kp;
+        if (stream_to_wait) {
+            AKZ_HIP(hipEventRecord(c->ev_input, akz_wait_stream(stream_to_wait)));
+            AKZ_HIP(hipStreamWaitEvent(s, c->ev_input, 0));
+        }
+        hipLaunchKernelGGL(k_bicubic_rgb8_batch, dim3((cap_per_img + 255) / 256, (unsigned)n), dim3(256), 0, s, (const uint8_t*)d_rgb, w, h,
+                           (size_t)stride, (const akz_keypoint*)d_kps, (const uint32_t*)d_counts, cap_per_img, (uint8_t*)d_colors);
+        AKZ_LAUNCH_CHECK();
         return AKZ_OK;
     });
 }

@@ -284,3 +284,16 @@ def merge_reconstructions(torch, consensus, dst_table, src_table, d_kps, cap, ca
         result = regenerate(torch, consensus, table, d_kps, cap, cam, d_poses, np.array([lo, hi], np.uint32),
                             np.array([0, merged.lm_room], np.uint32), targets=np.array(src_blocks, np.uint32), reason=reason, params=params, **kw)
     return merge_map, merged, (world, reason), result
+
+
+def export_reconstruction(torch, consensus, table, world, colors, view_blocks, counts, landmarks, cap, d_poses, path, camera_faces=True,
+                          room=None, n_world=None):
+    """VSlam::export_reconstruction (cv-sfm/src/lib.rs:2285-2340): the export on rs_stream() behind the current torch stream,
+    ONE wait, the copy of the used rows, then the file (rs_write_ply).  table, world, colors, view_blocks, counts, landmarks,
+    cap, d_poses, room, n_world: export.ReconstructionExport.export_tensors' arguments.  With a `room` below the number of
+    points the file holds the first `room` of them and the result's verdict says so.  -> export.ExportResult."""
+    from .export import ReconstructionExport, write_ply
+    result = ReconstructionExport(consensus).run_export(torch, table, world, colors, view_blocks, counts, landmarks, cap, d_poses, room=room,
+                                                        n_world=n_world)
+    write_ply(path, result.xyz, result.rgb, result.n_views, camera_faces)
+    return result

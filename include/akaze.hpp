@@ -1037,6 +1037,49 @@ private:
     rs_ctx* ctx_ = nullptr;
     bool owned_ = false;
 };
+
+// VSlam::export_reconstruction (cv-sfm/src/lib.rs:2285-2340) with export.rs over rs_export_reconstruction_device and
+// rs_write_ply: the coloured point cloud and the cameras' frusta as the vertex arrays of the .ply file, made on the device, and
+// the file's text, written by the host.  It works on the context of the consensus whose stream made the world table (`ctx`,
+// not owned) or, built from a device number, on a small context of its own.  Every argument named d_* is device memory the
+// caller owns (the layouts are include/akz.h's); export_device enqueues and returns.
+class ReconstructionExport {
+public:
+    enum Verdict : uint32_t { Ok = RS_EX_OK, Overflow = RS_EX_OVERFLOW, BadTable = RS_EX_BAD_TABLE };
+    explicit ReconstructionExport(rs_ctx* ctx) : ctx_(ctx) { akaze::require_abi(); }
+    explicit ReconstructionExport(int device = 0) : owned_(true)
+    {
+        akaze::require_abi();
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+    }
+    ~ReconstructionExport() { if (owned_ && ctx_) rs_destroy(ctx_); }
+    ReconstructionExport(const ReconstructionExport&) = delete;
+    ReconstructionExport& operator=(const ReconstructionExport&) = delete;
+    void export_device(const void* d_world, uint32_t n_world, const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks,
+                       const void* d_colors, const std::vector<uint32_t>& view_blocks, const void* d_counts, const void* d_landmarks,
+                       uint32_t cap_per_img, uint32_t n_blocks, const void* d_poses, uint32_t room, void* d_xyz, void* d_rgb, void* d_key,
+                       void* d_cameras, void* d_counts_out, void* d_verdict, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_export_reconstruction_device(ctx_, d_world, n_world, d_obs_start, d_obs, n_obs, n_landmarks, d_colors, view_blocks.data(),
+                                                     (uint32_t)view_blocks.size(), d_counts, d_landmarks, cap_per_img, n_blocks, d_poses, room,
+                                                     d_xyz, d_rgb, d_key, d_cameras, d_counts_out, d_verdict, stream_to_wait),
+                     "rs_export_reconstruction_device");
+    }
+    // host arrays xyz [n][3], rgb [n][3] whose first 5 * n_cameras rows are the cameras' vertices -> the file export.rs writes
+    static void write_ply(const std::string& path, const std::vector<double>& xyz, const std::vector<uint8_t>& rgb, uint32_t n_cameras,
+                          bool camera_faces)
+    {
+        if (xyz.size() != rgb.size() || xyz.size() % 3) throw std::invalid_argument("one colour per vertex");
+        akaze::check(rs_write_ply(path.c_str(), xyz.data(), rgb.data(), (uint32_t)(xyz.size() / 3), n_cameras, camera_faces ? 1 : 0),
+                     "rs_write_ply");
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_ctx* ctx_ = nullptr;
+    bool owned_ = false;
+};
 }  // namespace cv_sfm
 
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over

@@ -282,6 +282,14 @@ int32_t akz_half_size(akz_ctx* ctx, const float* img, int32_t w, int32_t h, floa
  * reference's default [0,0,0]. */
 int32_t akz_sample_colors_rgb8(akz_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h, int32_t stride,
                                const akz_keypoint* kps, uint32_t n, uint8_t* colors);
+/* The same lookup for a whole micro-batch, where the data already lies on the device: d_rgb [n] RGB8 images of h rows of
+ * `stride` bytes (an image is h * stride bytes), d_kps [n][cap_per_img] akz_keypoint and d_counts [n] u32 as
+ * akz_extract_batch_device leaves them.  d_colors [n][cap_per_img][3] u8: feature j < min(count, cap_per_img) of frame f gets
+ * interpolate_bicubic at its point; the rows at or behind the count are not written.  n within [1, 65535], stride >= 3 * w, else
+ * AKZ_E_INVALID (decided before the context is looked at).  One launch on akz_stream() — the stream the extraction's outputs
+ * complete on — after stream_to_wait (may be NULL); returns after enqueueing; allocates nothing. */
+int32_t akz_sample_colors_batch_device(akz_ctx* ctx, const void* d_rgb, int32_t n, int32_t w, int32_t h, int32_t stride, const void* d_kps,
+                                       const void* d_counts, uint32_t cap_per_img, void* d_colors, void* stream_to_wait);
 
 typedef struct hm_ctx hm_ctx;
 int32_t hm_create(int32_t device, uint32_t max_queries, uint32_t max_targets, hm_ctx** out);
@@ -1356,6 +1364,52 @@ int32_t rs_normalize_reconstruction_device(rs_ctx* ctx, const uint32_t* view_blo
                                            const void* d_landmarks, uint32_t cap_per_img, uint32_t n_blocks, const void* d_world,
                                            uint32_t n_world, void* d_poses, void* d_constraint_poses, uint32_t n_constraints, void* d_stats,
                                            void* d_verdict, void* stream_to_wait);
+/* ---- a reconstruction leaves the device: the coloured point cloud and the cameras' frusta of export_reconstruction ----
+ * VSlam::export_reconstruction (cv-sfm/src/lib.rs:2285-2340) with export.rs: everything but the text of the file.  The decisions
+ * and the arithmetic are include/akz_export_math.h (compiled for the device and, by the tests, for the host: equal byte for
+ * byte), whose head lists the departures from the reference. */
+enum {
+    RS_EX_OK = 0,
+    RS_EX_OVERFLOW = 1,        /* more points than `room`: the first `room` are written, nothing lands behind them */
+    RS_EX_BAD_TABLE = 2,       /* d_obs_start[0] != 0, or the starts do not ascend inside [0, n_obs]: no point is written */
+    /* d_counts_out words (u32): */
+    RS_EX_C_POINTS = 0,        /* points exported: the true number, even beyond `room` */
+    RS_EX_C_NO_POINT = 1,      /* rows skipped for w < 0 (the triangulation's "none") */
+    RS_EX_C_INFINITE = 2,      /* rows skipped for w == 0 (a NaN among them) */
+    RS_EX_C_BAD_ROWS = 3,      /* rows with w > 0 skipped for their list: empty, outside the table, a first entry outside the colours */
+    RS_EX_COUNTS = 4,
+    RS_EX_CAMERA_WORDS = 10,   /* a row of d_cameras: centre [3], up [3], forward [3], focal length */
+    RS_EX_CAMERA_VERTICES = 5  /* the vertices of a camera: the centre, then up-right, up-left, down-left, down-right */
+};
+/* d_world [n_world][4] f64 (rs_triangulate_landmarks_device's), the landmark table (d_obs_start [n_landmarks + 1], d_obs
+ * [n_obs][2] {block, feature}), d_colors [n_blocks][cap_per_img][3] u8 (akz_sample_colors_batch_device's), view_blocks [n_views] a
+ * host list of distinct blocks below n_blocks with n_views >= 1 (else AKZ_E_INVALID), d_counts [n_blocks] u32, d_landmarks
+ * [n_blocks][cap_per_img] u32 (a d_landmarks_out), d_poses [n_blocks][12] f64 WorldToCamera.
+ * Outputs, in the order export.rs adds the vertices: d_xyz [5 * n_views + room][3] f64 and d_rgb [5 * n_views + room][3] u8 —
+ * vertices [5 v, 5 v + 5) are camera v's (colour {255, 0, 255}), vertex 5 * n_views + k is point k; d_key [room] u32 the landmark
+ * of point k; d_cameras [n_views][RS_EX_CAMERA_WORDS] f64; d_counts_out [RS_EX_COUNTS] u32; d_verdict [1] u32 (RS_EX_*).
+ * Row l < n_world is a point iff w > 0: x / w, y / w, z / w, coloured by the first entry of its observation list; the points
+ * ascend with l.  A row with w > 0 whose list is empty or leaves [0, n_obs] (a row at or behind n_landmarks has none), or whose
+ * first entry names a block >= n_blocks or a feature >= cap_per_img, is skipped alone and counted.  Points at or behind `room`
+ * are counted and not written.  A camera's focal length is 0.01 times the mean distance of the view's features j < min(count,
+ * cap_per_img) whose landmark is below n_world and has a Euclidean point, summed in include/akz_sum_order.h's order for 256
+ * threads; a mean over nothing is 0.  On RS_EX_BAD_TABLE the counters are 0 and the cameras are still written.  Nothing is read
+ * out of bounds.  Refused from the arguments alone, before the context is looked at: a null pointer, cap_per_img, n_blocks or
+ * n_views of 0, a repeated or out-of-range block, an output that overlaps an input (AKZ_E_INVALID), sizes that overflow 32-bit
+ * arithmetic (AKZ_E_TOO_LARGE).  Five launches on rs_stream() after stream_to_wait (may be NULL); returns after enqueueing;
+ * allocates nothing beyond growing the context's scratch. */
+int32_t rs_export_reconstruction_device(rs_ctx* ctx, const void* d_world, uint32_t n_world, const void* d_obs_start, const void* d_obs,
+                                        uint32_t n_obs, uint32_t n_landmarks, const void* d_colors, const uint32_t* view_blocks,
+                                        uint32_t n_views, const void* d_counts, const void* d_landmarks, uint32_t cap_per_img,
+                                        uint32_t n_blocks, const void* d_poses, uint32_t room, void* d_xyz, void* d_rgb, void* d_key,
+                                        void* d_cameras, void* d_counts_out, void* d_verdict, void* stream_to_wait);
+/* The file export.rs writes, from host arrays (no GPU): an ASCII .ply with the comment "Exported from rust-cv/vslam-sandbox",
+ * `element vertex` (double x y z, uchar red green blue) and, with camera_faces != 0, `element face` (property list uchar int
+ * vertex_index).  xyz [n_vertices][3] f64 and rgb [n_vertices][3] u8 in the given order; the first 5 * n_cameras vertices are
+ * the cameras' (more than n_vertices: AKZ_E_INVALID), and camera v with b = 5 v gets the triangles (b, b + 4, b + 1), (b, b + 1,
+ * b + 2), (b, b + 2, b + 3), (b, b + 3, b + 4).  Numbers are written with %.17g: a reader gets the same f64 bits back.  A file
+ * that cannot be written: AKZ_E_INVALID. */
+int32_t rs_write_ply(const char* path, const double* xyz, const uint8_t* rgb, uint32_t n_vertices, uint32_t n_cameras, int32_t camera_faces);
 int32_t rs_sync(rs_ctx* ctx);
 void* rs_stream(rs_ctx* ctx);
 /* parity tap: match count, calibrated bearings [n][3] (a, b) and scoring order [n] of scene `scene` of the last batched

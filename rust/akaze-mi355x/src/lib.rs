@@ -195,6 +195,15 @@ extern "C" {
                                           d_landmarks: *const c_void, cap_per_img: u32, n_blocks: u32, d_world: *const c_void, n_world: u32,
                                           d_poses: *mut c_void, d_constraint_poses: *mut c_void, n_constraints: u32, d_stats: *mut c_void,
                                           d_verdict: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_export_reconstruction_device(ctx: *mut c_void, d_world: *const c_void, n_world: u32, d_obs_start: *const c_void, d_obs: *const c_void,
+                                       n_obs: u32, n_landmarks: u32, d_colors: *const c_void, view_blocks: *const u32, n_views: u32,
+                                       d_counts: *const c_void, d_landmarks: *const c_void, cap_per_img: u32, n_blocks: u32,
+                                       d_poses: *const c_void, room: u32, d_xyz: *mut c_void, d_rgb: *mut c_void, d_key: *mut c_void,
+                                       d_cameras: *mut c_void, d_counts_out: *mut c_void, d_verdict: *mut c_void,
+                                       stream_to_wait: *mut c_void) -> i32;
+    fn rs_write_ply(path: *const std::os::raw::c_char, xyz: *const f64, rgb: *const u8, n_vertices: u32, n_cameras: u32, camera_faces: i32) -> i32;
+    fn akz_sample_colors_batch_device(ctx: *mut c_void, d_rgb: *const c_void, n: i32, w: i32, h: i32, stride: i32, d_kps: *const c_void,
+                                      d_counts: *const c_void, cap_per_img: u32, d_colors: *mut c_void, stream_to_wait: *mut c_void) -> i32;
     fn hm_landmark_original_matches_batch_device(ctx: *mut c_void, d_best: *const c_void, d_decision: *const c_void, d_merge_ok: *const c_void,
                                                  d_obs_counts: *const c_void, d_nq: *const c_void, iq: *const u32, cap_per_img: u32,
                                                  n_frames: u32, n_world: u32, d_pairs: *mut c_void, d_npairs: *mut c_void,
@@ -1643,6 +1652,60 @@ impl ReconstructionMerge {
         let st = rs_normalize_reconstruction_device(self.ctx, view_blocks.as_ptr(), view_blocks.len() as u32, d_counts, d_landmarks,
                                                     cap_per_img, n_blocks, d_world, n_world, d_poses, d_constraint_poses, n_constraints,
                                                     d_stats, d_verdict, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+}
+
+/// The verdict on `ReconstructionExport::export_device` (`d_verdict`).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ExportVerdict {
+    Ok = 0,
+    Overflow = 1,
+    BadTable = 2,
+}
+
+/// The words of `d_counts_out` of `ReconstructionExport::export_device`, the words of a camera row and a camera's vertices.
+pub const RS_EX_C_POINTS: usize = 0;
+pub const RS_EX_C_NO_POINT: usize = 1;
+pub const RS_EX_C_INFINITE: usize = 2;
+pub const RS_EX_C_BAD_ROWS: usize = 3;
+pub const RS_EX_COUNTS: usize = 4;
+pub const RS_EX_CAMERA_WORDS: usize = 10;
+pub const RS_EX_CAMERA_VERTICES: usize = 5;
+
+/// `VSlam::export_reconstruction` (cv-sfm/src/lib.rs:2285-2340) with export.rs: the coloured point cloud and the cameras'
+/// frusta as the vertex arrays of the .ply file (`rs_export_reconstruction_device`), on the context of the consensus whose
+/// stream made the world table (not owned), and the file's text (`rs_write_ply`, host code).  Every `d_*` argument is device
+/// memory the caller owns, laid out as include/akz.h documents; `export_device` enqueues and returns.
+/// Like the other declarations of this file these are source only: they are not compiled here (no toolchain).
+pub struct ReconstructionExport {
+    ctx: *mut c_void,
+}
+impl ReconstructionExport {
+    /// # Safety
+    /// `ctx` is a live `rs_ctx` that outlives this object.
+    pub unsafe fn new(ctx: *mut c_void) -> Self {
+        require_abi();
+        Self { ctx }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn export_device(&self, d_world: *const c_void, n_world: u32, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32,
+                                n_landmarks: u32, d_colors: *const c_void, view_blocks: &[u32], d_counts: *const c_void,
+                                d_landmarks: *const c_void, cap_per_img: u32, n_blocks: u32, d_poses: *const c_void, room: u32,
+                                d_xyz: *mut c_void, d_rgb: *mut c_void, d_key: *mut c_void, d_cameras: *mut c_void,
+                                d_counts_out: *mut c_void, d_verdict: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = rs_export_reconstruction_device(self.ctx, d_world, n_world, d_obs_start, d_obs, n_obs, n_landmarks, d_colors,
+                                                 view_blocks.as_ptr(), view_blocks.len() as u32, d_counts, d_landmarks, cap_per_img, n_blocks,
+                                                 d_poses, room, d_xyz, d_rgb, d_key, d_cameras, d_counts_out, d_verdict, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// Host arrays `xyz` [n][3] and `rgb` [n][3] whose first `5 * n_cameras` rows are the cameras' vertices -> the file.
+    pub fn write_ply(path: &std::ffi::CStr, xyz: &[f64], rgb: &[u8], n_cameras: u32, camera_faces: bool) -> Result<(), i32> {
+        if xyz.len() != rgb.len() || xyz.len() % 3 != 0 { return Err(-1); }
+        let st = unsafe { rs_write_ply(path.as_ptr(), xyz.as_ptr(), rgb.as_ptr(), (xyz.len() / 3) as u32, n_cameras, camera_faces as i32) };
         if st == 0 { Ok(()) } else { Err(st) }
     }
 }
