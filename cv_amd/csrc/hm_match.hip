@@ -22,6 +22,7 @@
 
 #include "akz_common.h"
 #include "hm_plan.h"
+#include "hm_rule.h"
 
 namespace {
 
@@ -803,6 +804,10 @@ struct HmPairProb {
     uint32_t* pairs;          // [cap][2]
     uint32_t cap;
     uint32_t* n_out;
+    // the reverse side answered from the forward lists (k_decide, k_verify): one keep flag per a, read when *rev_nq == 0;
+    // both null: `rev` holds the reverse search
+    const uint32_t* keep;
+    const uint32_t* rev_nq;
 };
 
 __device__ __forceinline__ bool accept(int rule, uint32_t d0, uint32_t d1, uint32_t pu, float pf)
@@ -822,6 +827,7 @@ __global__ __launch_bounds__(1024) void k_pairs(const HmPairProb* __restrict__ p
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t base = 0;
     if (na < 2 || nb < 2) na = 0;  // cv-sfm/src/lib.rs:3099-3101 (the other call sites would panic)
+    const bool lists = P.rev_nq && *P.rev_nq == 0u;   // this problem's reverse search was skipped: k_decide
     for (uint32_t a0 = 0; a0 < na; a0 += 1024) {
         uint32_t a = a0 + threadIdx.x;
         bool keep = false;
@@ -831,7 +837,8 @@ __global__ __launch_bounds__(1024) void k_pairs(const HmPairProb* __restrict__ p
             if (accept(rule, n0.distance, n1.distance, pu, pf)) {
                 bidx = n0.index;
                 keep = true;
-                if (symmetric) {
+                if (symmetric && lists) keep = P.keep[a] != 0u;
+                else if (symmetric) {
                     akz_neighbor r0 = P.rev[(size_t)bidx * 2], r1 = P.rev[(size_t)bidx * 2 + 1];
                     keep = accept(rule, r0.distance, r1.distance, pu, pf) && r0.index == a;
                 }
@@ -858,6 +865,209 @@ __global__ __launch_bounds__(1024) void k_pairs(const HmPairProb* __restrict__ p
     if (threadIdx.x == 0) *P.n_out = base;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The reverse side of a symmetric match from the forward lists (hm_rule.h states the question: does any other query a'
+// lie within tau of the pair's target b?).  If b is not among the two nearest of a', then d(a', b) >= d1(a'), the
+// second-best distance of a': every a' with d1(a') > tau is cleared unseen.  What remains is
+//   (1) the a' with d1(a') <= tau: their distance to b is computed (k_verify walks them in ascending d1), and
+//   (2) the a' whose BEST is b with d0(a') <= tau, whatever their d1: the two smallest (d0, a') keys per b, scattered here.
+// k_decide also counts the distances (1) asks for; a problem whose count is above `share` of na * nb (clustered
+// descriptors: small second-best distances everywhere) keeps the reverse search: its word rev_nq — the query count of the
+// problem's reverse k-NN blocks — is nb instead of 0, and nothing is read back to the host.
+struct HmRevProb {
+    const uint4* a;            // the descriptors of both sides
+    const uint4* b;
+    const akz_neighbor* fwd;   // [na][2]
+    const uint32_t* na;
+    const uint32_t* nb;
+    uint32_t a_cap, b_cap;
+    uint32_t* hdr;             // [kRevHdr]: rev_nq, the number of accepted a, then cum[513]: cum[t] = #{a : d1(a) <= t}
+    uint32_t* order;           // [a_cap] every a, ascending d1
+    uint32_t* acc;             // [a_cap] the forward-accepted a, DESCENDING tau (the longest walks start first)
+    uint32_t* keep;            // [a_cap] the pair of a survives
+    uint32_t* best;            // [2][b_cap] smallest and second-smallest key d0 << 22 | a' among the a' whose best is b
+    uint32_t* units;           // [u_cap] k_verify's work list: block of 64 accepted pairs | segment of its candidates << 16
+    uint32_t u_cap;            // at least twice the number of 64-pair blocks
+};
+constexpr uint32_t kRevBins = kHmMaxDistance + 1u;   // distances 0..512
+constexpr uint32_t kRevHdr = 576;                    // 2 + kRevBins words, the two below, rounded up
+constexpr uint32_t kRevHdrUnits = 2 + kRevBins, kRevHdrSeg = 3 + kRevBins;   // entries of the work list, candidates per segment
+enum { kRevAuto = 0, kRevSearch = 1, kRevLists = 2 };
+
+// inclusive scan of s[0..kRevBins) by the whole block (1024 threads)
+__device__ __forceinline__ void rev_scan(uint32_t* s)
+{
+    for (uint32_t off = 1; off < kRevBins; off <<= 1) {
+        const uint32_t v = (threadIdx.x >= off && threadIdx.x < kRevBins) ? s[threadIdx.x - off] : 0u;
+        __syncthreads();
+        if (threadIdx.x < kRevBins) s[threadIdx.x] += v;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_decide(const HmRevProb* __restrict__ probs, int rule, uint32_t pu, float pf, int mode,
+                                                 float share)
+{
+    __shared__ uint32_t s_cum[kRevBins];     // histogram of d1, then cum
+    __shared__ uint32_t s_tau[kRevBins];     // histogram of tau over the accepted a, then its inclusive scan
+    __shared__ uint32_t s_pos1[kRevBins], s_post[kRevBins];   // running positions of the two counting sorts
+    __shared__ unsigned long long s_evals, s_walk;
+    __shared__ uint32_t s_fallback, s_units;
+    const HmRevProb P = probs[blockIdx.x];
+    uint32_t na = min(*P.na, P.a_cap);
+    const uint32_t nb = min(*P.nb, P.b_cap);
+    if (na < 2 || nb < 2) na = 0;            // k_pairs' rule: no pairs, and nothing to search for
+    for (uint32_t i = threadIdx.x; i < kRevBins; i += 1024) s_cum[i] = s_tau[i] = 0u;
+    if (threadIdx.x == 0) {
+        s_evals = s_walk = 0ull;
+        s_units = 0u;
+    }
+    // (everything this kernel communicates stays inside its block — one compute unit, one L2 — so the block barrier's
+    // workgroup-scope release, which waits for the stores and atomics issued before it, orders it; the values the atomics
+    // left in L2 are read back by atomic loads.  A device-scope fence here writes the whole L2 back: measured 0.3 ms a call.)
+    for (uint32_t b = threadIdx.x; b < nb; b += 1024) P.best[b] = P.best[(size_t)P.b_cap + b] = 0xFFFFFFFFu;
+    __syncthreads();
+    for (uint32_t a = threadIdx.x; a < na; a += 1024) {
+        const akz_neighbor n0 = P.fwd[(size_t)a * 2], n1 = P.fwd[(size_t)a * 2 + 1];
+        atomicAdd(&s_cum[min(n1.distance, kHmMaxDistance)], 1u);
+        if (accept(rule, n0.distance, n1.distance, pu, pf)) atomicAdd(&s_tau[hm_rival_bound(rule, pu, n0.distance)], 1u);
+        atomicMin(&P.best[n0.index], (n0.distance << kIdxBits) | a);
+    }
+    __syncthreads();
+    const uint32_t h1 = threadIdx.x < kRevBins ? s_cum[threadIdx.x] : 0u;
+    const uint32_t ht = threadIdx.x < kRevBins ? s_tau[threadIdx.x] : 0u;
+    rev_scan(s_cum);
+    if (ht) atomicAdd(&s_evals, (unsigned long long)ht * s_cum[threadIdx.x]);
+    rev_scan(s_tau);
+    const uint32_t n_acc = s_tau[kRevBins - 1];
+    if (threadIdx.x < kRevBins) {
+        P.hdr[2 + threadIdx.x] = s_cum[threadIdx.x];
+        s_pos1[threadIdx.x] = s_cum[threadIdx.x] - h1;              // ascending d1
+        s_post[threadIdx.x] = n_acc - s_tau[threadIdx.x];           // descending tau
+    }
+    if (threadIdx.x == 0) {
+        const bool fb = mode != kRevLists && (double)s_evals > (double)share * (double)na * (double)nb;
+        s_fallback = fb ? 1u : 0u;
+        P.hdr[0] = fb ? nb : 0u;
+        P.hdr[1] = fb ? 0u : n_acc;
+        P.hdr[kRevHdrUnits] = 0u;
+    }
+    __syncthreads();
+    if (s_fallback) return;
+    for (uint32_t a = threadIdx.x; a < na; a += 1024) {
+        const akz_neighbor n0 = P.fwd[(size_t)a * 2], n1 = P.fwd[(size_t)a * 2 + 1];
+        P.order[atomicAdd(&s_pos1[min(n1.distance, kHmMaxDistance)], 1u)] = a;
+        const uint32_t key = (n0.distance << kIdxBits) | a;
+        if (__hip_atomic_load(&P.best[n0.index], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != key)
+            atomicMin(&P.best[(size_t)P.b_cap + n0.index], key);
+    }
+    __syncthreads();
+    for (uint32_t a = threadIdx.x; a < na; a += 1024) {
+        const akz_neighbor n0 = P.fwd[(size_t)a * 2], n1 = P.fwd[(size_t)a * 2 + 1];
+        uint32_t keep = 0u;
+        if (accept(rule, n0.distance, n1.distance, pu, pf)) {
+            const uint32_t tau = (uint32_t)hm_rival_bound(rule, pu, n0.distance);
+            P.acc[atomicAdd(&s_post[tau], 1u)] = a;
+            // (2): the nearest other query whose best is this pair's target
+            const uint32_t m0 = __hip_atomic_load(&P.best[n0.index], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t m1 = __hip_atomic_load(&P.best[(size_t)P.b_cap + n0.index], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t rival = m0 == ((n0.distance << kIdxBits) | a) ? m1 : m0;     // (none: all ones, distance 1023)
+            keep = (rival >> kIdxBits) > tau ? 1u : 0u;
+        }
+        P.keep[a] = keep;
+    }
+    // k_verify's work list.  The accepted pairs go 64 to a block in descending tau, and block x walks the candidates
+    // [0, cum[its largest tau]): a few blocks at the head carry most of the walk (measured on benchmark frames: 4 954, 3 102,
+    // 2 131, ... of 18 541 candidate steps in 70 blocks), so each block's walk is cut into segments of `seg` candidates and
+    // every (block, segment) is one workgroup of k_verify.  seg is the smallest multiple of 256 at which the list fits u_cap.
+    const uint32_t nblk = (n_acc + 63u) / 64u;
+    auto walk_of = [&](uint32_t x) {           // cum[tau of the pair ranked 64 x]: the largest t with #{tau >= t} > 64 x
+        uint32_t lo = 0, hi = kHmMaxDistance;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1u) / 2u;
+            if (n_acc - s_tau[mid - 1u] > 64u * x) lo = mid;
+            else hi = mid - 1u;
+        }
+        return s_cum[lo];
+    };
+    for (uint32_t x = threadIdx.x; x < nblk; x += 1024) atomicAdd(&s_walk, (unsigned long long)walk_of(x));
+    __syncthreads();
+    const unsigned long long room = 256ull * (P.u_cap - nblk);          // (u_cap >= 2 nblk)
+    const uint32_t seg = 256u * (uint32_t)max(1ull, (s_walk + room - 1ull) / max(room, 1ull));
+    for (uint32_t x = threadIdx.x; x < nblk; x += 1024) {
+        const uint32_t nu = (walk_of(x) + seg - 1u) / seg;
+        const uint32_t at = atomicAdd(&s_units, nu);
+        for (uint32_t i = 0; i < nu; ++i) P.units[at + i] = x | (i << 16);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        P.hdr[kRevHdrUnits] = s_units;
+        P.hdr[kRevHdrSeg] = seg;
+    }
+}
+
+// (1): one entry of the problem's work list per block: 64 accepted pairs, lane <-> pair with its target's 16 words in
+// registers, and one segment of their walk over the candidates order[0 .. cum[largest tau of the 64]), which the block's four
+// waves share in chunks of 64: lane l fetches candidate l of the chunk
+// (one coalesced index load, one 64-byte row per lane), then the wave steps through the chunk with the candidate's words
+// broadcast from their lane by v_readlane_b32: per distance 16 x (v_readlane_b32, v_xor_b32 with the SGPR, v_bcnt_u32_b32
+// accumulating), no LDS, no barrier, and memory latency met once per 64 candidates.  (The candidate fetched by scalar loads
+// instead — the 32-instruction form — measured 2.8 ms per 256 frame pairs against 0.2 ms of arithmetic: the scalar cache
+// does not keep enough misses in flight for rows scattered over 300 KB per problem.)
+// A lane whose own bound is below the wave's only meets candidates that cannot be within it, or are and then are rivals all
+// the same: no mask but a' != a is needed.  Clearing a flag is idempotent, so the waves need not agree on who does it.
+__global__ __launch_bounds__(256) void k_verify(const HmRevProb* __restrict__ probs, int rule, uint32_t pu)
+{
+    const HmRevProb P = probs[blockIdx.y];
+    if (blockIdx.x >= P.hdr[kRevHdrUnits]) return;                   // (a fallback problem has no work list)
+    const uint32_t unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.units[blockIdx.x]);
+    const uint32_t seg = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.hdr[kRevHdrSeg]);
+    const uint32_t n_acc = P.hdr[1];
+    const uint32_t base = (unit & 0xFFFFu) * 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t a = P.acc[min(base + lane, n_acc - 1u)];          // (lanes past the end repeat the last pair)
+    const akz_neighbor n0 = P.fwd[(size_t)a * 2];
+    const uint32_t tau = (uint32_t)hm_rival_bound(rule, pu, n0.distance);
+    uint32_t tmax = tau;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) tmax = max(tmax, (uint32_t)__shfl_xor((int)tmax, s));
+    tmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)tmax);
+    const uint32_t limit = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.hdr[2 + tmax]);
+    uint32_t bd[16];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const uint4 x = P.b[(size_t)n0.index * 4 + v];
+        bd[4 * v + 0] = x.x;
+        bd[4 * v + 1] = x.y;
+        bd[4 * v + 2] = x.z;
+        bd[4 * v + 3] = x.w;
+    }
+    uint32_t rival = 0u;                       // (a lane value, not a condition: one v_cndmask_b32 / v_or_b32 per candidate)
+    const uint32_t begin = (unit >> 16) * seg, end = min(limit, begin + seg);
+    for (uint32_t c0 = begin + wv * 64u; c0 < end; c0 += 256u) {
+        const uint32_t n = min(64u, end - c0);
+        const uint32_t mine = P.order[min(c0 + lane, end - 1u)];     // (lanes past the end: the last one again, never stepped to)
+        uint32_t cd[16];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const uint4 x = P.a[(size_t)mine * 4 + v];
+            cd[4 * v + 0] = x.x;
+            cd[4 * v + 1] = x.y;
+            cd[4 * v + 2] = x.z;
+            cd[4 * v + 3] = x.w;
+        }
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t cand = (uint32_t)__builtin_amdgcn_readlane((int)mine, (int)j);
+            uint32_t dist = 0;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) dist += __popc(bd[v] ^ (uint32_t)__builtin_amdgcn_readlane((int)cd[v], (int)j));
+            rival |= (dist <= tau ? 1u : 0u) & (cand != a ? 1u : 0u);
+        }
+    }
+    if (rival) P.keep[a] = 0u;
+}
+
 }  // namespace
 
 // The per-launch event pool behind hm_timing_enable / hm_timing_get (bench.py's MFMA roofline): optional timing of the k-NN
@@ -870,7 +1080,9 @@ struct HmKnnTimer {
     uint64_t launches = 0;
     // the start / stop events of the next k-NN launch, which is counted; two nulls (an untimed launch) when timing is off or
     // no event is to be had
-    std::pair<hipEvent_t, hipEvent_t> take()
+    // (counted = false: a further kernel of a launch that is already counted — the decision and verification kernels and the
+    // skippable reverse search of a symmetric match: their time is added, the launch count stays one per call)
+    std::pair<hipEvent_t, hipEvent_t> take(bool counted = true)
     {
         hipEvent_t e[2] = {nullptr, nullptr};
         if (!on) return {nullptr, nullptr};
@@ -884,7 +1096,7 @@ struct HmKnnTimer {
             return {nullptr, nullptr};
         }
         pending.emplace_back(e[0], e[1]);
-        launches += 1;
+        launches += counted ? 1 : 0;
         return pending.back();
     }
     // waits for the pending launches, adds their durations to `ms` and hands their events back to the pool
@@ -938,6 +1150,10 @@ struct hm_ctx {
     bool use_mfma = true;
     bool use_fp4 = true;           // E2M1 recoding + v_mfma_scale_f32_32x32x64_f8f6f4 (AKZ_MATCH_FP4=0: int8 MFMA)
     bool use_glds = true;          // the wide FP4 kernel, tiles by LDS-DMA (HM_OPT_NO_LDS_DMA: k_knn_mfma4, register-staged)
+    int rev_mode = kRevAuto;       // the reverse side of a symmetric match: HM_OPT_REVERSE_SEARCH / HM_OPT_REVERSE_LISTS
+    float rev_share = 0.25f;       // kRevAuto: a problem asking for more than this share of na * nb distances keeps the search
+    void* d_rev_scratch = nullptr; // k_decide / k_verify: per problem kRevHdr + 5 * cap + cap / 32 words
+    size_t rev_scratch_bytes = 0;
     HmKnnTimer timer;
     // scratch knn results: hm_knn / hm_knn_targets / hm_knn2 (forward) and the batched device calls (both directions)
     void* d_bfwd = nullptr;
@@ -995,7 +1211,9 @@ extern "C" int32_t hm_create_ex(int32_t device, uint32_t max_queries, uint32_t m
     return akz_guard([&]() -> int32_t {
         // the MFMA kernel carries (2 * hamming) << 21 | row: rows need 21 bits
         if (!out || max_queries == 0 || max_targets == 0 || max_targets >= (1u << (kIdxBits - 1))) return AKZ_E_INVALID;
-        if (flags & ~(HM_OPT_NO_FP4 | HM_OPT_NO_MFMA | HM_OPT_STREAM_PRIORITY | HM_OPT_NO_LDS_DMA | HM_OPT_CU_MASK)) return AKZ_E_INVALID;   // unknown switches
+        if (flags & ~(HM_OPT_NO_FP4 | HM_OPT_NO_MFMA | HM_OPT_STREAM_PRIORITY | HM_OPT_NO_LDS_DMA | HM_OPT_CU_MASK | HM_OPT_REVERSE_SEARCH |
+                      HM_OPT_REVERSE_LISTS | HM_OPT_REVERSE_SHARE_MASK)) return AKZ_E_INVALID;   // unknown switches
+        if ((flags & HM_OPT_REVERSE_SEARCH) && (flags & HM_OPT_REVERSE_LISTS)) return AKZ_E_INVALID;
         const int cus = (int)((flags & HM_OPT_CU_MASK) >> HM_OPT_CU_SHIFT);
         if (cus > 32) return AKZ_E_INVALID;            // (before anything is allocated)
         int ndev = 0;
@@ -1016,6 +1234,8 @@ extern "C" int32_t hm_create_ex(int32_t device, uint32_t max_queries, uint32_t m
         c->use_mfma = !(flags & HM_OPT_NO_MFMA);
         c->use_fp4 = !(flags & HM_OPT_NO_FP4);
         c->use_glds = !(flags & HM_OPT_NO_LDS_DMA);
+        c->rev_mode = (flags & HM_OPT_REVERSE_SEARCH) ? kRevSearch : (flags & HM_OPT_REVERSE_LISTS) ? kRevLists : kRevAuto;
+        if (const uint32_t sh = (flags & HM_OPT_REVERSE_SHARE_MASK) >> HM_OPT_REVERSE_SHARE_SHIFT) c->rev_share = 1.0f / (float)(1u << sh);
         AKZ_HIP(hipMalloc(&c->d_a, (size_t)m * 64));
         AKZ_HIP(hipMalloc(&c->d_b, (size_t)m * 64));
         AKZ_HIP(hipMalloc(&c->d_na, sizeof(uint32_t) * 4));
@@ -1056,6 +1276,7 @@ extern "C" int32_t hm_destroy(hm_ctx* c)
         hipFree(c->d_exp);
         hipFree(c->d_bfwd);
         hipFree(c->d_brev);
+        hipFree(c->d_rev_scratch);
         hipFree(c->d_lsh);
         if (c->ev) hipEventDestroy(c->ev);
         if (c->stream) hipStreamDestroy(c->stream);
@@ -1096,11 +1317,11 @@ static const HmKnnKernel kKnnKernels[3][3] = {
 };
 static int knn_family(const hm_ctx* c) { return !c->use_fp4 ? 2 : c->use_glds ? 0 : 1; }
 
-static int32_t launch_knn_valu(hm_ctx* c, const HmProb* h_probs, uint32_t n_probs, uint32_t max_nq)
+// (the problems [first, first + n) of the n_all staged ones)
+static int32_t launch_knn_valu(hm_ctx* c, uint32_t first, uint32_t n, uint32_t max_nq)
 {
-    AKZ_TRY(hm_stage_push(c, 0, h_probs, sizeof(HmProb) * n_probs));
-    dim3 grid((max_nq + kQPB - 1) / kQPB, n_probs);
-    hipLaunchKernelGGL(k_knn2, grid, dim3(kBlock), 0, c->stream, hm_staged<HmProb>(c, 0));
+    dim3 grid((max_nq + kQPB - 1) / kQPB, n);
+    hipLaunchKernelGGL(k_knn2, grid, dim3(kBlock), 0, c->stream, hm_staged<HmProb>(c, 0) + first);
     AKZ_LAUNCH_CHECK();
     return AKZ_OK;
 }
@@ -1130,30 +1351,47 @@ static int32_t launch_expand(hm_ctx* c, uint32_t n_probs, const HmPlan& plan)
     return AKZ_OK;
 }
 
-static int32_t launch_knn_mfma(hm_ctx* c, uint32_t n_probs, uint32_t max_nq, int k)
+static int32_t launch_knn_mfma(hm_ctx* c, uint32_t first, uint32_t n_probs, uint32_t max_nq, int k, bool counted = true)
 {
     // timing: the launch carries its own start / stop events (hipExtLaunchKernel: the dispatch's begin and end timestamps,
     // i.e. the duration rocprofv3's kernel trace reports) — an event bracket on the stream would also count the time the
     // launch waits for the other streams' kernels
-    const std::pair<hipEvent_t, hipEvent_t> ev = c->timer.take();
+    const std::pair<hipEvent_t, hipEvent_t> ev = c->timer.take(counted);
     const HmKnnKernel& kn = kKnnKernels[knn_family(c)][k - 1];
     hipExtLaunchKernelGGL(kn.fn, dim3((max_nq + 255) / 256, n_probs), dim3(kn.block), 0, c->stream, ev.first, ev.second, 0,
-                          hm_staged<HmProbX>(c, 0));
+                          hm_staged<HmProbX>(c, 0) + first);
     AKZ_LAUNCH_CHECK();
     return AKZ_OK;
 }
 
-// k neighbours (1, 2 or 3) of every query of every problem, in the staging slot the caller took (knn_stage_bytes(n_probs))
-static int32_t launch_knn(hm_ctx* c, const HmProb* h_probs, uint32_t n_probs, uint32_t max_nq, int k)
+// k neighbours (1, 2 or 3) of every query of every problem, in the staging slot the caller took (knn_stage_bytes(n_probs)).
+// A symmetric match that may skip its reverse side stages all n_probs problems (every block they name is recoded once) but
+// searches only the first n_now of them here; knn_rest searches the others.  run_nq (null, or one entry per problem, null
+// entries allowed): the count the KERNEL reads for the problem's queries instead of its own — the recoding keeps the own one.
+static int32_t launch_knn(hm_ctx* c, const HmProb* h_probs, uint32_t n_probs, uint32_t max_nq, int k, uint32_t n_now = ~0u,
+                          const uint32_t* const* run_nq = nullptr)
 {
     if (n_probs == 0) return AKZ_OK;
-    if (!c->use_mfma && k == 2) return launch_knn_valu(c, h_probs, n_probs, max_nq);   // the VALU kernel exists for k = 2 only
+    n_now = std::min(n_now, n_probs);
+    std::vector<HmProb> run(h_probs, h_probs + n_probs);
+    for (uint32_t i = 0; run_nq && i < n_probs; ++i)
+        if (run_nq[i]) run[i].nq = run_nq[i];
+    if (!c->use_mfma && k == 2) {                                                       // the VALU kernel exists for k = 2 only
+        AKZ_TRY(hm_stage_push(c, 0, run.data(), sizeof(HmProb) * n_probs));
+        return launch_knn_valu(c, 0, n_now, max_nq);
+    }
     // unique descriptor blocks referenced by the problems -> one +-1 recoding each
     const HmPlan plan = hm_plan_recoding(h_probs, n_probs, c->use_fp4 ? 64 : 128);
     AKZ_TRY(akz_grow_scratch(c->stream, &c->d_exp, &c->exp_bytes, sizeof(uint32_t) * plan.words));
-    AKZ_TRY(push_recoded(c, h_probs, n_probs, plan));
+    AKZ_TRY(push_recoded(c, run.data(), n_probs, plan));
     AKZ_TRY(launch_expand(c, n_probs, plan));
-    return launch_knn_mfma(c, n_probs, max_nq, k);
+    return launch_knn_mfma(c, 0, n_now, max_nq, k);
+}
+// the 2-NN search of the staged problems [first, first + n) that launch_knn left out
+static int32_t knn_rest(hm_ctx* c, uint32_t first, uint32_t n, uint32_t max_nq)
+{
+    if (!c->use_mfma) return launch_knn_valu(c, first, n, max_nq);
+    return launch_knn_mfma(c, first, n, max_nq, 2, false);
 }
 
 // ---- the host-buffer calls --------------------------------------------------------------------------------------------
@@ -1656,6 +1894,59 @@ extern "C" int32_t hm_timing_get(hm_ctx* c, double* ms, uint64_t* launches, int3
     });
 }
 
+// ---- matching / symmetric_matching of n_pairs problems ------------------------------------------------------------------
+// hp: the forward problems, then (symmetric) the reverse ones in the same order; hpp: their k_pairs problems; max_n: the
+// largest capacity of any side.  Takes the call's staging slot: [k-NN stage][HmPairProb x n_pairs][HmRevProb x n_pairs].
+//
+// Symmetric under a rule with a rival bound (hm_rule.h), unless the context asks for the search: the forward search alone,
+// k_decide, then the reverse search of the SAME staged problems with their query counts read from k_decide's rev_nq words —
+// every block of a problem that takes the shortcut leaves at the kernels' `qblk >= nq` test — then k_verify, then k_pairs.
+static_assert(HM_RULE_BETTER_BY_STRICT == kHmRuleStrict && HM_RULE_BETTER_BY == kHmRuleBetterBy, "hm_rule.h names the rules of akz.h");
+static int32_t match_enqueue(hm_ctx* c, const std::vector<HmProb>& hp, std::vector<HmPairProb>& hpp, uint32_t n_pairs, uint32_t max_n,
+                             int32_t rule, uint32_t pu, float pf, int32_t symmetric)
+{
+    const uint32_t n_probs = (uint32_t)hp.size();
+    const size_t pair_off = akz_align_up(knn_stage_bytes(n_probs), 256);
+    const size_t rev_off = akz_align_up(pair_off + sizeof(HmPairProb) * n_pairs, 256);
+    const bool by_lists = symmetric && c->rev_mode != kRevSearch && hm_rival_bound_applies(rule, pu);
+    AKZ_TRY(hm_stage_take(c, rev_off + (by_lists ? sizeof(HmRevProb) * n_pairs : 0) + 256));
+    if (!by_lists) {
+        AKZ_TRY(launch_knn(c, hp.data(), n_probs, max_n, 2));
+    } else {
+        const uint32_t u_cap = 2u * ((max_n + 63u) / 64u);
+        const size_t per = kRevHdr + 5 * (size_t)max_n + u_cap;   // words per problem: hdr, order, acc, keep, best[2], units
+        AKZ_TRY(akz_grow_scratch(c->stream, &c->d_rev_scratch, &c->rev_scratch_bytes, sizeof(uint32_t) * per * n_pairs));
+        std::vector<HmRevProb> hr(n_pairs);
+        std::vector<const uint32_t*> run_nq(n_probs, nullptr);
+        for (uint32_t p = 0; p < n_pairs; ++p) {
+            uint32_t* w = static_cast<uint32_t*>(c->d_rev_scratch) + per * p;
+            const HmProb& f = hp[p];
+            hr[p] = HmRevProb{f.q, f.t, f.out, f.nq, f.nt, f.q_cap, f.t_cap, w, w + kRevHdr, w + kRevHdr + max_n,
+                              w + kRevHdr + 2 * (size_t)max_n, w + kRevHdr + 3 * (size_t)max_n, w + kRevHdr + 5 * (size_t)max_n, u_cap};
+            hpp[p].keep = hr[p].keep;
+            hpp[p].rev_nq = w;
+            run_nq[n_pairs + p] = w;
+        }
+        AKZ_TRY(launch_knn(c, hp.data(), n_probs, max_n, 2, n_pairs, run_nq.data()));
+        AKZ_TRY(hm_stage_push(c, rev_off, hr.data(), sizeof(HmRevProb) * n_pairs));
+        // (the VALU switch times nothing of a match: launch_knn's k = 2 branch takes no events either)
+        std::pair<hipEvent_t, hipEvent_t> ev = c->use_mfma ? c->timer.take(false) : std::pair<hipEvent_t, hipEvent_t>{nullptr, nullptr};
+        hipExtLaunchKernelGGL(k_decide, dim3(n_pairs), dim3(1024), 0, c->stream, ev.first, ev.second, 0, hm_staged<HmRevProb>(c, rev_off),
+                              (int)rule, pu, pf, c->rev_mode, c->rev_share);
+        AKZ_LAUNCH_CHECK();
+        if (c->rev_mode != kRevLists) AKZ_TRY(knn_rest(c, n_pairs, n_pairs, max_n));
+        ev = c->use_mfma ? c->timer.take(false) : std::pair<hipEvent_t, hipEvent_t>{nullptr, nullptr};
+        hipExtLaunchKernelGGL(k_verify, dim3(u_cap, n_pairs), dim3(256), 0, c->stream, ev.first, ev.second, 0,
+                              hm_staged<HmRevProb>(c, rev_off), (int)rule, pu);
+        AKZ_LAUNCH_CHECK();
+    }
+    AKZ_TRY(hm_stage_push(c, pair_off, hpp.data(), sizeof(HmPairProb) * n_pairs));
+    hipLaunchKernelGGL(k_pairs, dim3(n_pairs), dim3(1024), 0, c->stream, hm_staged<HmPairProb>(c, pair_off), (int)rule, pu, pf,
+                       (int)symmetric);
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
+}
+
 extern "C" int32_t hm_match(hm_ctx* c, const akz_descriptor* a, uint32_t na, const akz_descriptor* b, uint32_t nb,
                             int32_t rule, uint32_t param_u, float param_f, int32_t symmetric, uint32_t* pairs,
                             uint32_t cap, uint32_t* n_out)
@@ -1671,18 +1962,12 @@ extern "C" int32_t hm_match(hm_ctx* c, const akz_descriptor* a, uint32_t na, con
             return rule == HM_RULE_BETTER_BY ? AKZ_OK : AKZ_E_INVALID;
         }
         AKZ_HIP(hipSetDevice(c->device));
-        const size_t pair_off = akz_align_up(knn_stage_bytes(2), 256);
-        AKZ_TRY(hm_stage_take(c, pair_off + sizeof(HmPairProb) + 256));
         AKZ_TRY(hm_upload(c, a, na, b, nb));
-        HmProb p[2] = {{c->d_a, c->d_na, na, c->d_b, c->d_na + 1, nb, c->d_fwd},
-                       {c->d_b, c->d_na + 1, nb, c->d_a, c->d_na, na, c->d_rev}};
-        AKZ_TRY(launch_knn(c, p, symmetric ? 2 : 1, na > nb ? na : nb, 2));
+        std::vector<HmProb> p = {{c->d_a, c->d_na, na, c->d_b, c->d_na + 1, nb, c->d_fwd}};
+        if (symmetric) p.push_back(HmProb{c->d_b, c->d_na + 1, nb, c->d_a, c->d_na, na, c->d_rev});
         uint32_t kcap = cap < na ? cap : na;
-        HmPairProb pp = {c->d_fwd, c->d_rev, c->d_na, c->d_na + 1, na, nb, c->d_pairs, kcap, c->d_npairs};
-        AKZ_TRY(hm_stage_push(c, pair_off, &pp, sizeof(pp)));
-        hipLaunchKernelGGL(k_pairs, dim3(1), dim3(1024), 0, c->stream, hm_staged<HmPairProb>(c, pair_off), (int)rule, param_u, param_f,
-                           (int)symmetric);
-        AKZ_LAUNCH_CHECK();
+        std::vector<HmPairProb> pp = {{c->d_fwd, c->d_rev, c->d_na, c->d_na + 1, na, nb, c->d_pairs, kcap, c->d_npairs}};
+        AKZ_TRY(match_enqueue(c, p, pp, 1, na > nb ? na : nb, rule, param_u, param_f, symmetric));
         uint32_t n = 0;
         AKZ_HIP(hipMemcpyAsync(&n, c->d_npairs, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         AKZ_HIP(hipStreamSynchronize(c->stream));
@@ -1706,8 +1991,6 @@ extern "C" int32_t hm_match_batch_device(hm_ctx* c, const void* d_a, const void*
         AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
         const uint32_t ndir = symmetric ? 2u : 1u;
         AKZ_TRY(hm_grow_lists(c, (size_t)n_pairs * cap_per_img * 2));
-        size_t knn_bytes = akz_align_up(knn_stage_bytes(n_pairs * ndir), 256);
-        AKZ_TRY(hm_stage_take(c, knn_bytes + sizeof(HmPairProb) * n_pairs));
         std::vector<HmProb> hp(n_pairs * ndir);
         std::vector<HmPairProb> hpp(n_pairs);
         const uint4* A = (const uint4*)d_a;
@@ -1725,12 +2008,7 @@ extern "C" int32_t hm_match_batch_device(hm_ctx* c, const void* d_a, const void*
                                 (uint32_t*)d_pairs + (size_t)p * cap_per_img * 2, cap_per_img,
                                 (uint32_t*)d_n_out + p};
         }
-        AKZ_TRY(launch_knn(c, hp.data(), n_pairs * ndir, cap_per_img, 2));
-        AKZ_TRY(hm_stage_push(c, knn_bytes, hpp.data(), sizeof(HmPairProb) * n_pairs));
-        hipLaunchKernelGGL(k_pairs, dim3(n_pairs), dim3(1024), 0, c->stream, hm_staged<HmPairProb>(c, knn_bytes), (int)rule, param_u,
-                           param_f, (int)symmetric);
-        AKZ_LAUNCH_CHECK();
-        return AKZ_OK;
+        return match_enqueue(c, hp, hpp, n_pairs, cap_per_img, rule, param_u, param_f, symmetric);
     });
 }
 

@@ -32,11 +32,15 @@ class Neighbor:
 class Matcher:
     """Owns one hm_ctx."""
 
-    def __init__(self, max_descriptors=16384, device=0, kernel="fp4", low_priority=False, cus=0):
+    def __init__(self, max_descriptors=16384, device=0, kernel="fp4", low_priority=False, cus=0, reverse_check="auto",
+                 fallback_share_log2=0):
         """kernel: "fp4" (default, FP4 MFMA, target tiles by LDS-DMA), "fp4_regs" (the same with a register stage), "int8"
         (int8 MFMA) or "valu" (xor/popcount, k = 2 only).
         low_priority: the matcher's stream as least-urgent filler work (HM_OPT_STREAM_PRIORITY).
-        cus: the matcher's stream on the last `cus` compute units of every XCD (0 = the whole chip)."""
+        cus: the matcher's stream on the last `cus` compute units of every XCD (0 = the whole chip).
+        reverse_check: the reverse side of a symmetric match: "auto" (per problem, from the forward lists unless that asks for
+        more than the fallback share of na * nb distances), "search" (always the reverse 2-NN search) or "lists" (never).
+        fallback_share_log2: n in 1..31 sets that share to 2^-n (0: the library's own)."""
         self._h = C.c_void_p()
         self.cap = max_descriptors
         flags = {"fp4": 0, "fp4_regs": _lib.HM_OPT_NO_LDS_DMA, "int8": _lib.HM_OPT_NO_FP4, "valu": _lib.HM_OPT_NO_MFMA}[kernel]
@@ -44,6 +48,10 @@ class Matcher:
         if not 0 <= int(cus) <= 32:
             raise ValueError(f"cus = {cus}: the matcher's stream takes 0 (the whole chip) to 32 compute units per XCD")
         flags |= int(cus) << 16
+        flags |= {"auto": 0, "search": _lib.HM_OPT_REVERSE_SEARCH, "lists": _lib.HM_OPT_REVERSE_LISTS}[reverse_check]
+        if not 0 <= int(fallback_share_log2) <= 31:
+            raise ValueError(f"fallback_share_log2 = {fallback_share_log2}: 0 (the library's share) or 1..31")
+        flags |= int(fallback_share_log2) << _lib.HM_OPT_REVERSE_SHARE_SHIFT
         check(_lib.lib().hm_create_ex(device, max_descriptors, max_descriptors, flags, C.byref(self._h)), "hm_create_ex")
 
     def close(self):

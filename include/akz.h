@@ -297,7 +297,13 @@ int32_t hm_create(int32_t device, uint32_t max_queries, uint32_t max_targets, hm
  * wave, target tiles by LDS-DMA) unless a flag selects its register-staged predecessor (HM_OPT_NO_LDS_DMA), the int8
  * MFMA or the xor/popcount VALU kernel (k = 2 only); all four are bit-identical. */
 enum { HM_OPT_NO_FP4 = 1u << 0, HM_OPT_NO_MFMA = 1u << 1, HM_OPT_STREAM_PRIORITY = 1u << 2, HM_OPT_NO_LDS_DMA = 1u << 3,
-       HM_OPT_CU_SHIFT = 16, HM_OPT_CU_MASK = 0x3Fu << 16 /* bits 16..21: the matcher's stream on the LAST n compute units of every XCD (0 = all) */ };
+       HM_OPT_CU_SHIFT = 16, HM_OPT_CU_MASK = 0x3Fu << 16 /* bits 16..21: the matcher's stream on the LAST n compute units of every XCD (0 = all) */,
+       /* The reverse side of a symmetric match (hm_match, hm_match_batch_device; rules BETTER_BY_STRICT, and BETTER_BY with
+        * param_u >= 1).  Default: per problem, answered from the forward lists where that asks for at most a share of na * nb
+        * explicit distances, by the reverse 2-NN search otherwise — decided on the device, same pairs either way.
+        * HM_OPT_REVERSE_SEARCH: always the search; HM_OPT_REVERSE_LISTS: never (the two exclude each other: AKZ_E_INVALID).
+        * Bits 8..12: n > 0 sets the share to 2^-n (0: the built-in 1/4). */
+       HM_OPT_REVERSE_SEARCH = 1u << 4, HM_OPT_REVERSE_LISTS = 1u << 5, HM_OPT_REVERSE_SHARE_SHIFT = 8, HM_OPT_REVERSE_SHARE_MASK = 0x1Fu << 8 };
 int32_t hm_create_ex(int32_t device, uint32_t max_queries, uint32_t max_targets, uint32_t flags, hm_ctx** out);
 int32_t hm_destroy(hm_ctx* ctx);
 /* LinearKnn::knn(q, 2) for every query (akaze/tests/estimate_pose.rs:82-88): out[2*i+0/1] are the
@@ -444,7 +450,10 @@ int32_t hm_hash_bag_device(hm_ctx* ctx, const void* d_descs, const void* d_count
 int32_t hm_hash_knn(hm_ctx* ctx, const uint8_t* query, const uint8_t* hashes, uint32_t n, uint32_t hash_bytes,
                     uint32_t k, akz_neighbor* out, uint32_t* n_out);
 /* Optional timing of the k-NN kernel launches with HIP events on hm_stream() (bench.py's matcher roofline):
- * hm_timing_get waits for the pending events and returns the accumulated milliseconds / launch count. */
+ * hm_timing_get waits for the pending events and returns the accumulated milliseconds / launch count.  A symmetric match
+ * whose reverse side is answered from the forward lists counts as ONE launch, and its decision and verification kernels and
+ * the skippable reverse search add their time to it: an operation count divided by this time is an equivalent brute-force
+ * rate.  (The VALU switch times nothing of a match.) */
 int32_t hm_timing_enable(hm_ctx* ctx, int32_t on);
 int32_t hm_timing_get(hm_ctx* ctx, double* ms, uint64_t* launches, int32_t reset);
 void* hm_stream(hm_ctx* ctx);
