@@ -202,6 +202,11 @@ RS_NR_OK, RS_NR_NOT_NORMAL, RS_NR_BAD_INDEX = range(3)
 RS_EX_OK, RS_EX_OVERFLOW, RS_EX_BAD_TABLE = range(3)
 RS_EX_C_POINTS, RS_EX_C_NO_POINT, RS_EX_C_INFINITE, RS_EX_C_BAD_ROWS, RS_EX_COUNTS = range(5)
 RS_EX_CAMERA_WORDS, RS_EX_CAMERA_VERTICES = 10, 5
+RS_JP_OK, RS_JP_NO_MODEL, RS_JP_FEW_INLIERS, RS_JP_BAD_INDEX = range(4)
+RS_JP_DEFAULT_MINIMUM_ROBUST_MATCHES, RS_JP_MAX_FEATURES = 256, 9216
+RS_AR_OK, RS_AR_NOT_ACCEPTED, RS_AR_BAD_INDEX, RS_AR_TAKEN, RS_AR_BAD_TABLE = range(5)
+RS_AR_S_TRIPLES, RS_AR_S_FIRST, RS_AR_S_SECOND, RS_AR_S_LANDMARKS = range(4)
+RS_AR_STATS, RS_AR_COUNTS = 4, 4
 
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
@@ -250,6 +255,7 @@ ABI_SYMBOLS = [
     "rs_landmarks_sharing_view_device", "rs_add_views_device",
     "rs_merge_map_device", "rs_incorporate_reconstruction_device", "rs_normalize_reconstruction_device",
     "rs_export_reconstruction_device", "rs_write_ply", "akz_sample_colors_batch_device",
+    "rs_join_pairs_batch_device", "rs_add_reconstruction_batch_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -411,6 +417,9 @@ def lib():
     L.rs_normalize_reconstruction_device.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, u32, vp, vp, u32, vp, vp, vp]
     L.rs_export_reconstruction_device.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     L.rs_write_ply.argtypes = [C.c_char_p, vp, vp, u32, u32, i32]
+    L.rs_join_pairs_batch_device.argtypes = [vp] * 7 + [u32, u32, vp, vp, u32, u32, u32, C.c_uint64] + [vp] * 10
+    L.rs_add_reconstruction_batch_device.argtypes = ([vp] * 15 + [u32, vp, vp, u32, u32, vp, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, u32, u32, u32] +
+                                                     [vp] * 14)
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

@@ -286,6 +286,77 @@ def merge_reconstructions(torch, consensus, dst_table, src_table, d_kps, cap, ca
     return merge_map, merged, (world, reason), result
 
 
+@dataclass
+class StartResult:
+    consensus: tuple          # (d_pose [slots][12], d_best_id, d_inliers [slots][cap], d_n_inliers) of the two-view consensus
+    join: object              # bootstrap.JoinTensors
+    bootstrap: tuple          # (d_verdict, d_pose_out [scenes][24], d_combined, d_first_ok, d_second_ok) of the three-view bootstrap
+    tv_stats: object          # [scenes][RS_TV_STATS] int32
+    start: object             # bootstrap.StartTensors: the new table, maps, ranges and constraint arrays
+    first_world: object       # [lm_room][4] float64 of the new table under the bootstrap's poses
+    first_reason: object      # [lm_room] uint8
+    edges: tuple              # PoseGraph.edges' result over the first constraints
+    rows: tuple               # (d_row_start, d_row_edges, d_flags)
+    verdict: object           # d_verdict [reconstructions] int32 (RS_OR_*)
+    pose_graph: tuple         # (d_graph_verdict, d_view_state, d_pg_stats)
+    filter: object            # ObservationFilterTensors
+    world: object             # [lm_room][4] float64 of the filtered table
+    world_reason: object      # [lm_room] uint8
+
+
+def start_reconstructions(torch, consensus, d_kps, counts, cap, cam, d_pairs, d_npairs, ia, ib, arrsac_params, scenes, ic, i_first, i_second,
+                          n_blocks, view_base, d_kps_dst=None, d_counts_dst=None, d_poses=None, table=None, recon_start=None, view_start=None,
+                          skip=None, minimum=_lib.RS_JP_DEFAULT_MINIMUM_ROBUST_MATCHES, shuffle=True, seed=0, consensus_shuffle=True,
+                          tv_params=None, pg_params=None, params=None):
+    """What VSlam::try_init does (cv-sfm/src/lib.rs:901-990: init_reconstruction, add_reconstruction, optimize_reconstruction) for
+    the scenes of a call, with ONE wait at the end: the two-view consensus of the slots (ia[k], ib[k]) over the matcher's d_pairs /
+    d_npairs -> the join of the slots scenes[s] = (first, second) -> the three-view bootstrap of the source blocks ic / i_first /
+    i_second -> add_reconstruction into the destination pool (d_kps_dst [n_blocks][cap] keypoints, d_counts_dst, d_poses; made
+    here when not given) behind `table` (a LandmarkTable with recon_start / view_start, or None) -> the robust triangulation of
+    the new table with (lm_room, obs_room) as its sizes, so that nothing is read back -> the edges and rows of the first
+    constraints -> optimize_reconstruction over the ranges add_reconstruction wrote.  The consensus needs room for the slots
+    (reserve).  counts [n_src_blocks]: the feature counts of d_kps.  -> StartResult of device tensors."""
+    from .bootstrap import PairJoin, ReconstructionStart
+    from .three_view import ThreeViewInit
+    dev = d_pairs.device
+    n_slots, n_scenes = len(ia), len(scenes)
+    opt = ReconstructionOptimizer(PoseGraph(consensus))
+    params, tv_params = params or opt.params(), tv_params or ThreeViewInit.params()
+    z = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=dev)
+    m = max(n_scenes, 1)
+    d_pose, d_best, d_inliers, d_n_inliers = z(torch.float64, n_slots, 12), z(torch.int32, n_slots), z(torch.int32, n_slots, cap), z(torch.int32, n_slots)
+    consensus.model_inliers_batch_device(d_kps, d_kps, cap, ia, ib, d_pairs, d_npairs, cam, cam, arrsac_params, d_pose, d_best, d_inliers,
+                                         d_n_inliers, shuffle=consensus_shuffle, stream_to_wait=torch.cuda.current_stream(dev))
+    join = PairJoin(consensus).join_tensors(torch, d_pairs, d_npairs, d_inliers, d_n_inliers, d_best, d_pose, cap, [a for a, _ in scenes],
+                                            [b for _, b in scenes], minimum, shuffle, seed)
+    d_tv_verdict, d_pose_out, d_tv_stats = z(torch.int32, m), z(torch.float64, m, 24), z(torch.int32, m, _lib.RS_TV_STATS)
+    d_masks = z(torch.uint8, 3, m, cap)
+    n_src_blocks = int(np.prod(counts.shape))
+    ThreeViewInit(consensus).init_batch_device(d_kps, cap, n_src_blocks, ic, i_first, i_second, cam, join.pose_first, join.pose_second, join.triples,
+                                               join.ntriples, join.first_only, join.nfirst, join.second_only, join.nsecond, tv_params, d_pose_out,
+                                               d_tv_verdict, d_masks[0], d_masks[1], d_masks[2], d_tv_stats, torch.cuda.current_stream(dev))
+    if d_kps_dst is None:
+        d_kps_dst = z(torch.uint8, n_blocks, cap, _lib.KP_DTYPE.itemsize)
+    d_counts_dst = z(torch.int32, n_blocks) if d_counts_dst is None else d_counts_dst
+    d_poses = z(torch.float64, n_blocks, 12) if d_poses is None else d_poses
+    start = ReconstructionStart(consensus).add_tensors(torch, join, d_masks[0], d_masks[1], d_masks[2], d_pose_out, d_tv_verdict, ic, i_first,
+                                                       i_second, d_kps, counts, cap, d_kps_dst, d_counts_dst, d_poses, view_base, table,
+                                                       recon_start, view_start, skip)
+    new_table = start.table(torch)
+    first_world = new_table.new_world()
+    first_reason = z(torch.uint8, max(new_table.n_landmarks, 1))
+    triangulate_landmarks_device(consensus._h, new_table, d_kps_dst, cap, n_blocks, d_poses, cam, params.triangulate, first_world, first_reason,
+                                 torch.cuda.current_stream(dev))
+    pg = opt._pg
+    edges = pg.edges(torch, start.views_out, (start.constraint_poses_out, start.constraint_verdict_out))
+    rows = pg.rows(torch, start.views_out, n_blocks)
+    d_verdict, pose_graph, o, d_world, d_world_reason = opt.run_tensors(torch, d_poses, start.view_start_out, rows[0], rows[1], edges, new_table,
+                                                                        d_kps_dst, cap, cam, start.recon_start_out, pg_params, params)
+    consensus.sync()
+    return StartResult((d_pose, d_best, d_inliers, d_n_inliers), join, (d_tv_verdict, d_pose_out, d_masks[0], d_masks[1], d_masks[2]), d_tv_stats,
+                       start, first_world, first_reason, edges, rows, d_verdict, pose_graph, o, d_world, d_world_reason)
+
+
 def export_reconstruction(torch, consensus, table, world, colors, view_blocks, counts, landmarks, cap, d_poses, path, camera_faces=True,
                           room=None, n_world=None):
     """VSlam::export_reconstruction (cv-sfm/src/lib.rs:2285-2340): the export on rs_stream() behind the current torch stream,

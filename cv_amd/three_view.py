@@ -2,11 +2,12 @@
 
   VSlam::init_reconstruction, from the common matches on     cv-sfm/src/lib.rs:1002-1300
   three_view_simple_optimize_l2                               cv-optimize/src/three_view_optimizer.rs:126-200
-  the join of the two pair lists (stays with the caller)     cv-sfm/src/lib.rs:992-998, 1190-1191, 1216, 1234
+  the join of the two pair lists (host form: join_pairs)     cv-sfm/src/lib.rs:992-998, 1190-1191, 1216, 1234
 
 Every triple is worked by one persistent workgroup on the device (cv_amd/csrc/rs_three_view.hip); there is no CPU fallback.
-The join and the shuffle of the common matches use the caller's HashMap and RNG in the reference and stay on the host here:
-`join_pairs` builds the three index lists in the reference's order.
+The join and the shuffle of the common matches use the caller's HashMap and RNG in the reference; on the device they are
+rs_join_pairs_batch_device's (cv_amd.bootstrap.PairJoin).  `join_pairs` is the host form: it builds the three index lists in the
+reference's order.
 
 And of the pose graph's three-view constraints over rs_three_view_constraint_batch_device:
 

@@ -648,7 +648,7 @@ private:
 
 // cv-sfm's three-view bootstrap (VSlam::init_reconstruction from its common matches on, cv-sfm/src/lib.rs:1002-1300) over
 // rs_three_view_init_batch_device: every argument named d_* is device memory the caller owns (the layouts are include/akz.h's),
-// the call enqueues on stream() and returns.  The join of the two pair lists and the shuffle stay with the caller.
+// the call enqueues on stream() and returns.  The join of the two pair lists and the shuffle are ReconstructionStart's (below).
 namespace cv_sfm {
 class ThreeViewInit {
 public:
@@ -1072,6 +1072,69 @@ public:
         if (xyz.size() != rgb.size() || xyz.size() % 3) throw std::invalid_argument("one colour per vertex");
         akaze::check(rs_write_ply(path.c_str(), xyz.data(), rgb.data(), (uint32_t)(xyz.size() / 3), n_cameras, camera_faces ? 1 : 0),
                      "rs_write_ply");
+    }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_ctx* ctx_ = nullptr;
+    bool owned_ = false;
+};
+
+// The two integer steps of cv-sfm's try_init around the three-view bootstrap, over rs_join_pairs_batch_device (the join and the
+// shuffle of VSlam::init_reconstruction, cv-sfm/src/lib.rs:992-999, 1190-1191, 1216, 1234) and
+// rs_add_reconstruction_batch_device (VSlamData::add_reconstruction, lib.rs:377-427): the lists the bootstrap reads and the first
+// generation of the landmark table, made on the device.  It works on the context of the consensus whose stream made the inlier
+// lists (`ctx`, not owned) or, built from a device number, on a small context of its own.  Every argument named d_* is device
+// memory the caller owns (the layouts are include/akz.h's); both calls enqueue and return.
+class ReconstructionStart {
+public:
+    enum JoinVerdict : uint32_t { JoinOk = RS_JP_OK, NoModel = RS_JP_NO_MODEL, FewInliers = RS_JP_FEW_INLIERS, JoinBadIndex = RS_JP_BAD_INDEX };
+    enum Verdict : uint32_t { Ok = RS_AR_OK, NotAccepted = RS_AR_NOT_ACCEPTED, BadIndex = RS_AR_BAD_INDEX, Taken = RS_AR_TAKEN, BadTable = RS_AR_BAD_TABLE };
+    explicit ReconstructionStart(rs_ctx* ctx) : ctx_(ctx) { akaze::require_abi(); }
+    explicit ReconstructionStart(int device = 0) : owned_(true)
+    {
+        akaze::require_abi();
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+    }
+    ~ReconstructionStart() { if (owned_ && ctx_) rs_destroy(ctx_); }
+    ReconstructionStart(const ReconstructionStart&) = delete;
+    ReconstructionStart& operator=(const ReconstructionStart&) = delete;
+    void join_pairs_device(const void* d_pairs, const void* d_npairs, const void* d_inliers, const void* d_n_inliers, const void* d_best_id,
+                           const void* d_pose, uint32_t n_slots, uint32_t cap_per_img, const std::vector<uint32_t>& slot_first,
+                           const std::vector<uint32_t>& slot_second, uint32_t two_view_minimum_robust_matches, uint32_t flags, uint64_t seed,
+                           void* d_triples, void* d_ntriples, void* d_first_only, void* d_nfirst, void* d_second_only, void* d_nsecond,
+                           void* d_pose_first, void* d_pose_second, void* d_verdict, void* stream_to_wait = nullptr)
+    {
+        if (slot_second.size() != slot_first.size()) throw std::invalid_argument("one first and one second slot per scene");
+        akaze::check(rs_join_pairs_batch_device(ctx_, d_pairs, d_npairs, d_inliers, d_n_inliers, d_best_id, d_pose, n_slots, cap_per_img,
+                                                slot_first.data(), slot_second.data(), (uint32_t)slot_first.size(),
+                                                two_view_minimum_robust_matches, flags, seed, d_triples, d_ntriples, d_first_only, d_nfirst,
+                                                d_second_only, d_nsecond, d_pose_first, d_pose_second, d_verdict, stream_to_wait),
+                     "rs_join_pairs_batch_device");
+    }
+    void add_reconstruction_device(const void* d_triples, const void* d_ntriples, const void* d_first_only, const void* d_nfirst,
+                                   const void* d_second_only, const void* d_nsecond, const void* d_combined, const void* d_first_ok,
+                                   const void* d_second_ok, const void* d_pose_out, const void* d_verdict, const std::vector<uint32_t>& ic,
+                                   const std::vector<uint32_t>& i_first, const std::vector<uint32_t>& i_second, const void* d_kps,
+                                   const void* d_counts, uint32_t n_src_blocks, uint32_t cap_per_img, const void* d_skip, const void* d_obs_start,
+                                   const void* d_obs, uint32_t n_obs, uint32_t n_landmarks, const void* d_recon_start, const void* d_view_start,
+                                   uint32_t n_recons, void* d_kps_dst, void* d_counts_dst, void* d_poses, uint32_t n_blocks, uint32_t view_base,
+                                   uint32_t obs_room, uint32_t lm_room, void* d_obs_start_out, void* d_obs_out, void* d_obs_counts_out,
+                                   void* d_counts_out, void* d_landmarks_out, void* d_recon_start_out, void* d_view_start_out, void* d_views_out,
+                                   void* d_constraint_poses_out, void* d_constraint_verdict_out, void* d_frame_verdict, void* d_stats,
+                                   void* d_call_verdict, void* stream_to_wait = nullptr)
+    {
+        if (i_first.size() != ic.size() || i_second.size() != ic.size()) throw std::invalid_argument("one centre, first and second block per scene");
+        akaze::check(rs_add_reconstruction_batch_device(ctx_, d_triples, d_ntriples, d_first_only, d_nfirst, d_second_only, d_nsecond, d_combined,
+                                                        d_first_ok, d_second_ok, d_pose_out, d_verdict, ic.data(), i_first.data(), i_second.data(),
+                                                        (uint32_t)ic.size(), d_kps, d_counts, n_src_blocks, cap_per_img, d_skip, d_obs_start, d_obs,
+                                                        n_obs, n_landmarks, d_recon_start, d_view_start, n_recons, d_kps_dst, d_counts_dst, d_poses,
+                                                        n_blocks, view_base, obs_room, lm_room, d_obs_start_out, d_obs_out, d_obs_counts_out,
+                                                        d_counts_out, d_landmarks_out, d_recon_start_out, d_view_start_out, d_views_out,
+                                                        d_constraint_poses_out, d_constraint_verdict_out, d_frame_verdict, d_stats, d_call_verdict,
+                                                        stream_to_wait),
+                     "rs_add_reconstruction_batch_device");
     }
     void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
     void* stream() { return rs_stream(ctx_); }

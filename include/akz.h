@@ -750,8 +750,8 @@ int32_t rs_triangulate_pairs_batch_device(rs_ctx* ctx, const void* d_kps_a, cons
  * final masks and counts.  One persistent workgroup per triple, one launch.  The arithmetic is
  * include/akz_three_view_math.h (compiled for the device and, by the tests, for the host: equal bit for bit); its head
  * lists what is unpinned against the reference — nalgebra's from_scaled_axis, and the order of the sum over landmarks,
- * which is fixed there.  The HashMap join of the two pair lists and the shuffle (lib.rs:992-999) use the caller's RNG and
- * stay with the caller.
+ * which is fixed there.  The HashMap join of the two pair lists and the shuffle (lib.rs:992-999, the caller's RNG in the
+ * reference) are not this call's: rs_join_pairs_batch_device writes the lists it reads.
  * Verdicts.  The reference `continue`s to the next combination on every one of them but RS_TV_FEW_BEARING_PAIRS, where it
  * `return`s None: a caller that mirrors it ends its whole search there. */
 enum {
@@ -1373,6 +1373,100 @@ int32_t rs_normalize_reconstruction_device(rs_ctx* ctx, const uint32_t* view_blo
                                            const void* d_landmarks, uint32_t cap_per_img, uint32_t n_blocks, const void* d_world,
                                            uint32_t n_world, void* d_poses, void* d_constraint_poses, uint32_t n_constraints, void* d_stats,
                                            void* d_verdict, void* stream_to_wait);
+/* ---- a reconstruction starts on the device: the join of the pair lists, add_reconstruction ----
+ * The two integer steps of cv-sfm's try_init around rs_three_view_init_batch_device: the join and the shuffle of
+ * VSlam::init_reconstruction (cv-sfm/src/lib.rs:992-999, 1190-1191, 1216, 1234) in front of it, VSlamData::add_reconstruction
+ * (lib.rs:377-427, with add_view / add_landmark, lib.rs:432-500) behind it, so that two-view consensus -> join -> bootstrap -> new
+ * reconstruction -> world table -> rs_optimize_reconstruction_batch_device runs on rs_stream() without a host step.  The
+ * decisions are include/akz_bootstrap_table_math.h (compiled for the device and, by the tests, for the host: equal byte for
+ * byte), whose head lists the departures from the reference. */
+enum {
+    RS_JP_OK = 0,
+    RS_JP_NO_MODEL = 1,        /* d_best_id of either slot is 0xFFFFFFFF */
+    RS_JP_FEW_INLIERS = 2,     /* an inlier list shorter than two_view_minimum_robust_matches (lib.rs:1421) */
+    RS_JP_BAD_INDEX = 3,       /* a count above cap_per_img, an inlier index not below the slot's d_npairs, or a feature not below
+                                * cap_per_img: nothing is read out of bounds */
+    RS_JP_DEFAULT_MINIMUM_ROBUST_MATCHES = 256,   /* cv-sfm/src/settings.rs:393-395 */
+    RS_JP_MAX_FEATURES = 9216, /* cap_per_img at the most (RS_TV_MAX_COMMON: the bootstrap takes no more; a scene's two maps live in
+                                * LDS): AKZ_E_TOO_LARGE beyond */
+    RS_AR_OK = 0,
+    RS_AR_NOT_ACCEPTED = 1,    /* the scene's bootstrap verdict is not RS_TV_OK, d_skip names it, or the call was refused */
+    RS_AR_BAD_INDEX = 2,       /* two of its frames are one block, one of its six counts is above cap_per_img, an accepted match names
+                                * a feature not below its block's count, or a feature of one view occurs in two accepted matches:
+                                * the scene is refused alone */
+    RS_AR_TAKEN = 3,           /* an earlier accepted scene of the call names one of its three source frames */
+    RS_AR_BAD_TABLE = 4,       /* d_call_verdict only */
+    /* d_stats words (u32) of a scene, all 0 unless it is accepted: */
+    RS_AR_S_TRIPLES = 0,       /* accepted triples */
+    RS_AR_S_FIRST = 1,         /* accepted first-only pairs */
+    RS_AR_S_SECOND = 2,        /* accepted second-only pairs */
+    RS_AR_S_LANDMARKS = 3,     /* rows of the new reconstruction */
+    RS_AR_STATS = 4,
+    RS_AR_COUNTS = 4           /* d_counts_out: {rows filled, observations filled, reconstructions, scenes accepted} */
+};
+/* The join.  Scene s < n_scenes names two slots of one rs_essential_arrsac_batch_device call run with the centre frame as side a:
+ * slot_first[s] and slot_second[s] (host lists, below n_slots, else AKZ_E_INVALID).  Inputs as that call and the matcher left
+ * them: d_pairs [n_slots][cap_per_img][2], d_npairs, d_inliers [n_slots][cap_per_img], d_n_inliers, d_best_id [n_slots], d_pose
+ * [n_slots][12] f64.  A slot's list is d_pairs[d_inliers[i]] = {centre, other feature} in inlier order.  Outputs, indexed by
+ * scene, are what rs_three_view_init_batch_device reads: d_triples [n_scenes][cap_per_img][3] {centre, first, second} with
+ * d_ntriples — one per entry of the first list whose centre feature the second list has, in the order of the first list,
+ * duplicates included, the second feature from the LAST entry of the second list with that centre; d_first_only / d_second_only
+ * [n_scenes][cap_per_img][2] with d_nfirst / d_nsecond — the entries of a list whose centre feature the other list lacks, in the
+ * order of their own list; d_pose_first / d_pose_second [n_scenes][12] f64 the slots' poses (always copied); d_verdict [n_scenes]
+ * u32 (RS_JP_*).  A scene that is not RS_JP_OK gets three zero counts — the bootstrap refuses it by itself — and its lists are
+ * not written.  With RS_BATCH_SHUFFLE in flags (no other bit, else AKZ_E_INVALID) the triples are shuffled by that flag's rule
+ * with the scene seed seed + 0x9E3779B97F4A7C15 * s; it needs cap_per_img <= 8192 (AKZ_E_TOO_LARGE).  Entries behind a count are
+ * not written.  n_scenes <= 65535.  One launch, one workgroup per scene, on rs_stream() after stream_to_wait (may be NULL);
+ * returns after enqueueing; allocates nothing beyond growing the context's scratch. */
+int32_t rs_join_pairs_batch_device(rs_ctx* ctx, const void* d_pairs, const void* d_npairs, const void* d_inliers, const void* d_n_inliers,
+                                   const void* d_best_id, const void* d_pose, uint32_t n_slots, uint32_t cap_per_img,
+                                   const uint32_t* slot_first, const uint32_t* slot_second, uint32_t n_scenes,
+                                   uint32_t two_view_minimum_robust_matches, uint32_t flags, uint64_t seed, void* d_triples,
+                                   void* d_ntriples, void* d_first_only, void* d_nfirst, void* d_second_only, void* d_nsecond,
+                                   void* d_pose_first, void* d_pose_second, void* d_verdict, void* stream_to_wait);
+/* add_reconstruction for the accepted scenes of an rs_three_view_init_batch_device call, out of place.
+ * Inputs: that call's lists, masks, d_pose_out [n_scenes][2][12] and d_verdict where it left them; ic / i_first / i_second the
+ * host lists of source blocks (below n_src_blocks, else AKZ_E_INVALID) of d_kps [n_src_blocks][cap_per_img] akz_keypoint with
+ * d_counts [n_src_blocks] u32; d_skip [n_scenes] u32 (optional, non-zero: leave the scene out); an optional existing table
+ * (d_obs_start [n_landmarks + 1], d_obs [n_obs][2]) with the ranges of its reconstructions d_recon_start / d_view_start
+ * [n_recons + 1] u32 over its rows and its views — all NULL / 0 for none.  The destination pool: d_kps_dst [n_blocks][cap_per_img],
+ * d_counts_dst [n_blocks], d_poses [n_blocks][12] f64.  Scene s is reconstruction n_recons + s and owns the views (destination
+ * blocks) view_base + 3 s .. + 3 in the order {centre, first, second}.
+ * Refused before anything is enqueued (AKZ_E_INVALID): view_base + 3 n_scenes > n_blocks; d_kps_dst partially overlaps d_kps;
+ * d_kps_dst == d_kps and the destination range holds a named source block; lm_room < n_landmarks + 3 n_scenes cap_per_img or
+ * obs_room < n_obs + 3 n_scenes cap_per_img; an output table or range array that overlaps the input table or its ranges.
+ * An accepted match is a triple with d_combined != 0, a first-only pair with d_first_ok != 0, a second-only pair with
+ * d_second_ok != 0.  In scene order, scene s is accepted iff its verdict is RS_TV_OK, it is not skipped, it is valid
+ * (RS_AR_BAD_INDEX otherwise) and no earlier accepted scene of the call names one of its three source frames (RS_AR_TAKEN).
+ * Outputs in rs_add_views_device's shapes: d_obs_start_out [lm_room + 1], d_obs_out [obs_room][2], d_obs_counts_out [lm_room],
+ * d_counts_out [RS_AR_COUNTS], d_landmarks_out [n_blocks][cap_per_img] every word written (global keys, 0xFFFFFFFF for none).  The
+ * old rows keep their keys and lists.  Behind them the rows of the accepted scenes in scene order: row j for every centre
+ * feature j below its count = {centre view, j}, then {first view, f} if an accepted match maps f to j, then {second view, s}
+ * likewise; one row for every first-frame feature in no accepted match, ascending; one for every second-frame feature in none.  A
+ * refused scene owns an empty row range (and three views no accepted constraint names).  Every start behind the total equals
+ * the total; d_obs_out behind it is not written.  d_recon_start_out / d_view_start_out [n_recons + n_scenes + 1]: the old ranges,
+ * then the scenes'.  For the accepted scenes the three keypoint blocks and counts are copied to their views and d_poses gets
+ * the identity, d_pose_out[s][0] and d_pose_out[s][1].  The first ThreeViewConstraint of every scene, as
+ * rs_pose_graph_edges_device and rs_pose_graph_rows_device take it: d_views_out [n_scenes][3], d_constraint_poses_out
+ * [n_scenes][24] f64 (accepted scenes only), d_constraint_verdict_out [n_scenes] u32: RS_TVC_OK for an accepted scene, else
+ * RS_CV_NOT_RECORDED.  d_frame_verdict [n_scenes] u32 (RS_AR_*), d_stats [n_scenes][RS_AR_STATS] u32, d_call_verdict [1] u32:
+ * RS_AR_OK, or RS_AR_BAD_TABLE for an existing table whose starts do not ascend inside [0, n_obs], whose reconstruction ranges do
+ * not ascend up to n_landmarks, or whose view ranges do not ascend up to view_base — no scene is accepted then and the outputs
+ * describe the old table unchanged, word for word, every new range empty.  n_scenes <= 65535.  Enqueues on rs_stream() after
+ * stream_to_wait (may be NULL) and returns; allocates nothing beyond growing the context's scratch. */
+int32_t rs_add_reconstruction_batch_device(rs_ctx* ctx, const void* d_triples, const void* d_ntriples, const void* d_first_only,
+                                           const void* d_nfirst, const void* d_second_only, const void* d_nsecond, const void* d_combined,
+                                           const void* d_first_ok, const void* d_second_ok, const void* d_pose_out, const void* d_verdict,
+                                           const uint32_t* ic, const uint32_t* i_first, const uint32_t* i_second, uint32_t n_scenes,
+                                           const void* d_kps, const void* d_counts, uint32_t n_src_blocks, uint32_t cap_per_img,
+                                           const void* d_skip, const void* d_obs_start, const void* d_obs, uint32_t n_obs,
+                                           uint32_t n_landmarks, const void* d_recon_start, const void* d_view_start, uint32_t n_recons,
+                                           void* d_kps_dst, void* d_counts_dst, void* d_poses, uint32_t n_blocks, uint32_t view_base,
+                                           uint32_t obs_room, uint32_t lm_room, void* d_obs_start_out, void* d_obs_out,
+                                           void* d_obs_counts_out, void* d_counts_out, void* d_landmarks_out, void* d_recon_start_out,
+                                           void* d_view_start_out, void* d_views_out, void* d_constraint_poses_out,
+                                           void* d_constraint_verdict_out, void* d_frame_verdict, void* d_stats, void* d_call_verdict,
+                                           void* stream_to_wait);
 /* ---- a reconstruction leaves the device: the coloured point cloud and the cameras' frusta of export_reconstruction ----
  * VSlam::export_reconstruction (cv-sfm/src/lib.rs:2285-2340) with export.rs: everything but the text of the file.  The decisions
  * and the arithmetic are include/akz_export_math.h (compiled for the device and, by the tests, for the host: equal byte for

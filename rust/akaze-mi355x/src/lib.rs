@@ -202,6 +202,25 @@ extern "C" {
                                        d_cameras: *mut c_void, d_counts_out: *mut c_void, d_verdict: *mut c_void,
                                        stream_to_wait: *mut c_void) -> i32;
     fn rs_write_ply(path: *const std::os::raw::c_char, xyz: *const f64, rgb: *const u8, n_vertices: u32, n_cameras: u32, camera_faces: i32) -> i32;
+    fn rs_join_pairs_batch_device(ctx: *mut c_void, d_pairs: *const c_void, d_npairs: *const c_void, d_inliers: *const c_void,
+                                  d_n_inliers: *const c_void, d_best_id: *const c_void, d_pose: *const c_void, n_slots: u32, cap_per_img: u32,
+                                  slot_first: *const u32, slot_second: *const u32, n_scenes: u32, two_view_minimum_robust_matches: u32, flags: u32,
+                                  seed: u64, d_triples: *mut c_void, d_ntriples: *mut c_void, d_first_only: *mut c_void, d_nfirst: *mut c_void,
+                                  d_second_only: *mut c_void, d_nsecond: *mut c_void, d_pose_first: *mut c_void, d_pose_second: *mut c_void,
+                                  d_verdict: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_add_reconstruction_batch_device(ctx: *mut c_void, d_triples: *const c_void, d_ntriples: *const c_void, d_first_only: *const c_void,
+                                          d_nfirst: *const c_void, d_second_only: *const c_void, d_nsecond: *const c_void, d_combined: *const c_void,
+                                          d_first_ok: *const c_void, d_second_ok: *const c_void, d_pose_out: *const c_void, d_verdict: *const c_void,
+                                          ic: *const u32, i_first: *const u32, i_second: *const u32, n_scenes: u32, d_kps: *const c_void,
+                                          d_counts: *const c_void, n_src_blocks: u32, cap_per_img: u32, d_skip: *const c_void,
+                                          d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32,
+                                          d_recon_start: *const c_void, d_view_start: *const c_void, n_recons: u32, d_kps_dst: *mut c_void,
+                                          d_counts_dst: *mut c_void, d_poses: *mut c_void, n_blocks: u32, view_base: u32, obs_room: u32, lm_room: u32,
+                                          d_obs_start_out: *mut c_void, d_obs_out: *mut c_void, d_obs_counts_out: *mut c_void,
+                                          d_counts_out: *mut c_void, d_landmarks_out: *mut c_void, d_recon_start_out: *mut c_void,
+                                          d_view_start_out: *mut c_void, d_views_out: *mut c_void, d_constraint_poses_out: *mut c_void,
+                                          d_constraint_verdict_out: *mut c_void, d_frame_verdict: *mut c_void, d_stats: *mut c_void,
+                                          d_call_verdict: *mut c_void, stream_to_wait: *mut c_void) -> i32;
     fn akz_sample_colors_batch_device(ctx: *mut c_void, d_rgb: *const c_void, n: i32, w: i32, h: i32, stride: i32, d_kps: *const c_void,
                                       d_counts: *const c_void, cap_per_img: u32, d_colors: *mut c_void, stream_to_wait: *mut c_void) -> i32;
     fn hm_landmark_original_matches_batch_device(ctx: *mut c_void, d_best: *const c_void, d_decision: *const c_void, d_merge_ok: *const c_void,
@@ -1706,6 +1725,94 @@ impl ReconstructionExport {
     pub fn write_ply(path: &std::ffi::CStr, xyz: &[f64], rgb: &[u8], n_cameras: u32, camera_faces: bool) -> Result<(), i32> {
         if xyz.len() != rgb.len() || xyz.len() % 3 != 0 { return Err(-1); }
         let st = unsafe { rs_write_ply(path.as_ptr(), xyz.as_ptr(), rgb.as_ptr(), (xyz.len() / 3) as u32, n_cameras, camera_faces as i32) };
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+}
+
+/// The verdict on a scene of `ReconstructionStart::join_pairs_device` (`RS_JP_*` of include/akz.h).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum JoinVerdict {
+    Ok = 0,
+    NoModel = 1,
+    FewInliers = 2,
+    BadIndex = 3,
+}
+/// The verdict on a scene, and on a call, of `ReconstructionStart::add_reconstruction_device` (`RS_AR_*`).
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum AddReconstructionVerdict {
+    Ok = 0,
+    NotAccepted = 1,
+    BadIndex = 2,
+    Taken = 3,
+    BadTable = 4,
+}
+pub const RS_JP_DEFAULT_MINIMUM_ROBUST_MATCHES: u32 = 256;
+pub const RS_JP_MAX_FEATURES: u32 = 9216;
+pub const RS_AR_S_TRIPLES: usize = 0;
+pub const RS_AR_S_FIRST: usize = 1;
+pub const RS_AR_S_SECOND: usize = 2;
+pub const RS_AR_S_LANDMARKS: usize = 3;
+pub const RS_AR_STATS: usize = 4;
+pub const RS_AR_COUNTS: usize = 4;
+
+/// The two integer steps of cv-sfm's `try_init` around the three-view bootstrap (`rs_join_pairs_batch_device`: the join and
+/// shuffle of `init_reconstruction`, cv-sfm/src/lib.rs:992-999; `rs_add_reconstruction_batch_device`: `add_reconstruction`,
+/// lib.rs:377-427), on the context of the consensus whose stream made the inlier lists (not owned).  Every `d_*` argument is
+/// device memory the caller owns, laid out as include/akz.h documents; both calls enqueue and return.
+/// Like the other declarations of this file these are source only: they are not compiled here (no toolchain).
+pub struct ReconstructionStart {
+    ctx: *mut c_void,
+}
+impl ReconstructionStart {
+    /// # Safety
+    /// `ctx` is a live `rs_ctx` that outlives this object.
+    pub unsafe fn new(ctx: *mut c_void) -> Self {
+        require_abi();
+        Self { ctx }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn join_pairs_device(&self, d_pairs: *const c_void, d_npairs: *const c_void, d_inliers: *const c_void, d_n_inliers: *const c_void,
+                                           d_best_id: *const c_void, d_pose: *const c_void, n_slots: u32, cap_per_img: u32, slot_first: &[u32],
+                                           slot_second: &[u32], two_view_minimum_robust_matches: u32, flags: u32, seed: u64, d_triples: *mut c_void,
+                                           d_ntriples: *mut c_void, d_first_only: *mut c_void, d_nfirst: *mut c_void, d_second_only: *mut c_void,
+                                           d_nsecond: *mut c_void, d_pose_first: *mut c_void, d_pose_second: *mut c_void, d_verdict: *mut c_void,
+                                           stream_to_wait: *mut c_void) -> Result<(), i32> {
+        if slot_second.len() != slot_first.len() { return Err(-1); }
+        let st = rs_join_pairs_batch_device(self.ctx, d_pairs, d_npairs, d_inliers, d_n_inliers, d_best_id, d_pose, n_slots, cap_per_img,
+                                            slot_first.as_ptr(), slot_second.as_ptr(), slot_first.len() as u32, two_view_minimum_robust_matches,
+                                            flags, seed, d_triples, d_ntriples, d_first_only, d_nfirst, d_second_only, d_nsecond, d_pose_first,
+                                            d_pose_second, d_verdict, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the context's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn add_reconstruction_device(&self, d_triples: *const c_void, d_ntriples: *const c_void, d_first_only: *const c_void,
+                                                   d_nfirst: *const c_void, d_second_only: *const c_void, d_nsecond: *const c_void,
+                                                   d_combined: *const c_void, d_first_ok: *const c_void, d_second_ok: *const c_void,
+                                                   d_pose_out: *const c_void, d_verdict: *const c_void, ic: &[u32], i_first: &[u32], i_second: &[u32],
+                                                   d_kps: *const c_void, d_counts: *const c_void, n_src_blocks: u32, cap_per_img: u32,
+                                                   d_skip: *const c_void, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32,
+                                                   n_landmarks: u32, d_recon_start: *const c_void, d_view_start: *const c_void, n_recons: u32,
+                                                   d_kps_dst: *mut c_void, d_counts_dst: *mut c_void, d_poses: *mut c_void, n_blocks: u32,
+                                                   view_base: u32, obs_room: u32, lm_room: u32, d_obs_start_out: *mut c_void, d_obs_out: *mut c_void,
+                                                   d_obs_counts_out: *mut c_void, d_counts_out: *mut c_void, d_landmarks_out: *mut c_void,
+                                                   d_recon_start_out: *mut c_void, d_view_start_out: *mut c_void, d_views_out: *mut c_void,
+                                                   d_constraint_poses_out: *mut c_void, d_constraint_verdict_out: *mut c_void,
+                                                   d_frame_verdict: *mut c_void, d_stats: *mut c_void, d_call_verdict: *mut c_void,
+                                                   stream_to_wait: *mut c_void) -> Result<(), i32> {
+        if i_first.len() != ic.len() || i_second.len() != ic.len() { return Err(-1); }
+        let st = rs_add_reconstruction_batch_device(self.ctx, d_triples, d_ntriples, d_first_only, d_nfirst, d_second_only, d_nsecond, d_combined,
+                                                    d_first_ok, d_second_ok, d_pose_out, d_verdict, ic.as_ptr(), i_first.as_ptr(), i_second.as_ptr(),
+                                                    ic.len() as u32, d_kps, d_counts, n_src_blocks, cap_per_img, d_skip, d_obs_start, d_obs, n_obs,
+                                                    n_landmarks, d_recon_start, d_view_start, n_recons, d_kps_dst, d_counts_dst, d_poses, n_blocks,
+                                                    view_base, obs_room, lm_room, d_obs_start_out, d_obs_out, d_obs_counts_out, d_counts_out,
+                                                    d_landmarks_out, d_recon_start_out, d_view_start_out, d_views_out, d_constraint_poses_out,
+                                                    d_constraint_verdict_out, d_frame_verdict, d_stats, d_call_verdict, stream_to_wait);
         if st == 0 { Ok(()) } else { Err(st) }
     }
 }
