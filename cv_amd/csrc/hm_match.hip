@@ -655,12 +655,107 @@ __device__ __forceinline__ void knn_chain4w(const uint4* __restrict__ tp, const 
     }
 }
 
+// The search of one wave's 64 resident queries qb over the rows [0, nt) of a streamed side, nt > 0: the ring, the waits and
+// the tile loop of the wide kernel, run by every wave of the block (idle waves, wave_on false, carry their share of the
+// tiles and hit the barriers).  Streamed row r is the descriptor row_of(r) of the recoded block tg (256 B per descriptor):
+// the forward search streams its targets in order, k_verify_mfma gathers its candidates through a list.  k0 / k1 take the
+// KNN smallest keys (nacc << 21) | r of the two column blocks.
+struct HmRowSame {
+    __device__ __forceinline__ uint32_t operator()(uint32_t r) const { return r; }
+};
+template <int KNN, typename RowOf>
+__device__ __forceinline__ void knn_wide_search(unsigned char* s_t, const v4i32 (&qb)[2][8], const unsigned char* tg, uint32_t nt,
+                                                uint32_t wv, uint32_t lane, bool wave_on, RowOf row_of, int (&k0)[KNN], int (&k1)[KNN])
+{
+    static_assert(kGStages >= 3 && kGTps == 2, "ring shape");
+    const uint32_t col = lane & 31u, half = lane >> 5;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)s_t;                          // LDS byte address of the ring (the low half of its flat address)
+    const uint32_t drow = 8u * wv + (lane & 3u), dchunk = lane >> 2;          // this lane's share: rows drow and drow + 4
+    // request the tiles of stage `st` (rows past the end repeat the last descriptor: the counts stay uniform)
+    auto issue = [&](uint32_t st) {
+        const uint32_t slot = lds0 + (st % kGStages) * (uint32_t)(kGTps * kGTile) + 2u * wv * kGSeg;
+#pragma unroll
+        for (uint32_t h = 0; h < (uint32_t)kGTps; ++h)
+#pragma unroll
+            for (uint32_t g = 0; g < 2; ++g) {
+                const uint32_t row = row_of(min((st * kGTps + h) * 32u + drow + 4u * g, nt - 1u));
+                glds16(tg + (size_t)row * 256 + dchunk * 16, slot + h * kGTile + g * kGSeg);
+            }
+    };
+    // the wave's query fragments must have arrived before the first DMA: the compiler's own vmcnt bookkeeping does not
+    // see the DMAs, so none of its loads may be outstanding when they start
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (uint32_t st = 0; st + 1 < (uint32_t)kGStages; ++st) issue(st);
+    v16f32 bias;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) bias[i] = 12582912.0f + (float)((i & 3) + 8 * (i >> 2));   // + off(r): the row tag
+    asm volatile("" : "+v"(bias));
+    v16f32 a00 = bias, a01 = bias, a10 = bias, a11 = bias;      // [ping-pong][column block]
+    const uint4* tlane = reinterpret_cast<const uint4*>(s_t + (col >> 2) * kGSeg + (col & 3u) * 16 + half * 64);
+    uint32_t t0 = 0;
+#define HM_LAST(x0, x1)                                                                                      \
+    if (wave_on) {                                                                                           \
+        const v16i32 n0 = __builtin_bit_cast(v16i32, x0), n1 = __builtin_bit_cast(v16i32, x1);               \
+        if (t0 + 32u <= nt) {                                                                                \
+            knn_keys_tagged<false, KNN>(n0, t0, half, nt, k0);                                               \
+            knn_keys_tagged<false, KNN>(n1, t0, half, nt, k1);                                               \
+        } else {                                                                                             \
+            knn_keys_tagged<true, KNN>(n0, t0, half, nt, k0);                                                \
+            knn_keys_tagged<true, KNN>(n1, t0, half, nt, k1);                                                \
+        }                                                                                                    \
+    }
+    // The stage boundary, run by every wave between steps 3 and 4 of a stage's last tile: this wave's reads of the stage
+    // have returned; the next stage has landed (its requests are the oldest; those of the kGStages - 2 stages behind it
+    // may stay in flight) — for every wave of the block once the barrier is passed, and by then everybody is done reading
+    // the current stage, whose slot the next request takes.
+    uint32_t st = 0;
+    auto boundary = [&]() {
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((kGStages - 2) * kGTps * 2) : "memory");
+        asm volatile("s_barrier" ::: "memory");
+        issue(st + (uint32_t)kGStages);
+    };
+    auto nothing = [&]() {};
+    // stage 0 has landed; the last slot of the ring takes its first request
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kGStages - 2) * kGTps * 2) : "memory");
+    asm volatile("s_barrier" ::: "memory");
+    issue((uint32_t)kGStages - 1u);
+    uint4 f[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = tlane[(128 / 16) * i];
+    for (;; ++st) {
+        const uint4* ta = tlane + (size_t)((st % kGStages) * (uint32_t)(kGTps * kGTile)) / 16;
+        const uint4* tb = ta + kGTile / 16;
+        const uint4* tn = tlane + (size_t)(((st + 1u) % kGStages) * (uint32_t)(kGTps * kGTile)) / 16;
+        const bool last_a = t0 + 32u >= nt, last_b = t0 + 64u >= nt;
+        // (idle waves skip the arithmetic, not the boundary)
+        if (wave_on) {
+            if (st == 0) knn_chain4w<KNN, false>(ta, last_a ? ta : tb, f, qb, bias, a00, a01, a10, a11, 0u, half, k0, k1, nothing);
+            else knn_chain4w<KNN, true>(ta, last_a ? ta : tb, f, qb, bias, a00, a01, a10, a11, t0 - 32u, half, k0, k1, nothing);
+        }
+        if (last_a) {
+            HM_LAST(a00, a01)
+            break;
+        }
+        t0 += 32u;
+        if (last_b) {
+            if (wave_on) knn_chain4w<KNN, true>(tb, tb, f, qb, bias, a10, a11, a00, a01, t0 - 32u, half, k0, k1, nothing);
+            HM_LAST(a10, a11)
+            break;
+        }
+        if (wave_on) knn_chain4w<KNN, true>(tb, tn, f, qb, bias, a10, a11, a00, a01, t0 - 32u, half, k0, k1, boundary);
+        else boundary();
+        t0 += 32u;
+    }
+#undef HM_LAST
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the requests past the end
+}
+
 // Two accumulator sets: the previous tile's keys are taken inside the next tile's chain (two waves per SIMD).  (One set with the
 // keys taken right behind the chain, three waves per SIMD at 168 registers, measured 3.32 against 2.82 ms per 256 frame pairs.)
 template <int KNN>
 __global__ __launch_bounds__(kWideBlock, 2) void k_knn_mfma4w(const HmProbX* __restrict__ probs)
 {
-    static_assert(kGStages >= 3 && kGTps == 2, "ring shape");
     __shared__ __attribute__((aligned(16))) unsigned char s_t[kGStages * kGTps * kGTile];
     uint32_t bx, by;
     {
@@ -692,87 +787,7 @@ __global__ __launch_bounds__(kWideBlock, 2) void k_knn_mfma4w(const HmProbX* __r
 #pragma unroll
             for (int i = 0; i < 8; ++i) qb[cb][i] = qp[2 * i] ^ (int)0x88888888;
         }
-        const unsigned char* tg = reinterpret_cast<const unsigned char*>(P.t);   // 256 B per descriptor
-        const uint32_t lds0 = (uint32_t)(uintptr_t)s_t;                          // LDS byte address of the ring (the low half of its flat address)
-        const uint32_t drow = 8u * wv + (lane & 3u), dchunk = lane >> 2;          // this lane's share: rows drow and drow + 4
-        // request the tiles of stage `st` (rows past the end repeat the last descriptor: the counts stay uniform)
-        auto issue = [&](uint32_t st) {
-            const uint32_t slot = lds0 + (st % kGStages) * (uint32_t)(kGTps * kGTile) + 2u * wv * kGSeg;
-#pragma unroll
-            for (uint32_t h = 0; h < (uint32_t)kGTps; ++h)
-#pragma unroll
-                for (uint32_t g = 0; g < 2; ++g) {
-                    const uint32_t row = min((st * kGTps + h) * 32u + drow + 4u * g, nt - 1u);
-                    glds16(tg + (size_t)row * 256 + dchunk * 16, slot + h * kGTile + g * kGSeg);
-                }
-        };
-        // the wave's query fragments must have arrived before the first DMA: the compiler's own vmcnt bookkeeping does not
-        // see the DMAs, so none of its loads may be outstanding when they start
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (uint32_t st = 0; st + 1 < (uint32_t)kGStages; ++st) issue(st);
-        v16f32 bias;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) bias[i] = 12582912.0f + (float)((i & 3) + 8 * (i >> 2));   // + off(r): the row tag
-        asm volatile("" : "+v"(bias));
-        v16f32 a00 = bias, a01 = bias, a10 = bias, a11 = bias;      // [ping-pong][column block]
-        const uint4* tlane = reinterpret_cast<const uint4*>(s_t + (col >> 2) * kGSeg + (col & 3u) * 16 + half * 64);
-        uint32_t t0 = 0;
-#define HM_LAST(x0, x1)                                                                                          \
-        if (wave_on) {                                                                                           \
-            const v16i32 n0 = __builtin_bit_cast(v16i32, x0), n1 = __builtin_bit_cast(v16i32, x1);               \
-            if (t0 + 32u <= nt) {                                                                                \
-                knn_keys_tagged<false, KNN>(n0, t0, half, nt, k0);                                               \
-                knn_keys_tagged<false, KNN>(n1, t0, half, nt, k1);                                               \
-            } else {                                                                                             \
-                knn_keys_tagged<true, KNN>(n0, t0, half, nt, k0);                                                \
-                knn_keys_tagged<true, KNN>(n1, t0, half, nt, k1);                                                \
-            }                                                                                                    \
-        }
-        // The stage boundary, run by every wave between steps 3 and 4 of a stage's last tile: this wave's reads of the stage
-        // have returned; the next stage has landed (its requests are the oldest; those of the kGStages - 2 stages behind it
-        // may stay in flight) — for every wave of the block once the barrier is passed, and by then everybody is done reading
-        // the current stage, whose slot the next request takes.
-        uint32_t st = 0;
-        auto boundary = [&]() {
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((kGStages - 2) * kGTps * 2) : "memory");
-            asm volatile("s_barrier" ::: "memory");
-            issue(st + (uint32_t)kGStages);
-        };
-        auto nothing = [&]() {};
-        // stage 0 has landed; the last slot of the ring takes its first request
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kGStages - 2) * kGTps * 2) : "memory");
-        asm volatile("s_barrier" ::: "memory");
-        issue((uint32_t)kGStages - 1u);
-        uint4 f[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f[i] = tlane[(128 / 16) * i];
-        for (;; ++st) {
-            const uint4* ta = tlane + (size_t)((st % kGStages) * (uint32_t)(kGTps * kGTile)) / 16;
-            const uint4* tb = ta + kGTile / 16;
-            const uint4* tn = tlane + (size_t)(((st + 1u) % kGStages) * (uint32_t)(kGTps * kGTile)) / 16;
-            const bool last_a = t0 + 32u >= nt, last_b = t0 + 64u >= nt;
-            // (idle waves skip the arithmetic, not the boundary)
-            if (wave_on) {
-                if (st == 0) knn_chain4w<KNN, false>(ta, last_a ? ta : tb, f, qb, bias, a00, a01, a10, a11, 0u, half, k0, k1, nothing);
-                else knn_chain4w<KNN, true>(ta, last_a ? ta : tb, f, qb, bias, a00, a01, a10, a11, t0 - 32u, half, k0, k1, nothing);
-            }
-            if (last_a) {
-                HM_LAST(a00, a01)
-                break;
-            }
-            t0 += 32u;
-            if (last_b) {
-                if (wave_on) knn_chain4w<KNN, true>(tb, tb, f, qb, bias, a10, a11, a00, a01, t0 - 32u, half, k0, k1, nothing);
-                HM_LAST(a10, a11)
-                break;
-            }
-            if (wave_on) knn_chain4w<KNN, true>(tb, tn, f, qb, bias, a10, a11, a00, a01, t0 - 32u, half, k0, k1, boundary);
-            else boundary();
-            t0 += 32u;
-        }
-#undef HM_LAST
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the requests past the end
+        knn_wide_search<KNN>(s_t, qb, reinterpret_cast<const unsigned char*>(P.t), nt, wv, lane, wave_on, HmRowSame(), k0, k1);
     }
     if (!wave_on) return;
 #pragma unroll
@@ -804,7 +819,7 @@ struct HmPairProb {
     uint32_t* pairs;          // [cap][2]
     uint32_t cap;
     uint32_t* n_out;
-    // the reverse side answered from the forward lists (k_decide, k_verify): one keep flag per a, read when *rev_nq == 0;
+    // the reverse side answered from the forward lists (k_decide, k_verify / k_verify_mfma): one keep flag per a, read when *rev_nq == 0;
     // both null: `rev` holds the reverse search
     const uint32_t* keep;
     const uint32_t* rev_nq;
@@ -869,7 +884,7 @@ __global__ __launch_bounds__(1024) void k_pairs(const HmPairProb* __restrict__ p
 // The reverse side of a symmetric match from the forward lists (hm_rule.h states the question: does any other query a'
 // lie within tau of the pair's target b?).  If b is not among the two nearest of a', then d(a', b) >= d1(a'), the
 // second-best distance of a': every a' with d1(a') > tau is cleared unseen.  What remains is
-//   (1) the a' with d1(a') <= tau: their distance to b is computed (k_verify walks them in ascending d1), and
+//   (1) the a' with d1(a') <= tau: their distance to b is computed (k_verify / k_verify_mfma walk them in ascending d1), and
 //   (2) the a' whose BEST is b with d0(a') <= tau, whatever their d1: the two smallest (d0, a') keys per b, scattered here.
 // k_decide also counts the distances (1) asks for; a problem whose count is above `share` of na * nb (clustered
 // descriptors: small second-best distances everywhere) keeps the reverse search: its word rev_nq — the query count of the
@@ -886,9 +901,16 @@ struct HmRevProb {
     uint32_t* acc;             // [a_cap] the forward-accepted a, DESCENDING tau (the longest walks start first)
     uint32_t* keep;            // [a_cap] the pair of a survives
     uint32_t* best;            // [2][b_cap] smallest and second-smallest key d0 << 22 | a' among the a' whose best is b
-    uint32_t* units;           // [u_cap] k_verify's work list: block of 64 accepted pairs | segment of its candidates << 16
-    uint32_t u_cap;            // at least twice the number of 64-pair blocks
+    uint32_t* units;           // [u_cap] the verify kernel's work list: block of accepted pairs | segment of its candidates << 16
+    uint32_t u_cap;            // at least twice the number of pair blocks
 };
+// The shape of the work list's units: k_verify takes 64 pairs and segments that are multiples of 256 candidates (its four
+// waves' chunks), k_verify_mfma 256 pairs and multiples of 512 (eight of its 64-row stages: measured against 256 and 1 024,
+// docs/EXPERIMENTS.md #71).
+struct HmRevShape {
+    uint32_t pairs, seg;
+};
+constexpr HmRevShape kRevShapeValu = {64u, 256u}, kRevShapeMfma = {256u, 512u};
 constexpr uint32_t kRevBins = kHmMaxDistance + 1u;   // distances 0..512
 constexpr uint32_t kRevHdr = 576;                    // 2 + kRevBins words, the two below, rounded up
 constexpr uint32_t kRevHdrUnits = 2 + kRevBins, kRevHdrSeg = 3 + kRevBins;   // entries of the work list, candidates per segment
@@ -906,7 +928,7 @@ __device__ __forceinline__ void rev_scan(uint32_t* s)
 }
 
 __global__ __launch_bounds__(1024) void k_decide(const HmRevProb* __restrict__ probs, int rule, uint32_t pu, float pf, int mode,
-                                                 float share)
+                                                 float share, HmRevShape shape)
 {
     __shared__ uint32_t s_cum[kRevBins];     // histogram of d1, then cum
     __shared__ uint32_t s_tau[kRevBins];     // histogram of tau over the accepted a, then its inclusive scan
@@ -976,24 +998,25 @@ __global__ __launch_bounds__(1024) void k_decide(const HmRevProb* __restrict__ p
         }
         P.keep[a] = keep;
     }
-    // k_verify's work list.  The accepted pairs go 64 to a block in descending tau, and block x walks the candidates
-    // [0, cum[its largest tau]): a few blocks at the head carry most of the walk (measured on benchmark frames: 4 954, 3 102,
-    // 2 131, ... of 18 541 candidate steps in 70 blocks), so each block's walk is cut into segments of `seg` candidates and
-    // every (block, segment) is one workgroup of k_verify.  seg is the smallest multiple of 256 at which the list fits u_cap.
-    const uint32_t nblk = (n_acc + 63u) / 64u;
-    auto walk_of = [&](uint32_t x) {           // cum[tau of the pair ranked 64 x]: the largest t with #{tau >= t} > 64 x
+    // The verify kernel's work list.  The accepted pairs go shape.pairs to a block in descending tau, and block x walks the
+    // candidates [0, cum[its largest tau]): a few blocks at the head carry most of the walk (measured on benchmark frames, 64
+    // pairs to a block: 4 954, 3 102, 2 131, ... of 18 541 candidate steps in 70 blocks), so each block's walk is cut into
+    // segments of `seg` candidates and every (block, segment) is one workgroup of the verify kernel.  seg is the smallest
+    // multiple of shape.seg at which the list fits u_cap.
+    const uint32_t nblk = (n_acc + shape.pairs - 1u) / shape.pairs;
+    auto walk_of = [&](uint32_t x) {           // cum[tau of the pair ranked pairs * x]: the largest t with #{tau >= t} > pairs * x
         uint32_t lo = 0, hi = kHmMaxDistance;
         while (lo < hi) {
             const uint32_t mid = (lo + hi + 1u) / 2u;
-            if (n_acc - s_tau[mid - 1u] > 64u * x) lo = mid;
+            if (n_acc - s_tau[mid - 1u] > shape.pairs * x) lo = mid;
             else hi = mid - 1u;
         }
         return s_cum[lo];
     };
     for (uint32_t x = threadIdx.x; x < nblk; x += 1024) atomicAdd(&s_walk, (unsigned long long)walk_of(x));
     __syncthreads();
-    const unsigned long long room = 256ull * (P.u_cap - nblk);          // (u_cap >= 2 nblk)
-    const uint32_t seg = 256u * (uint32_t)max(1ull, (s_walk + room - 1ull) / max(room, 1ull));
+    const unsigned long long room = (unsigned long long)shape.seg * (P.u_cap - nblk);          // (u_cap >= 2 nblk)
+    const uint32_t seg = shape.seg * (uint32_t)max(1ull, (s_walk + room - 1ull) / max(room, 1ull));
     for (uint32_t x = threadIdx.x; x < nblk; x += 1024) {
         const uint32_t nu = (walk_of(x) + seg - 1u) / seg;
         const uint32_t at = atomicAdd(&s_units, nu);
@@ -1066,6 +1089,93 @@ __global__ __launch_bounds__(256) void k_verify(const HmRevProb* __restrict__ pr
         }
     }
     if (rival) P.keep[a] = 0u;
+}
+
+// (1) on the matrix unit, for the FP4 families: the walk is the wide kernel's search (knn_wide_search) with the roles of a
+// forward block turned round.  The RESIDENT side is 256 accepted pairs of `acc` (64 per wave, descending tau): the recoded
+// rows of their targets, gathered by fwd[a][0].index from the problem's recoded B, which the forward launch of the same call
+// left in d_exp (px: the call's staged forward problems).  The STREAMED side is one segment of the block's walk
+// order[0 .. cum[largest tau of the 256]): the candidates' recoded rows of A, gathered by the DMA's per-lane address through
+// the segment's slice of order[], which the block first copies to LDS (kVerifyWin indices at a time: a segment longer than
+// that — the work list's growth under u_cap — is searched window by window).  The search keeps the two smallest
+// (distance, position) keys per pair; rows past the segment's end never enter them (the last tile's mask).  Two keys and
+// not one because the pair's own a can be a row of its walk: the smallest key whose candidate is not a is the nearest
+// rival of the segment, and it clears keep[a] when it lies within the pair's OWN tau — a walk longer than a pair needs
+// only shows it candidates whose d1, hence whose distance to any target, is above its bound.
+constexpr uint32_t kVerifyWin = 1024;           // (4 KB of indices beside the 51 KB ring: two blocks per CU as in the forward search)
+
+struct HmRowListed {
+    const uint32_t* list;                       // LDS
+    __device__ __forceinline__ uint32_t operator()(uint32_t r) const { return list[r]; }
+};
+
+__global__ __launch_bounds__(kWideBlock, 2) void k_verify_mfma(const HmRevProb* __restrict__ probs, const HmProbX* __restrict__ px,
+                                                                int rule, uint32_t pu)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_t[kGStages * kGTps * kGTile];
+    __shared__ uint32_t s_ord[kVerifyWin];
+    const HmRevProb P = probs[blockIdx.y];
+    if (blockIdx.x >= P.hdr[kRevHdrUnits]) return;                   // (a fallback problem has no work list)
+    const uint32_t unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.units[blockIdx.x]);
+    const uint32_t seg = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.hdr[kRevHdrSeg]);
+    const uint32_t n_acc = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.hdr[1]);
+    const uint32_t base = (unit & 0xFFFFu) * kRevShapeMfma.pairs;   // (a listed block is not empty: base < n_acc)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t col = lane & 31u, half = lane >> 5;
+    const bool wave_on = base + wv * 64u < n_acc;
+    // the block's walk ends where its first pair's does (descending tau)
+    const uint32_t tmax = (uint32_t)hm_rival_bound(rule, pu, P.fwd[(size_t)P.acc[base] * 2].distance);
+    const uint32_t limit = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.hdr[2 + tmax]);
+    const uint32_t begin = (unit >> 16) * seg, end = min(limit, begin + seg);
+    // B fragments: the targets of pairs (base + 64 wv + col) and (+ 32), as the forward kernel holds its queries (lanes past
+    // the end repeat the last pair)
+    v4i32 qb[2][8];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+        const uint32_t a = P.acc[min(base + wv * 64u + 32u * cb + col, n_acc - 1u)];
+        const uint32_t bi = P.fwd[(size_t)a * 2].index;
+        const v4i32* qp = reinterpret_cast<const v4i32*>(px[blockIdx.y].t + (size_t)bi * 64) + half;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) qb[cb][i] = qp[2 * i] ^ (int)0x88888888;
+    }
+    const unsigned char* cand = reinterpret_cast<const unsigned char*>(px[blockIdx.y].q);
+    int k0[2] = {0x7FFFFFFF, 0x7FFFFFFF}, k1[2] = {0x7FFFFFFF, 0x7FFFFFFF};     // keys (nacc << 21) | position in order[]
+    for (uint32_t w0 = begin; w0 < end; w0 += kVerifyWin) {
+        const uint32_t n = min(kVerifyWin, end - w0);
+        __syncthreads();                                             // (the previous window's ring and indices are done with)
+        for (uint32_t i = threadIdx.x; i < n; i += kWideBlock) s_ord[i] = P.order[w0 + i];
+        __syncthreads();
+        int w[2][2] = {{0x7FFFFFFF, 0x7FFFFFFF}, {0x7FFFFFFF, 0x7FFFFFFF}};
+        knn_wide_search<2>(s_t, qb, cand, n, wv, lane, wave_on, HmRowListed{s_ord}, w[0], w[1]);
+        // window positions -> positions in order[] (below 2^21, the row bits never carry), ascending as they were
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            w[0][i] = w[0][i] == 0x7FFFFFFF ? 0x7FFFFFFF : w[0][i] + (int)w0;
+            w[1][i] = w[1][i] == 0x7FFFFFFF ? 0x7FFFFFFF : w[1][i] + (int)w0;
+        }
+        topk_merge2<2>(k0, w[0]);
+        topk_merge2<2>(k1, w[1]);
+    }
+    if (!wave_on) return;
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+        int (&k)[2] = cb ? k1 : k0;
+        int o[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) o[i] = __shfl_xor(k[i], 32);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) topk_insert<2>(k, o[i]);
+        const uint32_t pi = base + wv * 64u + 32u * cb + col;
+        if (half == 0 && pi < n_acc) {                               // (lanes past the end write nothing)
+            const uint32_t a = P.acc[pi];
+            const uint32_t tau = (uint32_t)hm_rival_bound(rule, pu, P.fwd[(size_t)a * 2].distance);
+            // the smallest key of another query: the second when the first is a itself (a is in order[] once)
+            int r = k[0];
+            if (r != 0x7FFFFFFF && P.order[(uint32_t)r & ((1u << 21) - 1u)] == a) r = k[1];
+            if (r != 0x7FFFFFFF && (((uint32_t)r + (512u << 21)) >> kIdxBits) <= tau) P.keep[a] = 0u;
+        }
+    }
 }
 
 }  // namespace
@@ -1900,7 +2010,8 @@ extern "C" int32_t hm_timing_get(hm_ctx* c, double* ms, uint64_t* launches, int3
 //
 // Symmetric under a rule with a rival bound (hm_rule.h), unless the context asks for the search: the forward search alone,
 // k_decide, then the reverse search of the SAME staged problems with their query counts read from k_decide's rev_nq words —
-// every block of a problem that takes the shortcut leaves at the kernels' `qblk >= nq` test — then k_verify, then k_pairs.
+// every block of a problem that takes the shortcut leaves at the kernels' `qblk >= nq` test — then the verify kernel of the
+// context's family (k_verify_mfma or k_verify), then k_pairs.
 static_assert(HM_RULE_BETTER_BY_STRICT == kHmRuleStrict && HM_RULE_BETTER_BY == kHmRuleBetterBy, "hm_rule.h names the rules of akz.h");
 static int32_t match_enqueue(hm_ctx* c, const std::vector<HmProb>& hp, std::vector<HmPairProb>& hpp, uint32_t n_pairs, uint32_t max_n,
                              int32_t rule, uint32_t pu, float pf, int32_t symmetric)
@@ -1913,7 +2024,10 @@ static int32_t match_enqueue(hm_ctx* c, const std::vector<HmProb>& hp, std::vect
     if (!by_lists) {
         AKZ_TRY(launch_knn(c, hp.data(), n_probs, max_n, 2));
     } else {
-        const uint32_t u_cap = 2u * ((max_n + 63u) / 64u);
+        // the FP4 families verify on the matrix unit, in blocks of 256 pairs; the others keep k_verify and its blocks of 64
+        const bool by_mfma = c->use_mfma && c->use_fp4;
+        const HmRevShape shape = by_mfma ? kRevShapeMfma : kRevShapeValu;
+        const uint32_t u_cap = 2u * ((max_n + shape.pairs - 1u) / shape.pairs);
         const size_t per = kRevHdr + 5 * (size_t)max_n + u_cap;   // words per problem: hdr, order, acc, keep, best[2], units
         AKZ_TRY(akz_grow_scratch(c->stream, &c->d_rev_scratch, &c->rev_scratch_bytes, sizeof(uint32_t) * per * n_pairs));
         std::vector<HmRevProb> hr(n_pairs);
@@ -1932,12 +2046,16 @@ static int32_t match_enqueue(hm_ctx* c, const std::vector<HmProb>& hp, std::vect
         // (the VALU switch times nothing of a match: launch_knn's k = 2 branch takes no events either)
         std::pair<hipEvent_t, hipEvent_t> ev = c->use_mfma ? c->timer.take(false) : std::pair<hipEvent_t, hipEvent_t>{nullptr, nullptr};
         hipExtLaunchKernelGGL(k_decide, dim3(n_pairs), dim3(1024), 0, c->stream, ev.first, ev.second, 0, hm_staged<HmRevProb>(c, rev_off),
-                              (int)rule, pu, pf, c->rev_mode, c->rev_share);
+                              (int)rule, pu, pf, c->rev_mode, c->rev_share, shape);
         AKZ_LAUNCH_CHECK();
         if (c->rev_mode != kRevLists) AKZ_TRY(knn_rest(c, n_pairs, n_pairs, max_n));
         ev = c->use_mfma ? c->timer.take(false) : std::pair<hipEvent_t, hipEvent_t>{nullptr, nullptr};
-        hipExtLaunchKernelGGL(k_verify, dim3(u_cap, n_pairs), dim3(256), 0, c->stream, ev.first, ev.second, 0,
-                              hm_staged<HmRevProb>(c, rev_off), (int)rule, pu);
+        if (by_mfma)
+            hipExtLaunchKernelGGL(k_verify_mfma, dim3(u_cap, n_pairs), dim3(kWideBlock), 0, c->stream, ev.first, ev.second, 0,
+                                  hm_staged<HmRevProb>(c, rev_off), hm_staged<HmProbX>(c, 0), (int)rule, pu);
+        else
+            hipExtLaunchKernelGGL(k_verify, dim3(u_cap, n_pairs), dim3(256), 0, c->stream, ev.first, ev.second, 0,
+                                  hm_staged<HmRevProb>(c, rev_off), (int)rule, pu);
         AKZ_LAUNCH_CHECK();
     }
     AKZ_TRY(hm_stage_push(c, pair_off, hpp.data(), sizeof(HmPairProb) * n_pairs));
