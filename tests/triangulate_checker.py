@@ -87,8 +87,9 @@ def landmarks(kps, poses, cam, start, obs, st=None, n_obs=None):
     return world, reason
 
 
-def merged(kps, poses, cam, start, obs, best, decision, merge_ok, n_world, world, st=None):
-    """Writes the merge candidates' rows into `world` (in place); returns reason [frames][cap] (255 = row not written)."""
+def merged(kps, poses, cam, start, obs, best, decision, merge_ok, n_world, world, st=None, n_obs=None):
+    """Writes the merge candidates' rows into `world` (in place); returns reason [frames][cap] (255 = row not written).
+    n_obs: the length of the observation array as the call states it (len(obs) where not given)."""
     kps = np.ascontiguousarray(kps)
     P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
     start = np.ascontiguousarray(start, np.uint32)
@@ -100,24 +101,29 @@ def merged(kps, poses, cam, start, obs, best, decision, merge_ok, n_world, world
     assert best.shape == (F, cap, 3, 2) and merge_ok.shape == (F, cap) and cap == kps.shape[1] and world.flags.c_contiguous
     reason = np.full((F, cap), 255, np.uint8)
     st = st or settings()
-    lib().tri_merged(kps.ctypes.data, cap, kps.shape[0], P.ctypes.data, C.byref(cam), start.ctypes.data, obs.ctypes.data, len(obs),
-                     len(start) - 1, C.byref(st), best.ctypes.data, decision.ctypes.data, merge_ok.ctypes.data, F, n_world,
+    lib().tri_merged(kps.ctypes.data, cap, kps.shape[0], P.ctypes.data, C.byref(cam), start.ctypes.data, obs.ctypes.data,
+                     len(obs) if n_obs is None else n_obs, len(start) - 1, C.byref(st), best.ctypes.data, decision.ctypes.data, merge_ok.ctypes.data, F, n_world,
                      world.ctypes.data, reason.ctypes.data)
     return reason
 
 
-def pairs_scene(kps_a, kps_b, pairs, npairs, cam_a, cam_b, pose, inliers, st=None):
-    """(points [n_inliers][4], reason) of one scene of a two-view consensus; kps_a / kps_b [cap] KP_DTYPE, pairs [cap][2]."""
+def pairs_scene(kps_a, kps_b, pairs, npairs, cam_a, cam_b, pose, inliers, st=None, n_inliers=None):
+    """(points [n_inliers][4], reason) of one scene of a two-view consensus; kps_a / kps_b [cap] KP_DTYPE, pairs [cap][2].
+    n_inliers: the count as the call states it (len(inliers) where not given); one above the capacity is clamped to it, and
+    the rows that come back are the clamped count's."""
     kps_a, kps_b = np.ascontiguousarray(kps_a), np.ascontiguousarray(kps_b)
     pairs = np.ascontiguousarray(pairs, np.uint32)
     pose = np.ascontiguousarray(pose, np.float64).reshape(12)
     inliers = np.ascontiguousarray(inliers, np.uint32)
-    n = len(inliers)
+    stated = len(inliers) if n_inliers is None else int(n_inliers)
+    n = min(stated, len(kps_a))
+    assert len(inliers) >= n
     pts = np.empty((max(n, 1), 4), np.float64)
     reason = np.empty(max(n, 1), np.uint8)
     st = st or settings()
     lib().tri_pairs_scene(kps_a.ctypes.data, kps_b.ctypes.data, len(kps_a), pairs.ctypes.data, int(npairs), C.byref(cam_a),
-                          C.byref(cam_b), pose.ctypes.data, inliers.ctypes.data, n, C.byref(st), pts.ctypes.data, reason.ctypes.data)
+                          C.byref(cam_b), pose.ctypes.data, inliers.ctypes.data, stated, C.byref(st), pts.ctypes.data,
+                          reason.ctypes.data)
     return pts[:n], reason[:n]
 
 
