@@ -324,13 +324,14 @@ def _refused(stage):
                            table_map=np.full((N_VIEWS, CAP), NONE, np.uint32), views=[], refused=stage)
 
 
-def start(w, triple, view_base, alter=()):
+def start(w, triple, view_base, alter=(), lists=None):
     """What reconstruction.start_reconstructions does for one scene: the two-view consensus of (centre, first) and (centre,
-    second) -> the join -> the three-view bootstrap -> add_reconstruction at view_base -> the pose graph over the first
-    constraint -> the observation filter -> the world table of the filtered rows.
+    second; the designed pair_lists, or `lists` = (pairs, npairs) where a matcher made them) -> the join -> the three-view
+    bootstrap -> add_reconstruction at view_base -> the pose graph over the first constraint -> the observation filter -> the
+    world table of the filtered rows.
     -> SimpleNamespace(poses [13][12], rows, split, landmark_map, world [rows][4], reason [rows], views, ...)"""
     bear = bearings_of(w)
-    pairs, npairs = pair_lists(w, triple)
+    pairs, npairs = lists or pair_lists(w, triple)
     c, f, s = triple
     # consensus: slot k is the pair list k; its pose takes the centre's camera frame to the other's, translation of unit length
     slots = []
@@ -392,6 +393,7 @@ def start(w, triple, view_base, alter=()):
     out = _optimize(px, kps, poses, rows, [(views, aout["constraint_poses_out"][0][:12].reshape(3, 4), aout["constraint_poses_out"][0][12:].reshape(3, 4))],
                     (int(aout["view_start_out"][0]), int(aout["view_start_out"][1])), strict=not alter)
     out.table_rows, out.table_map, out.views, out.px = rows, aout["landmarks_out"].copy(), views, px
+    out.table_counts = aout["obs_counts_out"][:n_rows].copy()
     return out
 
 
@@ -540,22 +542,25 @@ def normalize(w, state, view_range):
 NORMALIZE = True
 
 
-def merge(w, grown_a, grown_b, alter=()):
-    """The bridging frame is registered in B (add_views_and_regenerate over [6, 13)) and in A (add_views alone), then what
+def merge(w, grown_a, grown_b, alter=(), register_with=None):
+    """The bridging frame is registered in B (add_views_and_regenerate over [6, 13)) and in A (add_views alone) — by register(),
+    or by `register_with` where a caller brings its own form of it —, then what
     reconstruction.merge_reconstructions does: the landmark map of the frame's final matches -> incorporate B into A under
     inverse(src_pose) * dst_pose -> regenerate over [0, 13) with B's views as targets.
     -> (B with the frame, A with the frame, the merged state)"""
+    reg = register_with or register
     if NORMALIZE:
         grown_a, grown_b = normalize(w, grown_a, A_VIEWS), normalize(w, grown_b, B_VIEWS)
-    b = register(w, grown_b, [BRIDGE], list(range(*B_VIEWS)), B_WITH_BRIDGE)
+    b = reg(w, grown_b, [BRIDGE], list(range(*B_VIEWS)), B_WITH_BRIDGE)
     # B -> merge: the frame's pose IN B, taken before A's add_views overwrites the block's row; B's per-feature landmark map
     src_pose, src_map, src_rows = b.poses[BRIDGE].copy(), b.table_map, b.table_rows
-    a = register(w, grown_a, [BRIDGE], list(range(*A_VIEWS)), A_VIEWS, regenerated=False)
+    a = reg(w, grown_a, [BRIDGE], list(range(*A_VIEWS)), A_VIEWS, regenerated=False)
     if "src_pose_from_a" in alter:
         src_pose = a.poses[BRIDGE].copy()
     # A's refinement -> the map: a final match of the frame's feature j on A's row l, where B's map knows j, pairs B's row with l
     n = int(a.nmatches[0])
-    named = {int(j): [int(l)] for (j, l), ok in zip(a.matches[0, :n], a.final[0, :n]) if ok and l < a.n_world}
+    # (a merged match, row >= n_world, stands for its two landmarks: the map takes the first, which add_views kept)
+    named = {int(j): [int(l) if l < a.n_world else int(a.best[0, j, 0, 0])] for (j, l), ok in zip(a.matches[0, :n], a.final[0, :n]) if ok}
     view_lms = [None if int(l) == NONE else int(l) for l in src_map[BRIDGE]]
     pairs = RM.merge_map(named, view_lms)
     poses = b.poses.copy()                               # one pool: B's rows as B left them, A's rows and the frame's as A left them
