@@ -208,6 +208,16 @@ RS_AR_OK, RS_AR_NOT_ACCEPTED, RS_AR_BAD_INDEX, RS_AR_TAKEN, RS_AR_BAD_TABLE = ra
 RS_AR_S_TRIPLES, RS_AR_S_FIRST, RS_AR_S_SECOND, RS_AR_S_LANDMARKS = range(4)
 RS_AR_STATS, RS_AR_COUNTS = 4, 4
 
+
+class PlaceParams(C.Structure):
+    """hm_place_params (include/akz.h)."""
+    _fields_ = [("num_similar", C.c_uint32), ("num_recent", C.c_uint32), ("recent_threshold", C.c_uint32), ("search_num", C.c_uint32)]
+
+
+HM_PL_OK, HM_PL_BAD_INDEX, HM_PL_BAD_TABLE = range(3)
+HM_PL_C_RECENT, HM_PL_C_SIMILAR, HM_PL_C_SEARCHED, HM_PL_C_GROUPS, HM_PL_C_FREE, HM_PL_COUNTS = range(6)
+HM_PL_MAX_HASH_BYTES, HM_PL_MAX_SEARCH, HM_PL_MAX_RECENT, HM_PL_NONE = 4096, 2048, 256, 0xFFFFFFFF
+
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
 
@@ -256,6 +266,7 @@ ABI_SYMBOLS = [
     "rs_merge_map_device", "rs_incorporate_reconstruction_device", "rs_normalize_reconstruction_device",
     "rs_export_reconstruction_device", "rs_write_ply", "akz_sample_colors_batch_device",
     "rs_join_pairs_batch_device", "rs_add_reconstruction_batch_device",
+    "hm_place_params_default", "hm_place_room", "hm_find_frames_batch_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -420,6 +431,10 @@ def lib():
     L.rs_join_pairs_batch_device.argtypes = [vp] * 7 + [u32, u32, vp, vp, u32, u32, u32, C.c_uint64] + [vp] * 10
     L.rs_add_reconstruction_batch_device.argtypes = ([vp] * 15 + [u32, vp, vp, u32, u32, vp, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, u32, u32, u32] +
                                                      [vp] * 14)
+    L.hm_place_params_default.argtypes = [C.POINTER(PlaceParams)]
+    L.hm_place_room.restype = u32
+    L.hm_place_room.argtypes = [C.POINTER(PlaceParams)]
+    L.hm_find_frames_batch_device.argtypes = [vp] * 6 + [u32, u32, vp, vp, u32, C.POINTER(PlaceParams), u32] + [vp] * 9
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

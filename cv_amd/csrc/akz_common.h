@@ -200,6 +200,20 @@ struct RsLandmarkTableState {
 };
 RsLandmarkTableState* rs_internal_landmark_table(rs_ctx* c);
 
+// What hm_place.hip needs of an hm_ctx (defined in hm_match.hip): its device, its stream and wait event; and what it keeps
+// there, grown on demand and freed by hm_destroy: the distances of one hm_find_frames_batch_device call ([nq][n_stored] u16).
+struct HmHandles {
+    int device;
+    hipStream_t stream;
+    hipEvent_t ev;
+};
+HmHandles hm_internal_handles(hm_ctx* c);
+struct HmPlaceState {
+    void* d_scratch = nullptr;
+    size_t bytes = 0;
+};
+HmPlaceState* hm_internal_place(hm_ctx* c);
+
 // A context's scratch, grown on demand: *d holds at least `need` bytes afterwards (what it held before is not kept).
 inline int32_t akz_grow_scratch(hipStream_t stream, void** d, size_t* have, size_t need)
 {

@@ -1273,6 +1273,7 @@ struct hm_ctx {
     // scratch of the host-buffer place-recognition calls (hm_hash_bag, hm_hash_knn)
     void* d_lsh = nullptr;
     size_t lsh_bytes = 0;
+    HmPlaceState place;            // hm_place.hip's scratch (hm_find_frames_batch_device)
 };
 
 // Problem descriptors are built in pinned host memory and copied stream-ordered; the staging
@@ -1388,6 +1389,7 @@ extern "C" int32_t hm_destroy(hm_ctx* c)
         hipFree(c->d_brev);
         hipFree(c->d_rev_scratch);
         hipFree(c->d_lsh);
+        hipFree(c->place.d_scratch);
         if (c->ev) hipEventDestroy(c->ev);
         if (c->stream) hipStreamDestroy(c->stream);
         delete c;
@@ -1396,6 +1398,8 @@ extern "C" int32_t hm_destroy(hm_ctx* c)
 }
 
 extern "C" void* hm_stream(hm_ctx* c) { return c ? (void*)c->stream : nullptr; }
+HmHandles hm_internal_handles(hm_ctx* c) { return HmHandles{c->device, c->stream, c->ev}; }
+HmPlaceState* hm_internal_place(hm_ctx* c) { return &c->place; }
 extern "C" int32_t hm_sync(hm_ctx* c)
 {
     return akz_guard([&]() -> int32_t {

@@ -13,8 +13,9 @@ The reference walks this per feature on the CPU; here one call enqueues, for ALL
 hm_hash_bag_device -> hm_knn_batch_device (k = 3, frames x views problems) -> hm_best_of_views_batch_device ->
 hm_landmark_matches_batch_device -> rs_p3p_arrsac_batch_device (and, with refine(), hm_landmark_original_matches_batch_device ->
 rs_refine_poses_batch_device: the single-view optimiser and consistency filter of cv-sfm/src/lib.rs:1625-1775) on the blocks where akz_extract_batch_device left them; nothing
-returns to the host in between.  What stays with the caller is the reference's control plane: which views a frame is matched
-against.  Which landmark each stored feature observes, which features observe each landmark (a LandmarkTable) and the row
+returns to the host in between.  Which views a frame is matched against is decided on the device too
+(cv_amd/place_recognition.py: FrameIndex.find over the hashes this chain writes, view_blocks for match_views' host list); what
+stays with the caller is the reference's control plane over that answer (try_localize).  Which landmark each stored feature observes, which features observe each landmark (a LandmarkTable) and the row
 lengths come from the device too: add_views() behind refine() is VSlamData::add_view for the accepted frames of the
 micro-batch (cv-sfm/src/lib.rs:432-483, merge_landmarks :699-721) and leaves the next generation of the table, the landmark
 map match_views() reads and the counts consensus() sorts by where the next call takes them; sharing_view() behind

@@ -1143,6 +1143,70 @@ private:
     rs_ctx* ctx_ = nullptr;
     bool owned_ = false;
 };
+
+// Which frames a frame is compared with, over hm_find_frames_batch_device: VSlamData::find_visually_similar_and_recent_frames
+// (cv-sfm/src/lib.rs:597-668) and the order try_localize gives its reconstructions (:853-855), for a batch of queries on the
+// matcher's stream.  The frame table is the caller's device memory (the layouts are include/akz.h's); this class keeps its five
+// addresses, its capacity and its row count.  This header knows no HIP: the rows' feed / pos / recon / view words are copied by
+// the caller to the addresses append_rows / set_views hand out; the hashes are written by hm_hash_bag_device, whose d_hash is the
+// tail.  find enqueues and returns.
+class FrameIndex {
+public:
+    enum Verdict : uint32_t { Ok = HM_PL_OK, BadIndex = HM_PL_BAD_INDEX, BadTable = HM_PL_BAD_TABLE };
+    struct Rows {              // the addresses of rows [first, first + count) in the five arrays
+        uint32_t first, count;
+        void *hashes, *feed, *pos, *recon, *view;
+    };
+    FrameIndex(space::Matcher& m, void* d_hashes, void* d_feed, void* d_pos, void* d_recon, void* d_view, uint32_t capacity, uint32_t hash_bytes)
+        : m_(m), hashes_(d_hashes), feed_(d_feed), pos_(d_pos), recon_(d_recon), view_(d_view), capacity_(capacity), hb_(hash_bytes)
+    {
+        akaze::require_abi();
+        if (hash_bytes == 0 || hash_bytes % 4 || hash_bytes > HM_PL_MAX_HASH_BYTES) throw std::invalid_argument("hash_bytes");
+    }
+    static hm_place_params params()
+    {
+        hm_place_params p;
+        akaze::check(hm_place_params_default(&p), "hm_place_params_default");
+        return p;
+    }
+    static uint32_t room(const hm_place_params& p) { return hm_place_room(&p); }
+    uint32_t size() const { return n_; }
+    // k frames appended in insertion order -> where their rows lie (hashes: the d_hash of hm_hash_bag_device); they have no view
+    // until set_views: the caller writes HM_PL_NONE to their recon words with the feed and pos
+    Rows append_rows(uint32_t k)
+    {
+        if (k > capacity_ - n_) throw std::length_error("FrameIndex: capacity");
+        const Rows r = rows(n_, k);
+        n_ += k;
+        return r;
+    }
+    // Frame::view of stored rows [first, first + k): where the caller copies their reconstruction and view keys
+    Rows set_views(uint32_t first, uint32_t k) const
+    {
+        if (first > n_ || k > n_ - first) throw std::out_of_range("FrameIndex: stored rows only");
+        return rows(first, k);
+    }
+    void find(const void* d_query, const void* d_visible, uint32_t nq, const hm_place_params& p, uint32_t room, void* d_found, void* d_views_out,
+              void* d_group_recon, void* d_group_start, void* d_free, void* d_search, void* d_counts, void* d_verdict,
+              void* stream_to_wait = nullptr)
+    {
+        akaze::check(hm_find_frames_batch_device(m_.handle(), hashes_, feed_, pos_, recon_, view_, n_, hb_, d_query, d_visible, nq, &p, room, d_found,
+                                                 d_views_out, d_group_recon, d_group_start, d_free, d_search, d_counts, d_verdict, stream_to_wait),
+                     "hm_find_frames_batch_device");
+    }
+    void sync() { akaze::check(hm_sync(m_.handle()), "hm_sync"); }
+    void* stream() { return hm_stream(m_.handle()); }
+
+private:
+    Rows rows(uint32_t first, uint32_t k) const
+    {
+        auto at = [first](void* base, std::size_t width) { return static_cast<void*>(static_cast<char*>(base) + width * first); };
+        return Rows{first, k, at(hashes_, hb_), at(feed_, 4), at(pos_, 4), at(recon_, 4), at(view_, 4)};
+    }
+    space::Matcher& m_;
+    void *hashes_, *feed_, *pos_, *recon_, *view_;
+    uint32_t capacity_, hb_, n_ = 0;
+};
 }  // namespace cv_sfm
 
 // hamming_lsh::HammingHasher<64, H> and the lsh_to_frame map of cv-sfm (cv-sfm/src/lib.rs:205-217, 672, 622-624) over

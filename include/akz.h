@@ -449,6 +449,51 @@ int32_t hm_hash_bag_device(hm_ctx* ctx, const void* d_descs, const void* d_count
  * nearest to `query`, ascending (distance, index); hash_bytes a multiple of 4 (512 in cv-sfm). */
 int32_t hm_hash_knn(hm_ctx* ctx, const uint8_t* query, const uint8_t* hashes, uint32_t n, uint32_t hash_bytes,
                     uint32_t k, akz_neighbor* out, uint32_t* n_out);
+/* ---- which frames a frame is compared with, on the device ----
+ * VSlamData::find_visually_similar_and_recent_frames (cv-sfm/src/lib.rs:597-668) and the order try_localize gives its
+ * reconstructions (:853-855), for a batch of queries over a frame table that lives in the caller's device memory; add_frame
+ * (:790-806) and try_localize_and_incorporate (:926-939) are the reference's callers.  Row i of the table is frame i in
+ * insertion order: d_hashes [n_stored][hash_bytes] u8 the frame's lsh (hash_bytes a multiple of 4, <= HM_PL_MAX_HASH_BYTES; 512 in
+ * cv-sfm — hm_hash_bag_device writes rows where it is told, so appending is pointing its d_hash at the table's tail), d_feed /
+ * d_pos [n_stored] u32 Frame::feed / feed_frame, d_recon / d_view [n_stored] u32 the reconstruction and view key of Frame::view,
+ * d_recon HM_PL_NONE for None (d_view is not read there).
+ * Query q is about the stored row d_query[q] and sees the rows i < d_visible[q] (d_visible NULL: all n_stored; add_frame inserts
+ * the frame and then asks: visible = query + 1).  In the reference's order:
+ *   recent   the visible frames r != query of the query's feed with |pos[r] - pos[query]| < num_recent, ascending pos (:611-621);
+ *            (feed, pos) is unique in a well-formed table: a second visible frame on one slot of the window is HM_PL_BAD_TABLE;
+ *   search   the min(search_num, visible) visible hashes nearest to the query's, ascending (distance, row) over all bits, the
+ *            query's own row like any other — exact where the reference asks an approximate index, hm_hash_knn's statement;
+ *   similar  the search list in order without the query, without the recent frames and without the frames of the query's feed
+ *            with |pos difference| < recent_threshold, then the first num_similar (:626-637);
+ *   chain    recent then similar (:643): an entry with a view goes to its reconstruction's list, any other to the free list;
+ *   groups   reconstructions by descending number of views found (:853-855), equal counts by ascending reconstruction key (the
+ *            reference leaves those to a HashMap and an unstable sort).
+ * Outputs, rows of pitch `room` >= hm_place_room(params) = max(2 * num_recent - 2, 0) + num_similar, entries past a count NOT
+ * written: d_found [nq][room] the chain (stored rows); d_views_out [nq][room] the view keys, groups back to back in group order;
+ * d_group_recon [nq][room] and d_group_start [nq][room + 1] (n_groups + 1 words written); d_free [nq][room]; d_search
+ * [nq][search_num] akz_neighbor, optional: the search list; d_counts [nq][HM_PL_COUNTS] {n_recent, n_similar, n_searched,
+ * n_groups, n_free}; d_verdict [nq] HM_PL_OK, HM_PL_BAD_INDEX (query >= n_stored, visible > n_stored or query >= visible) or
+ * HM_PL_BAD_TABLE — on either refusal the query's counts are 0, nothing else of its rows is written and nothing was read through
+ * the bad index.  nq <= 65535, search_num <= HM_PL_MAX_SEARCH, num_similar <= search_num, num_recent <= HM_PL_MAX_RECENT
+ * (AKZ_E_INVALID / AKZ_E_TOO_LARGE, before the context is looked at).  Enqueued on hm_stream() after stream_to_wait; scratch
+ * from the context; no host synchronisation and no readback.  With num_similar == 0 and d_search NULL the search is left out. */
+typedef struct hm_place_params {
+    uint32_t num_similar;        /* similar_frames: 0 (settings.rs:437-451) */
+    uint32_t num_recent;         /* tracking_recent_frames: 32 */
+    uint32_t recent_threshold;   /* similar_recent_threshold: 0 */
+    uint32_t search_num;         /* similar_frames_search_num: 512 */
+} hm_place_params;
+enum { HM_PL_OK = 0, HM_PL_BAD_INDEX = 1, HM_PL_BAD_TABLE = 2 };
+enum { HM_PL_C_RECENT = 0, HM_PL_C_SIMILAR = 1, HM_PL_C_SEARCHED = 2, HM_PL_C_GROUPS = 3, HM_PL_C_FREE = 4, HM_PL_COUNTS = 5 };
+enum { HM_PL_MAX_HASH_BYTES = 4096, HM_PL_MAX_SEARCH = 2048, HM_PL_MAX_RECENT = 256 };
+#define HM_PL_NONE 0xFFFFFFFFu
+int32_t hm_place_params_default(hm_place_params* params);
+uint32_t hm_place_room(const hm_place_params* params);
+int32_t hm_find_frames_batch_device(hm_ctx* ctx, const void* d_hashes, const void* d_feed, const void* d_pos, const void* d_recon,
+                                    const void* d_view, uint32_t n_stored, uint32_t hash_bytes, const void* d_query,
+                                    const void* d_visible, uint32_t nq, const hm_place_params* params, uint32_t room, void* d_found,
+                                    void* d_views_out, void* d_group_recon, void* d_group_start, void* d_free, void* d_search,
+                                    void* d_counts, void* d_verdict, void* stream_to_wait);
 /* Optional timing of the k-NN kernel launches with HIP events on hm_stream() (bench.py's matcher roofline):
  * hm_timing_get waits for the pending events and returns the accumulated milliseconds / launch count.  A symmetric match
  * whose reverse side is answered from the forward lists counts as ONE launch, and its decision and verification kernels and

@@ -240,6 +240,13 @@ extern "C" {
                    hash: *mut u8, words: *mut AkzNeighbor) -> i32;
     fn hm_hash_knn(ctx: *mut c_void, query: *const u8, hashes: *const u8, n: u32, hash_bytes: u32, k: u32,
                    out: *mut AkzNeighbor, n_out: *mut u32) -> i32;
+    fn hm_place_params_default(params: *mut HmPlaceParams) -> i32;
+    fn hm_place_room(params: *const HmPlaceParams) -> u32;
+    fn hm_find_frames_batch_device(ctx: *mut c_void, d_hashes: *const c_void, d_feed: *const c_void, d_pos: *const c_void,
+                                   d_recon: *const c_void, d_view: *const c_void, n_stored: u32, hash_bytes: u32, d_query: *const c_void,
+                                   d_visible: *const c_void, nq: u32, params: *const HmPlaceParams, room: u32, d_found: *mut c_void,
+                                   d_views_out: *mut c_void, d_group_recon: *mut c_void, d_group_start: *mut c_void, d_free: *mut c_void,
+                                   d_search: *mut c_void, d_counts: *mut c_void, d_verdict: *mut c_void, stream_to_wait: *mut c_void) -> i32;
 }
 
 /// `akaze::KeyPoint` (akaze/src/lib.rs:69-93).
@@ -1813,6 +1820,121 @@ impl ReconstructionStart {
                                                     view_base, obs_room, lm_room, d_obs_start_out, d_obs_out, d_obs_counts_out, d_counts_out,
                                                     d_landmarks_out, d_recon_start_out, d_view_start_out, d_views_out, d_constraint_poses_out,
                                                     d_constraint_verdict_out, d_frame_verdict, d_stats, d_call_verdict, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+}
+
+/// `hm_place_params` of include/akz.h (the defaults: cv-sfm/src/settings.rs:437-451).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct HmPlaceParams {
+    pub num_similar: u32,
+    pub num_recent: u32,
+    pub recent_threshold: u32,
+    pub search_num: u32,
+}
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PlaceVerdict {
+    Ok = 0,
+    BadIndex = 1,
+    BadTable = 2,
+}
+pub const HM_PL_OK: u32 = 0;
+pub const HM_PL_BAD_INDEX: u32 = 1;
+pub const HM_PL_BAD_TABLE: u32 = 2;
+pub const HM_PL_C_RECENT: usize = 0;
+pub const HM_PL_C_SIMILAR: usize = 1;
+pub const HM_PL_C_SEARCHED: usize = 2;
+pub const HM_PL_C_GROUPS: usize = 3;
+pub const HM_PL_C_FREE: usize = 4;
+pub const HM_PL_COUNTS: usize = 5;
+pub const HM_PL_MAX_HASH_BYTES: u32 = 4096;
+pub const HM_PL_MAX_SEARCH: u32 = 2048;
+pub const HM_PL_MAX_RECENT: u32 = 256;
+pub const HM_PL_NONE: u32 = 0xFFFF_FFFF;
+
+/// The rows `[first, first + count)` of a [`FrameIndex`]: their addresses in the table's five arrays.
+#[derive(Clone, Copy, Debug)]
+pub struct FrameRows {
+    pub first: u32,
+    pub count: u32,
+    pub hashes: *mut c_void,
+    pub feed: *mut c_void,
+    pub pos: *mut c_void,
+    pub recon: *mut c_void,
+    pub view: *mut c_void,
+}
+
+/// Which frames a frame is compared with (`hm_find_frames_batch_device`: `find_visually_similar_and_recent_frames`,
+/// cv-sfm/src/lib.rs:597-668, and the order `try_localize` gives its reconstructions, :853-855), for a batch of queries on the
+/// matcher's stream.  The frame table is device memory the caller owns, laid out as include/akz.h documents; this struct keeps
+/// its five addresses, its capacity and its row count.  The rows' feed / pos / recon / view words are copied by the caller to the
+/// addresses `append_rows` / `set_views` hand out; the hashes are written by `hm_hash_bag_device`, whose `d_hash` is the tail.
+/// Like the other declarations of this file these are source only: they are not compiled here (no toolchain).
+pub struct FrameIndex {
+    ctx: *mut c_void,
+    hashes: *mut c_void,
+    feed: *mut c_void,
+    pos: *mut c_void,
+    recon: *mut c_void,
+    view: *mut c_void,
+    capacity: u32,
+    hash_bytes: u32,
+    n: u32,
+}
+impl FrameIndex {
+    /// # Safety
+    /// `ctx` is a live `hm_ctx` that outlives this object; the five pointers name device arrays of `capacity` rows.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn new(ctx: *mut c_void, d_hashes: *mut c_void, d_feed: *mut c_void, d_pos: *mut c_void, d_recon: *mut c_void,
+                      d_view: *mut c_void, capacity: u32, hash_bytes: u32) -> Result<Self, i32> {
+        require_abi();
+        if hash_bytes == 0 || hash_bytes % 4 != 0 || hash_bytes > HM_PL_MAX_HASH_BYTES { return Err(-1); }
+        Ok(Self { ctx, hashes: d_hashes, feed: d_feed, pos: d_pos, recon: d_recon, view: d_view, capacity, hash_bytes, n: 0 })
+    }
+    pub fn params() -> HmPlaceParams {
+        let mut p = HmPlaceParams { num_similar: 0, num_recent: 0, recent_threshold: 0, search_num: 0 };
+        unsafe { hm_place_params_default(&mut p) };
+        p
+    }
+    pub fn room(p: &HmPlaceParams) -> u32 {
+        unsafe { hm_place_room(p) }
+    }
+    pub fn len(&self) -> u32 {
+        self.n
+    }
+    pub fn is_empty(&self) -> bool {
+        self.n == 0
+    }
+    fn rows(&self, first: u32, count: u32) -> FrameRows {
+        let at = |base: *mut c_void, width: usize| (base as *mut u8).wrapping_add(width * first as usize) as *mut c_void;
+        FrameRows { first, count, hashes: at(self.hashes, self.hash_bytes as usize), feed: at(self.feed, 4), pos: at(self.pos, 4),
+                    recon: at(self.recon, 4), view: at(self.view, 4) }
+    }
+    /// `k` frames appended in insertion order -> where their rows lie.  They have no view until `set_views`: the caller writes
+    /// `HM_PL_NONE` to their recon words with the feed and pos.
+    pub fn append_rows(&mut self, k: u32) -> Result<FrameRows, i32> {
+        if k > self.capacity - self.n { return Err(-6); }
+        let r = self.rows(self.n, k);
+        self.n += k;
+        Ok(r)
+    }
+    /// `Frame::view` of the stored rows `[first, first + k)`: where the caller copies their reconstruction and view keys.
+    pub fn set_views(&self, first: u32, k: u32) -> Result<FrameRows, i32> {
+        if first > self.n || k > self.n - first { return Err(-1); }
+        Ok(self.rows(first, k))
+    }
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the matcher's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn find(&self, d_query: *const c_void, d_visible: *const c_void, nq: u32, params: &HmPlaceParams, room: u32,
+                       d_found: *mut c_void, d_views_out: *mut c_void, d_group_recon: *mut c_void, d_group_start: *mut c_void,
+                       d_free: *mut c_void, d_search: *mut c_void, d_counts: *mut c_void, d_verdict: *mut c_void,
+                       stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = hm_find_frames_batch_device(self.ctx, self.hashes, self.feed, self.pos, self.recon, self.view, self.n, self.hash_bytes,
+                                             d_query, d_visible, nq, params, room, d_found, d_views_out, d_group_recon, d_group_start, d_free,
+                                             d_search, d_counts, d_verdict, stream_to_wait);
         if st == 0 { Ok(()) } else { Err(st) }
     }
 }
