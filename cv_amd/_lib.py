@@ -207,6 +207,8 @@ RS_JP_DEFAULT_MINIMUM_ROBUST_MATCHES, RS_JP_MAX_FEATURES = 256, 9216
 RS_AR_OK, RS_AR_NOT_ACCEPTED, RS_AR_BAD_INDEX, RS_AR_TAKEN, RS_AR_BAD_TABLE = range(5)
 RS_AR_S_TRIPLES, RS_AR_S_FIRST, RS_AR_S_SECOND, RS_AR_S_LANDMARKS = range(4)
 RS_AR_STATS, RS_AR_COUNTS = 4, 4
+RS_RP_OK, RS_RP_BAD_TABLE, RS_RP_BAD_INDEX, RS_RP_BAD_MAP, RS_RP_NO_ROOM = range(5)
+RS_RP_C_ROWS, RS_RP_C_OBSERVATIONS, RS_RP_C_EMPTY_DROPPED, RS_RP_C_ROWS_DROPPED, RS_RP_C_OBS_DROPPED, RS_RP_COUNTS = range(6)
 
 
 class PlaceParams(C.Structure):
@@ -267,6 +269,7 @@ ABI_SYMBOLS = [
     "rs_export_reconstruction_device", "rs_write_ply", "akz_sample_colors_batch_device",
     "rs_join_pairs_batch_device", "rs_add_reconstruction_batch_device",
     "hm_place_params_default", "hm_place_room", "hm_find_frames_batch_device",
+    "rs_repack_table_device", "rs_gather_blocks_device", "rs_repack_constraints_device", "hm_place_remap_views_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
     "akz_comm_unique_id", "akz_comm_create", "akz_comm_destroy", "akz_comm_shift_blocks", "akz_comm_allgather_blocks", "akz_comm_sync",
@@ -435,6 +438,10 @@ def lib():
     L.hm_place_room.restype = u32
     L.hm_place_room.argtypes = [C.POINTER(PlaceParams)]
     L.hm_find_frames_batch_device.argtypes = [vp] * 6 + [u32, u32, vp, vp, u32, C.POINTER(PlaceParams), u32] + [vp] * 9
+    L.rs_repack_table_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u32, vp, u32, u32, u32] + [vp] * 9
+    L.rs_gather_blocks_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, vp]
+    L.rs_repack_constraints_device.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, u32] + [vp] * 6
+    L.hm_place_remap_views_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, vp]
     L.akz_comm_unique_id.argtypes = [vp]
     L.akz_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.akz_comm_destroy.argtypes = [vp]

@@ -97,6 +97,19 @@ class FrameIndex:
         self.recon[rows] = self._words(recon)
         self.view[rows] = self._words(view)
 
+    def remap_views(self, recon, block_map, flags=None, stream_to_wait=None):
+        """hm_place_remap_views_device, in place, behind a repack of reconstruction `recon`: the view of every stored frame of
+        it goes through block_map [n_blocks] (a numpy array or a device tensor of 4-byte words; 0xFFFFFFFF: the view is
+        removed, the frame loses its view — remove_view's frame.view = None).  Enqueued on the matcher's stream behind the
+        current torch stream (or stream_to_wait); no wait -> flags [1] int32 on the device: 1 iff a frame of `recon` names a
+        view >= n_blocks (its row is untouched)."""
+        m = self._words(block_map)
+        if flags is None:
+            flags = self.torch.zeros(1, dtype=self.torch.int32, device=self.dev)
+        call("hm_place_remap_views_device", self.matcher.handle, self.recon, self.view, self.n, int(recon), m, int(m.numel()), flags,
+             _device.wait_or_current(self.torch, stream_to_wait, self.dev))
+        return _device.keep_alive(flags, m, self)
+
     def find_device(self, d_query, d_visible, nq, prm, row_pitch, d_found, d_views_out, d_group_recon, d_group_start, d_free, d_search, d_counts,
                     d_verdict, stream_to_wait=None, n_stored=None):
         """hm_find_frames_batch_device over the table's first n_stored rows (default: all): d_* and stream_to_wait as

@@ -287,6 +287,56 @@ def merge_reconstructions(torch, consensus, dst_table, src_table, d_kps, cap, ca
 
 
 @dataclass
+class RepackedReconstruction:
+    table: object             # repack.RepackTensors: the new table, (lm_room, obs_room) = n_blocks_out * cap as its sizes
+    pools: dict               # name -> the pool moved through the map, [n_blocks_out][...]
+    pool_verdicts: dict       # name -> d_verdict [1] int32 (RS_RP_*)
+    constraints: object       # repack.ConstraintTensors, or None
+    world: object             # [lm_room][4] float64: the robust triangulation of the new table under the moved poses
+    world_reason: object      # [lm_room] uint8
+    regenerate: object        # RegenerateResult, or None
+
+
+def repack(torch, consensus, table, cap, cam, block_map, n_blocks_out, pools, constraints=None, recon_start=None, constraint_start=None,
+           graph_start=None, tri_params=None, **kw):
+    """VSlamData::remove_view (cv-sfm/src/lib.rs:517-546) for every view block_map removes ([n_blocks] u32, 0xFFFFFFFF: removed;
+    None: the identity), the compaction of the table and the renumbering of rows and blocks, with ONE wait at the end and nothing
+    read back in between: the table -> every per-block pool of `pools` (a dict of device tensors [n_blocks][...]; "kps" and
+    "poses" are needed, counts, colours, descriptors ride along) -> the constraints (views, poses, verdict) when given -> the
+    robust triangulation of the new table under the moved poses.  The rooms are n_blocks_out * cap, whatever the input's sizes
+    were: that bounds the table of a chain that never waits.  graph_start [n_graphs + 1] over the NEW blocks: continue into
+    regenerate on the new table (kw: its parameter arguments; its own wait is the one wait then).  -> RepackedReconstruction."""
+    from .repack import TableRepack
+    rp = TableRepack(consensus)
+    dev = table.dev
+    n_blocks = int(pools["poses"].shape[0])
+    first = _device.wait_or_current(torch, None, dev)
+    d_map = rp._map(torch, block_map, dev)               # uploaded once: every call below takes the same tensor
+    t = rp.table_tensors(torch, table, cap, n_blocks, d_map, n_blocks_out, recon_start=recon_start, stream_to_wait=first)
+    moved, verdicts = {}, {}
+    for name, pool in pools.items():
+        moved[name], verdicts[name] = rp.gather_tensors(torch, pool, d_map, n_blocks_out, stream_to_wait=first)
+    cons = None
+    if constraints is not None:
+        cons = rp.constraints_tensors(torch, *constraints, d_map, n_blocks, n_blocks_out, start=constraint_start, stream_to_wait=first)
+    new_table = t.table(torch)
+    tri_params = tri_params or ReconstructionOptimizer.params().triangulate
+    world = new_table.new_world()
+    reason = torch.zeros((max(new_table.n_landmarks, 1),), dtype=torch.uint8, device=dev)
+    triangulate_landmarks_device(consensus._h, new_table, moved["kps"], cap, n_blocks_out, moved["poses"], cam, tri_params, world, reason,
+                                 torch.cuda.current_stream(dev))
+    result = None
+    if graph_start is not None:
+        rs_stream = torch.cuda.ExternalStream(consensus.stream(), device=dev)
+        with torch.cuda.stream(rs_stream):               # regenerate orders itself behind the current torch stream
+            result = regenerate(torch, consensus, new_table, moved["kps"], cap, cam, moved["poses"], graph_start,
+                                np.array([0, t.lm_room], np.uint32) if recon_start is None else t.recon_start_out, reason=reason, **kw)
+    else:
+        consensus.sync()
+    return RepackedReconstruction(t, moved, verdicts, cons, world, reason, result)
+
+
+@dataclass
 class StartResult:
     consensus: tuple          # (d_pose [slots][12], d_best_id, d_inliers [slots][cap], d_n_inliers) of the two-view consensus
     join: object              # bootstrap.JoinTensors

@@ -980,6 +980,59 @@ private:
     bool owned_ = false;
 };
 
+// A reconstruction repacked over rs_repack_table_device, rs_gather_blocks_device and rs_repack_constraints_device:
+// VSlamData::remove_view (cv-sfm/src/lib.rs:517-546) for every view a block map removes at once, the table compacted, rows and
+// blocks renumbered, the per-block pools and the constraints moved along.  A repacked table always fits
+// room(n_blocks_out, cap_per_img) rows and observations.  Contexts and arguments as LandmarkBook's; the calls enqueue and return.
+class TableRepack {
+public:
+    enum Verdict : uint32_t { Ok = RS_RP_OK, BadTable = RS_RP_BAD_TABLE, BadIndex = RS_RP_BAD_INDEX, BadMap = RS_RP_BAD_MAP, NoRoom = RS_RP_NO_ROOM };
+    static constexpr uint32_t kRemoved = 0xFFFFFFFFu;       // a block map's entry for a removed view
+    explicit TableRepack(rs_ctx* ctx) : ctx_(ctx) { akaze::require_abi(); }
+    explicit TableRepack(int device = 0) : owned_(true)
+    {
+        akaze::require_abi();
+        akaze::check(rs_create(device, 8, 1, &ctx_), "rs_create");
+    }
+    ~TableRepack() { if (owned_ && ctx_) rs_destroy(ctx_); }
+    TableRepack(const TableRepack&) = delete;
+    TableRepack& operator=(const TableRepack&) = delete;
+    void table(const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks, uint32_t cap_per_img, uint32_t n_blocks,
+               const void* d_block_map, uint32_t n_blocks_out, const void* d_recon_start, uint32_t n_recons, uint32_t obs_room, uint32_t lm_room,
+               void* d_obs_start_out, void* d_obs_out, void* d_obs_counts_out, void* d_landmarks_out, void* d_key_out, void* d_recon_start_out,
+               void* d_counts_out, void* d_call_verdict, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_repack_table_device(ctx_, d_obs_start, d_obs, n_obs, n_landmarks, cap_per_img, n_blocks, d_block_map, n_blocks_out,
+                                            d_recon_start, n_recons, obs_room, lm_room, d_obs_start_out, d_obs_out, d_obs_counts_out,
+                                            d_landmarks_out, d_key_out, d_recon_start_out, d_counts_out, d_call_verdict, stream_to_wait),
+                     "rs_repack_table_device");
+    }
+    void gather(const void* d_src, void* d_dst, uint32_t row_bytes, uint32_t n_blocks, const void* d_block_map, uint32_t n_blocks_out,
+                void* d_verdict, void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_gather_blocks_device(ctx_, d_src, d_dst, row_bytes, n_blocks, d_block_map, n_blocks_out, d_verdict, stream_to_wait),
+                     "rs_gather_blocks_device");
+    }
+    void constraints(const void* d_views, const void* d_constraint_poses, const void* d_constraint_verdict, uint32_t n_constraints,
+                     const void* d_block_map, uint32_t n_blocks, uint32_t n_blocks_out, const void* d_start, uint32_t n_ranges, void* d_views_out,
+                     void* d_constraint_poses_out, void* d_constraint_verdict_out, void* d_count, void* d_start_out,
+                     void* stream_to_wait = nullptr)
+    {
+        akaze::check(rs_repack_constraints_device(ctx_, d_views, d_constraint_poses, d_constraint_verdict, n_constraints, d_block_map, n_blocks,
+                                                  n_blocks_out, d_start, n_ranges, d_views_out, d_constraint_poses_out, d_constraint_verdict_out,
+                                                  d_count, d_start_out, stream_to_wait),
+                     "rs_repack_constraints_device");
+    }
+    // the rooms no valid repacked table outgrows
+    static uint64_t room(uint32_t n_blocks_out, uint32_t cap_per_img) { return (uint64_t)n_blocks_out * cap_per_img; }
+    void sync() { akaze::check(rs_sync(ctx_), "rs_sync"); }
+    void* stream() { return rs_stream(ctx_); }
+
+private:
+    rs_ctx* ctx_ = nullptr;
+    bool owned_ = false;
+};
+
 // cv-sfm's loop closure between two reconstructions and its normalisation over rs_merge_map_device,
 // rs_incorporate_reconstruction_device and rs_normalize_reconstruction_device: the landmark map of the bridging frame
 // (VSlam::try_merge_reconstructions, cv-sfm/src/lib.rs:2159-2170), incorporate_reconstruction (lib.rs:1817-1887), out of place,

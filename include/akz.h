@@ -494,6 +494,12 @@ int32_t hm_find_frames_batch_device(hm_ctx* ctx, const void* d_hashes, const voi
                                     const void* d_visible, uint32_t nq, const hm_place_params* params, uint32_t room, void* d_found,
                                     void* d_views_out, void* d_group_recon, void* d_group_start, void* d_free, void* d_search,
                                     void* d_counts, void* d_verdict, void* stream_to_wait);
+/* The frame table behind rs_repack_table_device, in place: for the rows whose d_recon is `recon` (not HM_PL_NONE), d_view
+ * becomes d_block_map[view] (NULL: the identity), and a removed view (0xFFFFFFFF) makes d_recon HM_PL_NONE — remove_view's
+ * frame.view = None (cv-sfm/src/lib.rs:519); such a frame appears in d_free from then on.  A view >= n_blocks leaves its row
+ * untouched and sets d_flags [1] u32 to 1 (0 otherwise).  Elementwise, one launch on hm_stream() after stream_to_wait. */
+int32_t hm_place_remap_views_device(hm_ctx* ctx, void* d_recon, void* d_view, uint32_t n_stored, uint32_t recon, const void* d_block_map,
+                                    uint32_t n_blocks, void* d_flags, void* stream_to_wait);
 /* Optional timing of the k-NN kernel launches with HIP events on hm_stream() (bench.py's matcher roofline):
  * hm_timing_get waits for the pending events and returns the accumulated milliseconds / launch count.  A symmetric match
  * whose reverse side is answered from the forward lists counts as ONE launch, and its decision and verification kernels and
@@ -1200,7 +1206,8 @@ int32_t rs_covisibility_record_device(rs_ctx* ctx, const void* d_constraint_verd
 /* flatten_constraints: d_row_start [n_views + 1] and d_row_edges [6 * n_constraints] u32 of rs_pose_graph_relax_batch_device from
  * d_views [n_constraints][3]: view v's row holds the edge ids 6 * constraint + slot whose target is v in ascending order.
  * Refused constraints stay in the rows.  A triple that names a view >= n_views contributes nothing and sets d_flags [1] u32 to 1
- * (0 otherwise); d_row_edges behind d_row_start[n_views] is 0. */
+ * (0 otherwise); d_row_edges behind d_row_start[n_views] is 0.  The triples behind rs_repack_constraints_device's count (views
+ * 0xFFFFFFFF) are skipped this way: with that call's room as n_constraints the rows are those of the count, and the flag reads 1. */
 int32_t rs_pose_graph_rows_device(rs_ctx* ctx, const void* d_views, uint32_t n_constraints, uint32_t n_views, void* d_row_start,
                                   void* d_row_edges, void* d_flags, void* stream_to_wait);
 /* ---- the refinement of registered poses on the device: single-view L2 optimiser and consistency filter ----
@@ -1343,6 +1350,75 @@ int32_t rs_add_views_device(rs_ctx* ctx, const void* d_obs_start, const void* d_
                             uint32_t obs_room, uint32_t lm_room, void* d_poses, void* d_obs_start_out, void* d_obs_out, void* d_counts_out,
                             void* d_landmarks_out, void* d_obs_counts_out, void* d_frame_verdict, void* d_stats, void* d_call_verdict,
                             void* stream_to_wait);
+/* ---- a reconstruction repacked on the device: views removed, the table compacted, rows and blocks renumbered ----
+ * VSlamData::remove_view (cv-sfm/src/lib.rs:517-546) for any set of views at once — what apply_bundle_adjust's removed_views
+ * (:502-515), incorporate_reconstruction (:1880-1884) and try_merge_reconstructions (:2147) ask for — and the compaction the
+ * out-of-place generations of rs_add_views_device never do: tombstones, rows that lost every observation and the empty tail
+ * are dropped, rows and blocks renumbered.  A valid table has at most one row per feature of a kept view, so a repacked table
+ * always fits n_blocks_out * cap_per_img rows and observations, whatever its history.  Integer data movement; the decisions
+ * are include/akz_repack_math.h (compiled for the device and, by the tests, for the host: equal byte for byte), whose head
+ * lists the departures from the reference.
+ * The block map d_block_map [n_blocks] u32: entry b is the new block of old block b, or 0xFFFFFFFF when the view is removed.
+ * NULL is the identity, and then n_blocks_out == n_blocks (else AKZ_E_INVALID).  A map is valid iff every entry is 0xFFFFFFFF
+ * or below n_blocks_out and no two blocks share a target; that is checked on the device (a reference count per target). */
+enum {
+    RS_RP_OK = 0,
+    RS_RP_BAD_TABLE = 1,       /* the starts do not ascend inside [0, n_obs], or d_recon_start does not inside [0, n_landmarks] */
+    RS_RP_BAD_INDEX = 2,       /* an observation of a row names a block >= n_blocks, or a kept one a feature >= cap_per_img */
+    RS_RP_BAD_MAP = 3,         /* the map is not valid */
+    RS_RP_NO_ROOM = 4,         /* the kept rows exceed lm_room or the kept observations obs_room; d_counts_out holds the true numbers */
+    /* d_counts_out words (u32): */
+    RS_RP_C_ROWS = 0,          /* rows kept */
+    RS_RP_C_OBSERVATIONS = 1,  /* observations kept */
+    RS_RP_C_EMPTY_DROPPED = 2, /* empty rows dropped */
+    RS_RP_C_ROWS_DROPPED = 3,  /* rows dropped because every observation was in a removed view */
+    RS_RP_C_OBS_DROPPED = 4,   /* observations dropped */
+    RS_RP_COUNTS = 5
+};
+/* The next generation of the table without the removed views, out of place.  Inputs: the table as
+ * rs_triangulate_landmarks_device takes it (d_obs_start [n_landmarks + 1], d_obs [n_obs][2] {block, feature}; the rows'
+ * observations are the table's, whatever lies behind d_obs_start[n_landmarks] is not read), the map, the optional row ranges of
+ * the reconstructions d_recon_start [n_recons + 1] (NULL with n_recons 0 for none), and the rooms of the outputs — they may be
+ * smaller than the input, and that is the point.  An observation {b, j} is kept iff map[b] != 0xFFFFFFFF; a row is kept iff
+ * it keeps an observation.  Kept rows leave in ascending old key: the new key is the number of kept rows below.  A row's
+ * kept observations stay in order, their block replaced by map[b].
+ * Outputs, in rs_add_views_device's shapes: d_obs_start_out [lm_room + 1] (every start from the kept rows to lm_room equals
+ * the total), d_obs_out [obs_room][2] (not written behind the total), d_obs_counts_out [lm_room] (0 behind the kept rows),
+ * d_landmarks_out [n_blocks_out][cap_per_img], every word written: the new key of the row that lists {block, feature} (the
+ * lowest, where a broken table lists a feature twice), 0xFFFFFFFF for none; d_key_out [n_landmarks]: the new key of every old
+ * row, 0xFFFFFFFF for a dropped one; d_recon_start_out [n_recons + 1]: the kept rows with old key below d_recon_start[r];
+ * d_counts_out [RS_RP_COUNTS]; d_call_verdict [1] (RS_RP_*; where several apply: table, map, index, room in that order).
+ * On any verdict but RS_RP_OK the outputs describe an empty table: every start 0, every count 0, every map word and key
+ * 0xFFFFFFFF, every range start 0, d_obs_out untouched; d_counts_out is 0 unless the verdict is RS_RP_NO_ROOM.  Nothing is
+ * read or written out of bounds, and the caller still holds the old generation.  An output that overlaps an input:
+ * AKZ_E_INVALID; so are cap_per_img or n_blocks 0 and lm_room 0xFFFFFFFF.  Enqueues on rs_stream() after stream_to_wait (may be
+ * NULL) and returns; allocates nothing beyond growing the context's scratch. */
+int32_t rs_repack_table_device(rs_ctx* ctx, const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks,
+                               uint32_t cap_per_img, uint32_t n_blocks, const void* d_block_map, uint32_t n_blocks_out,
+                               const void* d_recon_start, uint32_t n_recons, uint32_t obs_room, uint32_t lm_room, void* d_obs_start_out,
+                               void* d_obs_out, void* d_obs_counts_out, void* d_landmarks_out, void* d_key_out, void* d_recon_start_out,
+                               void* d_counts_out, void* d_call_verdict, void* stream_to_wait);
+/* A per-block pool moved through the map: row map[b] of d_dst [n_blocks_out][row_bytes] is row b of d_src
+ * [n_blocks][row_bytes] for every kept b, every other row of d_dst is zero: every byte is written.  Keypoints, counts, poses,
+ * colours, descriptors, an old d_landmarks_out all move this way.  row_bytes is a multiple of 4 and every pointer 4-byte aligned (else AKZ_E_INVALID); 16-byte
+ * accesses where row_bytes and both pointers allow.  d_verdict [1] u32: RS_RP_OK, or RS_RP_BAD_MAP for a map that is not
+ * valid — d_dst is all zeros then.  d_src and d_dst may not overlap (AKZ_E_INVALID).  rs_stream(), as above. */
+int32_t rs_gather_blocks_device(rs_ctx* ctx, const void* d_src, void* d_dst, uint32_t row_bytes, uint32_t n_blocks, const void* d_block_map,
+                                uint32_t n_blocks_out, void* d_verdict, void* stream_to_wait);
+/* remove_view's retain over the three-view constraints (lib.rs:541-543), ordered and out of place: d_views [n_constraints][3],
+ * d_constraint_poses [n_constraints][2][12] f64 and d_constraint_verdict [n_constraints] as rs_pose_graph_edges_device takes
+ * them.  A constraint is kept iff all three of its views are kept (a view >= n_blocks or a map entry that names no block of the
+ * output drops it too; the map's validity is rs_repack_table_device's to judge).  The kept constraints leave in order with their
+ * views mapped, poses and verdicts moving along, into the same three arrays with room n_constraints; d_count [1] u32.  Behind
+ * the count the views are 0xFFFFFFFF, the verdict RS_TVC_BAD_INDEX and the poses 0, so that a caller can pass the room on as
+ * n_constraints without reading the count: rs_pose_graph_edges_device gives such a triple zero edges,
+ * rs_pose_graph_rows_device leaves it out of the rows (its flag word then reads 1), the relaxation never meets it.  Optional
+ * d_start [n_ranges + 1] u32, ranges of constraints (NULL with n_ranges 0 for none): d_start_out[r] = the kept constraints
+ * below min(d_start[r], n_constraints).  One workgroup-scan launch on rs_stream(), as above. */
+int32_t rs_repack_constraints_device(rs_ctx* ctx, const void* d_views, const void* d_constraint_poses, const void* d_constraint_verdict,
+                                     uint32_t n_constraints, const void* d_block_map, uint32_t n_blocks, uint32_t n_blocks_out,
+                                     const void* d_start, uint32_t n_ranges, void* d_views_out, void* d_constraint_poses_out,
+                                     void* d_constraint_verdict_out, void* d_count, void* d_start_out, void* stream_to_wait);
 /* ---- two reconstructions become one on the device: the landmark map of a bridging frame, incorporate, normalise ----
  * cv-sfm's loop closure between reconstructions (VSlam::try_merge_reconstructions, cv-sfm/src/lib.rs:2116-2193;
  * incorporate_reconstruction, lib.rs:1817-1887) and normalize_reconstruction (lib.rs:2241-2283) over the tables

@@ -179,6 +179,24 @@ extern "C" {
                            d_obs_out: *mut c_void, d_counts_out: *mut c_void, d_landmarks_out: *mut c_void, d_obs_counts_out: *mut c_void,
                            d_frame_verdict: *mut c_void, d_stats: *mut c_void, d_call_verdict: *mut c_void,
                            stream_to_wait: *mut c_void) -> i32;
+    fn rs_repack_table_device(ctx: *mut c_void, d_obs_start: *const c_void, d_obs: *const c_void, n_obs: u32, n_landmarks: u32,
+                              cap_per_img: u32, n_blocks: u32, d_block_map: *const c_void, n_blocks_out: u32,
+                              d_recon_start: *const c_void, n_recons: u32, obs_room: u32, lm_room: u32, d_obs_start_out: *mut c_void,
+                              d_obs_out: *mut c_void, d_obs_counts_out: *mut c_void, d_landmarks_out: *mut c_void,
+                              d_key_out: *mut c_void, d_recon_start_out: *mut c_void, d_counts_out: *mut c_void,
+                              d_call_verdict: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn rs_gather_blocks_device(ctx: *mut c_void, d_src: *const c_void, d_dst: *mut c_void, row_bytes: u32, n_blocks: u32,
+                               d_block_map: *const c_void, n_blocks_out: u32, d_verdict: *mut c_void,
+                               stream_to_wait: *mut c_void) -> i32;
+    fn rs_repack_constraints_device(ctx: *mut c_void, d_views: *const c_void, d_constraint_poses: *const c_void,
+                                    d_constraint_verdict: *const c_void, n_constraints: u32, d_block_map: *const c_void,
+                                    n_blocks: u32, n_blocks_out: u32, d_start: *const c_void, n_ranges: u32,
+                                    d_views_out: *mut c_void, d_constraint_poses_out: *mut c_void,
+                                    d_constraint_verdict_out: *mut c_void, d_count: *mut c_void, d_start_out: *mut c_void,
+                                    stream_to_wait: *mut c_void) -> i32;
+    fn hm_place_remap_views_device(ctx: *mut c_void, d_recon: *mut c_void, d_view: *mut c_void, n_stored: u32, recon: u32,
+                                   d_block_map: *const c_void, n_blocks: u32, d_flags: *mut c_void,
+                                   stream_to_wait: *mut c_void) -> i32;
     fn rs_merge_map_device(ctx: *mut c_void, d_matches: *const c_void, d_nmatches: *const c_void, d_final: *const c_void, d_best: *const c_void,
                            n_world: u32, n_dst_landmarks: u32, cap_per_img: u32, slot: u32, d_counts: *const c_void,
                            d_src_landmarks: *const c_void, n_blocks: u32, bridge_block: u32, d_map: *mut c_void, d_map_count: *mut c_void,
