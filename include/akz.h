@@ -56,7 +56,20 @@ typedef struct akz_config {
  * library's stream waits for the work enqueued on it so far.  NULL = nothing to wait for.  The legacy default stream's
  * own handle is NULL as well, so a caller that enqueues on it (torch without a stream context, plain `<<<>>>` launches)
  * passes AKZ_STREAM_LEGACY — the value of hipStreamLegacy — instead: the library's streams are non-blocking and do NOT
- * synchronise with the default stream on their own. */
+ * synchronise with the default stream on their own.
+ *
+ * What "returns after enqueueing" means for the `*_device` entries.  A call orders its work behind stream_to_wait and returns
+ * while that stream may still be busy; a host index list (`const uint32_t*`) has been read when the call returns, and the
+ * caller may overwrite or free it.  A call waits on the host in these cases only, and its results are the same when it does:
+ *   - rs_* and hm_* entries keep scratch in their context that grows to the largest call so far: a call that needs more than
+ *     the context holds waits for the context's stream — and so for stream_to_wait — before it frees and reallocates.  A
+ *     context in steady use has seen its sizes, and does not wait.
+ *   - hm_* entries that take host lists or build problem descriptors stage them through a ring of four pinned slots, each
+ *     sized on its first use (one such wait per slot, and again when a slot has to grow).  A fifth call while the copies of the
+ *     four before it are still held up waits for the oldest of them: the ring lets the host run four calls ahead, not more.
+ *   - the rs_* entries copy their host lists from the caller's pageable memory with hipMemcpyAsync.  On the ROCm runtime this
+ *     was measured on, the copy of a list of a few words is staged at once and the call returns; the library does not control
+ *     that ("Enqueue contract"). */
 #define AKZ_STREAM_LEGACY ((void*)1)
 
 /* akaze::KeyPoint — akaze/src/lib.rs:69-93. point=(x,y). 28 bytes, no padding. */

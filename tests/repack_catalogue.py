@@ -192,6 +192,61 @@ def table_cases():
     return cases
 
 
+SUMS_PASS = 256                          # tile sums one trip of k_rp_scan_sums takes (kRpBlock of cv_amd/csrc/rs_repack.hip)
+SUMS_CAP = 4096                          # features per view of the tables below: BIG_LIVE * SUMS_CAP rows have room
+
+
+def tile_sums_case(name, n, doomed):
+    """n rows of ONE observation each, built with numpy alone: row r observes live view r % BIG_LIVE at feature r // BIG_LIVE;
+    the k-th row of `doomed` observes a doomed view alone and loses everything under BIG_MAP.  No feature is handed out twice."""
+    doomed = np.array(sorted(doomed), np.int64)
+    assert n <= BIG_LIVE * SUMS_CAP and (len(doomed) == 0 or (doomed[0] >= 0 and doomed[-1] < n))
+    r = np.arange(n, dtype=np.int64)
+    obs = np.stack([r % BIG_LIVE, r // BIG_LIVE], 1)
+    k = np.arange(len(doomed), dtype=np.int64)
+    obs[doomed] = np.stack([BIG_LIVE + k % (BIG_BLOCKS - BIG_LIVE), k // (BIG_BLOCKS - BIG_LIVE)], 1)
+    c = Case(name, [], BIG_BLOCKS, BIG_MAP, BIG_LIVE, start=np.arange(n + 1), cap=SUMS_CAP, statement=False)
+    c.obs, c.n_obs, c.doomed = np.ascontiguousarray(obs.astype(np.uint32)).reshape(-1, 2), n, doomed
+    return c
+
+
+def tile_sums_cases():
+    """Tables on either side of one trip of the tile-sum scan: SUMS_PASS tiles exactly, one row more, three rows more.  The rows
+    removed are sparse — one in TILE + 7, so every tile and every trip keeps a sum that is not zero and no two tiles lose the
+    same place — plus the rows next to the trip's boundary: the last of the first trip in every table and, where the second trip
+    has more than one row, one of its own between two kept ones."""
+    edge = SUMS_PASS * TILE
+    sparse = set(range(5, edge, TILE + 7))
+    return [tile_sums_case("rows_256T", edge, sparse | {edge - 1}),
+            tile_sums_case("rows_256T+1", edge + 1, sparse | {edge - 1}),
+            tile_sums_case("rows_256T+3", edge + 3, sparse | {edge - 1, edge + 1})]
+
+
+def direct_table(case):
+    """The answer for a tile_sums_case-like table — every row one observation, a valid map, rooms that hold everything — by
+    numpy alone, not through the host build: the kept rows close up in order."""
+    o = blank(case)
+    m = np.array(case.list_map(), np.uint32)
+    obs = case.obs[:case.n_landmarks]
+    assert np.array_equal(case.start, np.arange(case.n_landmarks + 1)) and case.recon_start is None
+    to = m[obs[:, 0]]
+    keep = to != NONE
+    rows = int(keep.sum())
+    assert rows <= case.lm_room and rows <= case.obs_room
+    o["obs_start_out"][:rows] = np.arange(rows)
+    o["obs_start_out"][rows:] = rows
+    o["obs_counts_out"][:case.lm_room] = 0
+    o["obs_counts_out"][:rows] = 1
+    o["obs_out"][:rows] = np.stack([to[keep], obs[keep, 1]], 1)
+    o["landmarks_out"][:case.n_blocks_out] = NONE
+    o["landmarks_out"][to[keep], obs[keep, 1]] = np.arange(rows, dtype=np.uint32)
+    o["key_out"][:case.n_landmarks] = NONE
+    o["key_out"][np.flatnonzero(keep)] = np.arange(rows, dtype=np.uint32)
+    o["counts_out"][:] = (rows, rows, 0, case.n_landmarks - rows, case.n_landmarks - rows)
+    o["call_verdict"][0] = OK
+    return o
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 def blank(case):
     """the output arrays of a table call, every word POISON"""
@@ -310,6 +365,26 @@ def host_gather(src, row_bytes, n_blocks, block_map, n_blocks_out):
     m = None if block_map is None else np.array(block_map, np.uint32)
     assert _lib().rp_gather(ptr(src), ptr(dst), row_bytes, n_blocks, ptr(m), n_blocks_out, ptr(verdict)) == 0
     return dst, verdict
+
+
+# (row_bytes, (src offset, dst offset), blocks): rows around the edges of k_rp_gather's unroll (256 units a slot), of its grid
+# (1024 units a workgroup), the workload's row (cap 8192 x 28 bytes) and one beyond the grid's cap (256 workgroups x 1024 units)
+GATHER_LONG_ROWS = ([(16 * u, (0, 0), 9) for u in (255, 256, 257, 1023, 1024, 1025)] + [(229376, (0, 0), 5), (16 * (262144 + 1), (0, 0), 3)] +
+                    [(4 * 257, (4, 4), 9), (4 * 1025, (4, 4), 9), (4 * (262144 + 1), (4, 4), 3)])
+
+
+def direct_gather(src, block_map, n_blocks_out):
+    """the answer of a gather under a VALID map (or None, the identity) by numpy alone: row map[b] of dst is row b of src, a
+    row nothing maps to is zeros"""
+    dst = np.zeros((n_blocks_out, src.shape[1]), np.uint8)
+    if block_map is None:
+        dst[:] = src[:n_blocks_out]
+        return dst
+    m = np.asarray(block_map, np.uint32)
+    kept = np.flatnonzero(m != NONE)
+    assert len(set(m[kept].tolist())) == len(kept) and (len(kept) == 0 or int(m[kept].max()) < n_blocks_out)
+    dst[m[kept]] = src[kept]
+    return dst
 
 
 # ---- the constraints -----------------------------------------------------------------------------------------------------------

@@ -7,7 +7,8 @@ tables are clean and small enough to walk in Python the device's buffers are hel
 Shapes: T = RS_LT_TILE rows of either table are one workgroup's tile of the scans (256 threads x 4 rows), the workgroup that
 scans the tile sums takes 256 of them per pass; a row whose lists hold more than 64 entries together is walked by its wave, 64
 entries a step; cap_per_img = 8 and at most 40 blocks, so the large tables list a {block, feature} in many rows — the kernels
-do not care, d_landmarks_out takes the lowest key on both sides."""
+do not care, d_landmarks_out takes the lowest key on both sides.  One test stands on either side of the 65 536 blocks up to which
+the destination's blocks are marked in an LDS bitmap."""
 import numpy as np
 import pytest
 
@@ -166,6 +167,54 @@ def test_rows_at_the_wave_walks_boundaries_on_both_sides_of_a_tile_boundary(gpu,
     assert np.all(keys[T + 10 + np.arange(1, 6)] >= 2 * T + 5)                     # new rows
     skipped = dict(inp, skip=np.array([1 if k % 3 == 0 else 0 for k in range(len(SRC_BLOCKS))], np.uint32))
     check(gpu, cons, skipped)
+
+
+LDS_BLOCKS = 65536                       # kIrLdsBlocks of cv_amd/csrc/rs_reconstruction_merge.hip:46
+
+
+def many_blocks_case(n_blocks, dst_blocks, src_views, cap, skip=None):
+    """Two small clean tables in a pool of n_blocks blocks.  The destination's rows name dst_blocks in turn and, once, a block
+    that is not the pool's; the source's name src_views, the bridging frame's block 2 and a block that is not the pool's."""
+    outside = n_blocks + 3
+    bridge = 2
+    dst_rows = [[(b, k % cap)] + ([(bridge, 0)] if k == 0 else []) for k, b in enumerate(dst_blocks)] + [[(dst_blocks[0], cap - 1), (outside, 0)], []]
+    src_rows = [[(v, f) for v in src_views] for f in range(cap)] + [[(bridge, 1)], [(outside, 0)]]
+    pairs = [(0, 1), (len(src_rows) - 2, 0)]
+    inp = K.incorporate_inputs(dst_rows, src_rows, pairs, src_views, bridge, cap=cap, n_blocks=8, skip=skip, seed=n_blocks)
+    few = inp["poses"]
+    inp["poses"] = np.ascontiguousarray(few[np.arange(n_blocks) % len(few)] + (np.arange(n_blocks) // len(few))[:, None] * 1e-3)
+    inp["n_blocks"] = n_blocks
+    return inp
+
+
+@pytest.mark.parametrize("n_blocks", [LDS_BLOCKS, LDS_BLOCKS + 1])
+def test_destination_blocks_on_either_side_of_the_lds_bitmap(gpu, cons, n_blocks):
+    """cv_amd/csrc/rs_reconstruction_merge.hip:115, k_ir_check: `in_lds = n_blocks <= kIrLdsBlocks` with kIrLdsBlocks = 65536
+    — up to 65536 blocks the destination's blocks are marked in an LDS bitmap and its set bits handed on, above it they go to
+    the block words with global atomics.  65536 is the last size of the first branch, 65537 the first of the second.  The
+    destination names block 0, block 65535 (the last bit of the bitmap's last word) and, at 65537, block 65536; the source's
+    views lie on both sides of them.  Kept marks and destination marks must be the statement's: a clean merge where the views
+    are no destination's, SHARED_BLOCK where a kept view is block 65535 or block 65536 — a mark missed at the edge would merge,
+    one too many would refuse.  An observation whose block is not the pool's is skipped by both branches: it marks nothing, and
+    the row keeps it as it is.  cap_per_img 1 and 2."""
+    top = n_blocks - 1
+    dst_blocks = [0, LDS_BLOCKS - 1] + ([LDS_BLOCKS] if n_blocks > LDS_BLOCKS else [])
+    for cap in (1, 2):
+        # the source's views around the destination's blocks: nothing shared
+        clean = many_blocks_case(n_blocks, dst_blocks, [1, LDS_BLOCKS - 3, LDS_BLOCKS - 2], cap)
+        want = check(gpu, cons, clean, statement=True)
+        assert want["call_verdict"][0] == K.OK and want["counts_out"][2] == 2 and want["counts_out"][5] >= 2
+        assert np.any(want["obs_out"][:, 0] == n_blocks + 3)                       # the outside observation stays in its row
+        skipped = many_blocks_case(n_blocks, dst_blocks, [1, LDS_BLOCKS - 3, top], cap, skip=[0, 0, 1])
+        assert check(gpu, cons, skipped, statement=True)["call_verdict"][0] == K.OK    # a skipped view is not kept: at 65536 blocks `top` is the destination's and refuses nothing
+        # a kept view that the destination names: the first block, the last bit of the bitmap, the block above it
+        for shared in dst_blocks:
+            both = many_blocks_case(n_blocks, dst_blocks, [1, LDS_BLOCKS - 3, shared], cap)
+            assert check(gpu, cons, both, statement=True)["call_verdict"][0] == K.SHARED_BLOCK, shared
+    if n_blocks > LDS_BLOCKS:
+        # the destination stops below the boundary, the source's views straddle it
+        straddle = many_blocks_case(n_blocks, [0, LDS_BLOCKS - 1], [LDS_BLOCKS - 2, LDS_BLOCKS], 2)
+        assert check(gpu, cons, straddle, statement=True)["call_verdict"][0] == K.OK
 
 
 @pytest.mark.parametrize("name", list(K.designed_incorporate_cases()))

@@ -6,8 +6,9 @@ the stages that read it — triangulation, export, relaxation, merge_reconstruct
 Run with -m gpu.
 
 Shapes: T = RS_LT_TILE rows are one workgroup's tile of the scans (256 threads x 4 rows); a row of more than 64 observations
-is walked by its wave; the constraints are compacted 256 at a time by one workgroup; the gather takes 16-byte words where the row
-length and both pointers allow and 4-byte words elsewhere."""
+is walked by its wave; the tile sums are scanned 256 at a time by one workgroup, and so are the constraints compacted; the gather
+takes 16-byte words where the row length and both pointers allow and 4-byte words elsewhere, four a lane and trip, on a grid of at
+most 256 x 65 535 workgroups."""
 import numpy as np
 import pytest
 
@@ -85,6 +86,22 @@ def test_table_calls_back_to_back_share_the_scratch(gpu, cons):
         assert explain(device_table(gpu, cons, BY_NAME[name]), cat.host_table(BY_NAME[name])) is None, name
 
 
+@pytest.mark.parametrize("case", cat.tile_sums_cases(), ids=repr)
+def test_table_rows_beyond_one_pass_of_the_tile_sums(gpu, cons, case):
+    """cv_amd/csrc/rs_repack.hip:149, k_rp_scan_sums: `for (t0 = 0; t0 < n_tiles; t0 += kRpBlock)` with kRpBlock = 256 tile sums
+    a trip behind a running carry.  256 x 1024 rows are 256 tiles, the last size of one trip; 256 x 1024 + 1 and + 3 rows give
+    a 257th tile and the second trip, whose offsets are the carry of the first.  One observation a row, rows removed sparsely
+    (every tile and every trip keeps a sum that is not zero) and on both sides of row 256 x 1024.  Every output byte against the
+    host build and against the answer numpy gives directly (tests/test_repack_math.py ties the two to the statement)."""
+    edge = cat.SUMS_PASS * cat.TILE
+    assert cat.TILE == 1024 and case.n_landmarks in (edge, edge + 1, edge + 3)
+    assert (case.n_landmarks + cat.TILE - 1) // cat.TILE == (cat.SUMS_PASS if case.n_landmarks == edge else cat.SUMS_PASS + 1)
+    want = cat.host_table(case)
+    assert int(want["call_verdict"][0]) == cat.OK and cat.same(want, cat.direct_table(case)) is None
+    assert int(want["counts_out"][0]) == case.n_landmarks - len(case.doomed) and len(case.doomed) > 250
+    assert explain(device_table(gpu, cons, case), want) is None
+
+
 # ---- the pools ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("offsets", [(0, 0), (4, 0), (0, 4), (4, 4)], ids=lambda o: "src+%d_dst+%d" % o)
 @pytest.mark.parametrize("row_bytes", cat.GATHER_ROW_BYTES)
@@ -118,9 +135,83 @@ def test_gather_device_is_the_host_build_in_every_byte(gpu, cons, row_bytes, off
         assert int(d_verdict.cpu().numpy().view(np.uint32)[0]) == expect, name
 
 
+def gather_once(torch, cons, src, row_bytes, nb, block_map, out, offsets):
+    """one rs_gather_blocks_device call between 16-byte bands of 0xA5 -> (dst rows [out][row_bytes], the verdict); the bands
+    are asserted untouched"""
+    from cv_amd import _lib
+    from cv_amd.repack import TableRepack
+    dev = torch.device("cuda", 0)
+    n = out * row_bytes
+    d_src = torch.zeros(src.size + 32, dtype=torch.uint8, device=dev)
+    d_dst = torch.full((n + 48,), 0xA5, dtype=torch.uint8, device=dev)
+    so, do = 16 + offsets[0], 16 + offsets[1]
+    d_src[so:so + src.size] = torch.from_numpy(src.reshape(-1)).to(dev)
+    d_verdict = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    d_map = None if block_map is None else _lib.device_bytes(torch, np.asarray(block_map, np.uint32), dev)
+    TableRepack(cons).gather_device(d_src.data_ptr() + so, d_dst.data_ptr() + do, row_bytes, nb, d_map, out, d_verdict,
+                                    stream_to_wait=_lib.wait_handle(torch.cuda.current_stream(dev)))
+    cons.sync()
+    got = d_dst.cpu().numpy()
+    assert np.all(got[:do] == 0xA5) and np.all(got[do + n:] == 0xA5)
+    return got[do:do + n].reshape(out, row_bytes), int(d_verdict.cpu().numpy().view(np.uint32)[0])
+
+
+def first_difference(got, want):
+    bad = np.flatnonzero(got.reshape(-1) != want.reshape(-1))
+    return None if len(bad) == 0 else (len(bad), bad[:8], got.reshape(-1)[bad[:8]], want.reshape(-1)[bad[:8]])
+
+
+@pytest.mark.parametrize("row_bytes,offsets,nb", cat.GATHER_LONG_ROWS, ids=lambda v: str(v).replace(" ", ""))
+def test_gather_rows_across_the_unroll_the_grid_and_its_cap(gpu, cons, row_bytes, offsets, nb):
+    """cv_amd/csrc/rs_repack.hip:282-293, k_rp_gather: a workgroup of kRpBlock = 256 lanes takes kUnroll = 4 units a lane and
+    trip, unit u0 + k * 256 in slot k, so a row of at most 256 units uses slot 0 alone, 257 .. 1024 the slots above it with a
+    partial tail, and beyond 1024 units a second workgroup (rs_repack.hip:452, gx = ceil(units / 1024)); gx is capped at 256
+    (rs_repack.hip:453), so a row of 256 x 1024 + 1 units sends workgroup 0 on a second trip of the inner loop.  Units are 16
+    bytes where the row length and both pointers allow and 4 bytes elsewhere.  229 376 bytes is the workload's own row (cap 8192
+    x 28 bytes: 14 336 units, gx = 14).  The map removes one view and permutes the rest."""
+    wide = row_bytes % 16 == 0 and offsets == (0, 0)
+    units = row_bytes // (16 if wide else 4)
+    assert (row_bytes, wide) in {(16 * u, True) for u in (255, 256, 257, 1023, 1024, 1025, 14336, 262145)} | {(4 * u, False) for u in (257, 1025, 262145)}
+    assert units in (255, 256, 257, 1023, 1024, 1025, 14336, 262145)
+    gone = nb // 2
+    order = [b for b in range(nb) if b != gone]
+    block_map = np.full(nb, cat.NONE, np.uint32)
+    block_map[order] = np.roll(np.arange(nb - 1)[::-1], 1)                         # reversed and turned by one
+    src = cat.pool(nb, row_bytes)
+    want = cat.direct_gather(src, block_map, nb - 1)
+    if row_bytes <= 16 * 1025:
+        host, verdict = cat.host_gather(src, row_bytes, nb, [int(m) for m in block_map], nb - 1)
+        assert int(verdict[0]) == cat.OK and np.array_equal(host, want)
+    got, verdict = gather_once(gpu, cons, src, row_bytes, nb, block_map, nb - 1, offsets)
+    assert verdict == cat.OK and first_difference(got, want) is None
+
+
+@pytest.mark.parametrize("out,mapped", [(65534, True), (65535, True), (65536, True), (65536, False)],
+                         ids=lambda v: str(v))
+def test_gather_row_counts_across_the_cap_of_the_grids_second_dimension(gpu, cons, out, mapped):
+    """cv_amd/csrc/rs_repack.hip:453 launches min(n_blocks_out, 65535) workgroups in y and rs_repack.hip:278 strides over the rows
+    with gridDim.y: at 65536 rows workgroup 0 takes a second row, row 65535.  Rows of 16 bytes; with a map (one view removed, the
+    rest reversed) and, at 65536, with the null map of the identity, where n_blocks_out == n_blocks."""
+    nb = out + 1 if mapped else out
+    block_map = None
+    if mapped:
+        block_map = np.full(nb, cat.NONE, np.uint32)
+        block_map[[b for b in range(nb) if b != 7]] = np.arange(out, dtype=np.uint32)[::-1]
+    src = cat.pool(nb, 16)
+    want = cat.direct_gather(src, block_map, out)
+    host, verdict = cat.host_gather(src, 16, nb, None if block_map is None else [int(m) for m in block_map], out)
+    assert int(verdict[0]) == cat.OK and np.array_equal(host, want)
+    got, verdict = gather_once(gpu, cons, src, 16, nb, block_map, out, (0, 0))
+    assert verdict == cat.OK and first_difference(got, want) is None
+    assert np.array_equal(got[out - 1], src[0 if mapped else out - 1])              # the last row is one of the source's
+
+
 # ---- the constraints -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [0, 1, 255, 256, 257])
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 513])
 def test_constraints_device_is_the_host_build_in_every_byte(gpu, cons, n):
+    """cv_amd/csrc/rs_repack.hip:308, k_rp_constraints: ONE workgroup compacts kRpBlock = 256 constraints a trip behind a
+    running carry.  0, 1, 255 and 256 constraints are one trip, 257 two, 513 three: the third starts from a carry that was
+    itself added to a carry."""
     from cv_amd import _lib
     from cv_amd.repack import TableRepack
     torch = gpu

@@ -136,7 +136,7 @@ def test_gather_moves_rows_and_zeroes_the_rest(case, row_bytes):
 
 
 # ---- the constraints -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [0, 1, 255, 256, 257])
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 513])
 @pytest.mark.parametrize("gone", [(), (0,), (4,), (8,), (1, 7), tuple(range(9))])
 def test_constraints_are_the_statements_retain(n, gone):
     nb = 9
@@ -186,3 +186,45 @@ def test_frames_follow_their_views():
     assert [g[0] for g in got] == [w[0] for w in want]
     assert [g[1] for g in got if g[0] is not None] == [w[1] for w in want if w[0] is not None]
     assert int(cat.host_frames(recon[:6], view[:6], 0, block_map, nb)[2][0]) == 0
+
+
+def test_the_direct_answer_of_a_one_observation_table_is_the_host_builds_and_the_statements():
+    """cat.direct_table (numpy alone) is what the GPU test holds the tables beyond one pass of the tile sums to next to the host
+    build: here the three are tied together on a table small enough for the statement — three tiles, rows removed at the first
+    and last place of a tile — and the direct answer and the host build on the large tables themselves."""
+    small = cat.tile_sums_case("three_tiles", 2 * cat.TILE + 1, {0, 5, cat.TILE - 1, cat.TILE, 2 * cat.TILE})
+    direct = cat.direct_table(small)
+    assert cat.same(direct, cat.host_table(small)) is None
+    assert cat.same(direct, cat.statement_table(small)) is None
+    assert int(direct["counts_out"][0]) == 2 * cat.TILE + 1 - 5
+    for case in cat.tile_sums_cases():
+        direct = cat.direct_table(case)
+        assert cat.same(direct, cat.host_table(case)) is None, case.name
+        edge = cat.SUMS_PASS * cat.TILE
+        k = direct["key_out"]
+        assert k[edge - 1] == cat.NONE and k[edge - 2] != cat.NONE                  # removed below the boundary of the trips
+        tiles = np.add.reduceat((k[:case.n_landmarks] != cat.NONE).astype(np.int64), np.arange(0, case.n_landmarks, cat.TILE))
+        assert np.all(tiles > 0) and np.count_nonzero(tiles[:cat.SUMS_PASS] < cat.TILE) > 250    # every tile keeps rows, most lose one
+        if case.n_landmarks > edge:
+            assert k[edge] == edge - len(case.doomed[case.doomed < edge])           # the carry of the first trip
+        if case.n_landmarks == edge + 3:
+            assert k[edge + 1] == cat.NONE and k[edge + 2] == k[edge] + 1           # removed above it, between two kept rows
+
+
+def test_the_direct_answer_of_a_gather_is_the_host_builds():
+    """cat.direct_gather (numpy alone) stands in for the host build at the rows of megabytes tests/test_gpu_repack.py moves: here
+    the two agree on every accepted case of the catalogue, at every row length of the small table"""
+    for row_bytes in cat.GATHER_ROW_BYTES:
+        for name, nb, block_map, out, expect in cat.gather_cases():
+            if expect != cat.OK:
+                continue
+            src = cat.pool(nb, row_bytes)
+            host, verdict = cat.host_gather(src, row_bytes, nb, block_map, out)
+            assert int(verdict[0]) == cat.OK and np.array_equal(host[:out], cat.direct_gather(src, block_map, out)), (name, row_bytes)
+    for row_bytes, _, nb in cat.GATHER_LONG_ROWS:                                  # and at the long rows the host build still takes in a moment
+        if row_bytes > 16 * 1025:
+            continue
+        m, out = cat.compact(nb, {nb // 2})
+        src = cat.pool(nb, row_bytes)
+        host, _ = cat.host_gather(src, row_bytes, nb, m, out)
+        assert np.array_equal(host, cat.direct_gather(src, m, out)), row_bytes
