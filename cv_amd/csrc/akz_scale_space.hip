@@ -24,6 +24,7 @@
 // the image is evaluated at its clamped coordinate.  That is exactly what the reference's
 // edge-replicated scratch rows/columns produce stage by stage.
 #include "akz_ctx.h"
+#include "akz_det_window.h"
 #include <type_traits>
 
 // ---- the three arithmetic orders that live in un-vendored crates of the reference ([3P-unverified]) ----
@@ -2358,7 +2359,8 @@ template <int SG>  // SG = deriv_sigma (2, 3 or 4); 0 = generic (direct global g
 __global__ __launch_bounds__(256) void k_deriv_second_cand(const float2* __restrict__ Lxy, float* __restrict__ Ldet,
                                                            int w, int h, size_t fs, int s, OffK k, float sigma_quat,
                                                            CandParams cp, CandU* __restrict__ cand,
-                                                           uint32_t* __restrict__ ncand, uint32_t* __restrict__ err)
+                                                           uint32_t* __restrict__ ncand, uint32_t* __restrict__ err,
+                                                           int tx_org, int ty_org)
 {
     constexpr int TW = 64, TH = 32, GW = TW + 2, GH = TH + 2;
     constexpr int HL = (SG > 0 ? SG : 1) + 1;            // halo of the staged {Lx,Ly} tile
@@ -2366,7 +2368,7 @@ __global__ __launch_bounds__(256) void k_deriv_second_cand(const float2* __restr
     __shared__ float s_d[GH * GW];
     __shared__ float2 s_xy[SG > 0 ? SH * SW : 1];
     const int frame = blockIdx.z;
-    const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
+    const int tx0 = (tx_org + (int)blockIdx.x) * TW, ty0 = (ty_org + (int)blockIdx.y) * TH;   // the grid starts at tile (tx_org, ty_org)
     const float2* D = Lxy + (size_t)frame * fs;
     if (SG > 0) {
         // stage {Lx,Ly} at CLAMPED coordinates: consecutive lanes read consecutive 8-byte pixels of a row
@@ -2445,7 +2447,8 @@ template <int SG, int TH, int NT>
 __global__ __launch_bounds__(NT) void k_deriv_second_cand2(const float2* __restrict__ Lxy, float* __restrict__ Ldet,
                                                             int w, int h, size_t fs, int n, OffK k, float sigma_quat,
                                                             CandParams cp, CandU* __restrict__ cand,
-                                                            uint32_t* __restrict__ ncand, uint32_t* __restrict__ err)
+                                                            uint32_t* __restrict__ ncand, uint32_t* __restrict__ err,
+                                                            int tx_org, int ty_org)
 {
     constexpr int TW = 64;
     constexpr int CS = TW + 16, RS = TH + 2 + 2 * SG;    // staged tiles: x = tx0 - 8 + col, y = ty0 - 1 - SG + row
@@ -2457,7 +2460,7 @@ __global__ __launch_bounds__(NT) void k_deriv_second_cand2(const float2* __restr
     const int fa = 2 * (int)tile.z;
     const bool has_b = fa + 1 < n;
     const int fb = has_b ? fa + 1 : fa;
-    const int tx0 = (int)tile.x * TW, ty0 = (int)tile.y * TH;
+    const int tx0 = (tx_org + (int)tile.x) * TW, ty0 = (ty_org + (int)tile.y) * TH;   // the grid starts at tile (tx_org, ty_org)
     const int tid = threadIdx.x;
     const float2* Da = Lxy + (size_t)fa * fs;
     const float2* Db = Lxy + (size_t)fb * fs;
@@ -2615,6 +2618,11 @@ __global__ __launch_bounds__(NT) void k_deriv_second_cand2(const float2* __restr
 //     strictly greater than their maximum);
 //   * candidates (rare) collect in a small LDS buffer private to the wave and reach the frame's list with one atomic
 //     per flush.
+// The launch covers a WINDOW [x0, x1) x [y0, y1) of candidate positions (AkzDetWindow, akz_det_window.h), not the plane:
+// band b answers for columns x0 + b * BW .., segment s for rows y0 + s * seg_rows ...  Without the Ldet tap the window is
+// the level's candidate range (the pixels that pass the border test, akz_plan.cpp) and the ring of 10 sqrt(2) sigma pixels
+// outside it is neither fetched nor computed, but for the HB columns and 1 + SG rows of input that the window's own
+// determinant ring needs (read at clamped coordinates as before); with the tap (WRITE_DET) the window is the whole plane.
 template <int SG>
 __device__ __forceinline__ float off_combine_s(const OffK k, float a, float b, float c)
 {
@@ -2627,8 +2635,7 @@ __device__ __forceinline__ float off_combine_s(const OffK k, float a, float b, f
     else return __builtin_fmaf(c, k.n, __builtin_fmaf(b, k.m, pa));
 }
 
-constexpr int det_stream_halo(int SG) { return (SG + 2) & ~1; }                    // columns each side: even, >= SG + 1
-constexpr int det_stream_band(int SG) { return 128 - 2 * det_stream_halo(SG); }     // useful columns per wave
+// (det_stream_halo, det_stream_band: akz_det_window.h)
 
 // value of lane (lane - N) [N > 0] or (lane + |N|) [N < 0] of the WAVE, 0 beyond its ends: DPP wave_shr:1 /
 // wave_shl:1 (GFX9 encodings 0x138 / 0x130, one lane per instruction; two hops for |N| = 2)
@@ -2666,7 +2673,7 @@ template <int SG, bool WRITE_DET>
 __global__ __launch_bounds__(256) void k_det_stream(const float2* __restrict__ Lxy, float* __restrict__ Ldet, int w, int h,
                                                     size_t fs, OffK k, float sigma_quat, CandParams cp,
                                                     CandU* __restrict__ cand, uint32_t* __restrict__ ncand,
-                                                    uint32_t* __restrict__ err, int nbands, int seg_rows)
+                                                    uint32_t* __restrict__ err, int nbands, int seg_rows, AkzDetWindow win)
 {
     constexpr int NR = 2 * SG + 1;                 // ring length = unroll factor
     constexpr int KC = (SG + 1) / 2;               // neighbour lanes (2 pixels each) needed on either side
@@ -2684,13 +2691,14 @@ __global__ __launch_bounds__(256) void k_det_stream(const float2* __restrict__ L
     const int frame = (int)(gridDim.y - 1u - blockIdx.y);
     const int item = (int)blockIdx.x * 4 + wv;
     const int band = item % nbands, seg = item / nbands;
-    const int ys = seg * seg_rows;
-    if (ys >= h) return;                            // whole wave (no block barrier anywhere)
-    const int ye = min(ys + seg_rows, h);
+    // the wave answers for rows [ys, ye) and columns [bx, ux_hi) of the window `win`
+    const int ys = win.y0 + seg * seg_rows;
+    if (ys >= win.y1) return;                       // whole wave (no block barrier anywhere)
+    const int ye = min(ys + seg_rows, win.y1);
     // the lane's columns x0, x0 + 1 and the useful columns [bx, ux_hi) of the band
-    const int bx = band * BW;
+    const int bx = win.x0 + band * BW;
     const int x0 = bx - HB + 2 * lane;
-    const int ux_hi = min(bx + BW, w);
+    const int ux_hi = min(bx + BW, win.x1);
     const float2* D = Lxy + (size_t)frame * fs;
     const int cx0 = clampi(x0, 0, w - 1), cx1 = clampi(x0 + 1, 0, w - 1);
     const size_t list = (size_t)frame * kAkzMaxLevels + cp.level;
@@ -3541,32 +3549,36 @@ struct LevelPass {
         float* ldet_out = c->keep_all ? S.Ldet[i] : nullptr;   // refinement reads the candidates' own 3x3 values
         CandU* cand = (CandU*)S.d_cand_u;
         if (R.sigma_fused) akz_timer_begin(c, AKZ_T_DET_SG2 + (int)L.deriv_sigma - 2, s_det);
-        if (!R.sigma_fused) {   // any other derivative sigma: the generic tile kernel
-            AKZ_LAUNCH((k_deriv_second_cand<0>), dim3(akz_div_up(L.w, 64), akz_div_up(L.h, 32), n), dim3(256), 0, s_det, S.Lxy[i], ldet_out,
-                       L.w, L.h, fs, (int)L.deriv_sigma, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err);
+        // The pass visits the candidate window of the level (akz_det_window.h) and not the ring outside it, where the border
+        // test admits no candidate; with the Ldet tap on it visits the whole plane.  A level too small to hold a candidate
+        // launches nothing: its counter keeps the zero that contrast_factor's memset gave it.
+        const AkzDetWindow win = akz_det_window(L.w, L.h, L.cand_x_lo, L.cand_x_hi, L.cand_y_lo, L.cand_y_hi, ldet_out != nullptr);
+        if (win.empty()) {
+            // (no launch; the timer below still closes its interval)
+        } else if (!R.sigma_fused) {   // any other derivative sigma: the generic tile kernel
+            const AkzDetTileGrid T = akz_det_tile_grid(win, L.w, L.h, 64, 32);
+            AKZ_LAUNCH((k_deriv_second_cand<0>), dim3(T.ntx, T.nty, n), dim3(256), 0, s_det, S.Lxy[i], ldet_out,
+                       L.w, L.h, fs, (int)L.deriv_sigma, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err, T.tx0, T.ty0);
         } else {
             with_sigma(L.deriv_sigma, [&](auto sg) {
                 constexpr int SG = decltype(sg)::value;
                 if (R.stream) {
-                    // streaming kernel: a wave per (band of columns, segment of rows, frame); segments sized so that the
-                    // launch holds a few waves per SIMD of the chip, never shorter than 32 rows (each segment re-reads
-                    // 2 sigma + 2 rows of warm-up)
-                    const int nb = akz_div_up(L.w, det_stream_band(SG));
-                    int nseg = akz_div_up(c->det_stream_waves, nb * n);
-                    const int max_seg = akz_div_up(L.h, 32);
-                    nseg = nseg < 1 ? 1 : (nseg > max_seg ? max_seg : nseg);
-                    const int seg_rows = akz_div_up(L.h, nseg);
-                    nseg = akz_div_up(L.h, seg_rows);
+                    // streaming kernel: a wave per (band of columns, segment of rows, frame) of the window; segments sized
+                    // so that the launch holds a few waves per SIMD of the chip, never shorter than 32 rows (each segment
+                    // re-reads 2 sigma + 2 rows of warm-up)
+                    const AkzDetStreamGrid G = akz_det_stream_grid(win, det_stream_band(SG), c->det_stream_waves, n);
                     with_bool(ldet_out != nullptr, [&](auto write_det) {
-                        AKZ_LAUNCH((k_det_stream<SG, decltype(write_det)::value>), dim3(akz_div_up(nb * nseg, 4), n), dim3(256), 0, s_det,
-                                   S.Lxy[i], ldet_out, L.w, L.h, fs, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err, nb, seg_rows);
+                        AKZ_LAUNCH((k_det_stream<SG, decltype(write_det)::value>), dim3(akz_div_up(G.nb * G.nseg, 4), n), dim3(256), 0, s_det,
+                                   S.Lxy[i], ldet_out, L.w, L.h, fs, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err, G.nb, G.seg_rows, win);
                     });
                 } else if (R.pair) {
-                    AKZ_LAUNCH((k_deriv_second_cand2<SG, kDTH, 256>), dim3(akz_div_up(L.w, 64), akz_div_up(L.h, kDTH), (n + 1) / 2), dim3(256),
-                               0, s_det, S.Lxy[i], ldet_out, L.w, L.h, fs, n, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err);
+                    const AkzDetTileGrid T = akz_det_tile_grid(win, L.w, L.h, 64, kDTH);
+                    AKZ_LAUNCH((k_deriv_second_cand2<SG, kDTH, 256>), dim3(T.ntx, T.nty, (n + 1) / 2), dim3(256),
+                               0, s_det, S.Lxy[i], ldet_out, L.w, L.h, fs, n, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err, T.tx0, T.ty0);
                 } else {
-                    AKZ_LAUNCH((k_deriv_second_cand<SG>), dim3(akz_div_up(L.w, 64), akz_div_up(L.h, 32), n), dim3(256), 0, s_det, S.Lxy[i],
-                               ldet_out, L.w, L.h, fs, (int)L.deriv_sigma, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err);
+                    const AkzDetTileGrid T = akz_det_tile_grid(win, L.w, L.h, 64, 32);
+                    AKZ_LAUNCH((k_deriv_second_cand<SG>), dim3(T.ntx, T.nty, n), dim3(256), 0, s_det, S.Lxy[i],
+                               ldet_out, L.w, L.h, fs, (int)L.deriv_sigma, kk, L.sigma_quat, cp, cand, S.d_ncand, c->d_err, T.tx0, T.ty0);
                 }
             });
         }
