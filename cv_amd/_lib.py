@@ -219,6 +219,9 @@ class PlaceParams(C.Structure):
 HM_PL_OK, HM_PL_BAD_INDEX, HM_PL_BAD_TABLE = range(3)
 HM_PL_C_RECENT, HM_PL_C_SIMILAR, HM_PL_C_SEARCHED, HM_PL_C_GROUPS, HM_PL_C_FREE, HM_PL_COUNTS = range(6)
 HM_PL_MAX_HASH_BYTES, HM_PL_MAX_SEARCH, HM_PL_MAX_RECENT, HM_PL_NONE = 4096, 2048, 256, 0xFFFFFFFF
+HM_VP_OK, HM_VP_CUT, HM_VP_NO_GROUP, HM_VP_FIND_REFUSED, HM_VP_BAD_VIEW, HM_VP_NO_ROOM = range(6)
+HM_VP_C_BLOCKS, HM_VP_C_LIVE, HM_VP_C_VERDICT, HM_VP_C_FRAMES, HM_VP_COUNTS = range(5)
+HM_VP_PICK_RECON, HM_VP_MAX_VIEWS = 1, 64
 
 TRI_OK, TRI_TOO_FEW, TRI_NOT_ROBUST, TRI_EIGEN, TRI_NOT_FINITE, TRI_CHEIRALITY, TRI_BAD_INDEX = range(7)
 
@@ -269,6 +272,7 @@ ABI_SYMBOLS = [
     "rs_export_reconstruction_device", "rs_write_ply", "akz_sample_colors_batch_device",
     "rs_join_pairs_batch_device", "rs_add_reconstruction_batch_device",
     "hm_place_params_default", "hm_place_room", "hm_find_frames_batch_device",
+    "hm_view_plan_device", "hm_knn_planned_batch_device", "hm_best_of_views_planned_batch_device",
     "rs_repack_table_device", "rs_gather_blocks_device", "rs_repack_constraints_device", "hm_place_remap_views_device",
     "akz_strerror", "akz_last_hip_error", "akz_last_hip_error_string", "akz_version", "akz_abi_version",
     "akz_timing_enable", "akz_timing_reset", "akz_timing_get",
@@ -438,6 +442,9 @@ def lib():
     L.hm_place_room.restype = u32
     L.hm_place_room.argtypes = [C.POINTER(PlaceParams)]
     L.hm_find_frames_batch_device.argtypes = [vp] * 6 + [u32, u32, vp, vp, u32, C.POINTER(PlaceParams), u32] + [vp] * 9
+    L.hm_view_plan_device.argtypes = [vp] * 6 + [u32, vp] + [u32] * 5 + [vp] * 5
+    L.hm_knn_planned_batch_device.argtypes = [vp] * 5 + [u32, vp, vp, vp] + [u32] * 5 + [vp, vp]
+    L.hm_best_of_views_planned_batch_device.argtypes = [vp] * 4 + [u32, vp, vp] + [u32] * 4 + [vp, vp, u32, vp, vp, vp]
     L.rs_repack_table_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u32, vp, u32, u32, u32] + [vp] * 9
     L.rs_gather_blocks_device.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, vp]
     L.rs_repack_constraints_device.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, u32] + [vp] * 6

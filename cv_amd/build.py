@@ -11,16 +11,16 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libakz.so")
-SOURCES = ["akz_api.hip", "akz_scale_space.hip", "akz_arith.hip", "akz_keypoints.hip", "hm_match.hip", "rs_ransac.hip", "rs_triangulate.hip", "rs_three_view.hip", "rs_three_view_constraint.hip", "rs_pose_graph.hip", "rs_observation_filter.hip", "rs_single_view.hip", "rs_covisibility.hip", "rs_landmark_table.hip", "rs_reconstruction_merge.hip", "rs_export.hip", "rs_bootstrap_table.hip", "hm_place.hip", "rs_repack.hip", "akz_color.hip",
+SOURCES = ["akz_api.hip", "akz_scale_space.hip", "akz_arith.hip", "akz_keypoints.hip", "hm_match.hip", "rs_ransac.hip", "rs_triangulate.hip", "rs_three_view.hip", "rs_three_view_constraint.hip", "rs_pose_graph.hip", "rs_observation_filter.hip", "rs_single_view.hip", "rs_covisibility.hip", "rs_landmark_table.hip", "rs_reconstruction_merge.hip", "rs_export.hip", "rs_bootstrap_table.hip", "hm_place.hip", "hm_view_plan.hip", "rs_repack.hip", "akz_color.hip",
            "akz_comm.hip", "akz_plan.cpp"]
 # akz_scale_space.hip is compiled once per combination of the reference's three un-vendored arithmetic orders
 # (-DAKZ_ARITH=k, include/akz.h AKZ_ARITH_*); akz_arith.hip routes a context to its copy
 ARITH_VARIANTS = {"akz_scale_space.hip": range(8)}
-HEADERS = ["akz_common.h", "akz_ctx.h", "akz_det_window.h", "hm_plan.h", "hm_rule.h", "../../include/akz.h", "../../include/akz_portable_math.h", "../../include/akz_ransac_math.h", "../../include/akz_p3p_math.h",
+HEADERS = ["akz_common.h", "akz_ctx.h", "akz_det_window.h", "hm_plan.h", "hm_rule.h", "hm_tables.h", "../../include/akz.h", "../../include/akz_portable_math.h", "../../include/akz_ransac_math.h", "../../include/akz_p3p_math.h",
            "../../include/akz_triangulate_math.h", "../../include/akz_five_point_math.h", "../../include/akz_sum_order.h", "../../include/akz_three_view_math.h",
            "../../include/akz_three_view_constraint_math.h", "../../include/akz_pose_graph_math.h",
            "../../include/akz_observation_filter_math.h", "../../include/akz_single_view_math.h", "../../include/akz_covisibility_math.h", "../../include/akz_landmark_table_math.h",
-           "../../include/akz_reconstruction_merge_math.h", "../../include/akz_export_math.h", "../../include/akz_bootstrap_table_math.h", "../../include/akz_place_math.h", "../../include/akz_repack_math.h"]
+           "../../include/akz_reconstruction_merge_math.h", "../../include/akz_export_math.h", "../../include/akz_bootstrap_table_math.h", "../../include/akz_place_math.h", "../../include/akz_view_plan_math.h", "../../include/akz_repack_math.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 

@@ -213,6 +213,12 @@ struct HmPlaceState {
     size_t bytes = 0;
 };
 HmPlaceState* hm_internal_place(hm_ctx* c);
+// What hm_view_plan.hip keeps there: the zero words, the flag and rank of every target block and the tables of one planned call.
+struct HmViewPlanState {
+    void* d_scratch = nullptr;
+    size_t bytes = 0;
+};
+HmViewPlanState* hm_internal_view_plan(hm_ctx* c);
 
 // A context's scratch, grown on demand: *d holds at least `need` bytes afterwards (what it held before is not kept).
 inline int32_t akz_grow_scratch(hipStream_t stream, void** d, size_t* have, size_t need)

@@ -23,6 +23,7 @@
 #include "akz_common.h"
 #include "hm_plan.h"
 #include "hm_rule.h"
+#include "hm_tables.h"   // HmProb, HmExpandJob, HmProbX: the tables the kernels below read
 
 namespace {
 
@@ -31,16 +32,6 @@ constexpr int kBlock = 256;
 constexpr int kQPB = kQPT * kBlock;  // queries per workgroup
 constexpr int kTile = 256;       // targets per LDS tile (16 KB)
 constexpr uint32_t kIdxBits = 22;
-
-struct HmProb {            // one (queries -> targets) problem
-    const uint4* q;        // query descriptors (4 x uint4 each)
-    const uint32_t* nq;    // device count
-    uint32_t q_cap;
-    const uint4* t;
-    const uint32_t* nt;
-    uint32_t t_cap;
-    akz_neighbor* out;     // [q_cap][2]
-};
 
 __global__ __launch_bounds__(kBlock) void k_knn2(const HmProb* __restrict__ probs)
 {
@@ -115,13 +106,6 @@ __global__ __launch_bounds__(kBlock) void k_knn2(const HmProb* __restrict__ prob
 typedef int v4i32 __attribute__((ext_vector_type(4)));
 typedef int v16i32 __attribute__((ext_vector_type(16)));
 
-struct HmExpandJob {
-    const uint32_t* src;   // [cap][16] descriptor words
-    const uint32_t* count; // device count
-    uint32_t cap;
-    uint32_t* dst;         // [cap][128] words of +-1 bytes
-};
-
 __global__ __launch_bounds__(256) void k_expand(const HmExpandJob* __restrict__ jobs)
 {
     const HmExpandJob J = jobs[blockIdx.y];
@@ -143,16 +127,6 @@ __global__ __launch_bounds__(256) void k_expand(const HmExpandJob* __restrict__ 
     dst[0] = o[0];
     dst[1] = o[1];
 }
-
-struct HmProbX {           // like HmProb, on the +-1 recoded descriptors
-    const uint32_t* q;     // [q_cap][128] words
-    const uint32_t* nq;
-    uint32_t q_cap;
-    const uint32_t* t;
-    const uint32_t* nt;
-    uint32_t t_cap;
-    akz_neighbor* out;
-};
 
 constexpr int kMfmaBlock = 512;   // 8 waves x 32 queries
 
@@ -1274,6 +1248,7 @@ struct hm_ctx {
     void* d_lsh = nullptr;
     size_t lsh_bytes = 0;
     HmPlaceState place;            // hm_place.hip's scratch (hm_find_frames_batch_device)
+    HmViewPlanState view_plan;     // hm_view_plan.hip's scratch (the flags, ranks and tables of a planned call)
 };
 
 // Problem descriptors are built in pinned host memory and copied stream-ordered; the staging
@@ -1390,6 +1365,7 @@ extern "C" int32_t hm_destroy(hm_ctx* c)
         hipFree(c->d_rev_scratch);
         hipFree(c->d_lsh);
         hipFree(c->place.d_scratch);
+        hipFree(c->view_plan.d_scratch);
         if (c->ev) hipEventDestroy(c->ev);
         if (c->stream) hipStreamDestroy(c->stream);
         delete c;
@@ -1400,6 +1376,7 @@ extern "C" int32_t hm_destroy(hm_ctx* c)
 extern "C" void* hm_stream(hm_ctx* c) { return c ? (void*)c->stream : nullptr; }
 HmHandles hm_internal_handles(hm_ctx* c) { return HmHandles{c->device, c->stream, c->ev}; }
 HmPlaceState* hm_internal_place(hm_ctx* c) { return &c->place; }
+HmViewPlanState* hm_internal_view_plan(hm_ctx* c) { return &c->view_plan; }
 extern "C" int32_t hm_sync(hm_ctx* c)
 {
     return akz_guard([&]() -> int32_t {
@@ -1506,6 +1483,39 @@ static int32_t knn_rest(hm_ctx* c, uint32_t first, uint32_t n, uint32_t max_nq)
 {
     if (!c->use_mfma) return launch_knn_valu(c, first, n, max_nq);
     return launch_knn_mfma(c, first, n, max_nq, 2, false);
+}
+
+// A search whose tables a kernel of hm_view_plan.hip writes (hm_tables.h): the preparation, then the two launches.  The grids
+// come from the rooms alone — n_frames + exp_blocks jobs, n_probs problems of up to cap queries — and no count is read back:
+// a job or a problem the plan left dead names a zero count and its workgroups leave on their first test.
+int32_t hm_internal_planned(hm_ctx* c, HmPlannedSearch* s, bool launch)
+{
+    const uint32_t n_jobs = s->n_frames + s->exp_blocks;
+    if (!launch) {
+        s->valu = !c->use_mfma && s->k == 2;
+        s->words = c->use_fp4 ? 64u : 128u;
+        AKZ_TRY(hm_stage_take(c, sizeof(uint32_t) * s->n_frames + 64));
+        AKZ_TRY(hm_stage_push(c, 0, s->iq, sizeof(uint32_t) * s->n_frames));
+        s->d_iq = hm_staged<uint32_t>(c, 0);
+        if (!s->valu) AKZ_TRY(akz_grow_scratch(c->stream, &c->d_exp, &c->exp_bytes, sizeof(uint32_t) * (size_t)n_jobs * s->cap * s->words));
+        s->exp = static_cast<uint32_t*>(c->d_exp);
+        return AKZ_OK;
+    }
+    // (the grids of launch_knn_valu / launch_expand / launch_knn_mfma, over tables that lie in the view plan's scratch, not in
+    // the call's staging slot)
+    if (s->valu) {
+        hipLaunchKernelGGL(k_knn2, dim3((s->cap + kQPB - 1) / kQPB, s->n_probs), dim3(kBlock), 0, c->stream, static_cast<const HmProb*>(s->probs));
+        AKZ_LAUNCH_CHECK();
+        return AKZ_OK;
+    }
+    hipLaunchKernelGGL(c->use_fp4 ? k_expand4 : k_expand, dim3((s->cap * 16 + 255) / 256, n_jobs), dim3(256), 0, c->stream, s->jobs);
+    AKZ_LAUNCH_CHECK();
+    const std::pair<hipEvent_t, hipEvent_t> ev = c->timer.take();
+    const HmKnnKernel& kn = kKnnKernels[knn_family(c)][s->k - 1];
+    hipExtLaunchKernelGGL(kn.fn, dim3((s->cap + 255) / 256, s->n_probs), dim3(kn.block), 0, c->stream, ev.first, ev.second, 0,
+                          static_cast<const HmProbX*>(s->probs));
+    AKZ_LAUNCH_CHECK();
+    return AKZ_OK;
 }
 
 // ---- the host-buffer calls --------------------------------------------------------------------------------------------
@@ -1671,12 +1681,17 @@ extern "C" int32_t hm_knn_batch_device(hm_ctx* c, const void* d_q, const void* d
 // The reference collects the landmarks in a HashMap, so its order among equal distances is unspecified; here ties
 // go to the lower landmark key (parity unpinned for ties).  One thread per feature: n_views * k <= 64 * 3 = 192 entries,
 // read once each; only the best three are kept.
+// PLANNED (hm_best_of_views_planned_batch_device): the frame's own view count (frame_views[f], at most n_views; 0: no landmark,
+// decision 0) and a view list that a kernel wrote — a key >= n_blocks or a neighbour index at or behind the view's count is
+// passed over, nothing is read through either.  Not PLANNED: frame_views is null, the code is the one it always was.
+template <bool PLANNED>
 __global__ __launch_bounds__(256) void k_best_of_views(const akz_neighbor* __restrict__ knn, const uint32_t* __restrict__ nq,
                                                        uint32_t cap, uint32_t n_views, uint32_t k,
                                                        const uint32_t* __restrict__ landmarks, const uint32_t* __restrict__ view_idx,
                                                        const uint32_t* __restrict__ nviews, uint32_t better_by,
                                                        uint2* __restrict__ best, uint32_t* __restrict__ decision,
-                                                       const uint32_t* __restrict__ q_block)
+                                                       const uint32_t* __restrict__ q_block, const uint32_t* __restrict__ frame_views,
+                                                       uint32_t n_blocks)
 {
     // blockIdx.y = frame of a batched call: its slab of the k-NN output, its row of view indices, its count
     const uint32_t f = blockIdx.y;
@@ -1689,10 +1704,13 @@ __global__ __launch_bounds__(256) void k_best_of_views(const akz_neighbor* __res
     if (i >= min(*nq, cap)) return;
     const uint32_t NONE = 0xFFFFFFFFu;
     uint32_t bl[3] = {NONE, NONE, NONE}, bd[3] = {NONE, NONE, NONE};   // ascending (distance, landmark)
-    for (uint32_t v = 0; v < n_views; ++v) {
+    const uint32_t mine = PLANNED ? min(frame_views[f], n_views) : n_views;
+    for (uint32_t v = 0; v < mine; ++v) {
+        if (PLANNED && view_idx[v] >= n_blocks) continue;
         const uint32_t blk = view_idx[v], nt = min(nviews[blk], cap);
         for (uint32_t j = 0; j < k && j < nt; ++j) {
             const akz_neighbor nb = knn[((size_t)v * cap + i) * k + j];
+            if (PLANNED && nb.index >= nt) continue;
             const uint32_t l = landmarks[(size_t)blk * cap + nb.index], d = nb.distance;
             // already among the best three: keep the smaller distance
             int at = -1;
@@ -1731,10 +1749,10 @@ static int32_t best_of_views_enqueue(hm_ctx* c, const void* d_knn, const void* d
     AKZ_TRY(hm_stage_take(c, vi_bytes + sizeof(uint32_t) * n_frames + 64));
     AKZ_TRY(hm_stage_push(c, 0, view_idx, sizeof(uint32_t) * (size_t)n_frames * n_views));
     if (iq) AKZ_TRY(hm_stage_push(c, vi_bytes, iq, sizeof(uint32_t) * n_frames));
-    hipLaunchKernelGGL(k_best_of_views, dim3((cap_per_img + 255) / 256, n_frames), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_best_of_views<false>, dim3((cap_per_img + 255) / 256, n_frames), dim3(256), 0, c->stream,
                        (const akz_neighbor*)d_knn, (const uint32_t*)d_nq, cap_per_img, n_views, k, (const uint32_t*)d_landmarks,
                        hm_staged<uint32_t>(c, 0), (const uint32_t*)d_nviews, better_by, (uint2*)d_best, (uint32_t*)d_decision,
-                       iq ? hm_staged<uint32_t>(c, vi_bytes) : (const uint32_t*)nullptr);
+                       iq ? hm_staged<uint32_t>(c, vi_bytes) : (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0xFFFFFFFFu);
     AKZ_LAUNCH_CHECK();
     return AKZ_OK;
 }
@@ -1766,6 +1784,32 @@ extern "C" int32_t hm_best_of_views_batch_device(hm_ctx* c, const void* d_knn, c
         if (n_frames == 0) return AKZ_OK;
         return best_of_views_enqueue(c, d_knn, d_nq, iq, cap_per_img, view_idx, n_frames, n_views, k, d_landmarks, d_nviews, better_by,
                                      d_best, d_decision, stream_to_wait);
+    });
+}
+
+// The same behind a planned search (hm_knn_planned_batch_device): the view lists d_view_idx [n_frames][n_views] and the frames'
+// own counts d_n_views [n_frames] are on the device, as hm_view_plan_device (or any kernel) left them; only iq is the host's.
+// A frame with 0 views: best NONE, decision 0 for its features.  Rows at or behind a frame's feature count are not written.
+extern "C" int32_t hm_best_of_views_planned_batch_device(hm_ctx* c, const void* d_knn, const void* d_nq, const uint32_t* iq, uint32_t cap_per_img,
+                                                         const void* d_view_idx, const void* d_n_views, uint32_t n_frames, uint32_t n_views,
+                                                         uint32_t n_blocks, uint32_t k, const void* d_landmarks, const void* d_nviews,
+                                                         uint32_t better_by, void* d_best, void* d_decision, void* stream_to_wait)
+{
+    return akz_guard([&]() -> int32_t {
+        if (!d_knn || !d_nq || !iq || !d_view_idx || !d_n_views || !d_landmarks || !d_nviews || !d_best || !d_decision) return AKZ_E_INVALID;
+        if (k < 1 || k > 3 || n_views == 0 || n_views > 64 || cap_per_img == 0 || cap_per_img >= (1u << (kIdxBits - 1)) || n_frames > 65535u)
+            return AKZ_E_INVALID;
+        if (!c) return AKZ_E_INVALID;
+        if (n_frames == 0) return AKZ_OK;
+        AKZ_TRY(akz_enqueue_behind(c->device, c->stream, c->ev, stream_to_wait));
+        AKZ_TRY(hm_stage_take(c, sizeof(uint32_t) * n_frames + 64));
+        AKZ_TRY(hm_stage_push(c, 0, iq, sizeof(uint32_t) * n_frames));
+        hipLaunchKernelGGL(k_best_of_views<true>, dim3((cap_per_img + 255) / 256, n_frames), dim3(256), 0, c->stream,
+                           (const akz_neighbor*)d_knn, (const uint32_t*)d_nq, cap_per_img, n_views, k, (const uint32_t*)d_landmarks,
+                           (const uint32_t*)d_view_idx, (const uint32_t*)d_nviews, better_by, (uint2*)d_best, (uint32_t*)d_decision,
+                           hm_staged<uint32_t>(c, 0), (const uint32_t*)d_n_views, n_blocks);
+        AKZ_LAUNCH_CHECK();
+        return AKZ_OK;
     });
 }
 

@@ -19,6 +19,7 @@ from . import _device, _lib
 from ._device import call
 
 VERDICTS = ("ok", "bad_index", "bad_table")
+PLAN_VERDICTS = ("ok", "cut", "no_group", "find_refused", "bad_view", "no_room")
 NONE = _lib.HM_PL_NONE
 
 
@@ -141,6 +142,54 @@ class FrameIndex:
         if R == 0:      # (rows of pitch 0: the call still took an address for each)
             o.found, o.views_out, o.group_recon, o.free = (t[:, :0] for t in (o.found, o.views_out, o.group_recon, o.free))
         return _device.keep_alive(o, q, vis, self)
+
+
+@dataclass
+class ViewPlan:
+    """What an hm_view_plan_device call wrote, on the device: the views every frame is matched against, for
+    hm_knn_planned_batch_device and hm_best_of_views_planned_batch_device (Registration.match_found)."""
+    view_idx: object       # [F][V] int32: the frame's list, NONE at and behind its length
+    n_views: object        # [F] int32: the length
+    verdict: object        # [F] int32 (HM_VP_*)
+    counts: object         # [HM_VP_COUNTS] int32 {distinct target blocks, live problems, the call's verdict, frames with a view}
+    V: int
+    n_blocks: int
+    exp_blocks: int
+
+
+def plan_views(found, V, n_blocks, pick=None, by_recon=False, exp_blocks=None, matcher=None, stream_to_wait=None):
+    """hm_view_plan_device over a FoundFrames (FrameIndex.find): every frame takes the views of ONE of its groups — group 0, the
+    reconstruction with most views found (try_localize's first turn, cv-sfm/src/lib.rs:858); pick [F] ordinals: the pick[f]-th
+    turn; by_recon: pick [F] reconstruction keys (.remove(&reconstruction), :936) — the first min(V, length) of them.  n_blocks:
+    the blocks of the descriptor table (a view key is a block); exp_blocks: the room for distinct target blocks (default: as
+    many as there can be).  Enqueued on the matcher's stream, where the find is, behind the current torch stream (or
+    stream_to_wait), which fills the outputs; no wait -> ViewPlan."""
+    import torch
+    dev = found.verdict.device
+    F, V, n_blocks = int(found.verdict.shape[0]), int(V), int(n_blocks)
+    if exp_blocks is None:
+        exp_blocks = max(1, min(F * V, n_blocks, 65535 - F))
+    f = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device=dev)
+    plan = ViewPlan(f(F, V), torch.zeros(F, dtype=torch.int32, device=dev), f(F), torch.zeros(_lib.HM_VP_COUNTS, dtype=torch.int32, device=dev),
+                    V, n_blocks, int(exp_blocks))
+    d_pick = None
+    if pick is not None:
+        d_pick = pick if isinstance(pick, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pick, np.uint32).view(np.int32)).to(dev)
+        _device.require_device(d_pick, itemsize=4)
+        if d_pick.numel() != F:
+            raise ValueError("one pick per frame")
+    elif by_recon:
+        raise ValueError("by_recon names the reconstructions in pick")
+    if F == 0:
+        return plan
+    if found.room == 0:
+        raise ValueError("a find of room 0 holds no views")
+    if matcher is None:         # the index the find ran on keeps itself alive behind its result
+        matcher = next(m for m in getattr(found, "_inputs", ()) if isinstance(m, FrameIndex)).matcher
+    call("hm_view_plan_device", matcher.handle, found.views_out, found.group_recon, found.group_start, found.counts, found.verdict, found.room,
+         d_pick, _lib.HM_VP_PICK_RECON if by_recon else 0, F, V, n_blocks, plan.exp_blocks, plan.view_idx, plan.n_views, plan.verdict, plan.counts,
+         _device.wait_or_current(torch, stream_to_wait, dev))
+    return _device.keep_alive(plan, found, d_pick)
 
 
 def view_blocks(result, V, pad=None):

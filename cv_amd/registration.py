@@ -14,8 +14,12 @@ hm_hash_bag_device -> hm_knn_batch_device (k = 3, frames x views problems) -> hm
 hm_landmark_matches_batch_device -> rs_p3p_arrsac_batch_device (and, with refine(), hm_landmark_original_matches_batch_device ->
 rs_refine_poses_batch_device: the single-view optimiser and consistency filter of cv-sfm/src/lib.rs:1625-1775) on the blocks where akz_extract_batch_device left them; nothing
 returns to the host in between.  Which views a frame is matched against is decided on the device too
-(cv_amd/place_recognition.py: FrameIndex.find over the hashes this chain writes, view_blocks for match_views' host list); what
-stays with the caller is the reference's control plane over that answer (try_localize).  Which landmark each stored feature observes, which features observe each landmark (a LandmarkTable) and the row
+(cv_amd/place_recognition.py: FrameIndex.find over the hashes this chain writes), and match_found() takes that answer where it
+lies: hm_view_plan_device picks one found reconstruction's views per frame (try_localize's turn, cv-sfm/src/lib.rs:858-891, or
+the reconstruction try_localize_and_incorporate names, :926-939) and hm_knn_planned_batch_device /
+hm_best_of_views_planned_batch_device plan their searches from the device lists — no wait, no copy.  match_views() with
+view_blocks' host list stays for callers with lists of their own.  What stays with the caller is the reference's control plane
+over that answer (try_localize's loop over the turns, expressed as `pick`).  Which landmark each stored feature observes, which features observe each landmark (a LandmarkTable) and the row
 lengths come from the device too: add_views() behind refine() is VSlamData::add_view for the accepted frames of the
 micro-batch (cv-sfm/src/lib.rs:432-483, merge_landmarks :699-721) and leaves the next generation of the table, the landmark
 map match_views() reads and the counts consensus() sorts by where the next call takes them; sharing_view() behind
@@ -134,6 +138,37 @@ class Registration:
         call("hm_knn_batch_device", h, d_descs, d_counts, d_descs, d_counts, self.cap, iq_p, it_p, F * V, self.k, self.knn, None)
         call("hm_best_of_views_batch_device", h, self.knn, d_counts, fb_p, self.cap, it_p, F, V, self.k, d_landmarks, d_counts,
              self.better_by, self.best, self.decision, None)
+
+    def match_found(self, d_descs, d_counts, frame_blocks, found, d_landmarks, pick=None, by_recon=False, stream_to_wait=None):
+        """match_views() for the views a FrameIndex.find() found, without the host list: `found` (a FoundFrames whose query f is
+        the frame of frame_blocks[f], its find already enqueued on the matcher's stream) goes through
+        place_recognition.plan_views — every frame against the views of ONE reconstruction, group 0 or the one `pick` /
+        `by_recon` name, at most self.V of them — and the searches and the best-of-views decision are planned on the device
+        from that (hm_knn_planned_batch_device, hm_best_of_views_planned_batch_device).  Nothing is waited for and nothing
+        copied.  A view key is a block of d_descs.  Outputs as match_views(), and self.plan (a ViewPlan: lists, lengths, verdicts,
+        counts); a frame without a list gets no landmark and decision 0 for every feature."""
+        from .place_recognition import plan_views
+        cur = self._sets[self._calls & 1]
+        self._select(self._calls & 1)
+        self._calls += 1
+        self._cur = cur
+        if cur["used"]:
+            self._hm_s.wait_event(cur["done"])           # the consensus of two calls ago has read this set's pair lists
+        F, V, n_blocks = len(frame_blocks), self.V, int(d_descs.shape[0])
+        assert 1 <= F <= self.F and found.verdict.shape[0] == F
+        fb_p, _ = _device.index_list(frame_blocks)
+        fb = self._fb = fb_p[:F]
+        h = self.matcher.handle
+        b0, b1 = min(fb), max(fb) + 1
+        assert b1 - b0 <= self.F
+        call("hm_hash_bag_device", h, d_descs[b0:b1], d_counts[b0:b1], self.cap, b1 - b0, self.d_codewords, self.n_codewords, self.hash,
+             self.words, _device.wait(stream_to_wait))
+        self.hash_block0 = b0
+        plan = self.plan = plan_views(found, V, n_blocks, pick=pick, by_recon=by_recon, matcher=self.matcher)
+        call("hm_knn_planned_batch_device", h, d_descs, d_counts, d_descs, d_counts, self.cap, fb_p, plan.view_idx, plan.n_views, F, V, n_blocks,
+             plan.exp_blocks, self.k, self.knn, None)
+        call("hm_best_of_views_planned_batch_device", h, self.knn, d_counts, fb_p, self.cap, plan.view_idx, plan.n_views, F, V, n_blocks, self.k,
+             d_landmarks, d_counts, self.better_by, self.best, self.decision, None)
 
     def triangulate(self, table, d_kps, d_poses, d_world=None, d_reason=None, params=None, stream_to_wait=None):
         """The world table on the device: row l of d_world = triangulate_landmark_robust(landmark l) (cv-sfm/src/lib.rs:

@@ -1247,6 +1247,43 @@ public:
                                                  d_views_out, d_group_recon, d_group_start, d_free, d_search, d_counts, d_verdict, stream_to_wait),
                      "hm_find_frames_batch_device");
     }
+    // From a find's outputs to the searches, no host step in between (include/akz.h: hm_view_plan_device and the two planned
+    // calls).  A frame takes the views of ONE found reconstruction — try_localize's turn (cv-sfm/src/lib.rs:858-891: d_pick null
+    // = the first, else the ordinal) or, by_recon, the named one (.remove(&reconstruction), :926-939) — at most n_views of them.
+    enum PlanVerdict : uint32_t {
+        PlanOk = HM_VP_OK, PlanCut = HM_VP_CUT, NoGroup = HM_VP_NO_GROUP, FindRefused = HM_VP_FIND_REFUSED, BadView = HM_VP_BAD_VIEW,
+        NoRoom = HM_VP_NO_ROOM
+    };
+    struct ViewPlan {          // device addresses, the caller's: [n_frames][n_views], [n_frames], [n_frames], [HM_VP_COUNTS] u32
+        void *view_idx, *n_views_of, *verdict, *counts;
+        uint32_t n_frames, n_views, n_blocks, exp_blocks;
+    };
+    void plan_views(const void* d_views_out, const void* d_group_recon, const void* d_group_start, const void* d_counts, const void* d_verdict,
+                    uint32_t room, const void* d_pick, bool by_recon, const ViewPlan& plan, void* stream_to_wait = nullptr)
+    {
+        akaze::check(hm_view_plan_device(m_.handle(), d_views_out, d_group_recon, d_group_start, d_counts, d_verdict, room, d_pick,
+                                         by_recon ? (uint32_t)HM_VP_PICK_RECON : 0u, plan.n_frames, plan.n_views, plan.n_blocks, plan.exp_blocks,
+                                         plan.view_idx, plan.n_views_of, plan.verdict, plan.counts, stream_to_wait),
+                     "hm_view_plan_device");
+    }
+    // the k nearest of every feature of the frames' blocks iq [n_frames] (host) in every view of their lists: d_out
+    // [n_frames][n_views][cap][k]; slabs behind a frame's list are not written
+    void knn_planned(const void* d_descs, const void* d_counts, uint32_t cap_per_img, const uint32_t* iq, const ViewPlan& plan, uint32_t k,
+                     void* d_out, void* stream_to_wait = nullptr)
+    {
+        akaze::check(hm_knn_planned_batch_device(m_.handle(), d_descs, d_counts, d_descs, d_counts, cap_per_img, iq, plan.view_idx, plan.n_views_of,
+                                                 plan.n_frames, plan.n_views, plan.n_blocks, plan.exp_blocks, k, d_out, stream_to_wait),
+                     "hm_knn_planned_batch_device");
+    }
+    // register_frame_subset's landmark choice (:1489-1542) over those lists: d_best [n_frames][cap][3], d_decision [n_frames][cap]
+    void best_of_views_planned(const void* d_knn, const void* d_counts, uint32_t cap_per_img, const uint32_t* iq, const ViewPlan& plan, uint32_t k,
+                               const void* d_landmarks, uint32_t better_by, void* d_best, void* d_decision, void* stream_to_wait = nullptr)
+    {
+        akaze::check(hm_best_of_views_planned_batch_device(m_.handle(), d_knn, d_counts, iq, cap_per_img, plan.view_idx, plan.n_views_of,
+                                                           plan.n_frames, plan.n_views, plan.n_blocks, k, d_landmarks, d_counts, better_by, d_best,
+                                                           d_decision, stream_to_wait),
+                     "hm_best_of_views_planned_batch_device");
+    }
     void sync() { akaze::check(hm_sync(m_.handle()), "hm_sync"); }
     void* stream() { return hm_stream(m_.handle()); }
 

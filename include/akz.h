@@ -513,6 +513,57 @@ int32_t hm_find_frames_batch_device(hm_ctx* ctx, const void* d_hashes, const voi
  * untouched and sets d_flags [1] u32 to 1 (0 otherwise).  Elementwise, one launch on hm_stream() after stream_to_wait. */
 int32_t hm_place_remap_views_device(hm_ctx* ctx, void* d_recon, void* d_view, uint32_t n_stored, uint32_t recon, const void* d_block_map,
                                     uint32_t n_blocks, void* d_flags, void* stream_to_wait);
+/* From the frames found to the searches, without a host step (cv_amd/csrc/hm_view_plan.hip; the decisions:
+ * include/akz_view_plan_math.h).  The reference hands register_frame_subset the views of ONE reconstruction at a time
+ * (try_localize, cv-sfm/src/lib.rs:858-891: a turn of its loop per group, most views found first; try_localize_and_incorporate,
+ * :926-939: the group of one named reconstruction, .remove(&reconstruction)), and :1472-1486 walk exactly that list.
+ *
+ * hm_view_plan_device: frame f reads row f of an hm_find_frames_batch_device call's d_views_out, d_group_recon, d_group_start,
+ * d_counts and d_verdict (pitch `room`, any room).  Its group: d_pick NULL -> group 0; d_pick [n_frames] u32 without
+ * HM_VP_PICK_RECON in `flags` -> the ordinal d_pick[f]; with it -> the group whose d_group_recon equals d_pick[f].  Its list: the
+ * first min(n_views, group length) view keys of that group in the group's order; a view key is a block of the descriptor table
+ * (FrameIndex.set_views, hm_place_remap_views_device).  d_view_idx [n_frames][n_views] u32: the list, HM_PL_NONE at and behind
+ * its length; d_n_views [n_frames]: the length; d_plan_verdict [n_frames]: HM_VP_OK, HM_VP_CUT (the group was longer than
+ * n_views: still n_views of it), HM_VP_NO_GROUP (no such group, or none at all), HM_VP_FIND_REFUSED (the find's verdict is not
+ * HM_PL_OK: none of its rows is read) or HM_VP_BAD_VIEW (a taken key >= n_blocks: the frame is refused alone and nothing is read
+ * through the key) — length 0 for the last three.  d_plan_counts [HM_VP_COUNTS] u32 {distinct target blocks of all accepted
+ * frames, live problems = the sum of the lengths, the call's verdict, frames with at least one view}: more distinct blocks
+ * than exp_blocks is HM_VP_NO_ROOM — every frame's length is then 0 and its list HM_PL_NONE, so that a search planned from it
+ * searches nothing; the frames keep their own verdicts.  n_views 1..HM_VP_MAX_VIEWS, exp_blocks >= 1, n_frames * n_views <= 65535,
+ * n_frames + exp_blocks <= 65535 (AKZ_E_INVALID otherwise, before the context is looked at); n_frames 0: nothing to do.
+ *
+ * hm_knn_planned_batch_device: hm_knn_batch_device for the problems (f, v) = every feature of query block iq[f] (host list, the
+ * new frames' blocks) of d_q against block d_view_idx[f][v] of d_t, for v < min(d_n_views[f], n_views) — lists that
+ * hm_view_plan_device or any other kernel wrote.  d_out [n_frames][n_views][cap][k]; a live problem's slab holds the bytes
+ * hm_knn_batch_device writes for it; the slab of a dead problem (v at or behind the frame's length, or a key >= n_blocks) is not
+ * written.  The distinct target blocks are counted and ranked on the device and the recoding plan is written there: a job per
+ * frame's query block and per distinct target block in ascending block order, so that no byte depends on arrival order.  The
+ * grids come from the rooms alone — exp_blocks is the room for distinct target blocks — and no count is read back.  A list with
+ * MORE distinct blocks than exp_blocks searches NOTHING: no slab is written.  hm_view_plan_device with the same exp_blocks has
+ * then emptied every list (HM_VP_NO_ROOM); a caller with lists of its own makes exp_blocks min(n_frames * n_views, n_blocks).
+ * cap_per_img and k as hm_knn_batch_device; the other limits as above.
+ *
+ * hm_best_of_views_planned_batch_device: hm_best_of_views_batch_device over those lists: frame f reads its first
+ * min(d_n_views[f], n_views) slabs; a frame of length 0 gets {HM_PL_NONE, HM_PL_NONE} x 3 and decision 0 for each of its features.
+ * A key >= n_blocks and a neighbour index at or behind its view's count are passed over.
+ *
+ * All three are stream-ordered on hm_stream() behind stream_to_wait, return after enqueueing and take their scratch from the
+ * context. */
+enum { HM_VP_OK = 0, HM_VP_CUT = 1, HM_VP_NO_GROUP = 2, HM_VP_FIND_REFUSED = 3, HM_VP_BAD_VIEW = 4, HM_VP_NO_ROOM = 5 };
+enum { HM_VP_C_BLOCKS = 0, HM_VP_C_LIVE = 1, HM_VP_C_VERDICT = 2, HM_VP_C_FRAMES = 3, HM_VP_COUNTS = 4 };
+enum { HM_VP_PICK_RECON = 1 };
+enum { HM_VP_MAX_VIEWS = 64 };
+int32_t hm_view_plan_device(hm_ctx* ctx, const void* d_views_out, const void* d_group_recon, const void* d_group_start, const void* d_counts,
+                            const void* d_verdict, uint32_t room, const void* d_pick, uint32_t flags, uint32_t n_frames, uint32_t n_views,
+                            uint32_t n_blocks, uint32_t exp_blocks, void* d_view_idx, void* d_n_views, void* d_plan_verdict, void* d_plan_counts,
+                            void* stream_to_wait);
+int32_t hm_knn_planned_batch_device(hm_ctx* ctx, const void* d_q, const void* d_nq, const void* d_t, const void* d_nt, uint32_t cap_per_img,
+                                    const uint32_t* iq, const void* d_view_idx, const void* d_n_views, uint32_t n_frames, uint32_t n_views,
+                                    uint32_t n_blocks, uint32_t exp_blocks, uint32_t k, void* d_out, void* stream_to_wait);
+int32_t hm_best_of_views_planned_batch_device(hm_ctx* ctx, const void* d_knn, const void* d_nq, const uint32_t* iq, uint32_t cap_per_img,
+                                              const void* d_view_idx, const void* d_n_views, uint32_t n_frames, uint32_t n_views,
+                                              uint32_t n_blocks, uint32_t k, const void* d_landmarks, const void* d_nviews, uint32_t better_by,
+                                              void* d_best, void* d_decision, void* stream_to_wait);
 /* Optional timing of the k-NN kernel launches with HIP events on hm_stream() (bench.py's matcher roofline):
  * hm_timing_get waits for the pending events and returns the accumulated milliseconds / launch count.  A symmetric match
  * whose reverse side is answered from the forward lists counts as ONE launch, and its decision and verification kernels and

@@ -265,6 +265,17 @@ extern "C" {
                                    d_visible: *const c_void, nq: u32, params: *const HmPlaceParams, room: u32, d_found: *mut c_void,
                                    d_views_out: *mut c_void, d_group_recon: *mut c_void, d_group_start: *mut c_void, d_free: *mut c_void,
                                    d_search: *mut c_void, d_counts: *mut c_void, d_verdict: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn hm_view_plan_device(ctx: *mut c_void, d_views_out: *const c_void, d_group_recon: *const c_void, d_group_start: *const c_void,
+                           d_counts: *const c_void, d_verdict: *const c_void, room: u32, d_pick: *const c_void, flags: u32, n_frames: u32,
+                           n_views: u32, n_blocks: u32, exp_blocks: u32, d_view_idx: *mut c_void, d_n_views: *mut c_void,
+                           d_plan_verdict: *mut c_void, d_plan_counts: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn hm_knn_planned_batch_device(ctx: *mut c_void, d_q: *const c_void, d_nq: *const c_void, d_t: *const c_void, d_nt: *const c_void,
+                                   cap_per_img: u32, iq: *const u32, d_view_idx: *const c_void, d_n_views: *const c_void, n_frames: u32,
+                                   n_views: u32, n_blocks: u32, exp_blocks: u32, k: u32, d_out: *mut c_void, stream_to_wait: *mut c_void) -> i32;
+    fn hm_best_of_views_planned_batch_device(ctx: *mut c_void, d_knn: *const c_void, d_nq: *const c_void, iq: *const u32, cap_per_img: u32,
+                                             d_view_idx: *const c_void, d_n_views: *const c_void, n_frames: u32, n_views: u32, n_blocks: u32,
+                                             k: u32, d_landmarks: *const c_void, d_nviews: *const c_void, better_by: u32, d_best: *mut c_void,
+                                             d_decision: *mut c_void, stream_to_wait: *mut c_void) -> i32;
 }
 
 /// `akaze::KeyPoint` (akaze/src/lib.rs:69-93).
@@ -1871,6 +1882,43 @@ pub const HM_PL_MAX_HASH_BYTES: u32 = 4096;
 pub const HM_PL_MAX_SEARCH: u32 = 2048;
 pub const HM_PL_MAX_RECENT: u32 = 256;
 pub const HM_PL_NONE: u32 = 0xFFFF_FFFF;
+#[repr(u32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PlanVerdict {
+    Ok = 0,
+    Cut = 1,
+    NoGroup = 2,
+    FindRefused = 3,
+    BadView = 4,
+    NoRoom = 5,
+}
+pub const HM_VP_OK: u32 = 0;
+pub const HM_VP_CUT: u32 = 1;
+pub const HM_VP_NO_GROUP: u32 = 2;
+pub const HM_VP_FIND_REFUSED: u32 = 3;
+pub const HM_VP_BAD_VIEW: u32 = 4;
+pub const HM_VP_NO_ROOM: u32 = 5;
+pub const HM_VP_C_BLOCKS: usize = 0;
+pub const HM_VP_C_LIVE: usize = 1;
+pub const HM_VP_C_VERDICT: usize = 2;
+pub const HM_VP_C_FRAMES: usize = 3;
+pub const HM_VP_COUNTS: usize = 4;
+pub const HM_VP_PICK_RECON: u32 = 1;
+pub const HM_VP_MAX_VIEWS: u32 = 64;
+
+/// The outputs of `hm_view_plan_device`, device memory the caller owns: `view_idx [n_frames][n_views]`, `n_views_of [n_frames]`,
+/// `verdict [n_frames]`, `counts [HM_VP_COUNTS]` u32; and the rooms the planned calls size their grids from.
+#[derive(Clone, Copy, Debug)]
+pub struct ViewPlan {
+    pub view_idx: *mut c_void,
+    pub n_views_of: *mut c_void,
+    pub verdict: *mut c_void,
+    pub counts: *mut c_void,
+    pub n_frames: u32,
+    pub n_views: u32,
+    pub n_blocks: u32,
+    pub exp_blocks: u32,
+}
 
 /// The rows `[first, first + count)` of a [`FrameIndex`]: their addresses in the table's five arrays.
 #[derive(Clone, Copy, Debug)]
@@ -1953,6 +2001,43 @@ impl FrameIndex {
         let st = hm_find_frames_batch_device(self.ctx, self.hashes, self.feed, self.pos, self.recon, self.view, self.n, self.hash_bytes,
                                              d_query, d_visible, nq, params, room, d_found, d_views_out, d_group_recon, d_group_start, d_free,
                                              d_search, d_counts, d_verdict, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// From a find's outputs to the views every frame is matched against (`hm_view_plan_device`): ONE found reconstruction per
+    /// frame — `try_localize`'s turn (cv-sfm/src/lib.rs:858-891; `d_pick` null: the first) or, `by_recon`, the named one
+    /// (`.remove(&reconstruction)`, :926-939) — at most `plan.n_views` of its views.
+    /// # Safety
+    /// Every pointer names device memory of the documented size, alive until the matcher's stream has run the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn plan_views(&self, d_views_out: *const c_void, d_group_recon: *const c_void, d_group_start: *const c_void,
+                             d_counts: *const c_void, d_verdict: *const c_void, room: u32, d_pick: *const c_void, by_recon: bool,
+                             plan: &ViewPlan, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = hm_view_plan_device(self.ctx, d_views_out, d_group_recon, d_group_start, d_counts, d_verdict, room, d_pick,
+                                     if by_recon { HM_VP_PICK_RECON } else { 0 }, plan.n_frames, plan.n_views, plan.n_blocks, plan.exp_blocks,
+                                     plan.view_idx, plan.n_views_of, plan.verdict, plan.counts, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// `hm_knn_planned_batch_device`: the frames' blocks `iq` (host) against the views of their lists; `d_out
+    /// [n_frames][n_views][cap][k]`, the slabs behind a frame's list not written.
+    /// # Safety
+    /// As `plan_views`; `iq` names `plan.n_frames` words.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn knn_planned(&self, d_descs: *const c_void, d_counts: *const c_void, cap_per_img: u32, iq: *const u32, plan: &ViewPlan,
+                              k: u32, d_out: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = hm_knn_planned_batch_device(self.ctx, d_descs, d_counts, d_descs, d_counts, cap_per_img, iq, plan.view_idx, plan.n_views_of,
+                                             plan.n_frames, plan.n_views, plan.n_blocks, plan.exp_blocks, k, d_out, stream_to_wait);
+        if st == 0 { Ok(()) } else { Err(st) }
+    }
+    /// `hm_best_of_views_planned_batch_device` over those lists.
+    /// # Safety
+    /// As `knn_planned`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn best_of_views_planned(&self, d_knn: *const c_void, d_counts: *const c_void, cap_per_img: u32, iq: *const u32,
+                                        plan: &ViewPlan, k: u32, d_landmarks: *const c_void, better_by: u32, d_best: *mut c_void,
+                                        d_decision: *mut c_void, stream_to_wait: *mut c_void) -> Result<(), i32> {
+        let st = hm_best_of_views_planned_batch_device(self.ctx, d_knn, d_counts, iq, cap_per_img, plan.view_idx, plan.n_views_of,
+                                                       plan.n_frames, plan.n_views, plan.n_blocks, k, d_landmarks, d_counts, better_by,
+                                                       d_best, d_decision, stream_to_wait);
         if st == 0 { Ok(()) } else { Err(st) }
     }
 }
