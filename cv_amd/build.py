@@ -16,7 +16,7 @@ SOURCES = ["akz_api.hip", "akz_scale_space.hip", "akz_arith.hip", "akz_keypoints
 # akz_scale_space.hip is compiled once per combination of the reference's three un-vendored arithmetic orders
 # (-DAKZ_ARITH=k, include/akz.h AKZ_ARITH_*); akz_arith.hip routes a context to its copy
 ARITH_VARIANTS = {"akz_scale_space.hip": range(8)}
-HEADERS = ["akz_common.h", "akz_ctx.h", "akz_det_window.h", "hm_plan.h", "hm_rule.h", "hm_tables.h", "../../include/akz.h", "../../include/akz_portable_math.h", "../../include/akz_ransac_math.h", "../../include/akz_p3p_math.h",
+HEADERS = ["akz_common.h", "akz_ctx.h", "akz_det_window.h", "hm_plan.h", "hm_rule.h", "hm_tables.h", "rs_table.h", "rs_table_host.h", "../../include/akz.h", "../../include/akz_portable_math.h", "../../include/akz_ransac_math.h", "../../include/akz_p3p_math.h",
            "../../include/akz_triangulate_math.h", "../../include/akz_five_point_math.h", "../../include/akz_sum_order.h", "../../include/akz_three_view_math.h",
            "../../include/akz_three_view_constraint_math.h", "../../include/akz_pose_graph_math.h",
            "../../include/akz_observation_filter_math.h", "../../include/akz_single_view_math.h", "../../include/akz_covisibility_math.h", "../../include/akz_landmark_table_math.h",

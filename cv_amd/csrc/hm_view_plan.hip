@@ -13,8 +13,8 @@
 // problem without work names a zero count, and the matcher's workgroups leave on their own first test.  Nothing is read back.
 // Every decision is include/akz_view_plan_math.h's, the text the host build compiles too.  The search kernels are
 // hm_match.hip's and are launched there (hm_internal_planned of hm_tables.h).
-#include "akz_common.h"
 #include "hm_tables.h"
+#include "rs_table.h"
 #include "../../include/akz_view_plan_math.h"
 
 static_assert(HM_VP_OK == AKZ_VP_OK && HM_VP_CUT == AKZ_VP_CUT && HM_VP_NO_GROUP == AKZ_VP_NO_GROUP && HM_VP_FIND_REFUSED == AKZ_VP_FIND_REFUSED &&
@@ -103,15 +103,7 @@ __global__ __launch_bounds__(kVpScanThreads) void k_vp_scan(const uint32_t* __re
 {
     __shared__ uint32_t s_wave[kVpScanWaves];
     __shared__ uint32_t s_cnt[2][kVpScanWaves];
-    uint32_t carry = 0u;
-    for (uint32_t b0 = 0; b0 < n_blocks; b0 += kVpScanThreads) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t v = b < n_blocks ? flag[b] : 0u;
-        uint32_t total;
-        const uint32_t ex = akz_block_exclusive<kVpScanWaves>(v, s_wave, &total);
-        if (b < n_blocks) rank[b] = carry + ex;
-        carry += total;
-    }
+    const uint32_t carry = tbl_scan<kVpScanWaves>(flag, rank, n_blocks, s_wave);
     const uint32_t call = akz_vp_call_verdict(carry, exp_blocks);
     if (threadIdx.x == 0) {
         head[kVpHeadDistinct] = carry;

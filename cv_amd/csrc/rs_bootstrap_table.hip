@@ -19,26 +19,21 @@
 //   k_bt_accept      ONE lane walks the scenes in order: a valid scene none of whose frames an earlier accepted scene names is
 //                    accepted; its row and observation bases, the ranges, the constraint's views and verdict, the totals.
 //   k_bt_copy        the keypoint blocks, counts and poses of the accepted scenes, and the constraint's poses.
-//   k_bt_rows        the rows of the centre features: a workgroup per tile of kBtTile rows of a scene adds the lengths in front of
+//   k_bt_rows        the rows of the centre features: a workgroup per tile of kTblTile rows of a scene adds the lengths in front of
 //                    its tile, scans its own and writes starts, lengths and lists.
 //   k_bt_new_rows    one workgroup per scene: the features of the first, then the second frame in no accepted match, compacted in
 //                    feature order, one row each (their starts are arithmetic).
-//   k_bt_tail        every start behind the total equals the total.
+//   k_tbl_tail       (rs_table.h) every start behind the filled rows equals the total, every count there is 0.
 // Nothing here waits on a value another workgroup has yet to write: the levels are separate launches; every loop is bounded by
 // an argument of the call or a checked count.
-#include "akz_common.h"
+#include "rs_table.h"
 #include "../../include/akz_bootstrap_table_math.h"
 
 namespace {
 
 constexpr int kJpBlock = 1024;                               // lds_radix_sort_ids' block
 constexpr int kJpWaves = kJpBlock / 64;
-constexpr int kBtBlock = 256;
-constexpr int kBtWaves = kBtBlock / 64;
-constexpr int kBtItems = 4;                                  // rows per thread of a scan tile
-constexpr uint32_t kBtTile = kBtBlock * kBtItems;            // RS_LT_TILE rows
 constexpr uint32_t kKpWords = sizeof(akz_keypoint) / sizeof(uint32_t);
-static_assert(kBtTile == (uint32_t)RS_LT_TILE, "the tile size the header exports");
 static_assert(sizeof(akz_keypoint) % sizeof(uint32_t) == 0, "keypoint blocks are copied word by word");
 
 static_assert(RS_JP_OK == AKZ_JP_OK && RS_JP_NO_MODEL == AKZ_JP_NO_MODEL && RS_JP_FEW_INLIERS == AKZ_JP_FEW_INLIERS &&
@@ -204,25 +199,24 @@ struct ArCall {
     uint32_t cap, n_scenes, n_src_blocks, n_obs, n_landmarks, n_recons, n_blocks, view_base, lm_room;
 };
 
-__global__ __launch_bounds__(kBtBlock) void k_bt_check_table(ArCall a)
+__global__ __launch_bounds__(kTblBlock) void k_bt_check_table(ArCall a)
 {
-    const uint32_t l = blockIdx.x * kBtBlock + threadIdx.x;
+    const uint32_t l = blockIdx.x * kTblBlock + threadIdx.x;
     int bad = l <= a.n_landmarks && akz_lt_start_bad(a.obs_start, l, a.n_landmarks, a.n_obs);
     if (a.n_recons && l <= a.n_recons)
         bad = bad || akz_ar_range_bad(a.recon_start, l, a.n_recons, a.n_landmarks) || akz_ar_range_bad(a.view_start, l, a.n_recons, a.view_base);
-    if (__any(bad) && (threadIdx.x & 63u) == 0u) atomicOr(&a.info[kInfoBad], 1u);
+    tbl_flag(&a.info[kInfoBad], bad);
 }
 
 // observation {blk, feat} is written at obs_out[at] as a member of row `key`
 __device__ __forceinline__ void bt_put(const ArCall& a, uint32_t at, uint32_t blk, uint32_t feat, uint32_t key)
 {
-    a.obs_out[at] = make_uint2(blk, feat);
-    if (blk < a.n_blocks && feat < a.cap) atomicMin(&a.landmarks_out[(size_t)blk * a.cap + feat], key);
+    tbl_put(a.obs_out, a.landmarks_out, a.n_blocks, a.cap, at, make_uint2(blk, feat), key);
 }
 
-__global__ __launch_bounds__(kBtBlock) void k_bt_old(ArCall a)
+__global__ __launch_bounds__(kTblBlock) void k_bt_old(ArCall a)
 {
-    const uint32_t l = blockIdx.x * kBtBlock + threadIdx.x;
+    const uint32_t l = blockIdx.x * kTblBlock + threadIdx.x;
     const bool bad = a.info[kInfoBad] != 0u;
     if (l < a.n_landmarks) {
         a.obs_start_out[l] = a.obs_start[l];
@@ -238,7 +232,7 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_old(ArCall a)
 }
 
 // One workgroup per scene.  info and taken are zero in front of it.
-__global__ __launch_bounds__(kBtBlock) void k_bt_validate(ArCall a)
+__global__ __launch_bounds__(kTblBlock) void k_bt_validate(ArCall a)
 {
     __shared__ uint32_t s_bad, s_n[3];
     const uint32_t s = blockIdx.x, bc = a.frames[s], bf = a.frames[a.n_scenes + s], bs = a.frames[2 * a.n_scenes + s];   // below n_src_blocks: the host
@@ -247,14 +241,14 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_validate(ArCall a)
     const bool counts_ok = akz_ar_counts_ok(bc, bf, bs, cc, cf, cs, nt, nf, ns, a.cap);
     uint32_t* cen = a.maps + 5 * (size_t)s * a.cap;
     uint32_t *cen_f = cen + a.cap, *cen_s = cen + 2 * (size_t)a.cap, *fst = cen + 3 * (size_t)a.cap, *snd = cen + 4 * (size_t)a.cap;
-    for (uint32_t j = threadIdx.x; j < 5u * a.cap; j += kBtBlock) cen[j] = AKZ_LT_NONE;
+    for (uint32_t j = threadIdx.x; j < 5u * a.cap; j += kTblBlock) cen[j] = AKZ_LT_NONE;
     if (threadIdx.x < 3u) s_n[threadIdx.x] = 0u;
     if (threadIdx.x == 0) s_bad = 0u;
     __syncthreads();
     if (!off && counts_ok) {                                             // every count <= cap
         uint32_t bad = 0u, mt = 0u, mf = 0u, ms = 0u;
         const uint32_t *t = a.triples + 3 * (size_t)s * a.cap, *f = a.first_only + 2 * (size_t)s * a.cap, *g = a.second_only + 2 * (size_t)s * a.cap;
-        for (uint32_t i = threadIdx.x; i < nt; i += kBtBlock) {
+        for (uint32_t i = threadIdx.x; i < nt; i += kTblBlock) {
             if (!a.combined[(size_t)s * a.cap + i]) continue;
             const uint32_t c = t[3 * i], x = t[3 * i + 1], y = t[3 * i + 2];
             if (c >= cc || x >= cf || y >= cs) { bad = 1u; continue; }
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_validate(ArCall a)
             cen_f[c] = x; cen_s[c] = y;                                  // the only claimant of c
             ++mt;
         }
-        for (uint32_t i = threadIdx.x; i < nf; i += kBtBlock) {
+        for (uint32_t i = threadIdx.x; i < nf; i += kTblBlock) {
             if (!a.first_ok[(size_t)s * a.cap + i]) continue;
             const uint32_t c = f[2 * i], x = f[2 * i + 1];
             if (c >= cc || x >= cf) { bad = 1u; continue; }
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_validate(ArCall a)
             cen_f[c] = x;
             ++mf;
         }
-        for (uint32_t i = threadIdx.x; i < ns; i += kBtBlock) {
+        for (uint32_t i = threadIdx.x; i < ns; i += kTblBlock) {
             if (!a.second_ok[(size_t)s * a.cap + i]) continue;
             const uint32_t c = g[2 * i], y = g[2 * i + 1];
             if (c >= cc || y >= cs) { bad = 1u; continue; }
@@ -339,10 +333,10 @@ __global__ void k_bt_accept(ArCall a)
     *a.call_verdict = bad ? AKZ_AR_BAD_TABLE : AKZ_AR_OK;
 }
 
-// grid (words of a block / kBtBlock, 3, scenes)
-__global__ __launch_bounds__(kBtBlock) void k_bt_copy(ArCall a)
+// grid (words of a block / kTblBlock, 3, scenes)
+__global__ __launch_bounds__(kTblBlock) void k_bt_copy(ArCall a)
 {
-    const uint32_t s = blockIdx.z, k = blockIdx.y, w = blockIdx.x * kBtBlock + threadIdx.x;
+    const uint32_t s = blockIdx.z, k = blockIdx.y, w = blockIdx.x * kTblBlock + threadIdx.x;
     if (!a.scene[(size_t)kScWords * s + kScAccepted]) return;
     const uint32_t src = a.frames[k * a.n_scenes + s], view = akz_ar_view(a.view_base, s, k);       // view < n_blocks: the host
     const size_t words = (size_t)a.cap * kKpWords;
@@ -353,11 +347,11 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_copy(ArCall a)
 }
 
 // grid (tiles of a block's features, scenes)
-__global__ __launch_bounds__(kBtBlock) void k_bt_rows(ArCall a)
+__global__ __launch_bounds__(kTblBlock) void k_bt_rows(ArCall a)
 {
-    __shared__ uint32_t s_cnt[2][kBtWaves];
-    __shared__ uint32_t s_wave[kBtWaves];
-    const uint32_t s = blockIdx.y, first = blockIdx.x * kBtTile;
+    __shared__ uint32_t s_cnt[2][kTblWaves];
+    __shared__ uint32_t s_wave[kTblWaves];
+    const uint32_t s = blockIdx.y, first = blockIdx.x * kTblTile;
     const uint32_t* sc = a.scene + (size_t)kScWords * s;
     if (!sc[kScAccepted]) return;
     const uint32_t cc = a.counts[a.frames[s]];                            // <= cap: the scene is valid
@@ -365,16 +359,14 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_rows(ArCall a)
     const uint32_t* cen_f = a.maps + (5 * (size_t)s + 1) * a.cap;
     const uint32_t* cen_s = cen_f + a.cap;
     uint32_t before = 0u, tick = 0u;
-    for (uint32_t j = threadIdx.x; j < first; j += kBtBlock) before += akz_ar_row_length(cen_f[j], cen_s[j]);
-    uint32_t run = sc[kScAt] + akz_block_sum<kBtWaves>(s_cnt, tick, before);
+    for (uint32_t j = threadIdx.x; j < first; j += kTblBlock) before += akz_ar_row_length(cen_f[j], cen_s[j]);
+    uint32_t run = sc[kScAt] + akz_block_sum<kTblWaves>(s_cnt, tick, before);
 #pragma unroll 1
-    for (int it = 0; it < kBtItems; ++it) {
-        const uint32_t j = first + (uint32_t)it * kBtBlock + threadIdx.x;
+    for (int it = 0; it < kTblItems; ++it) {
+        const uint32_t j = first + (uint32_t)it * kTblBlock + threadIdx.x;
         const bool on = j < cc;
         const uint32_t x = on ? cen_f[j] : AKZ_LT_NONE, y = on ? cen_s[j] : AKZ_LT_NONE, len = on ? akz_ar_row_length(x, y) : 0u;
-        uint32_t total;
-        uint32_t dst = run + akz_block_exclusive<kBtWaves>(len, s_wave, &total);
-        run += total;
+        uint32_t dst = tbl_scan_step(run, len, s_wave);
         if (!on) continue;
         const uint32_t r = sc[kScRow] + j;
         a.obs_start_out[r] = dst;
@@ -385,9 +377,9 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_rows(ArCall a)
     }
 }
 
-__global__ __launch_bounds__(kBtBlock) void k_bt_new_rows(ArCall a)
+__global__ __launch_bounds__(kTblBlock) void k_bt_new_rows(ArCall a)
 {
-    __shared__ uint32_t s_cnt[2][kBtWaves];
+    __shared__ uint32_t s_cnt[2][kTblWaves];
     const uint32_t s = blockIdx.x;
     const uint32_t* sc = a.scene + (size_t)kScWords * s;
     if (!sc[kScAccepted]) return;
@@ -396,11 +388,11 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_new_rows(ArCall a)
     for (uint32_t k = 1; k < 3u; ++k) {
         const uint32_t count = a.counts[a.frames[k * a.n_scenes + s]];    // <= cap
         const uint32_t* used = a.maps + (5 * (size_t)s + 2 + k) * a.cap;
-        for (uint32_t j0 = 0; j0 < count; j0 += kBtBlock) {
+        for (uint32_t j0 = 0; j0 < count; j0 += kTblBlock) {
             const uint32_t j = j0 + threadIdx.x;
             const bool fresh = j < count && used[j] == AKZ_LT_NONE;
             uint32_t total;
-            const uint32_t rank = akz_block_scan<kBtWaves>(s_cnt, tick, fresh, &total);
+            const uint32_t rank = akz_block_scan<kTblWaves>(s_cnt, tick, fresh, &total);
             if (fresh) {
                 a.obs_start_out[row + rank] = at + rank;
                 a.obs_counts_out[row + rank] = 1u;
@@ -410,22 +402,6 @@ __global__ __launch_bounds__(kBtBlock) void k_bt_new_rows(ArCall a)
             at += total;
         }
     }
-}
-
-__global__ __launch_bounds__(kBtBlock) void k_bt_tail(ArCall a)
-{
-    const uint32_t k = blockIdx.x * kBtBlock + threadIdx.x;
-    if (k > a.lm_room - a.n_landmarks) return;
-    const uint32_t r = a.n_landmarks + k;
-    if (r < a.info[kInfoRows]) return;
-    a.obs_start_out[r] = a.info[kInfoTotal];
-    if (r < a.lm_room) a.obs_counts_out[r] = 0u;
-}
-
-bool bt_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 }   // namespace
@@ -501,7 +477,7 @@ extern "C" int32_t rs_add_reconstruction_batch_device(
         if ((n_recons != 0) != (d_recon_start != nullptr) || (n_recons != 0) != (d_view_start != nullptr)) return AKZ_E_INVALID;
         if (cap_per_img == 0 || n_blocks == 0 || n_scenes > 65535u || n_recons > 0xFFFFFFFFu - 65536u) return AKZ_E_INVALID;
         // row numbers of the last tile and the words of a keypoint block stay 32-bit
-        if (n_landmarks > 0xFFFFFFFFu - 2u * kBtTile || cap_per_img > kAkzMaxKeypoints) return AKZ_E_TOO_LARGE;
+        if (n_landmarks > 0xFFFFFFFFu - 2u * kTblTile || cap_per_img > kAkzMaxKeypoints) return AKZ_E_TOO_LARGE;
         if ((uint64_t)view_base + 3ull * n_scenes > (uint64_t)n_blocks) return AKZ_E_INVALID;
         // the rooms: no kernel can write past them (every feature of a scene's views adds one observation and at most one row)
         const uint64_t grow = 3ull * n_scenes * cap_per_img;
@@ -516,7 +492,7 @@ extern "C" int32_t rs_add_reconstruction_batch_device(
                 for (uint32_t s = 0; s < n_scenes; ++s)
                     for (uint32_t b : {ic[s], i_first[s], i_second[s]})
                         if (b >= view_base && b < view_base + 3u * n_scenes) return AKZ_E_INVALID;
-            } else if (bt_overlap(d_kps, block_bytes * n_src_blocks, d_kps_dst, block_bytes * n_blocks)) {
+            } else if (akz_ranges_overlap(d_kps, block_bytes * n_src_blocks, d_kps_dst, block_bytes * n_blocks)) {
                 return AKZ_E_INVALID;
             }
         }
@@ -528,24 +504,19 @@ extern "C" int32_t rs_add_reconstruction_batch_device(
         const size_t range_bytes = w * ((size_t)n_recons + n_scenes + 1);
         const size_t out_bytes[7] = {w * ((size_t)lm_room + 1), w * 2 * (size_t)obs_room, w * (size_t)lm_room, w * (size_t)n_blocks * cap_per_img,
                                      w * AKZ_AR_COUNTS, range_bytes, range_bytes};
-        for (int i = 0; i < 4; ++i)
-            for (int o = 0; o < 7; ++o)
-                if (bt_overlap(in[i], in_bytes[i], out[o], out_bytes[o])) return AKZ_E_INVALID;
+        if (!akz_outputs_clear_of_inputs(in, in_bytes, 4, out, out_bytes, 7)) return AKZ_E_INVALID;
         if (!c) return AKZ_E_INVALID;
         const RsHandles h = rs_internal_handles(c);
         RsLandmarkTableState* ls = rs_internal_landmark_table(c);
         AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
-        const size_t info_bytes = akz_align_up(w * kInfoWords, 256), taken_bytes = akz_align_up(w * ((size_t)n_src_blocks + 1), 256);
-        const size_t frame_bytes = akz_align_up(w * (3 * (size_t)n_scenes + 1), 256), scene_bytes = akz_align_up(w * (kScWords * (size_t)n_scenes + 1), 256);
-        const size_t map_bytes = w * (5 * (size_t)n_scenes * cap_per_img + 1);
-        AKZ_TRY(akz_grow_scratch(h.stream, &ls->d_scratch, &ls->bytes, info_bytes + taken_bytes + frame_bytes + scene_bytes + map_bytes));
+        AkzScratchPlan plan;                                             // zero: info, taken
+        const size_t at_info = plan.take(w * kInfoWords), at_taken = plan.take(w * ((size_t)n_src_blocks + 1)), at_frames = plan.take(w * (3 * (size_t)n_scenes + 1));
+        const size_t at_scene = plan.take(w * (kScWords * (size_t)n_scenes + 1)), at_maps = plan.take(w * (5 * (size_t)n_scenes * cap_per_img + 1));
+        AKZ_TRY(akz_grow_scratch(h.stream, &ls->d_scratch, &ls->bytes, plan.size()));
         char* base = (char*)ls->d_scratch;
         ArCall a;
-        a.info = (uint32_t*)base;
-        a.taken = (uint32_t*)(base + info_bytes);
-        a.frames = (uint32_t*)(base + info_bytes + taken_bytes);
-        a.scene = (uint32_t*)(base + info_bytes + taken_bytes + frame_bytes);
-        a.maps = (uint32_t*)(base + info_bytes + taken_bytes + frame_bytes + scene_bytes);
+        a.info = (uint32_t*)(base + at_info); a.taken = (uint32_t*)(base + at_taken); a.frames = (uint32_t*)(base + at_frames);
+        a.scene = (uint32_t*)(base + at_scene); a.maps = (uint32_t*)(base + at_maps);
         a.triples = (const uint32_t*)d_triples; a.ntriples = (const uint32_t*)d_ntriples; a.first_only = (const uint32_t*)d_first_only;
         a.nfirst = (const uint32_t*)d_nfirst; a.second_only = (const uint32_t*)d_second_only; a.nsecond = (const uint32_t*)d_nsecond;
         a.combined = (const unsigned char*)d_combined; a.first_ok = (const unsigned char*)d_first_ok; a.second_ok = (const unsigned char*)d_second_ok;
@@ -561,18 +532,18 @@ extern "C" int32_t rs_add_reconstruction_batch_device(
         a.call_verdict = (uint32_t*)d_call_verdict;
         a.cap = cap_per_img; a.n_scenes = n_scenes; a.n_src_blocks = n_src_blocks; a.n_obs = n_obs; a.n_landmarks = n_landmarks;
         a.n_recons = n_recons; a.n_blocks = n_blocks; a.view_base = view_base; a.lm_room = lm_room;
-        AKZ_HIP(hipMemsetAsync(base, 0, info_bytes + taken_bytes, h.stream));
+        AKZ_HIP(hipMemsetAsync(base + at_info, 0, at_frames - at_info, h.stream));
         AKZ_HIP(hipMemsetAsync(d_landmarks_out, 0xFF, out_bytes[3], h.stream));
         if (n_scenes) {
             AKZ_HIP(hipMemcpyAsync(a.frames, ic, w * n_scenes, hipMemcpyHostToDevice, h.stream));
             AKZ_HIP(hipMemcpyAsync(a.frames + n_scenes, i_first, w * n_scenes, hipMemcpyHostToDevice, h.stream));
             AKZ_HIP(hipMemcpyAsync(a.frames + 2 * (size_t)n_scenes, i_second, w * n_scenes, hipMemcpyHostToDevice, h.stream));
         }
-        const dim3 block(kBtBlock);
+        const dim3 block(kTblBlock);
         const uint32_t widest = n_landmarks > n_recons ? n_landmarks : n_recons, longest = widest > n_obs ? widest : n_obs;
-        hipLaunchKernelGGL(k_bt_check_table, dim3(widest / kBtBlock + 1), block, 0, h.stream, a);
+        hipLaunchKernelGGL(k_bt_check_table, dim3(widest / kTblBlock + 1), block, 0, h.stream, a);
         AKZ_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_bt_old, dim3(longest / kBtBlock + 1), block, 0, h.stream, a);
+        hipLaunchKernelGGL(k_bt_old, dim3(longest / kTblBlock + 1), block, 0, h.stream, a);
         AKZ_LAUNCH_CHECK();
         if (n_scenes) {
             hipLaunchKernelGGL(k_bt_validate, dim3(n_scenes), block, 0, h.stream, a);
@@ -582,14 +553,15 @@ extern "C" int32_t rs_add_reconstruction_batch_device(
         AKZ_LAUNCH_CHECK();
         if (n_scenes) {
             const uint32_t words = cap_per_img * kKpWords;                                // cap_per_img <= kAkzMaxKeypoints
-            hipLaunchKernelGGL(k_bt_copy, dim3((words + kBtBlock - 1) / kBtBlock, 3, n_scenes), block, 0, h.stream, a);
+            hipLaunchKernelGGL(k_bt_copy, dim3((words + kTblBlock - 1) / kTblBlock, 3, n_scenes), block, 0, h.stream, a);
             AKZ_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_bt_rows, dim3((cap_per_img + kBtTile - 1) / kBtTile, n_scenes), block, 0, h.stream, a);
+            hipLaunchKernelGGL(k_bt_rows, dim3((cap_per_img + kTblTile - 1) / kTblTile, n_scenes), block, 0, h.stream, a);
             AKZ_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_bt_new_rows, dim3(n_scenes), block, 0, h.stream, a);
             AKZ_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(k_bt_tail, dim3((lm_room - n_landmarks) / kBtBlock + 1), block, 0, h.stream, a);
+        hipLaunchKernelGGL(k_tbl_tail, dim3((lm_room - n_landmarks) / kTblBlock + 1), block, 0, h.stream, a.obs_start_out, a.obs_counts_out, n_landmarks,
+                           lm_room, (const uint32_t*)&a.info[kInfoRows], (const uint32_t*)&a.info[kInfoTotal]);
         AKZ_LAUNCH_CHECK();
         return AKZ_OK;
     });

@@ -26,7 +26,7 @@
 //
 // The decisions are include/akz_covisibility_math.h, the text the CPU checker (tests/cpp/covisibility_host.c) compiles too —
 // parity: host build == HIP in every output word.
-#include "akz_common.h"
+#include "rs_table.h"
 #include "../../include/akz_covisibility_math.h"
 
 namespace {
@@ -258,15 +258,7 @@ __global__ __launch_bounds__(kCvBlock) void k_cv_targets(CvCall a)
 __global__ __launch_bounds__(kCvBlock) void k_cv_scan(CvCall a)
 {
     __shared__ uint32_t s_wave[kCvWaves];
-    uint32_t carry = 0u;
-    for (uint32_t t0 = 0; t0 < a.n_targets; t0 += kCvBlock) {
-        const uint32_t t = t0 + threadIdx.x;
-        const uint32_t v = t < a.n_targets ? a.tot[t] : 0u;
-        uint32_t total;
-        const uint32_t ex = akz_block_exclusive<kCvWaves>(v, s_wave, &total);
-        if (t < a.n_targets) a.tot[t] = carry + ex;
-        carry += total;
-    }
+    const uint32_t carry = tbl_scan_in_place<kCvWaves>(a.tot, a.n_targets, s_wave);
     if (threadIdx.x == 0) a.lm_start[(size_t)a.n_targets * a.st.limit] = carry;
 }
 
@@ -365,15 +357,7 @@ __global__ __launch_bounds__(kCvBlock) void k_pgr_count(const uint32_t* __restri
 __global__ __launch_bounds__(kCvBlock) void k_pgr_scan(const uint32_t* __restrict__ cnt, uint32_t n_views, uint32_t* row_start)
 {
     __shared__ uint32_t s_wave[kCvWaves];
-    uint32_t carry = 0u;
-    for (uint32_t v0 = 0; v0 < n_views; v0 += kCvBlock) {
-        const uint32_t v = v0 + threadIdx.x;
-        const uint32_t c = v < n_views ? cnt[v] : 0u;
-        uint32_t total;
-        const uint32_t ex = akz_block_exclusive<kCvWaves>(c, s_wave, &total);
-        if (v < n_views) row_start[v] = carry + ex;
-        carry += total;
-    }
+    const uint32_t carry = tbl_scan<kCvWaves>(cnt, row_start, n_views, s_wave);
     if (threadIdx.x == 0) row_start[n_views] = carry;
 }
 // The ordered fill: the key of row entry e = 6 c + s is view << 32 | e (all ones for an entry of a triple outside the table and

@@ -9,7 +9,7 @@
 //   k_ex_check      one lane per start: do the starts begin at 0 and ascend inside [0, n_obs].
 //   k_ex_tile_sums  first level of the scan: one lane per row says what the row is (akz_ex_row), one workgroup per tile counts
 //                   its tile's points; the rows that are skipped are counted by their kind.
-//   k_ex_scan_sums  second level: ONE workgroup walks the tile sums kExBlock at a time behind a running carry; the counts and
+//   k_ex_scan_sums  second level: ONE workgroup walks the tile sums kTblBlock at a time behind a running carry; the counts and
 //                   the verdict.
 //   k_ex_points     third pass: a workgroup scans its tile again; the lane of a point below the room does the three divisions,
 //                   gathers the colour of the first observation and writes the key.
@@ -19,17 +19,12 @@
 // an argument.  The call shares the scratch rs_landmark_table.hip keeps in the context: the calls run on one stream.
 #include <stdio.h>
 
-#include "akz_common.h"
+#include "rs_table.h"
 #include "../../include/akz_export_math.h"
 
 namespace {
 
-constexpr int kExBlock = 256;
-constexpr int kExWaves = kExBlock / 64;
-constexpr int kExItems = 4;                                  // rows per thread of a scan tile
-constexpr uint32_t kExTile = kExBlock * kExItems;            // RS_LT_TILE rows
-static_assert(kExTile == (uint32_t)RS_LT_TILE, "the tile size the header exports");
-static_assert(kExBlock == AKZ_SUM_THREADS, "the workgroup akz_sum_order.h's T = 256 stands for");
+static_assert(kTblBlock == AKZ_SUM_THREADS, "the workgroup akz_sum_order.h's T = 256 stands for");
 
 static_assert(RS_EX_OK == AKZ_EX_OK && RS_EX_OVERFLOW == AKZ_EX_OVERFLOW && RS_EX_BAD_TABLE == AKZ_EX_BAD_TABLE, "verdicts");
 static_assert(RS_EX_C_POINTS == AKZ_EX_C_POINTS && RS_EX_C_NO_POINT == AKZ_EX_C_NO_POINT && RS_EX_C_INFINITE == AKZ_EX_C_INFINITE &&
@@ -64,11 +59,11 @@ struct ExCall {
 };
 
 // info is zero in front of it
-__global__ __launch_bounds__(kExBlock) void k_ex_check(ExCall a)
+__global__ __launch_bounds__(kTblBlock) void k_ex_check(ExCall a)
 {
-    const uint32_t l = blockIdx.x * kExBlock + threadIdx.x;
+    const uint32_t l = blockIdx.x * kTblBlock + threadIdx.x;
     const int bad = l <= a.n_landmarks && akz_ex_start_bad(a.start, l, a.n_landmarks, a.n_obs);
-    if (__any(bad) && (threadIdx.x & 63u) == 0u) atomicOr(&a.info[kExBadTable], 1u);
+    tbl_flag(&a.info[kExBadTable], bad);
 }
 
 // what row r is to the call; a refused table has no row
@@ -78,21 +73,21 @@ __device__ __forceinline__ uint32_t ex_row(const ExCall& a, bool ok, uint32_t r,
     return akz_ex_row(a.world, a.start, a.obs, r, a.n_landmarks, a.n_obs, a.n_blocks, a.cap, block, feature);
 }
 
-__global__ __launch_bounds__(kExBlock) void k_ex_tile_sums(ExCall a)
+__global__ __launch_bounds__(kTblBlock) void k_ex_tile_sums(ExCall a)
 {
-    __shared__ uint32_t s_cnt[2][kExWaves];
+    __shared__ uint32_t s_cnt[2][kTblWaves];
     const bool ok = a.info[kExBadTable] == 0u;
     uint32_t n[AKZ_EX_COUNTS] = {0u, 0u, 0u, 0u}, tick = 0u;
 #pragma unroll
-    for (int j = 0; j < kExItems; ++j) {
-        const uint32_t r = blockIdx.x * kExTile + (uint32_t)j * kExBlock + threadIdx.x;       // n_world + kExTile < 2^32: the entry point
+    for (int j = 0; j < kTblItems; ++j) {
+        const uint32_t r = blockIdx.x * kTblTile + (uint32_t)j * kTblBlock + threadIdx.x;       // n_world + kTblTile < 2^32: the entry point
         uint32_t blk, feat;
         const uint32_t what = ex_row(a, ok, r, &blk, &feat);
 #pragma unroll
         for (int k = 0; k < AKZ_EX_COUNTS; ++k) n[k] += what == (uint32_t)k ? 1u : 0u;
     }
 #pragma unroll
-    for (int k = 0; k < AKZ_EX_COUNTS; ++k) n[k] = akz_block_sum<kExWaves>(s_cnt, tick, n[k]);
+    for (int k = 0; k < AKZ_EX_COUNTS; ++k) n[k] = akz_block_sum<kTblWaves>(s_cnt, tick, n[k]);
     if (threadIdx.x == 0) {
         a.tile_points[blockIdx.x] = n[AKZ_EX_C_POINTS];
 #pragma unroll
@@ -101,18 +96,10 @@ __global__ __launch_bounds__(kExBlock) void k_ex_tile_sums(ExCall a)
     }
 }
 
-__global__ __launch_bounds__(kExBlock) void k_ex_scan_sums(ExCall a)
+__global__ __launch_bounds__(kTblBlock) void k_ex_scan_sums(ExCall a)
 {
-    __shared__ uint32_t s_wave[kExWaves];
-    uint32_t carry = 0u;
-    for (uint32_t t0 = 0; t0 < a.n_tiles; t0 += kExBlock) {
-        const uint32_t t = t0 + threadIdx.x;
-        const uint32_t x = t < a.n_tiles ? a.tile_points[t] : 0u;
-        uint32_t total;
-        const uint32_t ex = akz_block_exclusive<kExWaves>(x, s_wave, &total);
-        if (t < a.n_tiles) a.tile_points[t] = carry + ex;
-        carry += total;
-    }
+    __shared__ uint32_t s_wave[kTblWaves];
+    const uint32_t carry = tbl_scan_in_place(a.tile_points, a.n_tiles, s_wave);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < AKZ_EX_COUNTS; ++k) a.counts_out[k] = a.info[k];                   // carry == info[AKZ_EX_C_POINTS]
@@ -120,19 +107,18 @@ __global__ __launch_bounds__(kExBlock) void k_ex_scan_sums(ExCall a)
     }
 }
 
-__global__ __launch_bounds__(kExBlock) void k_ex_points(ExCall a)
+__global__ __launch_bounds__(kTblBlock) void k_ex_points(ExCall a)
 {
-    __shared__ uint32_t s_wave[kExWaves];
+    __shared__ uint32_t s_wave[kTblWaves];
     const bool ok = a.info[kExBadTable] == 0u;
     const size_t first = (size_t)AKZ_EX_CAMERA_VERTICES * a.n_views;
     uint32_t run = a.tile_points[blockIdx.x];
 #pragma unroll 1
-    for (int j = 0; j < kExItems; ++j) {
-        const uint32_t r = blockIdx.x * kExTile + (uint32_t)j * kExBlock + threadIdx.x;
-        uint32_t blk = 0u, feat = 0u, total;
+    for (int j = 0; j < kTblItems; ++j) {
+        const uint32_t r = blockIdx.x * kTblTile + (uint32_t)j * kTblBlock + threadIdx.x;
+        uint32_t blk = 0u, feat = 0u;
         const bool point = ex_row(a, ok, r, &blk, &feat) == (uint32_t)AKZ_EX_ROW_POINT;
-        const uint32_t k = run + akz_block_exclusive<kExWaves>(point ? 1u : 0u, s_wave, &total);
-        run += total;
+        const uint32_t k = tbl_scan_step(run, point ? 1u : 0u, s_wave);
         if (point && k < a.room) {                           // blk < n_blocks and feat < cap: akz_ex_row
             const size_t at = first + k;
             double p[3];
@@ -149,24 +135,24 @@ __global__ __launch_bounds__(kExBlock) void k_ex_points(ExCall a)
 }
 
 // one workgroup of AKZ_SUM_THREADS per view
-__global__ __launch_bounds__(kExBlock) void k_ex_cameras(ExCall a)
+__global__ __launch_bounds__(kTblBlock) void k_ex_cameras(ExCall a)
 {
-    __shared__ double s_red[2][kExWaves][1];
-    __shared__ uint32_t s_cnt[2][kExWaves];
+    __shared__ double s_red[2][kTblWaves][1];
+    __shared__ uint32_t s_cnt[2][kTblWaves];
     const uint32_t v = blockIdx.x, block = a.views[v];       // block < n_blocks: the entry point
     const uint32_t count = akz_ex_count(a.counts[block], a.cap);
     double pose[12];
     for (int k = 0; k < 12; ++k) pose[k] = a.poses[(size_t)12 * block + k];
     double part[1] = {0.0}, net[1];
     uint32_t n = 0u, tick = 0u;
-    for (uint32_t j = threadIdx.x; j < count; j += kExBlock) {
+    for (uint32_t j = threadIdx.x; j < count; j += kTblBlock) {
         double d;
         if (!akz_ex_feature_distance(pose, a.landmarks + (size_t)block * a.cap, j, a.world, a.n_world, &d)) continue;
         part[0] = part[0] + d;
         ++n;
     }
-    akz_block_sum<kExWaves, 1>(s_red, 0u, part, net);
-    n = akz_block_sum<kExWaves>(s_cnt, tick, n);
+    akz_block_sum<kTblWaves, 1>(s_red, 0u, part, net);
+    n = akz_block_sum<kTblWaves>(s_cnt, tick, n);
     // every thread holds the same bits: the lanes that hold a word write it
     const uint32_t t = threadIdx.x;
     if (t >= 3u * AKZ_EX_CAMERA_VERTICES) return;
@@ -178,12 +164,6 @@ __global__ __launch_bounds__(kExBlock) void k_ex_cameras(ExCall a)
     const size_t at = 3 * ((size_t)AKZ_EX_CAMERA_VERTICES * v + k) + i;
     a.xyz[at] = vert[i];
     a.rgb[at] = akz_ex_camera_color((int)i);
-}
-
-bool ex_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 }   // namespace
@@ -200,15 +180,12 @@ extern "C" int32_t rs_export_reconstruction_device(rs_ctx* c, const void* d_worl
             return AKZ_E_INVALID;
         if (cap_per_img == 0 || n_blocks == 0 || n_views == 0) return AKZ_E_INVALID;
         // row numbers of the last tile, start numbers of the last workgroup and vertex numbers stay 32-bit
-        if (n_world > 0xFFFFFFFFu - 2u * kExTile || n_landmarks > 0xFFFFFFFFu - 2u * kExBlock ||
+        if (n_world > 0xFFFFFFFFu - 2u * kTblTile || n_landmarks > 0xFFFFFFFFu - 2u * kTblBlock ||
             (uint64_t)AKZ_EX_CAMERA_VERTICES * n_views + room > 0xFFFFFFFFull)
             return AKZ_E_TOO_LARGE;
         // two workgroups never write one camera: the blocks are distinct and inside the table
-        std::vector<unsigned char> seen(n_blocks, 0);
-        for (uint32_t v = 0; v < n_views; ++v) {
-            if (view_blocks[v] >= n_blocks || seen[view_blocks[v]]) return AKZ_E_INVALID;
-            seen[view_blocks[v]] = 1;
-        }
+        std::vector<unsigned char> seen;
+        if (!akz_distinct_blocks(view_blocks, n_views, n_blocks, &seen)) return AKZ_E_INVALID;
         // the inputs are const: no output may lie over them
         const size_t n_vertices = (size_t)AKZ_EX_CAMERA_VERTICES * n_views + room, features = (size_t)n_blocks * cap_per_img;
         const void* in[7] = {d_world, d_obs_start, d_obs, d_colors, d_counts, d_landmarks, d_poses};
@@ -217,32 +194,29 @@ extern "C" int32_t rs_export_reconstruction_device(rs_ctx* c, const void* d_worl
         const void* out[6] = {d_xyz, d_rgb, d_key, d_cameras, d_counts_out, d_verdict};
         const size_t out_bytes[6] = {sizeof(double) * 3 * n_vertices, 3 * n_vertices, sizeof(uint32_t) * (size_t)room,
                                      sizeof(double) * AKZ_EX_CAMERA_WORDS * (size_t)n_views, sizeof(uint32_t) * AKZ_EX_COUNTS, sizeof(uint32_t)};
-        for (int i = 0; i < 7; ++i)
-            for (int o = 0; o < 6; ++o)
-                if (ex_overlap(in[i], in_bytes[i], out[o], out_bytes[o])) return AKZ_E_INVALID;
+        if (!akz_outputs_clear_of_inputs(in, in_bytes, 7, out, out_bytes, 6)) return AKZ_E_INVALID;
         if (!c) return AKZ_E_INVALID;
         const RsHandles h = rs_internal_handles(c);
         RsLandmarkTableState* ls = rs_internal_landmark_table(c);
         AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
-        const uint32_t n_tiles = (uint32_t)(((size_t)n_world + kExTile - 1) / kExTile);
+        const uint32_t n_tiles = (uint32_t)(((size_t)n_world + kTblTile - 1) / kTblTile);
         const size_t w = sizeof(uint32_t);
-        const size_t info_bytes = akz_align_up(w * kExInfoWords, 256), tile_bytes = akz_align_up(w * ((size_t)n_tiles + 1), 256);
-        AKZ_TRY(akz_grow_scratch(h.stream, &ls->d_scratch, &ls->bytes, info_bytes + tile_bytes + akz_align_up(w * (size_t)n_views, 256)));
+        AkzScratchPlan plan;
+        const size_t at_info = plan.take(w * kExInfoWords), at_tiles = plan.take(w * ((size_t)n_tiles + 1)), at_views = plan.take(w * (size_t)n_views);
+        AKZ_TRY(akz_grow_scratch(h.stream, &ls->d_scratch, &ls->bytes, plan.size()));
         char* base = (char*)ls->d_scratch;
         ExCall a;
         a.world = (const double*)d_world; a.start = (const uint32_t*)d_obs_start; a.obs = (const uint32_t*)d_obs; a.colors = (const uint8_t*)d_colors;
         a.counts = (const uint32_t*)d_counts; a.landmarks = (const uint32_t*)d_landmarks; a.poses = (const double*)d_poses;
         a.xyz = (double*)d_xyz; a.rgb = (uint8_t*)d_rgb; a.key = (uint32_t*)d_key; a.cameras = (double*)d_cameras;
         a.counts_out = (uint32_t*)d_counts_out; a.verdict = (uint32_t*)d_verdict;
-        a.info = (uint32_t*)base;
-        a.tile_points = (uint32_t*)(base + info_bytes);
-        a.views = (uint32_t*)(base + info_bytes + tile_bytes);
+        a.info = (uint32_t*)(base + at_info); a.tile_points = (uint32_t*)(base + at_tiles); a.views = (uint32_t*)(base + at_views);
         a.n_world = n_world; a.n_landmarks = n_landmarks; a.n_obs = n_obs; a.cap = cap_per_img; a.n_blocks = n_blocks; a.n_views = n_views;
         a.room = room; a.n_tiles = n_tiles;
-        AKZ_HIP(hipMemsetAsync(base, 0, info_bytes, h.stream));
+        AKZ_HIP(hipMemsetAsync(base + at_info, 0, at_tiles - at_info, h.stream));
         AKZ_HIP(hipMemcpyAsync(a.views, view_blocks, w * n_views, hipMemcpyHostToDevice, h.stream));
-        const dim3 block(kExBlock);
-        hipLaunchKernelGGL(k_ex_check, dim3(n_landmarks / kExBlock + 1), block, 0, h.stream, a);
+        const dim3 block(kTblBlock);
+        hipLaunchKernelGGL(k_ex_check, dim3(n_landmarks / kTblBlock + 1), block, 0, h.stream, a);
         AKZ_LAUNCH_CHECK();
         if (n_tiles) {
             hipLaunchKernelGGL(k_ex_tile_sums, dim3(n_tiles), block, 0, h.stream, a);

@@ -19,8 +19,8 @@
 //                    refs — applied (merged_from[a] = b, merged_into[b] = a; refs == 1 on both sides makes the lane their only
 //                    writer) or demoted.
 //   k_lt_tile_sums   the exclusive scan of the row lengths over the rows of the input table, first level: one lane per row
-//                    gives its length (to d_obs_counts_out), one workgroup per tile of kLtTile rows adds its tile.
-//   k_lt_scan_sums   second level: ONE workgroup walks the tile sums kLtBlock at a time behind a running carry, then the new
+//                    gives its length (to d_obs_counts_out), one workgroup per tile of kTblTile rows adds its tile.
+//   k_lt_scan_sums   second level: ONE workgroup walks the tile sums kTblBlock at a time behind a running carry, then the new
 //                    rows of the slots the same way; the counts and the call's verdict.
 //   k_lt_rows        third pass: a workgroup scans its tile again, adds the tile's offset, writes the starts and copies each
 //                    row's old list and the list merged into it (8-byte accesses).
@@ -30,20 +30,28 @@
 //   k_lt_new_rows    one workgroup per slot: the features in no final match, compacted in feature order, one row each.
 //   k_lt_fixup       one lane per row that gained two or more observations: its tail sorted into slot order, so that the
 //                    bytes do not depend on the order the cursor was taken in.
+// k_tbl_tail (rs_table.h), the tail of the stages whose rows behind the filled ones are all empty (rs_bootstrap_table.hip,
+// rs_reconstruction_merge.hip), is defined here, beside the scratch those stages share.
 // The landmark of every observation written goes to d_landmarks_out where the observation is written (atomicMin behind a fill
 // of 0xFFFFFFFF: a feature a broken table lists twice gets its lowest key).  Nothing here waits on a value another workgroup
 // has yet to write: the levels are separate launches; every loop is bounded by an argument of the call or a checked count.
-#include "akz_common.h"
+#include "rs_table.h"
 #include "../../include/akz_landmark_table_math.h"
+
+__global__ __launch_bounds__(kTblBlock) void k_tbl_tail(uint32_t* obs_start_out, uint32_t* obs_counts_out, uint32_t first_row, uint32_t lm_room,
+                                                        const uint32_t* rows, const uint32_t* total)
+{
+    const uint32_t k = blockIdx.x * kTblBlock + threadIdx.x;
+    if (k > lm_room - first_row) return;
+    const uint32_t r = first_row + k;
+    if (r < *rows) return;
+    obs_start_out[r] = *total;
+    if (r < lm_room) obs_counts_out[r] = 0u;
+}
 
 namespace {
 
-constexpr int kLtBlock = 256;
-constexpr int kLtWaves = kLtBlock / 64;
-constexpr int kLtItems = 4;                                  // rows per thread of a scan tile
-constexpr uint32_t kLtTile = kLtBlock * kLtItems;            // RS_LT_TILE rows
 constexpr uint32_t kLtShortPair = 32;                        // combined length up to which one lane walks a candidate
-static_assert(kLtTile == (uint32_t)RS_LT_TILE, "the tile size the header exports");
 
 static_assert(RS_AV_OK == AKZ_AV_OK && RS_AV_NOT_ACCEPTED == AKZ_AV_NOT_ACCEPTED && RS_AV_BAD_INDEX == AKZ_AV_BAD_INDEX &&
               RS_AV_BAD_TABLE == AKZ_AV_BAD_TABLE, "verdicts");
@@ -93,12 +101,12 @@ struct LtCall {
     uint32_t cap, n_blocks, n_obs, n_landmarks, n_world, split_room, n_frames, lm_room, n_tiles;
 };
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_sharing(const uint32_t* __restrict__ obs_start, const uint32_t* __restrict__ obs,
+__global__ __launch_bounds__(kTblBlock) void k_lt_sharing(const uint32_t* __restrict__ obs_start, const uint32_t* __restrict__ obs,
                                                          uint32_t n_obs, uint32_t n_landmarks, const uint32_t* __restrict__ best,
                                                          const uint32_t* __restrict__ decision, uint32_t cap,
                                                          unsigned char* __restrict__ merge_ok)
 {
-    const uint32_t j = blockIdx.x * kLtBlock + threadIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t j = blockIdx.x * kTblBlock + threadIdx.x, lane = threadIdx.x & 63u;
     const size_t at = (size_t)blockIdx.y * cap + j;
     const bool valid = j < cap;
     const uint32_t fill = akz_lt_fill(obs_start, n_landmarks, n_obs);
@@ -108,24 +116,21 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_sharing(const uint32_t* __restr
     const bool wide = cand && (ea - sa) + (eb - sb) > kLtShortPair;
     unsigned char ok = 0;
     if (cand && !wide) ok = akz_lt_lists_share(obs, sa, ea, sb, eb) ? 0 : 1;
-    unsigned long long pending = __ballot(wide);
-    while (pending) {                                   // wave-uniform: every lane walks the same candidates
-        const int src = __ffsll((long long)pending) - 1;
-        pending &= pending - 1ull;
+    tbl_for_wide_rows(wide, [&](int src) {              // wave-uniform: every lane walks the same candidates
         const uint32_t wsa = __shfl(sa, src, 64), wea = __shfl(ea, src, 64), wsb = __shfl(sb, src, 64), web = __shfl(eb, src, 64);
         int share = 0;
         for (uint32_t q = wsb + lane; q < web && !share; q += 64u) share = akz_lt_lists_share(obs, wsa, wea, q, q + 1u);
         const int any = __any(share);
         if ((int)lane == src) ok = any ? 0 : 1;
-    }
+    });
     if (valid) merge_ok[at] = ok;
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_check_table(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_check_table(LtCall a)
 {
-    const uint32_t l = blockIdx.x * kLtBlock + threadIdx.x;
+    const uint32_t l = blockIdx.x * kTblBlock + threadIdx.x;
     const int bad = l <= a.n_landmarks && akz_lt_start_bad(a.obs_start, l, a.n_landmarks, a.n_obs);
-    if (__any(bad) && (threadIdx.x & 63u) == 0u) atomicOr(&a.info[kInfoBad], 1u);
+    tbl_flag(&a.info[kInfoBad], bad);
 }
 
 // what final match i of slot f names; only for i < nmatches[f] <= cap
@@ -137,14 +142,14 @@ __device__ __forceinline__ int lt_match(const LtCall& a, uint32_t f, uint32_t i,
 }
 
 // One workgroup per slot.  info, refs, adds, cursor are zero and merged_into, merged_from, block_slot none in front of it.
-__global__ __launch_bounds__(kLtBlock) void k_lt_validate(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_validate(LtCall a)
 {
     __shared__ uint32_t s_bad, s_final;
     const uint32_t f = blockIdx.x, blk = a.frames[f];                     // blk < n_blocks: checked on the host
     const uint32_t count = a.counts[blk], nm = a.nmatches[f];
     const bool off = a.info[kInfoBad] != 0u || a.sv_verdict[f] != (uint32_t)AKZ_LT_SV_OK || (a.skip && a.skip[f] != 0u);
     uint32_t* feat = a.feat + (size_t)f * a.cap;
-    for (uint32_t j = threadIdx.x; j < a.cap; j += kLtBlock) feat[j] = AKZ_LT_NONE;
+    for (uint32_t j = threadIdx.x; j < a.cap; j += kTblBlock) feat[j] = AKZ_LT_NONE;
     if (threadIdx.x == 0) {
         s_bad = (count > a.cap || nm > a.cap) ? 1u : 0u;
         s_final = 0u;
@@ -153,7 +158,7 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_validate(LtCall a)
     __syncthreads();
     if (!off && s_bad == 0u) {                                           // nm <= cap, count <= cap
         uint32_t mine = 0u, bad = 0u;
-        for (uint32_t i = threadIdx.x; i < nm; i += kLtBlock) {
+        for (uint32_t i = threadIdx.x; i < nm; i += kTblBlock) {
             if (!a.final_mask[(size_t)f * a.cap + i]) continue;
             uint32_t feature, la, lb;
             if (lt_match(a, f, i, count, &feature, &la, &lb) == AKZ_LT_MATCH_BAD) bad = 1u;
@@ -184,13 +189,13 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_validate(LtCall a)
 __device__ __forceinline__ int lt_lane_match(const LtCall& a, uint32_t* f, uint32_t* blk, uint32_t* feature, uint32_t* la, uint32_t* lb)
 {
     *f = blockIdx.y;
-    const uint32_t i = blockIdx.x * kLtBlock + threadIdx.x;
+    const uint32_t i = blockIdx.x * kTblBlock + threadIdx.x;
     if (!a.accepted[*f] || i >= a.nmatches[*f] || !a.final_mask[(size_t)*f * a.cap + i]) return 0;   // accepted: nmatches <= cap
     *blk = a.frames[*f];
     return lt_match(a, *f, i, a.counts[*blk], feature, la, lb);          // never AKZ_LT_MATCH_BAD: the slot was accepted
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_refs(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_refs(LtCall a)
 {
     uint32_t f, blk, feature, la, lb;
     const int kind = lt_lane_match(a, &f, &blk, &feature, &la, &lb);
@@ -199,7 +204,7 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_refs(LtCall a)
     if (kind == AKZ_LT_MATCH_MERGED) atomicAdd(&a.refs[lb], 1u);
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_merges(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_merges(LtCall a)
 {
     uint32_t f, blk, feature, la, lb;
     const int kind = lt_lane_match(a, &f, &blk, &feature, &la, &lb);
@@ -226,45 +231,28 @@ __device__ __forceinline__ uint32_t lt_row_length(const LtCall& a, uint32_t r)
     return akz_lt_row_length(a.obs_start[r + 1] - a.obs_start[r], merged, a.adds[r], a.merged_into[r] != AKZ_LT_NONE);
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_tile_sums(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_tile_sums(LtCall a)
 {
-    __shared__ uint32_t s_cnt[2][kLtWaves];
+    __shared__ uint32_t s_cnt[2][kTblWaves];
     uint32_t tick = 0u, sum = 0u;
 #pragma unroll
-    for (int j = 0; j < kLtItems; ++j) {
-        const uint32_t r = blockIdx.x * kLtTile + (uint32_t)j * kLtBlock + threadIdx.x;    // n_landmarks + kLtTile < 2^32: rs_add_views_device
+    for (int j = 0; j < kTblItems; ++j) {
+        const uint32_t r = blockIdx.x * kTblTile + (uint32_t)j * kTblBlock + threadIdx.x;    // n_landmarks + kTblTile < 2^32: rs_add_views_device
         if (r < a.n_landmarks) {
             const uint32_t len = lt_row_length(a, r);
             a.obs_counts_out[r] = len;
             sum += len;
         }
     }
-    sum = akz_block_sum<kLtWaves>(s_cnt, tick, sum);
+    sum = akz_block_sum<kTblWaves>(s_cnt, tick, sum);
     if (threadIdx.x == 0) a.tile[blockIdx.x] = sum;
 }
 
-// ONE workgroup: tile sums -> tile offsets and slot rows -> the rows in front of a slot, kLtBlock at a time behind a running
-// carry; the totals.
-__global__ __launch_bounds__(kLtBlock) void k_lt_scan_sums(LtCall a)
+// ONE workgroup: tile sums -> tile offsets and slot rows -> the rows in front of a slot; the totals.
+__global__ __launch_bounds__(kTblBlock) void k_lt_scan_sums(LtCall a)
 {
-    __shared__ uint32_t s_wave[kLtWaves];
-    uint32_t carry = 0u, rows = 0u;
-    for (uint32_t t0 = 0; t0 < a.n_tiles; t0 += kLtBlock) {
-        const uint32_t t = t0 + threadIdx.x;
-        const uint32_t v = t < a.n_tiles ? a.tile[t] : 0u;
-        uint32_t total;
-        const uint32_t ex = akz_block_exclusive<kLtWaves>(v, s_wave, &total);
-        if (t < a.n_tiles) a.tile[t] = carry + ex;
-        carry += total;
-    }
-    for (uint32_t f0 = 0; f0 < a.n_frames; f0 += kLtBlock) {
-        const uint32_t f = f0 + threadIdx.x;
-        const uint32_t v = f < a.n_frames ? a.new_rows[f] : 0u;
-        uint32_t total;
-        const uint32_t ex = akz_block_exclusive<kLtWaves>(v, s_wave, &total);
-        if (f < a.n_frames) a.new_rows[f] = rows + ex;
-        rows += total;
-    }
+    __shared__ uint32_t s_wave[kTblWaves];
+    const uint32_t carry = tbl_scan_in_place(a.tile, a.n_tiles, s_wave), rows = tbl_scan_in_place(a.new_rows, a.n_frames, s_wave);
     if (threadIdx.x == 0) {
         const bool bad = a.info[kInfoBad] != 0u;
         uint32_t n_split = 0u;
@@ -285,21 +273,18 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_scan_sums(LtCall a)
 // observation o is written at obs_out[at] as a member of row `key`
 __device__ __forceinline__ void lt_put(const LtCall& a, uint32_t at, uint2 o, uint32_t key)
 {
-    a.obs_out[at] = o;
-    if (o.x < a.n_blocks && o.y < a.cap) atomicMin(&a.landmarks_out[(size_t)o.x * a.cap + o.y], key);
+    tbl_put(a.obs_out, a.landmarks_out, a.n_blocks, a.cap, at, o, key);
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_rows(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_rows(LtCall a)
 {
-    __shared__ uint32_t s_wave[kLtWaves];
+    __shared__ uint32_t s_wave[kTblWaves];
     uint32_t run = a.tile[blockIdx.x];
 #pragma unroll 1
-    for (int j = 0; j < kLtItems; ++j) {
-        const uint32_t r = blockIdx.x * kLtTile + (uint32_t)j * kLtBlock + threadIdx.x;
+    for (int j = 0; j < kTblItems; ++j) {
+        const uint32_t r = blockIdx.x * kTblTile + (uint32_t)j * kTblBlock + threadIdx.x;
         const uint32_t len = r < a.n_landmarks ? a.obs_counts_out[r] : 0u;
-        uint32_t total;
-        uint32_t dst = run + akz_block_exclusive<kLtWaves>(len, s_wave, &total);
-        run += total;
+        uint32_t dst = tbl_scan_step(run, len, s_wave);
         if (r >= a.n_landmarks) continue;
         a.obs_start_out[r] = dst;
         if (len == 0u) continue;                          // a tombstone, an empty row, or a refused table
@@ -311,9 +296,9 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_rows(LtCall a)
     }
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_tail(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_tail(LtCall a)
 {
-    const uint32_t k = blockIdx.x * kLtBlock + threadIdx.x;
+    const uint32_t k = blockIdx.x * kTblBlock + threadIdx.x;
     if (k > a.lm_room - a.n_landmarks) return;
     const uint32_t r = a.n_landmarks + k;
     if (a.info[kInfoBad] != 0u) {
@@ -327,7 +312,7 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_tail(LtCall a)
     if (k < a.info[kInfoSplit]) lt_put(a, at, a.split[k], r);           // k < min(split_count, split_room)
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_place(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_place(LtCall a)
 {
     uint32_t f, blk, feature, la, lb;
     if (!lt_lane_match(a, &f, &blk, &feature, &la, &lb)) return;
@@ -336,27 +321,27 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_place(LtCall a)
     lt_put(a, at, make_uint2(blk, feature), la);
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_new_rows(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_new_rows(LtCall a)
 {
-    __shared__ uint32_t s_cnt[2][kLtWaves];
+    __shared__ uint32_t s_cnt[2][kTblWaves];
     const uint32_t f = blockIdx.x;
     if (!a.accepted[f]) return;
     const uint32_t blk = a.frames[f], count = a.counts[blk];             // count <= cap: the slot was accepted
     const uint32_t* feat = a.feat + (size_t)f * a.cap;
     uint32_t row = a.n_landmarks + a.info[kInfoSplit] + a.new_rows[f], tick = 0u;
-    for (uint32_t j0 = 0; j0 < count; j0 += kLtBlock) {
+    for (uint32_t j0 = 0; j0 < count; j0 += kTblBlock) {
         const uint32_t j = j0 + threadIdx.x;
         const bool fresh = j < count && feat[j] == AKZ_LT_NONE;
         uint32_t total;
-        const uint32_t rank = akz_block_scan<kLtWaves>(s_cnt, tick, fresh, &total);
+        const uint32_t rank = akz_block_scan<kTblWaves>(s_cnt, tick, fresh, &total);
         if (fresh) lt_put(a, akz_lt_tail_start(a.info[kInfoOld], a.info[kInfoRows], a.n_landmarks, row + rank), make_uint2(blk, j), row + rank);
         row += total;
     }
 }
 
-__global__ __launch_bounds__(kLtBlock) void k_lt_fixup(LtCall a)
+__global__ __launch_bounds__(kTblBlock) void k_lt_fixup(LtCall a)
 {
-    const uint32_t r = blockIdx.x * kLtBlock + threadIdx.x;
+    const uint32_t r = blockIdx.x * kTblBlock + threadIdx.x;
     if (r >= a.n_landmarks) return;
     const uint32_t n = a.adds[r];
     if (n < 2u) return;
@@ -373,12 +358,6 @@ __global__ __launch_bounds__(kLtBlock) void k_lt_fixup(LtCall a)
     }
 }
 
-bool lt_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 }   // namespace
 
 extern "C" int32_t rs_landmarks_sharing_view_device(rs_ctx* c, const void* d_obs_start, const void* d_obs, uint32_t n_obs, uint32_t n_landmarks,
@@ -391,7 +370,7 @@ extern "C" int32_t rs_landmarks_sharing_view_device(rs_ctx* c, const void* d_obs
         const RsHandles h = rs_internal_handles(c);
         AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
         if (n_frames == 0) return AKZ_OK;
-        hipLaunchKernelGGL(k_lt_sharing, dim3((cap_per_img + kLtBlock - 1) / kLtBlock, n_frames), dim3(kLtBlock), 0, h.stream,
+        hipLaunchKernelGGL(k_lt_sharing, dim3((cap_per_img + kTblBlock - 1) / kTblBlock, n_frames), dim3(kTblBlock), 0, h.stream,
                            (const uint32_t*)d_obs_start, (const uint32_t*)d_obs, n_obs, n_landmarks, (const uint32_t*)d_best,
                            (const uint32_t*)d_decision, cap_per_img, (unsigned char*)d_merge_ok);
         AKZ_LAUNCH_CHECK();
@@ -416,38 +395,32 @@ extern "C" int32_t rs_add_views_device(rs_ctx* c, const void* d_obs_start, const
             return AKZ_E_INVALID;
         if ((d_split == nullptr) != (d_split_count == nullptr) || (!d_split && split_room != 0)) return AKZ_E_INVALID;
         if (cap_per_img == 0 || n_blocks == 0 || n_frames > 65535u) return AKZ_E_INVALID;
-        if (n_landmarks > 0xFFFFFFFFu - 2u * kLtTile) return AKZ_E_TOO_LARGE;      // row numbers of the last tile stay 32-bit
+        if (n_landmarks > 0xFFFFFFFFu - 2u * kTblTile) return AKZ_E_TOO_LARGE;      // row numbers of the last tile stay 32-bit
         // the rooms: no kernel can write past them (every feature of a frame adds one observation and at most one row)
         const uint64_t grow = (uint64_t)split_room + (uint64_t)n_frames * cap_per_img;
         if ((uint64_t)obs_room < (uint64_t)n_obs + grow || (uint64_t)lm_room < (uint64_t)n_landmarks + grow || lm_room == 0xFFFFFFFFu)
             return AKZ_E_INVALID;
-        if (n_frames) {
-            std::vector<unsigned char> seen(n_blocks, 0);
-            for (uint32_t f = 0; f < n_frames; ++f) {
-                if (ik[f] >= n_blocks || seen[ik[f]]) return AKZ_E_INVALID;
-                seen[ik[f]] = 1;
-            }
-        }
+        std::vector<unsigned char> seen;
+        if (n_frames && !akz_distinct_blocks(ik, n_frames, n_blocks, &seen)) return AKZ_E_INVALID;
         // the input table is const: no output table may lie over it
         const void* in[2] = {d_obs_start, d_obs};
         const size_t in_bytes[2] = {sizeof(uint32_t) * ((size_t)n_landmarks + 1), sizeof(uint32_t) * 2 * (size_t)n_obs};
         const void* out[5] = {d_obs_start_out, d_obs_out, d_obs_counts_out, d_landmarks_out, d_counts_out};
         const size_t out_bytes[5] = {sizeof(uint32_t) * ((size_t)lm_room + 1), sizeof(uint32_t) * 2 * (size_t)obs_room, sizeof(uint32_t) * (size_t)lm_room,
                                      sizeof(uint32_t) * (size_t)n_blocks * cap_per_img, sizeof(uint32_t) * AKZ_AV_COUNTS};
-        for (int i = 0; i < 2; ++i)
-            for (int o = 0; o < 5; ++o)
-                if (lt_overlap(in[i], in_bytes[i], out[o], out_bytes[o])) return AKZ_E_INVALID;
+        if (!akz_outputs_clear_of_inputs(in, in_bytes, 2, out, out_bytes, 5)) return AKZ_E_INVALID;
         if (!c) return AKZ_E_INVALID;
         const RsHandles h = rs_internal_handles(c);
         RsLandmarkTableState* ls = rs_internal_landmark_table(c);
         AKZ_TRY(akz_enqueue_behind(h, stream_to_wait));
-        const uint32_t n_tiles = (uint32_t)(((size_t)n_landmarks + kLtTile - 1) / kLtTile);
-        const size_t w = sizeof(uint32_t), lm_bytes = akz_align_up(w * ((size_t)n_landmarks + 1), 256);
-        const size_t info_bytes = akz_align_up(w * kInfoWords, 256), blocks_bytes = akz_align_up(w * (size_t)n_blocks, 256);
-        const size_t tile_bytes = akz_align_up(w * ((size_t)n_tiles + 1), 256), frame_bytes = akz_align_up(w * ((size_t)n_frames + 1), 256);
-        const size_t feat_bytes = akz_align_up(w * ((size_t)n_frames * cap_per_img + 1), 256);
-        const size_t zero_bytes = info_bytes + 3 * lm_bytes, none_bytes = 2 * lm_bytes + blocks_bytes;
-        AKZ_TRY(akz_grow_scratch(h.stream, &ls->d_scratch, &ls->bytes, zero_bytes + none_bytes + tile_bytes + 3 * frame_bytes + feat_bytes));
+        const uint32_t n_tiles = (uint32_t)(((size_t)n_landmarks + kTblTile - 1) / kTblTile);
+        const size_t w = sizeof(uint32_t), lm_bytes = w * ((size_t)n_landmarks + 1), frame_bytes = w * ((size_t)n_frames + 1);
+        AkzScratchPlan plan;                                             // zero: info .. cursor; none: merged_into .. block_slot
+        const size_t at_info = plan.take(w * kInfoWords), at_refs = plan.take(lm_bytes), at_adds = plan.take(lm_bytes), at_cursor = plan.take(lm_bytes);
+        const size_t at_into = plan.take(lm_bytes), at_from = plan.take(lm_bytes), at_slot = plan.take(w * (size_t)n_blocks);
+        const size_t at_tile = plan.take(w * ((size_t)n_tiles + 1)), at_frames = plan.take(frame_bytes), at_accepted = plan.take(frame_bytes);
+        const size_t at_new = plan.take(frame_bytes), at_feat = plan.take(w * ((size_t)n_frames * cap_per_img + 1));
+        AKZ_TRY(akz_grow_scratch(h.stream, &ls->d_scratch, &ls->bytes, plan.size()));
         char* base = (char*)ls->d_scratch;
         LtCall a;
         a.obs_start = (const uint32_t*)d_obs_start; a.obs = (const uint2*)d_obs; a.split = (const uint2*)d_split;
@@ -457,27 +430,18 @@ extern "C" int32_t rs_add_views_device(rs_ctx* c, const void* d_obs_start, const
         a.obs_start_out = (uint32_t*)d_obs_start_out; a.obs_out = (uint2*)d_obs_out; a.counts_out = (uint32_t*)d_counts_out;
         a.landmarks_out = (uint32_t*)d_landmarks_out; a.obs_counts_out = (uint32_t*)d_obs_counts_out; a.frame_verdict = (uint32_t*)d_frame_verdict;
         a.stats = (uint32_t*)d_stats; a.call_verdict = (uint32_t*)d_call_verdict;
-        a.info = (uint32_t*)base;
-        a.refs = (uint32_t*)(base + info_bytes);
-        a.adds = (uint32_t*)(base + info_bytes + lm_bytes);
-        a.cursor = (uint32_t*)(base + info_bytes + 2 * lm_bytes);
-        a.merged_into = (uint32_t*)(base + zero_bytes);
-        a.merged_from = (uint32_t*)(base + zero_bytes + lm_bytes);
-        a.block_slot = (uint32_t*)(base + zero_bytes + 2 * lm_bytes);
-        char* rest = base + zero_bytes + none_bytes;
-        a.tile = (uint32_t*)rest;
-        a.frames = (uint32_t*)(rest + tile_bytes);
-        a.accepted = (uint32_t*)(rest + tile_bytes + frame_bytes);
-        a.new_rows = (uint32_t*)(rest + tile_bytes + 2 * frame_bytes);
-        a.feat = (uint32_t*)(rest + tile_bytes + 3 * frame_bytes);
+        a.info = (uint32_t*)(base + at_info); a.refs = (uint32_t*)(base + at_refs); a.adds = (uint32_t*)(base + at_adds);
+        a.cursor = (uint32_t*)(base + at_cursor); a.merged_into = (uint32_t*)(base + at_into); a.merged_from = (uint32_t*)(base + at_from);
+        a.block_slot = (uint32_t*)(base + at_slot); a.tile = (uint32_t*)(base + at_tile); a.frames = (uint32_t*)(base + at_frames);
+        a.accepted = (uint32_t*)(base + at_accepted); a.new_rows = (uint32_t*)(base + at_new); a.feat = (uint32_t*)(base + at_feat);
         a.cap = cap_per_img; a.n_blocks = n_blocks; a.n_obs = n_obs; a.n_landmarks = n_landmarks; a.n_world = n_world;
         a.split_room = split_room; a.n_frames = n_frames; a.lm_room = lm_room; a.n_tiles = n_tiles;
-        AKZ_HIP(hipMemsetAsync(base, 0, zero_bytes, h.stream));
-        AKZ_HIP(hipMemsetAsync(base + zero_bytes, 0xFF, none_bytes, h.stream));
+        AKZ_HIP(hipMemsetAsync(base + at_info, 0, at_into - at_info, h.stream));
+        AKZ_HIP(hipMemsetAsync(base + at_into, 0xFF, at_tile - at_into, h.stream));
         AKZ_HIP(hipMemsetAsync(d_landmarks_out, 0xFF, out_bytes[3], h.stream));
         if (n_frames) AKZ_HIP(hipMemcpyAsync(a.frames, ik, w * n_frames, hipMemcpyHostToDevice, h.stream));
-        const dim3 block(kLtBlock), per_match((cap_per_img + kLtBlock - 1) / kLtBlock, n_frames ? n_frames : 1u);
-        hipLaunchKernelGGL(k_lt_check_table, dim3(n_landmarks / kLtBlock + 1), block, 0, h.stream, a);
+        const dim3 block(kTblBlock), per_match((cap_per_img + kTblBlock - 1) / kTblBlock, n_frames ? n_frames : 1u);
+        hipLaunchKernelGGL(k_lt_check_table, dim3(n_landmarks / kTblBlock + 1), block, 0, h.stream, a);
         AKZ_LAUNCH_CHECK();
         if (n_frames) {
             hipLaunchKernelGGL(k_lt_validate, dim3(n_frames), block, 0, h.stream, a);
@@ -497,7 +461,7 @@ extern "C" int32_t rs_add_views_device(rs_ctx* c, const void* d_obs_start, const
             hipLaunchKernelGGL(k_lt_rows, dim3(n_tiles), block, 0, h.stream, a);
             AKZ_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(k_lt_tail, dim3((lm_room - n_landmarks) / kLtBlock + 1), block, 0, h.stream, a);
+        hipLaunchKernelGGL(k_lt_tail, dim3((lm_room - n_landmarks) / kTblBlock + 1), block, 0, h.stream, a);
         AKZ_LAUNCH_CHECK();
         if (n_frames) {
             hipLaunchKernelGGL(k_lt_place, per_match, block, 0, h.stream, a);
@@ -505,7 +469,7 @@ extern "C" int32_t rs_add_views_device(rs_ctx* c, const void* d_obs_start, const
             hipLaunchKernelGGL(k_lt_new_rows, dim3(n_frames), block, 0, h.stream, a);
             AKZ_LAUNCH_CHECK();
             if (n_landmarks) {
-                hipLaunchKernelGGL(k_lt_fixup, dim3((n_landmarks + kLtBlock - 1) / kLtBlock), block, 0, h.stream, a);
+                hipLaunchKernelGGL(k_lt_fixup, dim3((n_landmarks + kTblBlock - 1) / kTblBlock), block, 0, h.stream, a);
                 AKZ_LAUNCH_CHECK();
             }
         }

@@ -9,8 +9,8 @@
 //                    a wave adds its lanes' with akz_wave_sum and one lane adds the sum to the reconstruction's words (a
 //                    wave that straddles two reconstructions adds lane by lane); integer sums do not depend on their order.
 //   k_of_tile_sums   the exclusive scan of the keep flags over the observations of the call, first level: one workgroup per
-//                    tile of kOfTile flags adds its tile.
-//   k_of_scan_sums   second level: ONE workgroup walks the tile sums kOfBlock at a time with a running carry, so there is no
+//                    tile of kTblTile flags (kTblItems per thread, as the rows of a table's tile) adds its tile.
+//   k_of_scan_sums   second level: ONE workgroup walks the tile sums kTblBlock at a time with a running carry, so there is no
 //                    third level however many tiles there are; it also closes the reconstructions' verdicts.
 //   k_of_scatter     third pass: a workgroup scans its tile again, adds the tile's offset and writes every observation to its
 //                    row of the filtered table or of the split list, and the kept-count in front of it to d_pos.
@@ -22,15 +22,11 @@
 //
 // The arithmetic is include/akz_observation_filter_math.h, the text the CPU checker
 // (tests/cpp/observation_filter_host.c) compiles too — parity: host build == HIP, bit for bit.
-#include "akz_common.h"
+#include "rs_table.h"
 #include "../../include/akz_observation_filter_math.h"
 
 namespace {
 
-constexpr int kOfBlock = 256;
-constexpr int kOfWaves = kOfBlock / 64;
-constexpr int kOfItems = 4;                          // keep flags per thread of a scan tile
-constexpr uint32_t kOfTile = kOfBlock * kOfItems;    // 1 024 observations
 constexpr uint32_t kOfNone = 0xFFFFFFFFu;
 
 static_assert(RS_OF_KEPT == AKZ_OF_KEPT && RS_OF_SINGLE == AKZ_OF_SINGLE && RS_OF_PAIR_SPLIT == AKZ_OF_PAIR_SPLIT &&
@@ -105,7 +101,7 @@ __device__ __forceinline__ uint32_t of_filled(const OfCall& a)
 // it and its range ascends inside [0, n_landmarks], (2) its view range ascends inside [0, n_blocks], (3) no start of
 // d_obs_start in front of its first landmark lies above that landmark's and the starts it owns ascend up to n_obs at the
 // most.  Two reconstructions that pass share no landmark and no observation, so no two lanes of k_of_decide write one flag.
-__global__ __launch_bounds__(kOfBlock) void k_of_prepare(OfCall a)
+__global__ __launch_bounds__(kTblBlock) void k_of_prepare(OfCall a)
 {
     __shared__ uint32_t s_bad;
     const uint32_t r = blockIdx.x;
@@ -113,18 +109,18 @@ __global__ __launch_bounds__(kOfBlock) void k_of_prepare(OfCall a)
     __syncthreads();
     const uint32_t rs = a.recon_start[r], re = a.recon_start[r + 1], vs = a.view_start[r], ve = a.view_start[r + 1];
     uint32_t bad = (rs > re || re > a.n_landmarks || vs > ve || ve > a.n_blocks) ? 1u : 0u;
-    for (uint32_t k = threadIdx.x; k < r; k += kOfBlock) bad |= a.recon_start[k] > rs ? 1u : 0u;
+    for (uint32_t k = threadIdx.x; k < r; k += kTblBlock) bad |= a.recon_start[k] > rs ? 1u : 0u;
     if (!bad) {                                   // rs <= re <= n_landmarks: every index below is inside d_obs_start
         const uint32_t first = a.obs_start[rs];
-        for (uint32_t l = threadIdx.x; l < rs; l += kOfBlock) bad |= a.obs_start[l] > first ? 1u : 0u;
-        for (uint32_t l = rs + threadIdx.x; l < re; l += kOfBlock) bad |= a.obs_start[l] > a.obs_start[l + 1] ? 1u : 0u;
+        for (uint32_t l = threadIdx.x; l < rs; l += kTblBlock) bad |= a.obs_start[l] > first ? 1u : 0u;
+        for (uint32_t l = rs + threadIdx.x; l < re; l += kTblBlock) bad |= a.obs_start[l] > a.obs_start[l + 1] ? 1u : 0u;
         bad |= a.obs_start[re] > a.n_obs ? 1u : 0u;
     }
     if (bad) atomicOr(&s_bad, 1u);
     __syncthreads();
     const bool refused = s_bad != 0u, skipped = !refused && a.skip && a.skip[r] != 0u;
     if (!refused && !skipped)
-        for (uint32_t l = rs + threadIdx.x; l < re; l += kOfBlock) a.lm_recon[l] = r;
+        for (uint32_t l = rs + threadIdx.x; l < re; l += kTblBlock) a.lm_recon[l] = r;
     if (threadIdx.x == 0) {
         uint32_t* stats = a.stats + (size_t)AKZ_OF_STATS * r;
 #pragma unroll
@@ -136,9 +132,9 @@ __global__ __launch_bounds__(kOfBlock) void k_of_prepare(OfCall a)
 }
 
 // One lane per landmark.  d_keep was set to 1 throughout in front of this kernel.
-__global__ __launch_bounds__(kOfBlock) void k_of_decide(OfCall a, rs_camera cam, akz_of_settings st)
+__global__ __launch_bounds__(kTblBlock) void k_of_decide(OfCall a, rs_camera cam, akz_of_settings st)
 {
-    const uint32_t l = blockIdx.x * kOfBlock + threadIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t l = blockIdx.x * kTblBlock + threadIdx.x, lane = threadIdx.x & 63u;
     const bool valid = l < a.n_landmarks;
     const uint32_t r = valid ? a.lm_recon[l] : kOfNone;
     int state = AKZ_OF_SKIPPED;
@@ -179,79 +175,71 @@ __global__ __launch_bounds__(kOfBlock) void k_of_decide(OfCall a, rs_camera cam,
 static_assert(AKZ_OF_S_ROBUST_BEFORE == 1 && AKZ_OF_S_ROBUST_AFTER == 2 && AKZ_OF_S_OBS_SPLIT == 3 && AKZ_OF_S_PAIR_SPLIT == 4 &&
               AKZ_OF_S_NO_POINT == 5 && AKZ_OF_S_KICKED == 6, "the order of k_of_decide's six counts");
 
-// the kOfItems flags of a thread of tile `tile`, as 0 / 1 (one 32-bit load where the array allows it); flags past the table's
+// the kTblItems flags of a thread of tile `tile`, as 0 / 1 (one 32-bit load where the array allows it); flags past the table's
 // observations count as 0
 __device__ __forceinline__ uint32_t of_thread_flags(const OfCall& a, uint32_t tile, uint32_t filled, uint32_t* k)
 {
-    static_assert(kOfItems == 4, "four flags are one word");
-    const size_t i0 = (size_t)tile * kOfTile + (size_t)threadIdx.x * kOfItems;
+    static_assert(kTblItems == 4, "four flags are one word");
+    const size_t i0 = (size_t)tile * kTblTile + (size_t)threadIdx.x * kTblItems;
     uint32_t word = 0u;
-    if (((uintptr_t)a.keep & 3u) == 0u && i0 + kOfItems <= (size_t)a.n_obs)
+    if (((uintptr_t)a.keep & 3u) == 0u && i0 + kTblItems <= (size_t)a.n_obs)
         word = *reinterpret_cast<const uint32_t*>(a.keep + i0);
     else {
 #pragma unroll
-        for (int j = 0; j < kOfItems; ++j)
+        for (int j = 0; j < kTblItems; ++j)
             if (i0 + j < (size_t)a.n_obs) word |= (uint32_t)a.keep[i0 + j] << (8 * j);
     }
     uint32_t sum = 0u;
 #pragma unroll
-    for (int j = 0; j < kOfItems; ++j) {
+    for (int j = 0; j < kTblItems; ++j) {
         k[j] = (i0 + j < filled && ((word >> (8 * j)) & 0xFFu) != 0u) ? 1u : 0u;
         sum += k[j];
     }
     return sum;
 }
 
-__global__ __launch_bounds__(kOfBlock) void k_of_tile_sums(OfCall a)
+__global__ __launch_bounds__(kTblBlock) void k_of_tile_sums(OfCall a)
 {
-    __shared__ uint32_t s_wave[kOfWaves];
-    uint32_t k[kOfItems];
+    __shared__ uint32_t s_wave[kTblWaves];
+    uint32_t k[kTblItems];
     uint32_t sum = akz_wave_sum(of_thread_flags(a, blockIdx.x, of_filled(a), k));
     if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = sum;
     __syncthreads();
     if (threadIdx.x == 0) {
         sum = 0u;
 #pragma unroll
-        for (int w = 0; w < kOfWaves; ++w) sum += s_wave[w];
+        for (int w = 0; w < kTblWaves; ++w) sum += s_wave[w];
         a.tile[blockIdx.x] = sum;
     }
 }
 
-// ONE workgroup: tile sums -> tile offsets, kOfBlock of them at a time behind a running carry; the totals; the verdicts.
-__global__ __launch_bounds__(kOfBlock) void k_of_scan_sums(OfCall a, uint32_t minimum_robust_landmarks)
+// ONE workgroup: tile sums -> tile offsets; the totals; the verdicts.
+__global__ __launch_bounds__(kTblBlock) void k_of_scan_sums(OfCall a, uint32_t minimum_robust_landmarks)
 {
-    __shared__ uint32_t s_wave[kOfWaves];
-    uint32_t carry = 0u;
-    for (uint32_t t0 = 0; t0 < a.n_tiles; t0 += kOfBlock) {
-        const uint32_t t = t0 + threadIdx.x;
-        const uint32_t v = t < a.n_tiles ? a.tile[t] : 0u;
-        uint32_t total;
-        const uint32_t ex = akz_block_exclusive<kOfWaves>(v, s_wave, &total);
-        if (t < a.n_tiles) a.tile[t] = carry + ex;
-        carry += total;
-    }
+    __shared__ uint32_t s_wave[kTblWaves];
+    const uint32_t carry = tbl_scan_in_place(a.tile, a.n_tiles, s_wave);
     if (threadIdx.x == 0) {
         const uint32_t filled = of_filled(a);
         a.pos[filled] = carry;
         a.counts[0] = carry;
         a.counts[1] = filled - carry;
     }
-    for (uint32_t r = threadIdx.x; r < a.n_recons; r += kOfBlock)
+    for (uint32_t r = threadIdx.x; r < a.n_recons; r += kTblBlock)
         if (a.verdict[r] == (uint32_t)AKZ_OF_OK)
             a.verdict[r] = (uint32_t)akz_of_verdict(a.stats[(size_t)AKZ_OF_STATS * r + AKZ_OF_S_ROBUST_AFTER], minimum_robust_landmarks);
 }
 
-__global__ __launch_bounds__(kOfBlock) void k_of_scatter(OfCall a)
+__global__ __launch_bounds__(kTblBlock) void k_of_scatter(OfCall a)
 {
-    __shared__ uint32_t s_wave[kOfWaves];
+    __shared__ uint32_t s_wave[kTblWaves];
     const uint32_t filled = of_filled(a);
-    uint32_t k[kOfItems], total;
+    uint32_t k[kTblItems], total;
     const uint32_t sum = of_thread_flags(a, blockIdx.x, filled, k);
-    uint32_t kept = a.tile[blockIdx.x] + akz_block_exclusive<kOfWaves>(sum, s_wave, &total);
-    const size_t i0 = (size_t)blockIdx.x * kOfTile + (size_t)threadIdx.x * kOfItems;
+    uint32_t kept = a.tile[blockIdx.x] + akz_block_exclusive<kTblWaves>(sum, s_wave, &total);
+    const size_t i0 = (size_t)blockIdx.x * kTblTile + (size_t)threadIdx.x * kTblItems;
     const uint2* obs = reinterpret_cast<const uint2*>(a.obs);
 #pragma unroll
-    for (int j = 0; j < kOfItems; ++j) {
+    for (int j = 0; j < kTblItems; ++j) {
         const size_t i = i0 + j;
         if (i >= filled) break;
         a.pos[i] = kept;
@@ -262,9 +250,9 @@ __global__ __launch_bounds__(kOfBlock) void k_of_scatter(OfCall a)
     }
 }
 
-__global__ __launch_bounds__(kOfBlock) void k_of_starts(OfCall a)
+__global__ __launch_bounds__(kTblBlock) void k_of_starts(OfCall a)
 {
-    const uint32_t l = blockIdx.x * kOfBlock + threadIdx.x;
+    const uint32_t l = blockIdx.x * kTblBlock + threadIdx.x;
     if (l > a.n_landmarks) return;
     const uint32_t filled = of_filled(a), s = a.obs_start[l];
     a.obs_start_out[l] = a.pos[s < filled ? s : filled];
@@ -297,12 +285,6 @@ int32_t of_settings(const rs_observation_filter_params* prm, akz_of_settings* st
     return AKZ_OK;
 }
 
-bool of_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // the tables of one pass and where it writes
 struct OfArgs {
     const void *d_kps, *d_poses, *d_obs_start, *d_obs, *d_recon_start, *d_view_start, *d_skip;
@@ -321,23 +303,21 @@ int32_t of_check(rs_ctx* c, const OfArgs& g, const rs_camera* cam)
     const size_t start_bytes = sizeof(uint32_t) * ((size_t)g.n_landmarks + 1), obs_bytes = sizeof(uint32_t) * 2 * (size_t)g.n_obs;
     const void* in[2] = {g.d_obs_start, g.d_obs};
     const size_t in_bytes[2] = {start_bytes, obs_bytes};
-    for (int k = 0; k < 2; ++k)
-        if (of_overlap(in[k], in_bytes[k], g.d_obs_start_out, start_bytes) || of_overlap(in[k], in_bytes[k], g.d_obs_out, obs_bytes) ||
-            of_overlap(in[k], in_bytes[k], g.d_split_out, obs_bytes) || of_overlap(in[k], in_bytes[k], g.d_keep, g.n_obs))
-            return AKZ_E_INVALID;
-    return AKZ_OK;
+    const void* out[4] = {g.d_obs_start_out, g.d_obs_out, g.d_split_out, g.d_keep};
+    const size_t out_bytes[4] = {start_bytes, obs_bytes, obs_bytes, g.n_obs};
+    return akz_outputs_clear_of_inputs(in, in_bytes, 2, out, out_bytes, 4) ? AKZ_OK : AKZ_E_INVALID;
 }
 
 // one pass on the stream (the device is current, the stream ordered behind the caller's)
 int32_t of_enqueue(rs_ctx* c, const RsHandles& h, const OfArgs& g, const rs_camera* cam, const akz_of_settings& st)
 {
     RsObsFilterState* fs = rs_internal_obs_filter(c);
-    const uint32_t n_tiles = (uint32_t)(((size_t)g.n_obs + kOfTile - 1) / kOfTile);
-    const size_t lm_bytes = akz_align_up(sizeof(uint32_t) * ((size_t)g.n_landmarks + 1), 256);
-    const size_t recon_bytes = akz_align_up(sizeof(uint32_t) * ((size_t)g.n_recons + 1), 256);
-    const size_t pos_bytes = akz_align_up(sizeof(uint32_t) * ((size_t)g.n_obs + 1), 256);
-    const size_t tile_bytes = akz_align_up(sizeof(uint32_t) * ((size_t)n_tiles + 1), 256);
-    AKZ_TRY(akz_grow_scratch(h.stream, &fs->d_scratch, &fs->bytes, lm_bytes + recon_bytes + pos_bytes + tile_bytes));
+    const uint32_t n_tiles = (uint32_t)(((size_t)g.n_obs + kTblTile - 1) / kTblTile);
+    const size_t w = sizeof(uint32_t);
+    AkzScratchPlan plan;
+    const size_t at_lm = plan.take(w * ((size_t)g.n_landmarks + 1)), at_views = plan.take(w * ((size_t)g.n_recons + 1));
+    const size_t at_pos = plan.take(w * ((size_t)g.n_obs + 1)), at_tile = plan.take(w * ((size_t)n_tiles + 1));
+    AKZ_TRY(akz_grow_scratch(h.stream, &fs->d_scratch, &fs->bytes, plan.size()));
     char* base = (char*)fs->d_scratch;
     OfCall a;
     a.kps = (const akz_keypoint*)g.d_kps; a.poses = (const double*)g.d_poses;
@@ -347,32 +327,30 @@ int32_t of_enqueue(rs_ctx* c, const RsHandles& h, const OfArgs& g, const rs_came
     a.robust = (unsigned char*)g.d_robust; a.obs_start_out = (uint32_t*)g.d_obs_start_out; a.obs_out = (uint2*)g.d_obs_out;
     a.split_out = (uint2*)g.d_split_out; a.counts = (uint32_t*)g.d_counts; a.verdict = (uint32_t*)g.d_recon_verdict;
     a.stats = (uint32_t*)g.d_stats;
-    a.lm_recon = (uint32_t*)base;
-    a.recon_views = (uint32_t*)(base + lm_bytes);
-    a.pos = (uint32_t*)(base + lm_bytes + recon_bytes);
-    a.tile = (uint32_t*)(base + lm_bytes + recon_bytes + pos_bytes);
+    a.lm_recon = (uint32_t*)(base + at_lm); a.recon_views = (uint32_t*)(base + at_views); a.pos = (uint32_t*)(base + at_pos);
+    a.tile = (uint32_t*)(base + at_tile);
     a.cap = g.cap; a.n_blocks = g.n_blocks; a.n_obs = g.n_obs; a.n_landmarks = g.n_landmarks; a.n_recons = g.n_recons; a.n_tiles = n_tiles;
     if (g.n_landmarks) AKZ_HIP(hipMemsetAsync(a.lm_recon, 0xFF, sizeof(uint32_t) * (size_t)g.n_landmarks, h.stream));
     if (g.n_obs) AKZ_HIP(hipMemsetAsync(a.keep, 1, g.n_obs, h.stream));
     if (g.n_recons) {
-        hipLaunchKernelGGL(k_of_prepare, dim3(g.n_recons), dim3(kOfBlock), 0, h.stream, a);
+        hipLaunchKernelGGL(k_of_prepare, dim3(g.n_recons), dim3(kTblBlock), 0, h.stream, a);
         AKZ_LAUNCH_CHECK();
     }
     if (g.n_landmarks) {
-        hipLaunchKernelGGL(k_of_decide, dim3((g.n_landmarks + kOfBlock - 1) / kOfBlock), dim3(kOfBlock), 0, h.stream, a, *cam, st);
+        hipLaunchKernelGGL(k_of_decide, dim3((g.n_landmarks + kTblBlock - 1) / kTblBlock), dim3(kTblBlock), 0, h.stream, a, *cam, st);
         AKZ_LAUNCH_CHECK();
     }
     if (n_tiles) {
-        hipLaunchKernelGGL(k_of_tile_sums, dim3(n_tiles), dim3(kOfBlock), 0, h.stream, a);
+        hipLaunchKernelGGL(k_of_tile_sums, dim3(n_tiles), dim3(kTblBlock), 0, h.stream, a);
         AKZ_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_of_scan_sums, dim3(1), dim3(kOfBlock), 0, h.stream, a, st.minimum_robust_landmarks);
+    hipLaunchKernelGGL(k_of_scan_sums, dim3(1), dim3(kTblBlock), 0, h.stream, a, st.minimum_robust_landmarks);
     AKZ_LAUNCH_CHECK();
     if (n_tiles) {
-        hipLaunchKernelGGL(k_of_scatter, dim3(n_tiles), dim3(kOfBlock), 0, h.stream, a);
+        hipLaunchKernelGGL(k_of_scatter, dim3(n_tiles), dim3(kTblBlock), 0, h.stream, a);
         AKZ_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_of_starts, dim3(g.n_landmarks / kOfBlock + 1), dim3(kOfBlock), 0, h.stream, a);
+    hipLaunchKernelGGL(k_of_starts, dim3(g.n_landmarks / kTblBlock + 1), dim3(kTblBlock), 0, h.stream, a);
     AKZ_LAUNCH_CHECK();
     return AKZ_OK;
 }

@@ -96,7 +96,10 @@ def test_header_constants_are_the_bindings_and_the_math_headers():
     assert int(re.search(r"AKZ_BT_NOT_RECORDED = (\d+)", math).group(1)) == _lib.RS_CV_NOT_RECORDED
     assert int(re.search(r"AKZ_BT_TV_OK = (\d+)", math).group(1)) == _lib.RS_TV_OK == _lib.RS_TVC_OK
     hip = read("cv_amd", "csrc", "rs_bootstrap_table.hip")
-    assert "static_assert(kBtTile == (uint32_t)RS_LT_TILE" in hip
+    # the tile the kernels scan is the exported one: stated once, in the header of the table stages' shared pieces
+    tbl = open(os.path.join(ROOT, "cv_amd", "csrc", "rs_table.h")).read()
+    assert "static_assert(kTblTile == (uint32_t)RS_LT_TILE" in tbl and '#include "rs_table.h"' in hip and "kTblTile" in hip
+    assert not re.search(r"constexpr \w+ k\w+Tile\b", hip)
     # the helpers are akz_common.h's: used, not copied
     assert "lds_radix_sort_ids(" in hip and "akz_block_scan<" in hip and "uint32_t* lds_radix_sort_ids" not in hip
     import bootstrap_table_checker as K

@@ -89,7 +89,10 @@ def test_header_constants_are_the_bindings_and_the_math_headers():
     for k, name in enumerate(("Ok", "Overflow", "BadTable")):
         assert re.search(r"%s = %d," % (name, k), rust.split("pub enum ExportVerdict")[1].split("}")[0])
     hip = read("cv_amd", "csrc", "rs_export.hip")
-    assert "static_assert(kExTile == (uint32_t)RS_LT_TILE" in hip and "static_assert(kExBlock == AKZ_SUM_THREADS" in hip
+    # the tile the kernels scan is the exported one: stated once, in the header of the table stages' shared pieces
+    tbl = open(os.path.join(ROOT, "cv_amd", "csrc", "rs_table.h")).read()
+    assert "static_assert(kTblTile == (uint32_t)RS_LT_TILE" in tbl and '#include "rs_table.h"' in hip and "kTblTile" in hip
+    assert not re.search(r"constexpr \w+ k\w+Tile\b", hip) and "static_assert(kTblBlock == AKZ_SUM_THREADS" in hip
     assert "akz_nr_distance(" in math and "akz_nr_mean(" in math and math.count("sqrt") == 0        # reused, not restated
     assert "not compiled here" in rust.split("pub struct ReconstructionExport")[0].rsplit("///", 1)[1]
     import export_checker as K

@@ -80,9 +80,11 @@ def test_header_constants_are_the_bindings():
     assert re.search(r"pub const RS_LT_TILE: u32 = 1024;", rust) and re.search(r"pub const RS_AV_STATS: usize = 4;", rust)
     # the verdict the math header takes for "registered" is the refinement's RS_SV_OK
     assert int(re.search(r"AKZ_LT_SV_OK = (\d+)", math).group(1)) == _lib.RS_SV_OK
-    # the tile the kernels scan is the exported one
     hip = open(os.path.join(ROOT, "cv_amd", "csrc", "rs_landmark_table.hip")).read()
-    assert "static_assert(kLtTile == (uint32_t)RS_LT_TILE" in hip
+    # the tile the kernels scan is the exported one: stated once, in the header of the table stages' shared pieces
+    tbl = open(os.path.join(ROOT, "cv_amd", "csrc", "rs_table.h")).read()
+    assert "static_assert(kTblTile == (uint32_t)RS_LT_TILE" in tbl and '#include "rs_table.h"' in hip and "kTblTile" in hip
+    assert not re.search(r"constexpr \w+ k\w+Tile\b", hip)
 
 
 class Call:

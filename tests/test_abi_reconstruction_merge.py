@@ -90,7 +90,10 @@ def test_header_constants_are_the_bindings_and_the_math_headers():
     for k, name in enumerate(("Ok", "NotNormal", "BadIndex")):
         assert re.search(r"%s = %d," % (name, k), rust.split("pub enum NormalizeVerdict")[1].split("}")[0])
     hip = read("cv_amd", "csrc", "rs_reconstruction_merge.hip")
-    assert "static_assert(kIrTile == (uint32_t)RS_LT_TILE" in hip and "static_assert(kIrBlock == AKZ_SUM_THREADS" in hip
+    # the tile the kernels scan is the exported one: stated once, in the header of the table stages' shared pieces
+    tbl = open(os.path.join(ROOT, "cv_amd", "csrc", "rs_table.h")).read()
+    assert "static_assert(kTblTile == (uint32_t)RS_LT_TILE" in tbl and '#include "rs_table.h"' in hip and "kTblTile" in hip
+    assert not re.search(r"constexpr \w+ k\w+Tile\b", hip) and "static_assert(kTblBlock == AKZ_SUM_THREADS" in hip
     # the source is "not compiled here" where the others say so
     assert "not compiled here" in rust.split("pub struct ReconstructionMerge")[0].rsplit("///", 1)[1]
 

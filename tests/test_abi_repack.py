@@ -86,8 +86,13 @@ def test_header_constants_are_the_bindings_and_the_math_headers():
     assert (cat.OK, cat.BAD_TABLE, cat.BAD_INDEX, cat.BAD_MAP, cat.NO_ROOM) == tuple(range(5)) and cat.TILE == _lib.RS_LT_TILE
     assert "#define AKZ_RP_NONE 0xFFFFFFFFu" in math and _lib.HM_PL_NONE == 0xFFFFFFFF == repack.NONE
     hip = open(os.path.join(ROOT, "cv_amd", "csrc", "rs_repack.hip")).read()
-    assert "static_assert(kRpTile == (uint32_t)RS_LT_TILE" in hip
-    assert "akz_block_sum" in hip and "akz_block_exclusive" in hip and "akz_block_scan" in hip
+    # the tile the kernels scan is the exported one: stated once, in the header of the table stages' shared pieces
+    tbl = open(os.path.join(ROOT, "cv_amd", "csrc", "rs_table.h")).read()
+    assert "static_assert(kTblTile == (uint32_t)RS_LT_TILE" in tbl and '#include "rs_table.h"' in hip and "kTblTile" in hip
+    assert not re.search(r"constexpr \w+ k\w+Tile\b", hip)
+    # the helpers are akz_common.h's and rs_table.h's: used, not copied
+    assert "akz_block_sum<" in hip and "akz_block_scan<" in hip and "tbl_scan_step(" in hip and "tbl_scan_in_place(" in hip
+    assert "akz_block_exclusive<" in tbl and "uint32_t tbl_scan" not in hip and "uint32_t akz_block_" not in hip
 
 
 class Table:

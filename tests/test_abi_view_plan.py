@@ -91,7 +91,9 @@ def test_header_constants_are_the_bindings_and_the_math_header():
         assert re.search(r"__global__[^;{]*\b%s\(" % kernel, hip) and kernel not in match, kernel
     for kernel in ("k_knn_mfma4w", "k_knn_mfma4", "k_knn_mfma", "k_knn2", "k_expand", "k_expand4", "k_best_of_views"):
         assert re.search(r"__global__[^;{]*\b%s\(" % kernel, match) and not re.search(r"\b%s\b" % kernel, hip), kernel
-    assert "akz_view_plan_math.h" in hip and "akz_block_exclusive<" in hip and "hm_internal_planned(" in hip and "hm_internal_planned(" in match
+    assert "akz_view_plan_math.h" in hip and "hm_internal_planned(" in hip and "hm_internal_planned(" in match
+    # the scan behind a running carry is the table stages' (rs_table.h, over akz_common.h's block scan): used, not copied
+    assert "tbl_scan<kVpScanWaves>(" in hip and "akz_block_exclusive<" in read("cv_amd", "csrc", "rs_table.h") and "uint32_t tbl_scan" not in hip
     for struct in ("HmProb", "HmProbX", "HmExpandJob"):
         assert len(re.findall(r"^struct %s \{" % struct, read("cv_amd", "csrc", "hm_tables.h"), re.M)) == 1
         assert not re.search(r"^struct %s \{" % struct, hip + match, re.M)

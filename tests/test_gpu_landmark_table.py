@@ -265,6 +265,26 @@ def test_the_mask_on_random_candidates_with_many_long_lists_in_one_wave(gpu, con
     assert np.array_equal(device_mask(gpu, cons, start, obs, len(obs) // 2, best, decision), want)
 
 
+def test_the_mask_on_both_sides_of_the_lanes_and_the_waves_walk(gpu, cons):
+    """k_lt_sharing hands a candidate to its wave above 32 entries in both lists together (kLtShortPair): 32 and 33, disjoint and
+    sharing the last element of either list only, in the first and the last lane of a wave and in the wave behind it"""
+    a16 = [(v, 0) for v in range(16)]
+    b16, b17 = [(100 + v, 0) for v in range(16)], [(100 + v, 0) for v in range(17)]
+    c16, c17 = [(200 + v, 0) for v in range(15)] + [(15, 1)], [(200 + v, 0) for v in range(16)] + [(15, 1)]     # view 15 is a16's last
+    lists = [a16, b16, b17, c16, c17]
+    cases = [((0, 1), 1), ((0, 2), 1), ((0, 3), 0), ((0, 4), 0), ((4, 0), 0), ((2, 0), 1)]                    # 32, 33, 32, 33, 33, 33
+    assert [len(lists[a]) + len(lists[b]) for (a, b), _ in cases] == [32, 33, 32, 33, 33, 33]
+    cap = 192
+    pairs, decisions, want = [(K.NONE, K.NONE)] * cap, [0] * cap, [0] * cap
+    for j0, turn in ((0, 0), (58, 2), (64, 4)):                            # lanes 0 .. 5, lanes 58 .. 63, and wave 1
+        for i, (pr, ok) in enumerate(cases[turn:] + cases[:turn]):
+            pairs[j0 + i], decisions[j0 + i], want[j0 + i] = pr, 2, ok
+    assert pairs[63] == (0, 2) and pairs[62] == (0, 1)                     # 33 entries in lane 63, 32 beside it
+    start, obs, n_obs, best, decision = K.mask_case(lists, pairs, decisions, cap=cap)
+    got = device_mask(gpu, cons, start, obs, n_obs, best, decision)
+    assert np.array_equal(got, K.sharing_view(start, obs, n_obs, best, decision)) and got[0].tolist() == want
+
+
 def test_refusals_with_a_context_launch_nothing(gpu, cons):
     """rooms too small, a repeated block, outputs over the input: AKZ_E_INVALID, and the outputs keep their fill"""
     from cv_amd import _lib

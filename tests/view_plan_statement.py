@@ -131,6 +131,8 @@ def cases():
     five = [one_group([1, 2]), one_group([2, 3]), one_group([9, 1, 5])]              # distinct blocks 1 2 3 5 9
     c["room_exact"] = case(designed(five), V, 40, exp_blocks=5)
     c["room_short"] = case(designed(five), V, 40, exp_blocks=4)
+    # k_vp_scan takes 1 024 flags a pass: distinct blocks on both sides of the pass's end, counted behind the carry
+    c["scan_second_pass"] = case(designed([one_group([1023, 1024, 5]), one_group([1099, 1023]), one_group([1025])]), V, 1100)
     c["two_groups_each"] = case(designed([[(3, 1), (8, 2), (8, 4), (3, 6)], [(8, 5), (3, 7), (3, 9)], [(2, 11)]]), V, 40, pick=[8, 8, 8], by_recon=True)
     for F in (1, 63, 64, 65):
         rng = P._rng(F, 0x5650)
